@@ -344,6 +344,27 @@ long long seg3d_patch_stats_blocks(int bx, int by, int bz);
 int seg3d_patch_gather_normalize(const float* volume, const int* starts_xyz, float* batch, double* workspace,
                                  float* mean_std, int Z, int Y, int X, int bx, int by, int bz, int P, int normalizer_type,
                                  float mean, float stddev, int clip, float clip_sigma, void* stream);
+/* M co-registered modalities (1 <= M <= 8), channels-last volume [Z][Y][X][M] -> batch [P][bz][by][bx][M] (NDHWC of
+ * the patch batch).  Replaces the per-modality crop + crop_normalizers[idx] of dataset.py:199-203 and the
+ * crop_normalizers[0]-only ROI normalisation of core/seg_infer.py:221-224.  One normaliser per modality, passed by
+ * value: type 0 = fixed ((x - mean) / stddev, clipped to [clip_lo, clip_hi] when clip != 0), 1 = adaptive (the patch's
+ * own fp64 mean / population std floored at 1e-6, clipped to [clip_lo, clip_hi]), -1 = none.  Channel m is
+ * bit-identical to seg3d_patch_gather_normalize on plane m with normaliser m.  Same starts / control-block contract;
+ * no host sync, no allocation (capturable).  workspace: seg3d_patch_stats_mc_doubles doubles; mean_std: P * M * 2
+ * floats (adaptive only). */
+typedef struct Seg3dNormalizer {
+  int type;
+  float mean, stddev;
+  int clip;
+  float clip_lo, clip_hi;
+} Seg3dNormalizer;
+typedef struct Seg3dNormalizers {
+  Seg3dNormalizer n[8];
+} Seg3dNormalizers;
+long long seg3d_patch_stats_mc_doubles(int bx, int by, int bz, int P, int M);
+int seg3d_patch_gather_normalize_mc(const float* volume, const int* starts_xyz, float* batch, double* workspace,
+                                    float* mean_std, int Z, int Y, int X, int bx, int by, int bz, int P, int M,
+                                    Seg3dNormalizers norms, void* stream);
 int seg3d_patch_scatter_accumulate(const float* probs, const int* starts_xyz, const int* ctl /* device int32[7] */,
                                    float* acc, float* count, int Z, int Y, int X, int bx, int by, int bz, int C,
                                    long long max_box_voxels, void* stream);
@@ -362,6 +383,13 @@ int seg3d_label_overlap_counts(const void* gt, const void* seg, int dtype, long 
  * or nearest neighbour (round half up). */
 int seg3d_resample_affine(const float* src, float* dst, int Xi, int Yi, int Zi, int Xo, int Yo, int Zo,
                           const double* affine_host, int linear, float pad, void* stream);
+/* the same resampling for M co-registered channels sharing one geometry (dataset.py:199-203 crops every modality at
+ * one centre and spacing; core/seg_infer.py:221-224 + image_tools.py:348-377 resample the case to the model spacing):
+ * src [Zi][Yi][Xi][M], output voxel (x, y, z) written as M floats at dst + ((z * Yo + y) * Xo + x) * dst_stride
+ * (dst_stride >= M; a crop goes straight into slot b of an NDHWC batch).  Channel m is bit-identical to
+ * seg3d_resample_affine on plane m.  1 <= M <= 8. */
+int seg3d_resample_affine_mc(const float* src, float* dst, int M, long long dst_stride, int Xi, int Yi, int Zi, int Xo,
+                             int Yo, int Zo, const double* affine_host, int linear, float pad, void* stream);
 /* box_device[6] initialised to {INT_MAX x3, -1 x3} -> inclusive (xmin, ymin, zmin, xmax, ymax, zmax) of the voxels whose
  * value is in labels_host (nlabels == 0: every voxel > 0); untouched when nothing is selected */
 int seg3d_mask_bounding_box(const signed char* mask, int X, int Y, int Z, const int* labels_host, int nlabels,

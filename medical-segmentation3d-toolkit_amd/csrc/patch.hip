@@ -146,6 +146,195 @@ extern "C" int seg3d_patch_gather_normalize(const float* volume, const int* star
   return SEG3D_OK;
 }
 
+// ---- M co-registered modalities in one launch chain (dataset.py:199-203 crops and normalises a list of images with
+// crop_normalizers[idx]; core/seg_infer.py:221-224 applies crop_normalizers[0] to the single one).  The volume is
+// channels-last [Z][Y][X][M]; the batch is [P][bz][by][bx][M] (NDHWC).  ONE stats pass reads each patch once for all
+// modalities; per (patch, modality) the chunking, the fp64 summation order and the finalisation are those of
+// patch_stats_partial_kernel / patch_stats_finalize_kernel (the latter is reused as is over P * M rows), and every
+// voxel is normalised with patch_gather_normalize_kernel's float expression, so channel m is bit-identical to
+// seg3d_patch_gather_normalize on plane m with normaliser m.
+// MC = 2, 3, 4: compile-time width (VEC: 8- / 16-byte rows); MC = 0: runtime M <= 8.
+
+// partial[(p * M + m)][blk][2] = (sum, sum of squares) in fp64 of modality m over a chunk of patch p's voxels
+template <int MC, bool VEC>
+__global__ __launch_bounds__(256) void patch_stats_partial_mc_kernel(const float* __restrict__ vol,
+                                                                       const int* __restrict__ starts,
+                                                                       double* __restrict__ partial, int Mrt, int Y, int X,
+                                                                       int bx, int by, int bz, int nblk) {
+  constexpr int MR = MC > 0 ? MC : 8;
+  const int M = MC > 0 ? MC : Mrt;
+  __shared__ double red[MR][8];
+  const int p = blockIdx.y;
+  const int sx = starts[3 * p], sy = starts[3 * p + 1], sz = starts[3 * p + 2];
+  const i64 nv = (i64)bx * by * bz;
+  const i64 e0 = (i64)blockIdx.x * PATCH_STAT_CHUNK;
+  i64 e1 = e0 + PATCH_STAT_CHUNK;
+  if (e1 > nv) e1 = nv;
+  double s[MR], ss[MR];
+#pragma unroll
+  for (int m = 0; m < MR; ++m) s[m] = ss[m] = 0.0;
+  for (i64 e = e0 + threadIdx.x; e < e1; e += 256) {
+    const int lx = (int)(e % bx);
+    const i64 t = e / bx;
+    const int ly = (int)(t % by), lz = (int)(t / by);
+    const float* row = vol + (((i64)(sz + lz) * Y + (sy + ly)) * X + (sx + lx)) * M;
+    float r[MR];
+    if constexpr (MC > 0) {
+      mc_load_row<MC, VEC>(row, r);
+    } else {
+#pragma unroll
+      for (int m = 0; m < MR; ++m) r[m] = m < M ? row[m] : 0.f;
+    }
+#pragma unroll
+    for (int m = 0; m < MR; ++m) {
+      const double v = (double)r[m];
+      s[m] += v;
+      ss[m] += v * v;
+    }
+  }
+#pragma unroll
+  for (int m = 0; m < MR; ++m) {
+    s[m] = wave_sum_d(s[m]);
+    ss[m] = wave_sum_d(ss[m]);
+  }
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int m = 0; m < MR; ++m) {
+      red[m][threadIdx.x >> 6] = s[m];
+      red[m][4 + (threadIdx.x >> 6)] = ss[m];
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < M) {
+    const int m = threadIdx.x;
+    const i64 row = ((i64)p * M + m) * nblk + blockIdx.x;
+    partial[row * 2 + 0] = red[m][0] + red[m][1] + red[m][2] + red[m][3];
+    partial[row * 2 + 1] = red[m][4] + red[m][5] + red[m][6] + red[m][7];
+  }
+}
+
+// batch[p][lz][ly][lx][m] = clip_m((vol[...][m] - mean_pm) / std_pm)
+template <int MC, bool VEC>
+// (vol and batch may be the same buffer: a crop normalised in place, P = 1 and the box = the volume)
+__global__ __launch_bounds__(256) void patch_gather_normalize_mc_kernel(const float* vol, const int* __restrict__ starts,
+                                                                          const float* __restrict__ mean_std, float* batch, int Mrt, int Y, int X,
+                                                                          int bx, int by, int bz, int P,
+                                                                          Seg3dNormalizers nrm) {
+  constexpr int MR = MC > 0 ? MC : 8;
+  const int M = MC > 0 ? MC : Mrt;
+  const i64 nv = (i64)bx * by * bz;
+  const i64 total = nv * P;
+  for (i64 idx = (i64)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (i64)gridDim.x * 256) {
+    const int p = (int)(idx / nv);
+    const i64 e = idx - (i64)p * nv;
+    const int lx = (int)(e % bx);
+    const i64 t = e / bx;
+    const int ly = (int)(t % by), lz = (int)(t / by);
+    const int sx = starts[3 * p], sy = starts[3 * p + 1], sz = starts[3 * p + 2];
+    const float* row = vol + (((i64)(sz + lz) * Y + (sy + ly)) * X + (sx + lx)) * M;
+    float r[MR];
+    if constexpr (MC > 0) {
+      mc_load_row<MC, VEC>(row, r);
+    } else {
+#pragma unroll
+      for (int m = 0; m < MR; ++m) r[m] = m < M ? row[m] : 0.f;
+    }
+#pragma unroll
+    for (int m = 0; m < MR; ++m) {
+      const Seg3dNormalizer& n = nrm.n[m];
+      const bool adaptive = n.type == 1;
+      const float mean = adaptive ? mean_std[((i64)p * M + m) * 2] : n.mean;
+      const float sd = adaptive ? mean_std[((i64)p * M + m) * 2 + 1] : n.stddev;
+      float v = (r[m] - mean) / sd;
+      if (n.clip) {
+        if (v < n.clip_lo) v = n.clip_lo;
+        if (v > n.clip_hi) v = n.clip_hi;
+      }
+      r[m] = v;
+    }
+    float* q = batch + idx * M;
+    if constexpr (MC > 0) {
+      mc_store_row<MC, VEC>(q, r);
+    } else {
+#pragma unroll
+      for (int m = 0; m < MR; ++m)
+        if (m < M) q[m] = r[m];
+    }
+  }
+}
+
+extern "C" long long seg3d_patch_stats_mc_doubles(int bx, int by, int bz, int P, int M) {
+  return (long long)P * M * seg3d_patch_stats_blocks(bx, by, bz) * 2;
+}
+
+template <int MC, bool VEC>
+static int patch_gather_normalize_mc_launch(const float* volume, const int* starts, float* batch, double* workspace,
+                                            float* mean_std, int M, int Y, int X, int bx, int by, int bz, int P,
+                                            const Seg3dNormalizers& nrm, bool any_adaptive, hipStream_t s) {
+  if (any_adaptive) {
+    const int nblk = (int)seg3d_patch_stats_blocks(bx, by, bz);
+    hipLaunchKernelGGL((patch_stats_partial_mc_kernel<MC, VEC>), dim3(nblk, P), dim3(256), 0, s, volume, starts, workspace,
+                       M, Y, X, bx, by, bz, nblk);
+    SEG3D_LAUNCH_CHECK("seg3d_patch_gather_normalize_mc(stats)");
+    hipLaunchKernelGGL(patch_stats_finalize_kernel, dim3(P * M), dim3(64), 0, s, workspace, mean_std, nblk,
+                       (double)bx * by * bz);
+    SEG3D_LAUNCH_CHECK("seg3d_patch_gather_normalize_mc(finalize)");
+  }
+  const i64 total = (i64)bx * by * bz * P;
+  hipLaunchKernelGGL((patch_gather_normalize_mc_kernel<MC, VEC>), dim3(seg3d_ew_grid(total, 256)), dim3(256), 0, s, volume,
+                     starts, mean_std, batch, M, Y, X, bx, by, bz, P, nrm);
+  SEG3D_LAUNCH_CHECK("seg3d_patch_gather_normalize_mc");
+  return SEG3D_OK;
+}
+
+// volume [Z][Y][X][M], batch [P][bz][by][bx][M]; starts: device int32 [P][3] as (x, y, z) (the sliding window's control
+// block).  norms.n[m] for m < M: type 0 = fixed (mean, stddev, clip to [clip_lo, clip_hi] when clip != 0), 1 = adaptive
+// (the patch's own mean / std, clip to [clip_lo, clip_hi]), -1 = none.  workspace: seg3d_patch_stats_mc_doubles doubles,
+// mean_std: P * M * 2 floats (both used only when a modality is adaptive).  batch may be volume itself when P = 1, the
+// start is 0 and the box is the whole volume (a training crop normalised in place).
+extern "C" int seg3d_patch_gather_normalize_mc(const float* volume, const int* starts, float* batch, double* workspace,
+                                               float* mean_std, int Z, int Y, int X, int bx, int by, int bz, int P, int M,
+                                               Seg3dNormalizers norms, void* stream) {
+  SEG3D_REQUIRE(volume && starts && batch && P > 0, "seg3d_patch_gather_normalize_mc: bad arguments");
+  SEG3D_REQUIRE(M >= 1 && M <= 8, "seg3d_patch_gather_normalize_mc: M = %d modalities, 1..8 are supported", M);
+  SEG3D_REQUIRE(bx > 0 && by > 0 && bz > 0 && bx <= X && by <= Y && bz <= Z,
+                "seg3d_patch_gather_normalize_mc: box (%d,%d,%d) does not fit volume (%d,%d,%d)", bx, by, bz, X, Y, Z);
+  Seg3dNormalizers nrm = {};
+  bool any_adaptive = false;
+  for (int m = 0; m < 8; ++m) {
+    Seg3dNormalizer n = {-1, 0.f, 1.f, 0, -1.f, 1.f};
+    if (m < M) {
+      n = norms.n[m];
+      if (n.type == 1) {
+        SEG3D_REQUIRE(n.clip_hi > n.clip_lo, "seg3d_patch_gather_normalize_mc: modality %d: empty clip range", m);
+        n.mean = 0.f;
+        n.stddev = 1.f;
+        n.clip = 1;
+        any_adaptive = true;
+      } else if (n.type == 0) {
+        SEG3D_REQUIRE(n.stddev > 0.f, "seg3d_patch_gather_normalize_mc: modality %d: stddev must be positive", m);
+        n.clip = n.clip ? 1 : 0;
+      } else if (n.type == -1) {
+        n = Seg3dNormalizer{-1, 0.f, 1.f, 0, -1.f, 1.f};
+      } else {
+        SEG3D_UNSUPPORTED("seg3d_patch_gather_normalize_mc: modality %d: unsupported normalization type %d", m, n.type);
+      }
+    }
+    nrm.n[m] = n;
+  }
+  SEG3D_REQUIRE(!any_adaptive || (workspace && mean_std),
+                "seg3d_patch_gather_normalize_mc: adaptive normaliser needs workspace and mean_std");
+  hipStream_t s = (hipStream_t)stream;
+  const bool vec4 = M == 4 && ((uintptr_t)volume & 15) == 0 && ((uintptr_t)batch & 15) == 0;
+  const bool vec2 = M == 2 && ((uintptr_t)volume & 7) == 0 && ((uintptr_t)batch & 7) == 0;
+  if (vec4) return patch_gather_normalize_mc_launch<4, true>(volume, starts, batch, workspace, mean_std, M, Y, X, bx, by, bz, P, nrm, any_adaptive, s);
+  if (M == 4) return patch_gather_normalize_mc_launch<4, false>(volume, starts, batch, workspace, mean_std, M, Y, X, bx, by, bz, P, nrm, any_adaptive, s);
+  if (vec2) return patch_gather_normalize_mc_launch<2, true>(volume, starts, batch, workspace, mean_std, M, Y, X, bx, by, bz, P, nrm, any_adaptive, s);
+  if (M == 2) return patch_gather_normalize_mc_launch<2, false>(volume, starts, batch, workspace, mean_std, M, Y, X, bx, by, bz, P, nrm, any_adaptive, s);
+  if (M == 3) return patch_gather_normalize_mc_launch<3, false>(volume, starts, batch, workspace, mean_std, M, Y, X, bx, by, bz, P, nrm, any_adaptive, s);
+  return patch_gather_normalize_mc_launch<0, false>(volume, starts, batch, workspace, mean_std, M, Y, X, bx, by, bz, P, nrm, any_adaptive, s);
+}
+
 // One thread per volume voxel of the batch's bounding box; patches are applied in list order so the float summation
 // order per voxel equals the reference's sequential loop (no atomics, reproducible).  The bounding box and the number
 // of valid patches come from a small DEVICE control block so that a captured hipGraph can be replayed for every

@@ -72,6 +72,136 @@ extern "C" int seg3d_resample_affine(const float* src, float* dst, int Xi, int Y
   return SEG3D_OK;
 }
 
+// ---- M co-registered channels in one pass (multi-modality training crops and inference resampling) ------------------
+// src [Zi][Yi][Xi][M] (channels-last), dst: voxel (x, y, z) of the output grid at dst + ((z * Yo + y) * Xo + x) * dst_stride,
+// M floats.  The affine coordinate, the inside test and the trilinear weights (or the NN index) are computed once per
+// output voxel; each of the 8 taps is one contiguous M-float row.  Per channel the arithmetic is resample_affine_kernel's
+// (double, same operation order, same clamping / padding), so channel m equals seg3d_resample_affine on plane m bit for
+// bit.  MC = 2, 3, 4: compile-time width (VEC: the rows are 8- / 16-byte aligned); MC = 0: runtime M <= 8.
+template <int MC>
+__device__ __forceinline__ void resample_mc_lerp(const float* t000, const float* t100, const float* t010, const float* t110,
+                                                 const float* t001, const float* t101, const float* t011, const float* t111,
+                                                 double dx, double dy, double dz, int m, float* out) {
+  const double v000 = t000[m], v100 = t100[m], v010 = t010[m], v110 = t110[m];
+  const double v001 = t001[m], v101 = t101[m], v011 = t011[m], v111 = t111[m];
+  const double a00 = v000 + (v100 - v000) * dx, a01 = v010 + (v110 - v010) * dx;
+  const double a10 = v001 + (v101 - v001) * dx, a11 = v011 + (v111 - v011) * dx;
+  const double b0 = a00 + (a01 - a00) * dy, b1 = a10 + (a11 - a10) * dy;
+  out[m] = (float)(b0 + (b1 - b0) * dz);
+}
+
+template <int MC, bool VEC>
+__global__ __launch_bounds__(256) void resample_affine_mc_kernel(const float* __restrict__ src, float* __restrict__ dst,
+                                                                   int Mrt, i64 dst_stride, int Xi, int Yi, int Zi, int Xo,
+                                                                   int Yo, int Zo, Affine12 A, int linear, float pad) {
+  constexpr int MR = MC > 0 ? MC : 8;          // register rows: MC, or the generic path's bound
+  const int M = MC > 0 ? MC : Mrt;
+  const i64 total = (i64)Xo * Yo * Zo;
+  for (i64 idx = (i64)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (i64)gridDim.x * 256) {
+    const int x = (int)(idx % Xo);
+    const i64 t = idx / Xo;
+    const int y = (int)(t % Yo), z = (int)(t / Yo);
+    const double cx = A.m[0] * x + A.m[1] * y + A.m[2] * z + A.m[3];
+    const double cy = A.m[4] * x + A.m[5] * y + A.m[6] * z + A.m[7];
+    const double cz = A.m[8] * x + A.m[9] * y + A.m[10] * z + A.m[11];
+    float out[MR];
+#pragma unroll
+    for (int m = 0; m < MR; ++m) out[m] = pad;
+    if (cx >= -0.5 && cx < Xi - 0.5 && cy >= -0.5 && cy < Yi - 0.5 && cz >= -0.5 && cz < Zi - 0.5) {
+      if (linear) {
+        const double fx = fmin(fmax(cx, 0.0), (double)(Xi - 1)), fy = fmin(fmax(cy, 0.0), (double)(Yi - 1)),
+                     fz = fmin(fmax(cz, 0.0), (double)(Zi - 1));
+        const int x0 = (int)floor(fx), y0 = (int)floor(fy), z0 = (int)floor(fz);
+        const int x1 = x0 + 1 < Xi ? x0 + 1 : x0, y1 = y0 + 1 < Yi ? y0 + 1 : y0, z1 = z0 + 1 < Zi ? z0 + 1 : z0;
+        const double dx = fx - x0, dy = fy - y0, dz = fz - z0;
+        const i64 r00 = ((i64)z0 * Yi + y0) * Xi, r01 = ((i64)z0 * Yi + y1) * Xi, r10 = ((i64)z1 * Yi + y0) * Xi,
+                  r11 = ((i64)z1 * Yi + y1) * Xi;
+        const float *p000 = src + (r00 + x0) * M, *p100 = src + (r00 + x1) * M, *p010 = src + (r01 + x0) * M,
+                    *p110 = src + (r01 + x1) * M, *p001 = src + (r10 + x0) * M, *p101 = src + (r10 + x1) * M,
+                    *p011 = src + (r11 + x0) * M, *p111 = src + (r11 + x1) * M;
+        if constexpr (MC > 0) {
+          float t000[MC], t100[MC], t010[MC], t110[MC], t001[MC], t101[MC], t011[MC], t111[MC];
+          mc_load_row<MC, VEC>(p000, t000);
+          mc_load_row<MC, VEC>(p100, t100);
+          mc_load_row<MC, VEC>(p010, t010);
+          mc_load_row<MC, VEC>(p110, t110);
+          mc_load_row<MC, VEC>(p001, t001);
+          mc_load_row<MC, VEC>(p101, t101);
+          mc_load_row<MC, VEC>(p011, t011);
+          mc_load_row<MC, VEC>(p111, t111);
+#pragma unroll
+          for (int m = 0; m < MC; ++m)
+            resample_mc_lerp<MC>(t000, t100, t010, t110, t001, t101, t011, t111, dx, dy, dz, m, out);
+        } else {
+#pragma unroll
+          for (int m = 0; m < MR; ++m)
+            if (m < M) resample_mc_lerp<MC>(p000, p100, p010, p110, p001, p101, p011, p111, dx, dy, dz, m, out);
+        }
+      } else {
+        int xn = (int)floor(cx + 0.5), yn = (int)floor(cy + 0.5), zn = (int)floor(cz + 0.5);
+        xn = xn < 0 ? 0 : (xn >= Xi ? Xi - 1 : xn);
+        yn = yn < 0 ? 0 : (yn >= Yi ? Yi - 1 : yn);
+        zn = zn < 0 ? 0 : (zn >= Zi ? Zi - 1 : zn);
+        const float* p = src + (((i64)zn * Yi + yn) * Xi + xn) * M;
+        if constexpr (MC > 0) {
+          mc_load_row<MC, VEC>(p, out);
+        } else {
+#pragma unroll
+          for (int m = 0; m < MR; ++m)
+            if (m < M) out[m] = p[m];
+        }
+      }
+    }
+    float* q = dst + idx * dst_stride;
+    if constexpr (MC > 0) {
+      mc_store_row<MC, VEC>(q, out);
+    } else {
+#pragma unroll
+      for (int m = 0; m < MR; ++m)
+        if (m < M) q[m] = out[m];
+    }
+  }
+}
+
+// src [Zi][Yi][Xi][M] -> rows of M floats at dst + voxel * dst_stride (dst_stride >= M floats); affine_host as above
+extern "C" int seg3d_resample_affine_mc(const float* src, float* dst, int M, long long dst_stride, int Xi, int Yi, int Zi,
+                                        int Xo, int Yo, int Zo, const double* affine_host, int linear, float pad,
+                                        void* stream) {
+  SEG3D_REQUIRE(src && dst && affine_host, "seg3d_resample_affine_mc: null pointer");
+  SEG3D_REQUIRE(M >= 1 && M <= 8, "seg3d_resample_affine_mc: M = %d channels, 1..8 are supported", M);
+  SEG3D_REQUIRE(dst_stride >= M, "seg3d_resample_affine_mc: voxel stride %lld below M = %d", dst_stride, M);
+  SEG3D_REQUIRE(Xi > 0 && Yi > 0 && Zi > 0 && Xo > 0 && Yo > 0 && Zo > 0, "seg3d_resample_affine_mc: bad dims");
+  Affine12 A;
+  for (int k = 0; k < 12; ++k) A.m[k] = affine_host[k];
+  const i64 total = (i64)Xo * Yo * Zo;
+  const dim3 grid(seg3d_ew_grid(total, 256)), block(256);
+  hipStream_t s = (hipStream_t)stream;
+  const int lin = linear ? 1 : 0;
+  // vector rows need the source base / destination base and stride aligned to the row width
+  const bool vec4 = M == 4 && ((uintptr_t)src & 15) == 0 && ((uintptr_t)dst & 15) == 0 && dst_stride % 4 == 0;
+  const bool vec2 = M == 2 && ((uintptr_t)src & 7) == 0 && ((uintptr_t)dst & 7) == 0 && dst_stride % 2 == 0;
+  if (vec4)
+    hipLaunchKernelGGL((resample_affine_mc_kernel<4, true>), grid, block, 0, s, src, dst, M, (i64)dst_stride, Xi, Yi, Zi, Xo,
+                       Yo, Zo, A, lin, pad);
+  else if (M == 4)
+    hipLaunchKernelGGL((resample_affine_mc_kernel<4, false>), grid, block, 0, s, src, dst, M, (i64)dst_stride, Xi, Yi, Zi,
+                       Xo, Yo, Zo, A, lin, pad);
+  else if (vec2)
+    hipLaunchKernelGGL((resample_affine_mc_kernel<2, true>), grid, block, 0, s, src, dst, M, (i64)dst_stride, Xi, Yi, Zi, Xo,
+                       Yo, Zo, A, lin, pad);
+  else if (M == 2)
+    hipLaunchKernelGGL((resample_affine_mc_kernel<2, false>), grid, block, 0, s, src, dst, M, (i64)dst_stride, Xi, Yi, Zi,
+                       Xo, Yo, Zo, A, lin, pad);
+  else if (M == 3)
+    hipLaunchKernelGGL((resample_affine_mc_kernel<3, false>), grid, block, 0, s, src, dst, M, (i64)dst_stride, Xi, Yi, Zi,
+                       Xo, Yo, Zo, A, lin, pad);
+  else
+    hipLaunchKernelGGL((resample_affine_mc_kernel<0, false>), grid, block, 0, s, src, dst, M, (i64)dst_stride, Xi, Yi, Zi,
+                       Xo, Yo, Zo, A, lin, pad);
+  SEG3D_LAUNCH_CHECK("seg3d_resample_affine_mc");
+  return SEG3D_OK;
+}
+
 // ---- bounding box -----------------------------------------------------------------------------------------------------
 struct LabelSet {
   int n;       // 0: every voxel > 0

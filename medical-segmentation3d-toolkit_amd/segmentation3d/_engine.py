@@ -15,6 +15,16 @@ LIB_PATH = os.environ.get('SEG3D_HIP_LIB', os.path.join(_PKG_ROOT, 'lib', 'libse
 
 _c_int, _c_ll, _c_f, _c_p = ctypes.c_int, ctypes.c_longlong, ctypes.c_float, ctypes.c_void_p
 
+
+class Normalizer(ctypes.Structure):
+    """Seg3dNormalizer of include/seg3d_hip.h: one modality's crop normaliser (type 0 fixed, 1 adaptive, -1 none)"""
+    _fields_ = [('type', _c_int), ('mean', _c_f), ('stddev', _c_f), ('clip', _c_int), ('clip_lo', _c_f), ('clip_hi', _c_f)]
+
+
+class Normalizers(ctypes.Structure):
+    """Seg3dNormalizers: up to 8 per-modality normalisers, passed BY VALUE to seg3d_patch_gather_normalize_mc"""
+    _fields_ = [('n', Normalizer * 8)]
+
 # name -> (restype, argtypes); keep in sync with include/seg3d_hip.h (tests/test_abi.py checks every symbol)
 _SIGNATURES = {
     'seg3d_last_error': (ctypes.c_char_p, []),
@@ -31,6 +41,7 @@ _SIGNATURES = {
     'seg3d_label_overlap_counts': (_c_int, [_c_p, _c_p, _c_int, _c_ll, _c_p, _c_int, _c_p, _c_p]),
     'seg3d_pack_weights_mfma_multi': (_c_int, [_c_p, _c_int, _c_ll, _c_p]),
     'seg3d_resample_affine': (_c_int, [_c_p, _c_p] + [_c_int] * 6 + [_c_p, _c_int, _c_f, _c_p]),
+    'seg3d_resample_affine_mc': (_c_int, [_c_p, _c_p, _c_int, _c_ll] + [_c_int] * 6 + [_c_p, _c_int, _c_f, _c_p]),
     'seg3d_mask_bounding_box': (_c_int, [_c_p, _c_int, _c_int, _c_int, _c_p, _c_int, _c_p, _c_p]),
     'seg3d_ccl_workspace_ints': (_c_ll, [_c_ll]),
     'seg3d_ccl26_select': (_c_int, [_c_p] + [_c_int] * 8 + [_c_p, _c_p, _c_p]),
@@ -138,6 +149,8 @@ _SIGNATURES = {
     'seg3d_adam_step_devstep': (_c_int, [_c_p] * 4 + [_c_ll, _c_p, _c_p] + [_c_f] * 6 + [_c_p]),
     'seg3d_patch_stats_blocks': (_c_ll, [_c_int] * 3),
     'seg3d_patch_gather_normalize': (_c_int, [_c_p] * 5 + [_c_int] * 8 + [_c_f, _c_f, _c_int, _c_f, _c_p]),
+    'seg3d_patch_stats_mc_doubles': (_c_ll, [_c_int] * 5),
+    'seg3d_patch_gather_normalize_mc': (_c_int, [_c_p] * 5 + [_c_int] * 8 + [Normalizers, _c_p]),
     'seg3d_patch_scatter_accumulate': (_c_int, [_c_p] * 5 + [_c_int] * 7 + [_c_ll, _c_p]),
     'seg3d_finalize_argmax': (_c_int, [_c_p, _c_p, _c_p, _c_int, _c_ll, _c_ll, _c_p]),
 }

@@ -24,6 +24,7 @@ import torch
 from segmentation3d import _engine as E
 from segmentation3d import _ops
 from segmentation3d.utils.image3d import Image3d
+from segmentation3d.utils import image_tools
 from segmentation3d.utils.image_tools import image_partition_by_fixed_size
 from segmentation3d.utils.model_io import get_checkpoint_folder, strip_module_prefix
 from segmentation3d.utils.normalizer import normalizer_from_dict
@@ -32,19 +33,23 @@ from segmentation3d.utils.normalizer import normalizer_from_dict
 class SlidingWindowBatcher(object):
     """device-side crop/normalise + accumulate for one resident volume.
 
-    :param volume: float32 device tensor [Z, Y, X]
+    :param volume: float32 device tensor [Z, Y, X], or [Z, Y, X, M] for M co-registered modalities (channels-last)
     :param starts: list of [x, y, z] patch start voxels (all patches share `box`)
     :param box: (bx, by, bz) patch size in voxels
     :param num_classes: C
-    :param normalizer: checkpoint-style dict {'type': 0|1, ...} or None (utils/normalizer.py:36-39,78-81)
+    :param normalizer: checkpoint-style dict {'type': 0|1, ...} or None (utils/normalizer.py:36-39,78-81); for a
+           [Z, Y, X, M] volume a list of M of them, one per modality
     """
 
     def __init__(self, volume, starts, box, num_classes, normalizer, max_batch=16):
         E.require_device(volume)
-        if volume.dim() != 3 or volume.dtype != torch.float32:
-            raise ValueError('volume must be a float32 [Z, Y, X] tensor')
+        if volume.dim() not in (3, 4) or volume.dtype != torch.float32:
+            raise ValueError('volume must be a float32 [Z, Y, X] or [Z, Y, X, M] tensor')
         self.volume = volume.contiguous()
-        self.Z, self.Y, self.X = (int(s) for s in volume.shape)
+        self.Z, self.Y, self.X = (int(s) for s in volume.shape[:3])
+        # M > 1: seg3d_patch_gather_normalize_mc, batches [P, bz, by, bx, M] handed out as [P, M, bz, by, bx] views
+        self.M = int(volume.shape[3]) if volume.dim() == 4 else 1
+        self.channels_last = volume.dim() == 4
         self.box = tuple(int(b) for b in box)
         self.C = int(num_classes)
         self.starts = [[int(v) for v in s] for s in starts]
@@ -53,7 +58,9 @@ class SlidingWindowBatcher(object):
             if s[0] < 0 or s[1] < 0 or s[2] < 0 or s[0] + bx > self.X or s[1] + by > self.Y or s[2] + bz > self.Z:
                 raise ValueError('patch {} with box {} leaves the volume {}'.format(s, self.box, (self.X, self.Y, self.Z)))
         self.normalizer = normalizer
-        if normalizer is None:
+        if self.channels_last:
+            self._norm_params = image_tools.normalizer_params(list(normalizer), self.M)
+        elif normalizer is None:
             self._norm = (-1, 0.0, 1.0, 0, 1.0)
         elif normalizer['type'] == 0:
             self._norm = (0, float(normalizer['mean']), float(normalizer['stddev']), int(bool(normalizer['clip'])), 1.0)
@@ -65,9 +72,14 @@ class SlidingWindowBatcher(object):
         self.acc = torch.zeros((self.C, self.Z, self.Y, self.X), dtype=torch.float32, device=dev)
         self.count = torch.zeros((self.Z, self.Y, self.X), dtype=torch.float32, device=dev)
         self.max_batch = int(max_batch)
-        nblk = E.query('seg3d_patch_stats_blocks', bx, by, bz)
-        self._stat_ws = torch.empty((self.max_batch * nblk * 2,), dtype=torch.float64, device=dev)
-        self._mean_std = torch.empty((self.max_batch, 2), dtype=torch.float32, device=dev)
+        if self.channels_last:
+            nws = E.query('seg3d_patch_stats_mc_doubles', bx, by, bz, self.max_batch, self.M)
+            self._stat_ws = torch.empty((nws,), dtype=torch.float64, device=dev)
+            self._mean_std = torch.empty((self.max_batch, self.M, 2), dtype=torch.float32, device=dev)
+        else:
+            nblk = E.query('seg3d_patch_stats_blocks', bx, by, bz)
+            self._stat_ws = torch.empty((self.max_batch * nblk * 2,), dtype=torch.float64, device=dev)
+            self._mean_std = torch.empty((self.max_batch, 2), dtype=torch.float32, device=dev)
         # control block on the device: [P][3] starts then {lo xyz, extent xyz, n_valid}
         self._ctl = torch.zeros((3 * self.max_batch + 7,), dtype=torch.int32, device=dev)
         self._plan = None
@@ -111,9 +123,20 @@ class SlidingWindowBatcher(object):
 
     # ---- kernels -----------------------------------------------------------------------------------------------------
     def gather_current(self, out=None):
-        """crop + normalise the max_batch patches described by the control block -> [P, 1, bz, by, bx]"""
+        """crop + normalise the max_batch patches described by the control block -> [P, 1, bz, by, bx]
+        ([P, M, bz, by, bx] view of NDHWC memory for a multi-modality volume)"""
         bx, by, bz = self.box
         P = self.max_batch
+        if self.channels_last:
+            if out is None:
+                out = torch.empty((P, bz, by, bx, self.M), dtype=torch.float32,
+                                  device=self.volume.device).permute(0, 4, 1, 2, 3)
+            elif tuple(out.shape) != (P, self.M, bz, by, bx) or not out.permute(0, 2, 3, 4, 1).is_contiguous():
+                raise ValueError('out must be the [P, M, bz, by, bx] view of a contiguous [P, bz, by, bx, M] batch')
+            E.call('seg3d_patch_gather_normalize_mc', E.ptr(self.volume), self._starts_ptr(), E.ptr(out),
+                   E.ptr(self._stat_ws), E.ptr(self._mean_std), self.Z, self.Y, self.X, bx, by, bz, P, self.M,
+                   self._norm_params, E.stream_ptr())
+            return out
         if out is None:
             out = torch.empty((P, 1, bz, by, bx), dtype=torch.float32, device=self.volume.device)
         ntype, mean, std, clip, sigma = self._norm
@@ -507,7 +530,7 @@ def load_single_model(model_folder, gpu_id=0):
     model.device = device
     model.spacing, model.max_stride, model.interpolation = state['spacing'], state['max_stride'], state['interpolation']
     model.in_channels, model.out_channels = state['in_channels'], state['out_channels']
-    model.crop_normalizers = [normalizer_from_dict(d) for d in state['crop_normalizers']]
+    model.crop_normalizers = [None if d is None else normalizer_from_dict(d) for d in state['crop_normalizers']]
     model.crop_normalizer_dicts = list(state['crop_normalizers'])
     return model
 
@@ -530,12 +553,44 @@ def load_models(model_folder, gpu_id=0):
     return models
 
 
+def _case_images(model, image, case=None):
+    """an Image3d, or a list of M co-registered Image3d -> (list of images, M); checks the frames and that the model
+    takes M input channels (ValueError naming the case)"""
+    images = list(image) if isinstance(image, (list, tuple)) else [image]
+    if not images or not all(isinstance(im, Image3d) for im in images):
+        raise ValueError('image must be an Image3d or a non-empty list of Image3d')
+    case = case if case is not None else 'with {} modalities'.format(len(images))
+    from segmentation3d.utils.image_io import check_modalities
+    check_modalities(images, case)
+    in_channels = model.get('in_channels') if hasattr(model, 'get') else None
+    if in_channels is not None and int(in_channels) != len(images):
+        raise ValueError('case {}: {} modalities but the model takes in_channels = {}'.format(case, len(images),
+                                                                                             in_channels))
+    return images, len(images)
+
+
+def _model_normalizers(model, M):
+    dicts = list(model['crop_normalizer_dicts'] or [])
+    if M == 1:
+        return dicts[0] if dicts else None
+    if len(dicts) != M:
+        raise ValueError('model has {} crop normalizers for {} modalities'.format(len(dicts), M))
+    return dicts
+
+
 def segmentation_voi(model, iso_image, start_voxel, end_voxel, use_gpu=True):
     """segment one volume of interest (reference: seg_infer.py:208-246); returns the list of per-class Image3d maps.
+    iso_image: an Image3d or a list of M co-registered Image3d (one per modality).
     Kept for API parity; whole volumes should go through segmentation_volume, which batches patches on the device."""
-    vol = torch.from_numpy(np.ascontiguousarray(iso_image.array, dtype=np.float32)).to(model['device'])
+    images, M = _case_images(model, iso_image)
+    iso_image = images[0]
+    if M == 1:
+        vol = torch.from_numpy(np.ascontiguousarray(iso_image.array, dtype=np.float32)).to(model['device'])
+    else:
+        with torch.cuda.device(model['device']):
+            vol = image_tools.images_to_device(images, model['device'])
     box = [int(end_voxel[d] - start_voxel[d]) for d in range(3)]
-    norm = model['crop_normalizer_dicts'][0] if model['crop_normalizer_dicts'] else None
+    norm = _model_normalizers(model, M)
     probs, _, _ = sliding_window_inference(model['net'], vol, [list(start_voxel)], box, model['out_channels'], norm,
                                            batch_size=1, use_graph=False)
     z0, y0, x0 = start_voxel[2], start_voxel[1], start_voxel[0]
@@ -566,15 +621,21 @@ def segmentation_volume(model, cfg, image, bbox_start_voxel, bbox_end_voxel, use
       resample the class probabilities back onto the image grid, padding 1.0 for class 0 and 0.0 otherwise (:330-333)
       arg-max -> int8 mask (:336-339); largest component / small-component removal (:342-348)
     `use_gpu` is kept for signature compatibility (the reference shrinks spacing / partitions on the CPU path only).
+    image: an Image3d, or a list of M co-registered Image3d (one per modality; the model must take in_channels = M):
+    the M modalities are resampled to the model grid in one launch (seg3d_resample_affine_mc) and every patch is
+    normalised with its modality's normaliser (seg3d_patch_gather_normalize_mc).
     Returns (mean_probs: list of Image3d, mask: Image3d int8).
     """
-    assert isinstance(image, Image3d)
+    images, M = _case_images(model, image)
     with torch.cuda.device(model['device']):
-        return _segmentation_volume(model, cfg, image, bbox_start_voxel, bbox_end_voxel, batch_size)
+        return _segmentation_volume(model, cfg, images[0] if M == 1 else images, bbox_start_voxel, bbox_end_voxel,
+                                    batch_size)
 
 
 def _segmentation_volume(model, cfg, image, bbox_start_voxel, bbox_end_voxel, batch_size):
-    from segmentation3d.utils import image_tools
+    images = image if isinstance(image, list) else None
+    if images is not None:
+        image = images[0]
     dev = model['device']
     ms = int(model['max_stride'])
     num_classes = int(model['out_channels'])
@@ -583,9 +644,14 @@ def _segmentation_volume(model, cfg, image, bbox_start_voxel, bbox_end_voxel, ba
     iso_frame = (spacing, image.GetOrigin(), image.GetDirection())
     X, Y, Z = image.GetSize()
     Xp, Yp, Zp = image_tools.resampled_size((X, Y, Z), image.GetSpacing(), spacing, ms)
-    src = torch.from_numpy(np.array(image.array, dtype=np.float32, order='C')).to(dev)
     interp = model.get('interpolation', 'LINEAR') or 'LINEAR'
-    vol = image_tools.resample_device(src, img_frame, (Xp, Yp, Zp), iso_frame, interp, 0.0)
+    if images is None:
+        src = torch.from_numpy(np.array(image.array, dtype=np.float32, order='C')).to(dev)
+        vol = image_tools.resample_device(src, img_frame, (Xp, Yp, Zp), iso_frame, interp, 0.0)
+    else:                       # all modalities to the model grid in one launch: [Zp, Yp, Xp, M]
+        src = image_tools.images_to_device(images, dev)
+        vol = image_tools.resample_device_mc(src, img_frame, (Xp, Yp, Zp), iso_frame, interp, 0.0)
+        del src
     if cfg.partition_type == 'DISABLE':
         starts, box = [[0, 0, 0]], (Xp, Yp, Zp)
     elif cfg.partition_type == 'SIZE':
@@ -602,7 +668,7 @@ def _segmentation_volume(model, cfg, image, bbox_start_voxel, bbox_end_voxel, ba
         box = tuple(ends[0][d] - starts[0][d] for d in range(3))
     else:
         raise ValueError('Unsupported partition type!')
-    norm = model['crop_normalizer_dicts'][0] if model['crop_normalizer_dicts'] else None
+    norm = _model_normalizers(model, 1 if images is None else len(images))
     probs, _, batcher = sliding_window_inference(model['net'], vol, starts, box, num_classes, norm,
                                                  batch_size=min(batch_size, max(1, len(starts))))
     # (voxels no patch covered -- bounding-box runs -- have count 0: their probabilities are 0 and the arg-max there is
@@ -630,8 +696,9 @@ _READABLE_SUFFIXES = ('.mha', '.mhd', '.nii', '.nii.gz')
 
 
 def read_test_txt(txt_file):
-    """single-modality list file: first line = number of cases, then `<case name> <image path>` per line
-    (reference: seg_infer.py:23-45)"""
+    """list file: first line = number of cases, then `<case name> <image path> [<path_1> ...]` per line (reference:
+    seg_infer.py:23-45 reads one path).  A case's entry is its path, or the list of its M paths when M files hold its
+    modalities (a single 4-D NIfTI path holds all of them)."""
     from segmentation3d.utils.file_io import readlines
     lines = readlines(txt_file)
     case_num = int(lines[0])
@@ -642,11 +709,26 @@ def read_test_txt(txt_file):
         parts = line.strip().split()
         if len(parts) < 2:
             raise ValueError('expected "<case name> <image path>", got: {}'.format(line))
-        if not os.path.isfile(parts[1]):
-            raise ValueError('image not exist: {}'.format(parts[1]))
+        for path in parts[1:]:
+            if not os.path.isfile(path):
+                raise ValueError('image not exist: {}'.format(path))
         names.append(parts[0])
-        paths.append(parts[1])
+        paths.append(parts[1] if len(parts) == 2 else parts[1:])
     return names, paths
+
+
+def read_case_images(entry, case):
+    """the images of one inference case: a 3-D file -> one Image3d (as the reference reads it); a 4-D NIfTI file or
+    several files -> the list of its M co-registered modalities (checked to share one grid)"""
+    from segmentation3d.utils.image_io import read_image, read_image_modalities, check_modalities
+    paths = [entry] if isinstance(entry, str) else list(entry)
+    images = []
+    for path in paths:
+        images += read_image_modalities(path) if len(paths) == 1 else [read_image(path)]
+    if len(images) == 1:
+        return images[0]
+    check_modalities(images, case)
+    return images
 
 
 def read_test_folder(folder_path):
@@ -673,9 +755,10 @@ def segmentation(input_path, model_folder, output_folder, seg_name, gpu_id, retu
                  save_prob):
     """volumetric image segmentation engine for image files (reference: seg_infer.py:353-493): single-scale
     ('coarse' / 'fine') or the coarse -> fine cascade ('DISABLE') through the coarse mask's bounding box.
-    input_path: a list file (.txt), one image file, or a folder of image files; results go to
-    `<output_folder>/<case name>/` with the reference's file names (seg_name, org.mha, mean_prob_<c>.mha)."""
-    from segmentation3d.utils.image_io import read_image, write_image
+    input_path: a list file (.txt, one or several co-registered modality paths per case), one image file, or a folder of
+    image files; a 4-D NIfTI file is one case of M modalities.  Results go to `<output_folder>/<case name>/` with the
+    reference's file names (seg_name, org.mha -- org_<m>.mha per modality when M > 1 --, mean_prob_<c>.mha)."""
+    from segmentation3d.utils.image_io import write_image
     begin = time.time()
     models = load_models(model_folder, gpu_id)
     load_model_time = time.time() - begin
@@ -692,9 +775,10 @@ def segmentation(input_path, model_folder, output_folder, seg_name, gpu_id, retu
             raise ValueError('Empty test folder!')
     else:
         raise ValueError('The file {} does not exist.'.format(input_path))
-    for path in paths:
-        if not path.endswith(_READABLE_SUFFIXES):
-            raise ValueError('Unsupported image format (MetaImage and NIfTI are read here): {}'.format(path))
+    for entry in paths:
+        for path in ([entry] if isinstance(entry, str) else entry):
+            if not path.endswith(_READABLE_SUFFIXES):
+                raise ValueError('Unsupported image format (MetaImage and NIfTI are read here): {}'.format(path))
     scale = models['infer_cfg'].general.single_scale
     if scale not in ('coarse', 'fine', 'DISABLE'):
         raise ValueError('Unsupported scale type!')
@@ -702,9 +786,12 @@ def segmentation(input_path, model_folder, output_folder, seg_name, gpu_id, retu
     for i, path in enumerate(paths):
         print('{}: {}'.format(i, path))
         begin = time.time()
-        image = read_image(path)
-        if image.array.dtype != np.float32:                                     # sitk.ReadImage(path, sitk.sitkFloat32)
-            image = image.like(image.array.astype(np.float32))
+        image = read_case_images(path, names[i])
+        modalities = image if isinstance(image, list) else [image]
+        for m, im in enumerate(modalities):
+            if im.array.dtype != np.float32:                                    # sitk.ReadImage(path, sitk.sitkFloat32)
+                modalities[m] = im.like(im.array.astype(np.float32))
+        image = modalities if len(modalities) > 1 else modalities[0]
         read_image_time = time.time() - begin
         begin = time.time()
         if scale == 'coarse':
@@ -737,7 +824,11 @@ def segmentation(input_path, model_folder, output_folder, seg_name, gpu_id, retu
         if save_mask:
             write_image(mask, os.path.join(output_folder, case, seg_name))
         if save_image:
-            write_image(image, os.path.join(output_folder, case, 'org.mha'))
+            if len(modalities) == 1:
+                write_image(image, os.path.join(output_folder, case, 'org.mha'))
+            else:
+                for m, im in enumerate(modalities):
+                    write_image(im, os.path.join(output_folder, case, 'org_{}.mha'.format(m)))
         if save_prob:
             for c, p in enumerate(mean_probs):
                 write_image(p, os.path.join(output_folder, case, 'mean_prob_{}.mha'.format(c)))

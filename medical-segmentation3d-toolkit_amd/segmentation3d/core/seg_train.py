@@ -163,7 +163,23 @@ def train(train_config_file, data_iter_factory=None):
     np.random.seed(cfg.general.seed)
     if cfg.general.num_gpus <= 0:
         raise RuntimeError('segmentation3d HIP engine needs general.num_gpus > 0 (no CPU training path)')
-    num_modality = int(getattr(cfg.dataset, 'num_modality', 1))
+    dataset = None
+    if data_iter_factory is None:
+        # the built-in dataset decides the number of input channels (core/seg_train.py:73: dataset.num_modality()); it
+        # reads only the list and the file headers here, the volumes are loaded on first use
+        from segmentation3d.dataloader.dataset import SegmentationDataset
+        dataset = SegmentationDataset(
+            imlist_file=cfg.general.imseg_list, num_classes=cfg.dataset.num_classes, spacing=cfg.dataset.spacing,
+            crop_size=cfg.dataset.crop_size, sampling_method=cfg.dataset.sampling_method,
+            random_translation=cfg.dataset.random_translation, random_scale=cfg.dataset.random_scale,
+            interpolation=cfg.dataset.interpolation, crop_normalizers=cfg.dataset.crop_normalizers, device=None)
+        num_modality = dataset.num_modality()
+        configured = getattr(cfg.dataset, 'num_modality', None)
+        if configured is not None and int(configured) != num_modality:
+            raise ValueError('cfg.dataset.num_modality = {} but the cases of {} have {} modalities'.format(
+                configured, cfg.general.imseg_list, num_modality))
+    else:
+        num_modality = int(getattr(cfg.dataset, 'num_modality', 1))
     _ops.set_activation_dtype(str(getattr(cfg.train, 'compute_dtype', 'fp32')))
     step = TrainStep(cfg.net.name, num_modality, cfg.dataset.num_classes, cfg.loss.name, cfg.loss.obj_weight,
                      cfg.loss.focal_gamma, cfg.train.lr, tuple(cfg.train.betas), seed=cfg.general.seed,
@@ -172,14 +188,10 @@ def train(train_config_file, data_iter_factory=None):
     last_save_epoch, batch_idx = 0, 0
     if cfg.general.resume_epoch >= 0:
         last_save_epoch, batch_idx = load_checkpoint(cfg.general.resume_epoch, step.net, step.opt, model_folder)
-    if data_iter_factory is None:
-        from segmentation3d.dataloader.dataset import SegmentationDataset, DeviceCropLoader
+    if dataset is not None:
+        from segmentation3d.dataloader.dataset import DeviceCropLoader
         from segmentation3d.dataloader.sampler import EpochConcateSampler, EpochConcateDistributedSampler
-        dataset = SegmentationDataset(
-            imlist_file=cfg.general.imseg_list, num_classes=cfg.dataset.num_classes, spacing=cfg.dataset.spacing,
-            crop_size=cfg.dataset.crop_size, sampling_method=cfg.dataset.sampling_method,
-            random_translation=cfg.dataset.random_translation, random_scale=cfg.dataset.random_scale,
-            interpolation=cfg.dataset.interpolation, crop_normalizers=cfg.dataset.crop_normalizers, device=step.device)
+        dataset.device = step.device
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
             sampler = EpochConcateDistributedSampler(dataset, cfg.train.epochs, max(0, cfg.general.resume_epoch))
         else:

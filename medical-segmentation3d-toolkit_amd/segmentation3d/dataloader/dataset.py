@@ -20,45 +20,115 @@ from segmentation3d import _engine as E
 from segmentation3d.utils.file_io import readlines
 from segmentation3d.utils.image3d import Image3d
 from segmentation3d.utils import image_tools
-from segmentation3d.utils.image_io import read_image
+from segmentation3d.utils.image_io import read_image, read_image_modalities, num_modalities, check_modalities
+
+
+def _is_4d_nifti(path):
+    return (path.endswith('.nii') or path.endswith('.nii.gz')) and os.path.isfile(path) and num_modalities(path) > 1
 
 
 def read_train_txt(imlist_file):
-    """single-modality txt list: first line = number of cases, then image path / mask path pairs (dataset.py:12-32)"""
+    """txt list (dataset.py:12-32): first line = `<number of cases>` or `<number of cases> <M>`, then per case M image
+    paths (one per line) and the mask path.  One 4-D NIfTI path may stand in for the M image paths.  A case's image entry
+    is a path, or the list of its M paths when M > 1 files hold its modalities; single-modality files give exactly the
+    reference's lists."""
     lines = readlines(imlist_file)
-    num_cases = int(lines[0])
-    if len(lines) - 1 < num_cases * 2:
+    head = lines[0].split()
+    num_cases = int(head[0])
+    num_mod = int(head[1]) if len(head) > 1 else 1
+    if num_mod < 1:
+        raise ValueError('{}: number of modalities must be positive, got {}'.format(imlist_file, num_mod))
+    if len(head) == 1 and len(lines) - 1 < num_cases * 2:
         raise ValueError('too few lines in imlist file')
     im_list, seg_list = [], []
+    pos = 1
     for i in range(num_cases):
-        im_path, seg_path = lines[1 + i * 2], lines[2 + i * 2]
-        assert os.path.isfile(im_path), 'image not exist: {}'.format(im_path)
+        if pos >= len(lines):
+            raise ValueError('too few lines in imlist file')
+        first = lines[pos]
+        if num_mod == 1 or _is_4d_nifti(first):
+            paths = [first]
+            if len(head) > 1 and case_modalities(first) != num_mod:
+                raise ValueError('case {}: {} holds {} modalities, the list declares {}'.format(
+                    i, first, case_modalities(first), num_mod))
+        else:
+            paths = lines[pos:pos + num_mod]
+        pos += len(paths)
+        if pos >= len(lines):
+            raise ValueError('too few lines in imlist file')
+        seg_path = lines[pos]
+        pos += 1
+        for im_path in paths:
+            assert os.path.isfile(im_path), 'image not exist: {}'.format(im_path)
         assert os.path.isfile(seg_path), 'mask not exist: {}'.format(seg_path)
-        im_list.append(im_path)
+        im_list.append(paths[0] if len(paths) == 1 else paths)
         seg_list.append(seg_path)
     return im_list, seg_list
 
 
+def _modality_columns(columns):
+    """image_path, image_path_1, ... image_path_{M-1} in modality order"""
+    cols = ['image_path']
+    while 'image_path_{}'.format(len(cols)) in columns:
+        cols.append('image_path_{}'.format(len(cols)))
+    return cols
+
+
 def read_train_csv(imlist_file, mode='train'):
-    """csv list with columns image_name, image_path (, mask_path) (dataset.py:35-52)"""
+    """csv list with columns image_name, image_path (, image_path_1 ... image_path_{M-1}) (, mask_path)
+    (dataset.py:35-52); with more than one image column a case's image entry is the list of its M paths"""
     images_df = pd.read_csv(imlist_file)
+    cols = _modality_columns(images_df.columns)
+    if len(cols) == 1:
+        image_paths = images_df['image_path'].tolist()
+    else:
+        image_paths = [list(row) for row in images_df[cols].itertuples(index=False, name=None)]
     if mode == 'test':
-        return images_df['image_name'].tolist(), images_df['image_path'].tolist()
+        return images_df['image_name'].tolist(), image_paths
     if mode in ('train', 'validation'):
-        return images_df['image_path'].tolist(), images_df['mask_path'].tolist()
+        return image_paths, images_df['mask_path'].tolist()
     raise ValueError('Unsupported mode type.')
 
 
+def case_modalities(entry):
+    """number of modalities of a case's image entry (a path or a list of paths) from the file headers alone"""
+    paths = [entry] if isinstance(entry, str) else list(entry)
+    if len(paths) == 1:
+        return num_modalities(paths[0])
+    for path in paths:
+        if num_modalities(path) != 1:
+            raise ValueError('{}: a 4-D file stands in for all modalities of a case, not one of several'.format(path))
+    return len(paths)
+
+
+def read_case_modalities(entry, case):
+    """list of M Image3d of one case (one 4-D NIfTI or M 3-D files), checked to share one grid"""
+    paths = [entry] if isinstance(entry, str) else list(entry)
+    images = []
+    for path in paths:
+        images += read_image_modalities(path)
+    check_modalities(images, case)
+    return images
+
+
 class _Case(object):
-    """one image / mask pair resident on the device, plus the host-side per-slice label histogram that lets MASK
-    sampling pick the k-th voxel of a label (in np.argwhere order) without scanning the volume"""
+    """one case resident on the device, plus the host-side per-slice label histogram that lets MASK sampling pick the k-th
+    voxel of a label (in np.argwhere order) without scanning the volume.  `image` is one modality as a [Z, Y, X] tensor,
+    or a list of M co-registered modalities, kept as ONE channels-last [Z, Y, X, M] fp32 tensor (a BraTS case of
+    240 x 240 x 155 x 4 is 143 MB resident); the mask and the histogram are the same for any M."""
 
     def __init__(self, image, seg, device):
+        images = image if isinstance(image, (list, tuple)) else [image]
+        image = images[0]
+        self.num_modality = len(images)
         self.frame = (image.GetSpacing(), image.GetOrigin(), image.GetDirection())
         self.seg_frame = (seg.GetSpacing(), seg.GetOrigin(), seg.GetDirection())
         self.size = image.GetSize()
         self.seg_size = seg.GetSize()
-        self.image = torch.from_numpy(np.array(image.array, dtype=np.float32, order='C')).to(device)
+        if self.num_modality == 1:
+            self.image = torch.from_numpy(np.array(image.array, dtype=np.float32, order='C')).to(device)
+        else:
+            self.image = image_tools.images_to_device(images, device)       # [Z, Y, X, M]
         self.seg_host = np.array(seg.array, order='C')                       # [z, y, x], label values as stored
         self.seg = torch.from_numpy(self.seg_host.astype(np.float32)).to(device)
         self._slice_counts = {}
@@ -107,6 +177,23 @@ class SegmentationDataset(Dataset):
         assert self.interpolation in ('LINEAR', 'NN'), 'interpolation must either be a LINEAR or NN'
         self.crop_normalizers = crop_normalizers
         assert isinstance(self.crop_normalizers, list), 'crop normalizers must be a list'
+        # modalities per case from the list and the file headers (no volume is read here): every case must have the same M,
+        # and there is one normaliser per modality (None: no normalisation, dataset.py:202)
+        self._num_modality = 1
+        for k, entry in enumerate(self.im_list):
+            m = case_modalities(entry)
+            if k == 0:
+                self._num_modality = m
+            elif m != self._num_modality:
+                raise ValueError('case {}: {} modalities, case {} has {}'.format(self.case_name(k), m, self.case_name(0),
+                                                                                 self._num_modality))
+        if not 1 <= self._num_modality <= 8:
+            raise ValueError('case {}: {} modalities, 1..8 are supported'.format(self.case_name(0), self._num_modality))
+        if self._num_modality > 1:
+            if len(self.crop_normalizers) != self._num_modality:
+                raise ValueError('case {}: {} modalities but {} crop normalizers (one per modality, None for none)'.format(
+                    self.case_name(0), self._num_modality, len(self.crop_normalizers)))
+            self._norm_params = image_tools.normalizer_params(self.crop_normalizers, self._num_modality)
         self.device = device if device is not None else torch.device('cuda', torch.cuda.current_device())
         self._cases = {}
 
@@ -114,13 +201,22 @@ class SegmentationDataset(Dataset):
         return len(self.im_list)
 
     def num_modality(self):
-        return 1
+        return self._num_modality
+
+    def case_name(self, index):
+        entry = self.im_list[index]
+        image_path = entry if isinstance(entry, str) else entry[0]
+        return os.path.basename(os.path.dirname(image_path)) + '_' + os.path.basename(image_path)
 
     # ---- resident volumes --------------------------------------------------------------------------------------------
     def case(self, index):
         c = self._cases.get(index)
         if c is None:
-            c = _Case(read_image(self.im_list[index]), read_image(self.seg_list[index], dtype=None), self.device)
+            if self._num_modality == 1:
+                image = read_image(self.im_list[index])
+            else:
+                image = read_case_modalities(self.im_list[index], self.case_name(index))
+            c = _Case(image, read_image(self.seg_list[index], dtype=None), self.device)
             self._cases[index] = c
         return c
 
@@ -168,18 +264,30 @@ class SegmentationDataset(Dataset):
 
     # ---- the sample ---------------------------------------------------------------------------------------------------
     def __getitem__(self, index):
-        """-> (image crop [1, z, y, x], mask crop [1, z, y, x] float labels, frame (15 floats), case name); device tensors"""
+        """-> (image crop [M, z, y, x], mask crop [1, z, y, x] float labels, frame (15 floats), case name); device tensors.
+        For M > 1 the image crop is a view of channels-last [z, y, x, M] memory (what the stem reads, without a copy)."""
+        return self.sample(index)
+
+    def sample(self, index, out=None):
+        """__getitem__; for M > 1 `out` may be a contiguous [z, y, x, M] destination (a slot of an NDHWC batch) into which
+        the crop is resampled (one launch for all modalities) and normalised in place (one launch)"""
         case = self.case(index)
-        image_path = self.im_list[index]
-        case_name = os.path.basename(os.path.dirname(image_path)) + '_' + os.path.basename(image_path)
+        case_name = self.case_name(index)
         center, crop_spacing = self.sample_crop_geometry(index)
-        im = image_tools.crop_image_device(case.image, case.frame, center, self.crop_size, crop_spacing, self.interpolation)
-        if self.crop_normalizers[0] is not None:
-            im = image_tools.normalize_crop_device(im, self.crop_normalizers[0])
+        if self._num_modality == 1:
+            im = image_tools.crop_image_device(case.image, case.frame, center, self.crop_size, crop_spacing,
+                                               self.interpolation)
+            if self.crop_normalizers[0] is not None:
+                im = image_tools.normalize_crop_device(im, self.crop_normalizers[0])
+            im = im.unsqueeze(0)
+        else:
+            im = image_tools.crop_image_device_mc(case.image, case.frame, center, self.crop_size, crop_spacing,
+                                                  self.interpolation, out=out)
+            im = image_tools.normalize_crop_device_mc(im, self._norm_params, out=im).permute(3, 0, 1, 2)
         seg = image_tools.crop_image_device(case.seg, case.seg_frame, center, self.crop_size, crop_spacing, 'NN')
         origin = image_tools.crop_origin(center, self.crop_size, crop_spacing)
         frame = np.array(list(crop_spacing) + list(origin) + list(case.seg_frame[2]), dtype=np.float32)
-        return im.unsqueeze(0), seg.unsqueeze(0), frame, case_name
+        return im, seg.unsqueeze(0), frame, case_name
 
 
 class DeviceCropLoader(object):
@@ -194,6 +302,9 @@ class DeviceCropLoader(object):
         return n // self.batch_size if self.drop_last else (n + self.batch_size - 1) // self.batch_size
 
     def __iter__(self):
+        if self.dataset.num_modality() > 1:
+            yield from self._iter_channels_last()
+            return
         ims, segs, frames, names = [], [], [], []
         for index in self.sampler:
             im, seg, frame, name = self.dataset[index]
@@ -206,3 +317,22 @@ class DeviceCropLoader(object):
                 ims, segs, frames, names = [], [], [], []
         if ims and not self.drop_last:
             yield torch.stack(ims), torch.stack(segs), np.stack(frames), names
+
+    def _iter_channels_last(self):
+        """M > 1: every sample is resampled straight into slot b of a fresh [B, z, y, x, M] batch (no stack, no layout
+        kernel); the batch is handed out as its [B, M, z, y, x] view"""
+        M = self.dataset.num_modality()
+        cz, cy, cx = (int(v) for v in self.dataset.crop_size[::-1])
+        batch, segs, frames, names = None, [], [], []
+        for index in self.sampler:
+            if batch is None:
+                batch = torch.empty((self.batch_size, cz, cy, cx, M), dtype=torch.float32, device=self.dataset.device)
+            _, seg, frame, name = self.dataset.sample(index, out=batch[len(segs)])
+            segs.append(seg)
+            frames.append(frame)
+            names.append(name)
+            if len(segs) == self.batch_size:
+                yield batch.permute(0, 4, 1, 2, 3), torch.stack(segs), np.stack(frames), names
+                batch, segs, frames, names = None, [], [], []
+        if segs and not self.drop_last:
+            yield batch[:len(segs)].permute(0, 4, 1, 2, 3), torch.stack(segs), np.stack(frames), names

@@ -33,16 +33,39 @@ def _quaternion_rotation(b, c, d):
                      [2 * (b * d - a * c), 2 * (c * d + a * b), a * a + d * d - b * b - c * c]])
 
 
-def read_nifti(path, dtype=np.float32):
-    opener = gzip.open if path.endswith('.gz') else open
-    with opener(path, 'rb') as f:
-        raw = f.read()
+def _nifti_byte_order(raw, path):
     end = '<' if struct.unpack('<i', raw[:4])[0] == 348 else '>'
     if struct.unpack(end + 'i', raw[:4])[0] != 348:
         raise ValueError('{}: not a NIfTI-1 file'.format(path))
+    return end
+
+
+def nifti_num_modalities(path):
+    """M of a NIfTI file from its header alone: dim[4] of a 4-D file (dim[0] == 4), else 1"""
+    opener = gzip.open if path.endswith('.gz') else open
+    with opener(path, 'rb') as f:
+        raw = f.read(56)
+    end = _nifti_byte_order(raw, path)
     dim = struct.unpack(end + '8h', raw[40:56])
-    if dim[0] < 3 or any(d > 1 for d in dim[4:1 + dim[0]]):
-        raise ValueError('{}: only 3-D scalar volumes are supported (dim = {})'.format(path, dim))
+    return max(1, int(dim[4])) if dim[0] == 4 else 1
+
+
+def read_nifti(path, dtype=np.float32):
+    return _read_nifti(path, dtype, False)[0]
+
+
+def _read_nifti(path, dtype, four_d):
+    """list of Image3d: one for a 3-D file; with four_d, one per volume of a 4-D file (dim[0] == 4, dim[4] = M, the
+    Medical Segmentation Decathlon's layout of co-registered modalities), all sharing the file's frame"""
+    opener = gzip.open if path.endswith('.gz') else open
+    with opener(path, 'rb') as f:
+        raw = f.read()
+    end = _nifti_byte_order(raw, path)
+    dim = struct.unpack(end + '8h', raw[40:56])
+    nt = int(dim[4]) if four_d and dim[0] == 4 and dim[4] > 1 else 1
+    if dim[0] < 3 or any(d > 1 for d in dim[4 + (nt > 1):1 + dim[0]]):
+        raise ValueError('{}: only 3-D scalar volumes{} are supported (dim = {})'.format(
+            path, ' and 4-D stacks of them' if four_d else '', dim))
     datatype = struct.unpack(end + 'h', raw[70:72])[0]
     if datatype not in _NIFTI_TYPES:
         raise ValueError('{}: unsupported NIfTI datatype {}'.format(path, datatype))
@@ -52,7 +75,7 @@ def read_nifti(path, dtype=np.float32):
     qform_code, sform_code = struct.unpack(end + '2h', raw[252:256])
     nx, ny, nz = dim[1:4]
     et = np.dtype(_NIFTI_TYPES[datatype]).newbyteorder(end)
-    data = np.frombuffer(raw, dtype=et, count=nx * ny * nz, offset=max(vox_offset, 352)).reshape(nz, ny, nx)
+    data = np.frombuffer(raw, dtype=et, count=nx * ny * nz * nt, offset=max(vox_offset, 352)).reshape(nt, nz, ny, nx)
     if slope not in (0.0, 1.0) or inter != 0.0:
         data = data.astype(np.float64) * (slope if slope != 0.0 else 1.0) + inter
     array = np.array(data, dtype=dtype if dtype is not None else data.dtype.newbyteorder('='), order='C')
@@ -71,7 +94,8 @@ def read_nifti(path, dtype=np.float32):
     else:
         direction, offset = np.eye(3), np.zeros(3)
     lps = np.diag([-1.0, -1.0, 1.0])            # RAS (NIfTI) -> LPS (ITK)
-    return Image3d(array, spacing.tolist(), (lps @ offset).tolist(), (lps @ direction).ravel().tolist())
+    frame = (spacing.tolist(), (lps @ offset).tolist(), (lps @ direction).ravel().tolist())
+    return [Image3d(np.ascontiguousarray(array[t]), *frame) for t in range(nt)]
 
 
 def write_nifti(image, path):
@@ -108,6 +132,36 @@ def read_image(path, dtype=np.float32):
     if path.endswith('.mha') or path.endswith('.mhd'):
         return read_mha(path, dtype)
     raise ValueError('unsupported image format: {} (MetaImage .mha/.mhd and NIfTI .nii/.nii.gz are supported)'.format(path))
+
+
+def read_image_modalities(path, dtype=np.float32):
+    """list of Image3d, one per modality: a 4-D NIfTI file (dim[0] == 4, dim[4] = M) gives its M volumes, sharing the
+    file's frame; a 3-D file gives a list of one.  MetaImage files stay 3-D."""
+    if _is_nifti(path):
+        return _read_nifti(path, dtype, True)
+    return [read_image(path, dtype)]
+
+
+def num_modalities(path):
+    """M of an image file from its header: dim[4] of a 4-D NIfTI, else 1"""
+    return nifti_num_modalities(path) if _is_nifti(path) else 1
+
+
+def check_modalities(images, case):
+    """the modalities of a case must share size, spacing, origin and direction (relative tolerance 1e-6): there is no
+    resampling of one modality onto another.  Raises ValueError naming the case."""
+    ref = images[0]
+    for m, im in enumerate(images[1:], 1):
+        if tuple(im.GetSize()) != tuple(ref.GetSize()):
+            raise ValueError('case {}: modality {} has size {}, modality 0 has {}'.format(case, m, im.GetSize(),
+                                                                                           ref.GetSize()))
+        for what in ('GetSpacing', 'GetOrigin', 'GetDirection'):
+            a = np.asarray(getattr(im, what)(), dtype=np.float64)
+            b = np.asarray(getattr(ref, what)(), dtype=np.float64)
+            scale = max(1.0, float(np.abs(b).max()))
+            if np.abs(a - b).max() > 1e-6 * scale:
+                raise ValueError('case {}: modality {} {} {} differs from modality 0 ({}); the modalities of a case must '
+                                 'be co-registered on one grid'.format(case, m, what[3:].lower(), tuple(a), tuple(b)))
 
 
 def write_image(image, path):

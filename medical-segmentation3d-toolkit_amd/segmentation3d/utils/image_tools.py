@@ -120,6 +120,69 @@ def resample_device(src, src_frame, out_size, dst_frame, interp_method, padding_
     return dst
 
 
+def resample_device_mc(src, src_frame, out_size, dst_frame, interp_method, padding_value=0.0, out=None):
+    """M co-registered channels in one launch: src float32 device tensor [Z, Y, X, M] (channels-last) -> [Zo, Yo, Xo, M].
+    `out`: a contiguous [Zo, Yo, Xo, M] destination, e.g. slot b of an NDHWC batch.  Channel m equals resample_device
+    on src[..., m] bit for bit (seg3d_resample_affine_mc)."""
+    if interp_method not in ('LINEAR', 'NN'):
+        raise ValueError('Unsupported interpolation type.')
+    E.require_device(src)
+    if src.dim() != 4 or src.dtype != torch.float32:
+        raise ValueError('src must be a float32 [Z, Y, X, M] tensor')
+    src = src.contiguous()
+    Zi, Yi, Xi, M = src.shape
+    Xo, Yo, Zo = (int(v) for v in out_size)
+    if out is None:
+        out = torch.empty((Zo, Yo, Xo, M), dtype=torch.float32, device=src.device)
+    elif tuple(out.shape) != (Zo, Yo, Xo, M) or not out.is_contiguous() or out.dtype != torch.float32:
+        raise ValueError('out must be a contiguous float32 [{}, {}, {}, {}] tensor'.format(Zo, Yo, Xo, M))
+    M_ = np.ascontiguousarray(index_affine(src_frame, dst_frame), dtype=np.float64)
+    E.call('seg3d_resample_affine_mc', E.ptr(src), E.ptr(out), int(M), int(M), Xi, Yi, Zi, Xo, Yo, Zo,
+           M_.ctypes.data_as(ctypes.c_void_p), int(interp_method == 'LINEAR'), float(padding_value), E.stream_ptr())
+    return out
+
+
+def planar_to_channels_last(planes):
+    """[M, Z, Y, X] float32 device tensor -> [Z, Y, X, M] (seg3d_ncdhw_to_ndhwc with N = 1, C = M)"""
+    E.require_device(planes)
+    planes = planes.contiguous()
+    M, Z, Y, X = planes.shape
+    out = torch.empty((Z, Y, X, M), dtype=torch.float32, device=planes.device)
+    E.call('seg3d_ncdhw_to_ndhwc', E.ptr(planes), E.ptr(out), 1, int(M), Z * Y * X, E.stream_ptr())
+    return out
+
+
+def images_to_device(images, device):
+    """list of M co-registered Image3d -> resident float32 [Z, Y, X, M] device tensor"""
+    planes = np.stack([np.asarray(im.array, dtype=np.float32) for im in images], 0)
+    return planar_to_channels_last(torch.from_numpy(planes).to(device))
+
+
+def normalizer_params(normalizers, num_modality):
+    """per-modality normalisers (objects with to_dict(), checkpoint dicts, or None = no normalisation) -> the
+    Seg3dNormalizers struct passed by value to seg3d_patch_gather_normalize_mc"""
+    if len(normalizers) != num_modality:
+        raise ValueError('{} crop normalizers for {} modalities: one normalizer per modality'.format(
+            len(normalizers), num_modality))
+    params = E.Normalizers()
+    for m in range(8):
+        n = params.n[m]
+        d = None if m >= num_modality or normalizers[m] is None else normalizers[m]
+        if d is not None and hasattr(d, 'to_dict'):
+            d = d.to_dict()
+        if d is None:
+            n.type, n.mean, n.stddev, n.clip, n.clip_lo, n.clip_hi = -1, 0.0, 1.0, 0, -1.0, 1.0
+        elif d['type'] == 0:
+            n.type, n.mean, n.stddev, n.clip, n.clip_lo, n.clip_hi = 0, float(d['mean']), float(d['stddev']), \
+                int(bool(d['clip'])), -1.0, 1.0
+        elif d['type'] == 1:
+            sigma = float(d['clip_sigma'])
+            n.type, n.mean, n.stddev, n.clip, n.clip_lo, n.clip_hi = 1, 0.0, 1.0, 1, -sigma, sigma
+        else:
+            raise ValueError('Unsupported normalization type.')
+    return params
+
+
 def _frame(image):
     return (image.GetSpacing(), image.GetOrigin(), image.GetDirection())
 
@@ -261,6 +324,32 @@ def normalize_crop_device(crop, normalizer):
     E.call('seg3d_patch_gather_normalize', E.ptr(crop), E.ptr(starts), E.ptr(out), E.ptr(ws), E.ptr(mean_std), bz, by, bx,
            bx, by, bz, 1, ntype, mean, std, clip, sigma, E.stream_ptr())
     return out[0, 0]
+
+
+def crop_image_device_mc(volume, frame, cropping_center, cropping_size, cropping_spacing, interp_method, out=None):
+    """crop_image_device for a channels-last [Z, Y, X, M] volume: one launch for all modalities -> [z, y, x, M]"""
+    size = [int(cropping_size[idx]) for idx in range(3)]
+    spacing = [float(cropping_spacing[idx]) for idx in range(3)]
+    dst_frame = (spacing, crop_origin(cropping_center, size, spacing), frame[2])
+    return resample_device_mc(volume, frame, size, dst_frame, interp_method, 0.0, out=out)
+
+
+def normalize_crop_device_mc(crop, params, out=None):
+    """per-modality normalisation of a channels-last device crop [z, y, x, M] with the multi-modality patch kernel
+    (P = 1, start 0); `params` from normalizer_params.  out may be `crop` itself (in place)."""
+    E.require_device(crop)
+    if not crop.is_contiguous():
+        raise ValueError('crop must be contiguous [z, y, x, M]')
+    bz, by, bx, M = crop.shape
+    dev = crop.device
+    if out is None:
+        out = torch.empty_like(crop)
+    starts = torch.zeros((1, 3), dtype=torch.int32, device=dev)
+    ws = torch.empty((E.query('seg3d_patch_stats_mc_doubles', bx, by, bz, 1, M),), dtype=torch.float64, device=dev)
+    mean_std = torch.empty((M, 2), dtype=torch.float32, device=dev)
+    E.call('seg3d_patch_gather_normalize_mc', E.ptr(crop), E.ptr(starts), E.ptr(out), E.ptr(ws), E.ptr(mean_std), bz, by,
+           bx, bx, by, bz, 1, int(M), params, E.stream_ptr())
+    return out
 
 
 def get_image_frame(image):

@@ -51,7 +51,7 @@ def checkpoint_state(net, epoch_idx, batch_idx, cfg, max_stride, num_modality):
     geometry = {'spacing': cfg.dataset.spacing, 'interpolation': cfg.dataset.interpolation, 'max_stride': max_stride}
     channels = {'in_channels': num_modality, 'out_channels': cfg.dataset.num_classes}
     state = {'epoch': epoch_idx, 'batch': batch_idx, 'net': cfg.net.name, 'state_dict': weights,
-             'crop_normalizers': [n.to_dict() for n in cfg.dataset.crop_normalizers]}
+             'crop_normalizers': [None if n is None else n.to_dict() for n in cfg.dataset.crop_normalizers]}
     state.update(geometry)
     state.update(channels)
     return state
