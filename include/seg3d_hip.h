@@ -377,6 +377,25 @@ int seg3d_finalize_argmax(float* acc, const float* count, signed char* mask, int
 int seg3d_label_overlap_counts(const void* gt, const void* seg, int dtype, long long n, const int* labels_host, int nlabels,
                                unsigned long long* counts, void* stream);
 
+/* ---- surface-distance metrics: HD, HD95, ASSD of one label --------------------------------
+ * seg3d_label_surface: surface[i] = 1 on the voxels of (labels == label) that have a 6-neighbour outside the label
+ * (voxels outside the volume count as outside), else 0, over an X x Y x Z volume ([Z][Y][X], < 2^31 voxels, dtype as
+ * above).  box_device[6] = inclusive (xmin, ymin, zmin, xmax, ymax, zmax), initialised by the caller to
+ * {INT_MAX x3, -1 x3}, is widened to the surface voxels; count_device[0] += their number.  Call it for the ground truth
+ * and the segmentation with ONE box: it then encloses both surfaces.
+ * seg3d_surface_distance: for every voxel of query_surface inside the box, the squared Euclidean distance (physical
+ * units, spacing (sx, sy, sz)) from its centre to the nearest centre of a feature_surface voxel, by an exact separable
+ * EDT over the box only.  The squared distances go compacted, in no fixed order, to dist2_out[0 .. capacity) with the
+ * linear voxel index in index_out (may be NULL); stats[3] = (count, max distance, sum of distances), the sum in fp64 and
+ * reduced in a fixed order.  Squared distances are exact for unit spacing.  workspace:
+ * seg3d_surface_distance_workspace_bytes (-1: bad size); no host sync, no allocation (capturable). */
+int seg3d_label_surface(const void* labels, int dtype, int X, int Y, int Z, int label, unsigned char* surface,
+                        int* box_device, int* count_device, void* stream);
+long long seg3d_surface_distance_workspace_bytes(int X, int Y, int Z);
+int seg3d_surface_distance(const unsigned char* feature_surface, const unsigned char* query_surface, int X, int Y, int Z,
+                           const int* box_device, double sx, double sy, double sz, void* workspace, double* dist2_out,
+                           int* index_out, long long capacity, double* stats, void* stream);
+
 /* ---- pre/post-processing around the patch path: utils/image_tools.py:329-432, 481-510 ----------
  * resample: dst[z][y][x] (Xo, Yo, Zo) = src sampled at the continuous index c = M * (x, y, z, 1), M = 12 doubles on the
  * HOST (row-major 3 x 4); ITK semantics: inside iff -0.5 <= c < size - 0.5, else `pad`; linear (clamped 8-neighbourhood)

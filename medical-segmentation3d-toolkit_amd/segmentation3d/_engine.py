@@ -39,6 +39,10 @@ _SIGNATURES = {
     'seg3d_packed_mfma_floats': (_c_ll, [_c_int, _c_int, _c_int]),
     'seg3d_pack_job_blocks': (_c_ll, [_c_int, _c_int, _c_int]),
     'seg3d_label_overlap_counts': (_c_int, [_c_p, _c_p, _c_int, _c_ll, _c_p, _c_int, _c_p, _c_p]),
+    'seg3d_label_surface': (_c_int, [_c_p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_p, _c_p, _c_p, _c_p]),
+    'seg3d_surface_distance_workspace_bytes': (_c_ll, [_c_int] * 3),
+    'seg3d_surface_distance': (_c_int, [_c_p, _c_p] + [_c_int] * 3 + [_c_p] + [ctypes.c_double] * 3
+                               + [_c_p, _c_p, _c_p, _c_ll, _c_p, _c_p]),
     'seg3d_pack_weights_mfma_multi': (_c_int, [_c_p, _c_int, _c_ll, _c_p]),
     'seg3d_resample_affine': (_c_int, [_c_p, _c_p] + [_c_int] * 6 + [_c_p, _c_int, _c_f, _c_p]),
     'seg3d_resample_affine_mc': (_c_int, [_c_p, _c_p, _c_int, _c_ll] + [_c_int] * 6 + [_c_p, _c_int, _c_f, _c_p]),
