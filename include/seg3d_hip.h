@@ -370,6 +370,29 @@ int seg3d_patch_scatter_accumulate(const float* probs, const int* starts_xyz, co
                                    long long max_box_voxels, void* stream);
 int seg3d_finalize_argmax(float* acc, const float* count, signed char* mask, int C, long long voxels,
                           long long class_stride, void* stream);
+/* ---- Gaussian patch blending and mirror test-time augmentation ---------------------------
+ * flip_mask: bit 0 = x, bit 1 = y, bit 2 = z, 0..7.
+ * The _flip gathers are the gathers above with every patch mirrored: batch element (lz, ly, lx) of patch p is the
+ * normalised volume voxel at start_p + (fx ? bx-1-lx : lx, fy ? by-1-ly : ly, fz ? bz-1-lz : lz).  The adaptive
+ * normaliser's mean / std are those of the un-mirrored patch bit for bit, so the result equals the flipped plain gather
+ * exactly.  The mirrored multi-modality gather cannot run in place.
+ * seg3d_patch_scatter_blend: seg3d_patch_scatter_accumulate with a weight per local voxel and mirrored inputs.
+ * wtab: device, bx + by + bz floats = the x, y and z tables one after the other (NULL = weight 1); the weight of local
+ * voxel (lx, ly, lz) is the float32 w = (g_z[lz] * g_y[ly]) * g_x[lx]; acc[c][v] = acc[c][v] + (w * prob) and
+ * count[v] = count[v] + w with a rounded multiply and a rounded add (no FMA), patches in list order, no atomics.  The
+ * probabilities of patch p are stored mirrored by flip_mask (the output of a net that was fed the _flip gather) and are
+ * accumulated un-mirrored.  wtab = NULL and flip_mask = 0 gives seg3d_patch_scatter_accumulate bit for bit.
+ * All three: no allocation, no host sync, control block on the device (capturable). */
+int seg3d_patch_gather_normalize_flip(const float* volume, const int* starts_xyz, float* batch, double* workspace,
+                                      float* mean_std, int Z, int Y, int X, int bx, int by, int bz, int P,
+                                      int normalizer_type, float mean, float stddev, int clip, float clip_sigma,
+                                      int flip_mask, void* stream);
+int seg3d_patch_gather_normalize_mc_flip(const float* volume, const int* starts_xyz, float* batch, double* workspace,
+                                         float* mean_std, int Z, int Y, int X, int bx, int by, int bz, int P, int M,
+                                         Seg3dNormalizers norms, int flip_mask, void* stream);
+int seg3d_patch_scatter_blend(const float* probs, const int* starts_xyz, const int* ctl /* device int32[7] */,
+                              const float* wtab, float* acc, float* count, int Z, int Y, int X, int bx, int by, int bz,
+                              int C, int flip_mask, long long max_box_voxels, void* stream);
 
 /* ---- evaluation metric: utils/metrics.py:5-37 cal_dsc, core/seg_eval.py:8-57 ---------------
  * counts[3k..3k+2] += (area_gt, area_seg, intersection) of labels_host[k] over two label volumes of n elements;

@@ -71,22 +71,30 @@ __global__ __launch_bounds__(64) void patch_stats_finalize_kernel(const double* 
   }
 }
 
-// batch[p][0][lz][ly][lx] = clip((vol[...] - mean_p) / std_p)
+// batch[p][0][lz][ly][lx] = clip((vol[...] - mean_p) / std_p).  FLIP: the volume voxel is read at the local position
+// mirrored along the axes of `flip` (bit 0 = x, 1 = y, 2 = z); the stores stay in batch order, the loads of a wave run
+// backwards through one contiguous row when x is mirrored.
+template <bool FLIP>
 __global__ __launch_bounds__(256) void patch_gather_normalize_kernel(const float* __restrict__ vol,
                                                                        const int* __restrict__ starts,
                                                                        const float* __restrict__ mean_std,
                                                                        float* __restrict__ batch, int Y, int X, int bx,
                                                                        int by, int bz, int P, float fixed_mean,
                                                                        float fixed_std, int clip, float clip_lo,
-                                                                       float clip_hi) {
+                                                                       float clip_hi, int flip) {
   const i64 nv = (i64)bx * by * bz;
   const i64 total = nv * P;
   for (i64 idx = (i64)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (i64)gridDim.x * 256) {
     const int p = (int)(idx / nv);
     const i64 e = idx - (i64)p * nv;
-    const int lx = (int)(e % bx);
+    int lx = (int)(e % bx);
     const i64 t = e / bx;
-    const int ly = (int)(t % by), lz = (int)(t / by);
+    int ly = (int)(t % by), lz = (int)(t / by);
+    if constexpr (FLIP) {
+      if (flip & 1) lx = bx - 1 - lx;
+      if (flip & 2) ly = by - 1 - ly;
+      if (flip & 4) lz = bz - 1 - lz;
+    }
     const int sx = starts[3 * p], sy = starts[3 * p + 1], sz = starts[3 * p + 2];
     const float mean = mean_std ? mean_std[2 * p] : fixed_mean;
     const float sd = mean_std ? mean_std[2 * p + 1] : fixed_std;
@@ -106,10 +114,13 @@ extern "C" long long seg3d_patch_stats_blocks(int bx, int by, int bz) {
 // normalizer_type: 0 = fixed (mean, stddev, clip to [-1,1] when clip != 0), 1 = adaptive (clip to +-clip_sigma),
 // -1 = none.  starts: device int32 [P][3] as (x, y, z).  workspace: P * seg3d_patch_stats_blocks * 2 doubles and
 // mean_std: P * 2 floats (adaptive only).
-extern "C" int seg3d_patch_gather_normalize(const float* volume, const int* starts, float* batch, double* workspace,
-                                            float* mean_std, int Z, int Y, int X, int bx, int by, int bz, int P,
-                                            int normalizer_type, float mean, float stddev, int clip, float clip_sigma,
-                                            void* stream) {
+// flip: mirror mask of the gathered patches (bit 0 = x, 1 = y, 2 = z; 0 = the plain gather).  The statistics of the
+// adaptive normaliser are taken over the same voxels in the same order whatever the mask, so mean / std are those of the
+// un-mirrored patch bit for bit and a mirrored gather equals the flipped plain gather exactly.
+static int patch_gather_normalize_impl(const float* volume, const int* starts, float* batch, double* workspace,
+                                       float* mean_std, int Z, int Y, int X, int bx, int by, int bz, int P,
+                                       int normalizer_type, float mean, float stddev, int clip, float clip_sigma, int flip,
+                                       void* stream) {
   SEG3D_REQUIRE(volume && starts && batch && P > 0, "seg3d_patch_gather_normalize: bad arguments");
   SEG3D_REQUIRE(bx > 0 && by > 0 && bz > 0 && bx <= X && by <= Y && bz <= Z,
                 "seg3d_patch_gather_normalize: box (%d,%d,%d) does not fit volume (%d,%d,%d)", bx, by, bz, X, Y, Z);
@@ -140,10 +151,33 @@ extern "C" int seg3d_patch_gather_normalize(const float* volume, const int* star
     SEG3D_UNSUPPORTED("seg3d_patch_gather_normalize: unsupported normalization type %d", normalizer_type);
   }
   const i64 total = (i64)bx * by * bz * P;
-  hipLaunchKernelGGL(patch_gather_normalize_kernel, dim3(seg3d_ew_grid(total, 256)), dim3(256), 0, s, volume, starts, ms,
-                     batch, Y, X, bx, by, bz, P, fm, fs, do_clip, lo, hi);
+  if (flip)
+    hipLaunchKernelGGL(patch_gather_normalize_kernel<true>, dim3(seg3d_ew_grid(total, 256)), dim3(256), 0, s, volume, starts,
+                       ms, batch, Y, X, bx, by, bz, P, fm, fs, do_clip, lo, hi, flip);
+  else
+    hipLaunchKernelGGL(patch_gather_normalize_kernel<false>, dim3(seg3d_ew_grid(total, 256)), dim3(256), 0, s, volume,
+                       starts, ms, batch, Y, X, bx, by, bz, P, fm, fs, do_clip, lo, hi, 0);
   SEG3D_LAUNCH_CHECK("seg3d_patch_gather_normalize");
   return SEG3D_OK;
+}
+
+extern "C" int seg3d_patch_gather_normalize(const float* volume, const int* starts, float* batch, double* workspace,
+                                            float* mean_std, int Z, int Y, int X, int bx, int by, int bz, int P,
+                                            int normalizer_type, float mean, float stddev, int clip, float clip_sigma,
+                                            void* stream) {
+  return patch_gather_normalize_impl(volume, starts, batch, workspace, mean_std, Z, Y, X, bx, by, bz, P, normalizer_type,
+                                     mean, stddev, clip, clip_sigma, 0, stream);
+}
+
+// the same gather with every patch mirrored by flip_mask (0..7): batch[p][0][lz][ly][lx] is the normalised voxel at
+// start_p + (fx ? bx-1-lx : lx, fy ? by-1-ly : ly, fz ? bz-1-lz : lz), i.e. torch.flip of the plain gather
+extern "C" int seg3d_patch_gather_normalize_flip(const float* volume, const int* starts, float* batch, double* workspace,
+                                                 float* mean_std, int Z, int Y, int X, int bx, int by, int bz, int P,
+                                                 int normalizer_type, float mean, float stddev, int clip, float clip_sigma,
+                                                 int flip_mask, void* stream) {
+  SEG3D_REQUIRE(flip_mask >= 0 && flip_mask <= 7, "seg3d_patch_gather_normalize_flip: flip mask %d outside 0..7", flip_mask);
+  return patch_gather_normalize_impl(volume, starts, batch, workspace, mean_std, Z, Y, X, bx, by, bz, P, normalizer_type,
+                                     mean, stddev, clip, clip_sigma, flip_mask, stream);
 }
 
 // ---- M co-registered modalities in one launch chain (dataset.py:199-203 crops and normalises a list of images with
@@ -214,12 +248,14 @@ __global__ __launch_bounds__(256) void patch_stats_partial_mc_kernel(const float
 }
 
 // batch[p][lz][ly][lx][m] = clip_m((vol[...][m] - mean_pm) / std_pm)
-template <int MC, bool VEC>
-// (vol and batch may be the same buffer: a crop normalised in place, P = 1 and the box = the volume)
+template <int MC, bool VEC, bool FLIP>
+// (vol and batch may be the same buffer: a crop normalised in place, P = 1 and the box = the volume; never with FLIP)
+// FLIP: the row of M channels is read at the local position mirrored along the axes of `flip` (bit 0 = x, 1 = y, 2 = z);
+// channels are innermost, so a mirrored row is still one 8- / 16-byte load
 __global__ __launch_bounds__(256) void patch_gather_normalize_mc_kernel(const float* vol, const int* __restrict__ starts,
                                                                           const float* __restrict__ mean_std, float* batch, int Mrt, int Y, int X,
                                                                           int bx, int by, int bz, int P,
-                                                                          Seg3dNormalizers nrm) {
+                                                                          Seg3dNormalizers nrm, int flip) {
   constexpr int MR = MC > 0 ? MC : 8;
   const int M = MC > 0 ? MC : Mrt;
   const i64 nv = (i64)bx * by * bz;
@@ -227,9 +263,14 @@ __global__ __launch_bounds__(256) void patch_gather_normalize_mc_kernel(const fl
   for (i64 idx = (i64)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (i64)gridDim.x * 256) {
     const int p = (int)(idx / nv);
     const i64 e = idx - (i64)p * nv;
-    const int lx = (int)(e % bx);
+    int lx = (int)(e % bx);
     const i64 t = e / bx;
-    const int ly = (int)(t % by), lz = (int)(t / by);
+    int ly = (int)(t % by), lz = (int)(t / by);
+    if constexpr (FLIP) {
+      if (flip & 1) lx = bx - 1 - lx;
+      if (flip & 2) ly = by - 1 - ly;
+      if (flip & 4) lz = bz - 1 - lz;
+    }
     const int sx = starts[3 * p], sy = starts[3 * p + 1], sz = starts[3 * p + 2];
     const float* row = vol + (((i64)(sz + lz) * Y + (sy + ly)) * X + (sx + lx)) * M;
     float r[MR];
@@ -270,7 +311,7 @@ extern "C" long long seg3d_patch_stats_mc_doubles(int bx, int by, int bz, int P,
 template <int MC, bool VEC>
 static int patch_gather_normalize_mc_launch(const float* volume, const int* starts, float* batch, double* workspace,
                                             float* mean_std, int M, int Y, int X, int bx, int by, int bz, int P,
-                                            const Seg3dNormalizers& nrm, bool any_adaptive, hipStream_t s) {
+                                            const Seg3dNormalizers& nrm, bool any_adaptive, int flip, hipStream_t s) {
   if (any_adaptive) {
     const int nblk = (int)seg3d_patch_stats_blocks(bx, by, bz);
     hipLaunchKernelGGL((patch_stats_partial_mc_kernel<MC, VEC>), dim3(nblk, P), dim3(256), 0, s, volume, starts, workspace,
@@ -281,8 +322,12 @@ static int patch_gather_normalize_mc_launch(const float* volume, const int* star
     SEG3D_LAUNCH_CHECK("seg3d_patch_gather_normalize_mc(finalize)");
   }
   const i64 total = (i64)bx * by * bz * P;
-  hipLaunchKernelGGL((patch_gather_normalize_mc_kernel<MC, VEC>), dim3(seg3d_ew_grid(total, 256)), dim3(256), 0, s, volume,
-                     starts, mean_std, batch, M, Y, X, bx, by, bz, P, nrm);
+  if (flip)
+    hipLaunchKernelGGL((patch_gather_normalize_mc_kernel<MC, VEC, true>), dim3(seg3d_ew_grid(total, 256)), dim3(256), 0, s,
+                       volume, starts, mean_std, batch, M, Y, X, bx, by, bz, P, nrm, flip);
+  else
+    hipLaunchKernelGGL((patch_gather_normalize_mc_kernel<MC, VEC, false>), dim3(seg3d_ew_grid(total, 256)), dim3(256), 0, s,
+                       volume, starts, mean_std, batch, M, Y, X, bx, by, bz, P, nrm, 0);
   SEG3D_LAUNCH_CHECK("seg3d_patch_gather_normalize_mc");
   return SEG3D_OK;
 }
@@ -292,9 +337,9 @@ static int patch_gather_normalize_mc_launch(const float* volume, const int* star
 // (the patch's own mean / std, clip to [clip_lo, clip_hi]), -1 = none.  workspace: seg3d_patch_stats_mc_doubles doubles,
 // mean_std: P * M * 2 floats (both used only when a modality is adaptive).  batch may be volume itself when P = 1, the
 // start is 0 and the box is the whole volume (a training crop normalised in place).
-extern "C" int seg3d_patch_gather_normalize_mc(const float* volume, const int* starts, float* batch, double* workspace,
-                                               float* mean_std, int Z, int Y, int X, int bx, int by, int bz, int P, int M,
-                                               Seg3dNormalizers norms, void* stream) {
+static int patch_gather_normalize_mc_impl(const float* volume, const int* starts, float* batch, double* workspace,
+                                          float* mean_std, int Z, int Y, int X, int bx, int by, int bz, int P, int M,
+                                          const Seg3dNormalizers& norms, int flip, void* stream) {
   SEG3D_REQUIRE(volume && starts && batch && P > 0, "seg3d_patch_gather_normalize_mc: bad arguments");
   SEG3D_REQUIRE(M >= 1 && M <= 8, "seg3d_patch_gather_normalize_mc: M = %d modalities, 1..8 are supported", M);
   SEG3D_REQUIRE(bx > 0 && by > 0 && bz > 0 && bx <= X && by <= Y && bz <= Z,
@@ -327,12 +372,31 @@ extern "C" int seg3d_patch_gather_normalize_mc(const float* volume, const int* s
   hipStream_t s = (hipStream_t)stream;
   const bool vec4 = M == 4 && ((uintptr_t)volume & 15) == 0 && ((uintptr_t)batch & 15) == 0;
   const bool vec2 = M == 2 && ((uintptr_t)volume & 7) == 0 && ((uintptr_t)batch & 7) == 0;
-  if (vec4) return patch_gather_normalize_mc_launch<4, true>(volume, starts, batch, workspace, mean_std, M, Y, X, bx, by, bz, P, nrm, any_adaptive, s);
-  if (M == 4) return patch_gather_normalize_mc_launch<4, false>(volume, starts, batch, workspace, mean_std, M, Y, X, bx, by, bz, P, nrm, any_adaptive, s);
-  if (vec2) return patch_gather_normalize_mc_launch<2, true>(volume, starts, batch, workspace, mean_std, M, Y, X, bx, by, bz, P, nrm, any_adaptive, s);
-  if (M == 2) return patch_gather_normalize_mc_launch<2, false>(volume, starts, batch, workspace, mean_std, M, Y, X, bx, by, bz, P, nrm, any_adaptive, s);
-  if (M == 3) return patch_gather_normalize_mc_launch<3, false>(volume, starts, batch, workspace, mean_std, M, Y, X, bx, by, bz, P, nrm, any_adaptive, s);
-  return patch_gather_normalize_mc_launch<0, false>(volume, starts, batch, workspace, mean_std, M, Y, X, bx, by, bz, P, nrm, any_adaptive, s);
+  if (vec4) return patch_gather_normalize_mc_launch<4, true>(volume, starts, batch, workspace, mean_std, M, Y, X, bx, by, bz, P, nrm, any_adaptive, flip, s);
+  if (M == 4) return patch_gather_normalize_mc_launch<4, false>(volume, starts, batch, workspace, mean_std, M, Y, X, bx, by, bz, P, nrm, any_adaptive, flip, s);
+  if (vec2) return patch_gather_normalize_mc_launch<2, true>(volume, starts, batch, workspace, mean_std, M, Y, X, bx, by, bz, P, nrm, any_adaptive, flip, s);
+  if (M == 2) return patch_gather_normalize_mc_launch<2, false>(volume, starts, batch, workspace, mean_std, M, Y, X, bx, by, bz, P, nrm, any_adaptive, flip, s);
+  if (M == 3) return patch_gather_normalize_mc_launch<3, false>(volume, starts, batch, workspace, mean_std, M, Y, X, bx, by, bz, P, nrm, any_adaptive, flip, s);
+  return patch_gather_normalize_mc_launch<0, false>(volume, starts, batch, workspace, mean_std, M, Y, X, bx, by, bz, P, nrm, any_adaptive, flip, s);
+}
+
+extern "C" int seg3d_patch_gather_normalize_mc(const float* volume, const int* starts, float* batch, double* workspace,
+                                               float* mean_std, int Z, int Y, int X, int bx, int by, int bz, int P, int M,
+                                               Seg3dNormalizers norms, void* stream) {
+  return patch_gather_normalize_mc_impl(volume, starts, batch, workspace, mean_std, Z, Y, X, bx, by, bz, P, M, norms, 0,
+                                        stream);
+}
+
+// the multi-modality gather with every patch mirrored by flip_mask (0..7), see seg3d_patch_gather_normalize_flip; batch
+// must not alias volume
+extern "C" int seg3d_patch_gather_normalize_mc_flip(const float* volume, const int* starts, float* batch, double* workspace,
+                                                    float* mean_std, int Z, int Y, int X, int bx, int by, int bz, int P,
+                                                    int M, Seg3dNormalizers norms, int flip_mask, void* stream) {
+  SEG3D_REQUIRE(flip_mask >= 0 && flip_mask <= 7, "seg3d_patch_gather_normalize_mc_flip: flip mask %d outside 0..7",
+                flip_mask);
+  SEG3D_REQUIRE(flip_mask == 0 || volume != batch, "seg3d_patch_gather_normalize_mc_flip: a mirrored gather cannot run in place");
+  return patch_gather_normalize_mc_impl(volume, starts, batch, workspace, mean_std, Z, Y, X, bx, by, bz, P, M, norms,
+                                        flip_mask, stream);
 }
 
 // One thread per volume voxel of the batch's bounding box; patches are applied in list order so the float summation
@@ -377,6 +441,78 @@ extern "C" int seg3d_patch_scatter_accumulate(const float* probs, const int* sta
   hipLaunchKernelGGL(patch_scatter_accumulate_kernel, dim3(seg3d_ew_grid(max_box_voxels, 256)), dim3(256), 0,
                      (hipStream_t)stream, probs, starts, ctl, acc, count, Z, Y, X, bx, by, bz, C);
   SEG3D_LAUNCH_CHECK("seg3d_patch_scatter_accumulate");
+  return SEG3D_OK;
+}
+
+// Weighted and / or mirrored accumulation, same thread mapping and patch order as patch_scatter_accumulate_kernel:
+//   w = (g_z[lz] * g_y[ly]) * g_x[lx]   (wtab = x table, y table, z table: bx + by + bz floats; WEIGHTED = false: w = 1)
+//   acc[c][v] = acc[c][v] + (w * prob),  count[v] = count[v] + w     -- a rounded multiply, then a rounded add
+// (the file is built with -ffp-contract=off and the pragma below pins it, so no FMA is formed and the result is bit-equal
+// to a float32 loop on the host).  The probabilities of a patch are stored mirrored by `flip`: the value that belongs to
+// local voxel (lx, ly, lz) is read at the mirrored position; the tables are symmetric, so the weight needs no mirror, but
+// it is indexed with the un-mirrored position all the same.  A mirror along x reverses the lanes' addresses inside one
+// contiguous row.  The table reads are L1 / L2 hits (a few hundred bytes shared by every thread).
+template <bool WEIGHTED>
+__global__ __launch_bounds__(256) void patch_scatter_blend_kernel(const float* __restrict__ probs,
+                                                                    const int* __restrict__ starts,
+                                                                    const int* __restrict__ ctl,
+                                                                    const float* __restrict__ wtab, float* __restrict__ acc,
+                                                                    float* __restrict__ count, int Z, int Y, int X, int bx,
+                                                                    int by, int bz, int C, int flip) {
+#pragma clang fp contract(off)
+  const int lox = ctl[0], loy = ctl[1], loz = ctl[2], ex = ctl[3], ey = ctl[4], ez = ctl[5], P = ctl[6];
+  const i64 total = (i64)ex * ey * ez;
+  const i64 vol = (i64)Z * Y * X;
+  const i64 nv = (i64)bx * by * bz;
+  for (i64 idx = (i64)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (i64)gridDim.x * 256) {
+    const int x = lox + (int)(idx % ex);
+    const i64 t = idx / ex;
+    const int y = loy + (int)(t % ey), z = loz + (int)(t / ey);
+    if (x >= X || y >= Y || z >= Z) continue;
+    const i64 v = ((i64)z * Y + y) * X + x;
+    float cnt = count[v];
+    bool hit = false;
+    for (int p = 0; p < P; ++p) {
+      const int lx = x - starts[3 * p], ly = y - starts[3 * p + 1], lz = z - starts[3 * p + 2];
+      if (lx >= 0 && lx < bx && ly >= 0 && ly < by && lz >= 0 && lz < bz) {
+        float w = 1.0f;
+        if constexpr (WEIGHTED) w = (wtab[bx + by + lz] * wtab[bx + ly]) * wtab[lx];
+        const int mx = (flip & 1) ? bx - 1 - lx : lx;
+        const int my = (flip & 2) ? by - 1 - ly : ly;
+        const int mz = (flip & 4) ? bz - 1 - lz : lz;
+        const i64 e = ((i64)mz * by + my) * bx + mx;
+        for (int c = 0; c < C; ++c) {
+          const float wp = w * probs[((i64)p * C + c) * nv + e];
+          acc[(i64)c * vol + v] = acc[(i64)c * vol + v] + wp;
+        }
+        cnt = cnt + w;
+        hit = true;
+      }
+    }
+    if (hit) count[v] = cnt;
+  }
+}
+
+// seg3d_patch_scatter_accumulate with Gaussian importance weights and mirrored inputs.  wtab: device, bx + by + bz floats
+// (x table, y table, z table), NULL = constant weight 1; flip_mask (0..7): probs of every patch are stored mirrored by it.
+// wtab = NULL and flip_mask = 0 is seg3d_patch_scatter_accumulate itself.
+extern "C" int seg3d_patch_scatter_blend(const float* probs, const int* starts, const int* ctl, const float* wtab,
+                                         float* acc, float* count, int Z, int Y, int X, int bx, int by, int bz, int C,
+                                         int flip_mask, long long max_box_voxels, void* stream) {
+  SEG3D_REQUIRE(flip_mask >= 0 && flip_mask <= 7, "seg3d_patch_scatter_blend: flip mask %d outside 0..7", flip_mask);
+  if (!wtab && flip_mask == 0)
+    return seg3d_patch_scatter_accumulate(probs, starts, ctl, acc, count, Z, Y, X, bx, by, bz, C, max_box_voxels, stream);
+  SEG3D_REQUIRE(probs && starts && ctl && acc && count && C > 0, "seg3d_patch_scatter_blend: bad arguments");
+  SEG3D_REQUIRE(bx > 0 && by > 0 && bz > 0 && bx <= X && by <= Y && bz <= Z && max_box_voxels > 0,
+                "seg3d_patch_scatter_blend: bad box");
+  const dim3 grid(seg3d_ew_grid(max_box_voxels, 256));
+  if (wtab)
+    hipLaunchKernelGGL(patch_scatter_blend_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, probs, starts, ctl, wtab,
+                       acc, count, Z, Y, X, bx, by, bz, C, flip_mask);
+  else
+    hipLaunchKernelGGL(patch_scatter_blend_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, probs, starts, ctl, wtab,
+                       acc, count, Z, Y, X, bx, by, bz, C, flip_mask);
+  SEG3D_LAUNCH_CHECK("seg3d_patch_scatter_blend");
   return SEG3D_OK;
 }
 

@@ -1,5 +1,11 @@
 """Default inference configuration -- same sections and keys as the reference's config/infer_config.py:9-113
 (general / coarse / fine).  Copied next to trained models by `seg_train` and read back by `load_models`."""
+#
+# Optional keys of a stage section (coarse / fine), read with defaults so that they may be absent; add them to the
+# infer_config.py of a model folder (they are not set here: this file keeps exactly the reference's keys):
+#   blend_mode = 'constant'        'constant' | 'gaussian': weight of a patch voxel when overlapping patches are averaged
+#   blend_sigma_scale = 0.125      Gaussian sigma as a fraction of the patch edge
+#   tta_mirror_axes = []           e.g. ['x', 'y']: mirror test-time augmentation, 2^k forwards per patch
 from easydict import EasyDict as edict
 
 __C = edict()

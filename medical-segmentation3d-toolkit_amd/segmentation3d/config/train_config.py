@@ -21,6 +21,7 @@ __C.dataset.crop_size = [96, 96, 96]                   # voxels, multiples of ma
 __C.dataset.sampling_method = 'HYBRID'                 # GLOBAL | MASK | HYBRID | CENTER
 __C.dataset.random_translation = [15, 15, 15]             # mm, uniform in [-t, t] per axis
 __C.dataset.random_scale = [0.9, 1.1]                     # crop spacing = spacing * uniform(lo, hi)
+__C.dataset.random_mirror_axes = []                       # e.g. ['x', 'y']: mirror each listed axis with probability 1/2
 __C.dataset.interpolation = 'LINEAR'                   # NN | LINEAR
 __C.dataset.crop_normalizers = [AdaptiveNormalizer()]
 

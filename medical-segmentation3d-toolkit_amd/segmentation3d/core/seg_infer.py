@@ -30,6 +30,74 @@ from segmentation3d.utils.model_io import get_checkpoint_folder, strip_module_pr
 from segmentation3d.utils.normalizer import normalizer_from_dict
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# Gaussian patch blending and mirror test-time augmentation (not in the reference)
+# ---------------------------------------------------------------------------------------------------------------------
+BLEND_MODES = ('constant', 'gaussian')
+_AXIS_BITS = {'x': 1, 'y': 2, 'z': 4}
+_MIN_CORNER_WEIGHT = 1e-30
+
+
+def check_blend_mode(blend):
+    if blend not in BLEND_MODES:
+        raise ValueError("unknown blend mode {!r}: 'constant' or 'gaussian'".format(blend))
+    return blend
+
+
+def check_mirror_axes(mirror_axes):
+    """-> tuple of distinct axis letters in the given order; accepts a list / tuple of letters or a string such as 'xy'"""
+    if mirror_axes is None:
+        return ()
+    out = []
+    for a in mirror_axes:
+        if not isinstance(a, str) or a not in _AXIS_BITS:
+            raise ValueError("unknown mirror axis {!r}: 'x', 'y' or 'z'".format(a))
+        if a not in out:
+            out.append(a)
+    return tuple(out)
+
+
+def mirror_flip_masks(mirror_axes):
+    """the flip set of mirror TTA: every subset of `mirror_axes` as a bit mask (bit 0 = x, 1 = y, 2 = z), ascending, 0 first"""
+    bits = 0
+    for a in check_mirror_axes(mirror_axes):
+        bits |= _AXIS_BITS[a]
+    return [m for m in range(8) if m & ~bits == 0]
+
+
+def blend_weight_tables(box, sigma_scale=0.125):
+    """the three 1-D float32 Gaussian tables (x, y, z) of a (bx, by, bz) box:
+    g[i] = exp(-0.5 * ((i - (n - 1) / 2) / (sigma_scale * n))^2) in float64, rounded to float32.  Centred at (n - 1) / 2,
+    so g[i] == g[n - 1 - i] exactly.  The weight of local voxel (lx, ly, lz) is (g_z[lz] * g_y[ly]) * g_x[lx].
+    ValueError for a sigma_scale that is not positive and finite or whose smallest (corner) weight is below 1e-30: 1 / count
+    must stay a finite normal float32."""
+    s = float(sigma_scale)
+    if not (np.isfinite(s) and s > 0.0):
+        raise ValueError('sigma_scale must be positive and finite, got {!r}'.format(sigma_scale))
+    tables = []
+    for n in box:
+        n = int(n)
+        if n <= 0:
+            raise ValueError('box {} must be positive'.format(tuple(box)))
+        i = np.arange(n, dtype=np.float64)
+        tables.append(np.exp(-0.5 * ((i - (n - 1) / 2.0) / (s * n)) ** 2).astype(np.float32))
+    corner = float(tables[0].min()) * float(tables[1].min()) * float(tables[2].min())
+    if not corner >= _MIN_CORNER_WEIGHT:
+        raise ValueError('sigma_scale = {!r} gives a corner weight of {:.3g} on box {} (below 1e-30)'.format(
+            sigma_scale, corner, tuple(int(b) for b in box)))
+    return tuple(tables)
+
+
+def blend_options(cfg):
+    """(blend mode, sigma scale, mirror axes) of a stage section of infer_config.py.  The three keys are optional -- a
+    config written by the reference has none of them -- and default to ('constant', 0.125, ())."""
+    blend = check_blend_mode(getattr(cfg, 'blend_mode', None) or 'constant')
+    sigma = getattr(cfg, 'blend_sigma_scale', None)
+    sigma = 0.125 if sigma is None else float(sigma)
+    axes = check_mirror_axes(getattr(cfg, 'tta_mirror_axes', None))
+    return blend, sigma, axes
+
+
 class SlidingWindowBatcher(object):
     """device-side crop/normalise + accumulate for one resident volume.
 
@@ -39,9 +107,11 @@ class SlidingWindowBatcher(object):
     :param num_classes: C
     :param normalizer: checkpoint-style dict {'type': 0|1, ...} or None (utils/normalizer.py:36-39,78-81); for a
            [Z, Y, X, M] volume a list of M of them, one per modality
+    :param blend: 'constant' (every patch counts 1, the reference) or 'gaussian' (blend_weight_tables, uploaded once)
+    :param sigma_scale: Gaussian sigma as a fraction of the box edge
     """
 
-    def __init__(self, volume, starts, box, num_classes, normalizer, max_batch=16):
+    def __init__(self, volume, starts, box, num_classes, normalizer, max_batch=16, blend='constant', sigma_scale=0.125):
         E.require_device(volume)
         if volume.dim() not in (3, 4) or volume.dtype != torch.float32:
             raise ValueError('volume must be a float32 [Z, Y, X] or [Z, Y, X, M] tensor')
@@ -83,6 +153,10 @@ class SlidingWindowBatcher(object):
         # control block on the device: [P][3] starts then {lo xyz, extent xyz, n_valid}
         self._ctl = torch.zeros((3 * self.max_batch + 7,), dtype=torch.int32, device=dev)
         self._plan = None
+        self.blend = check_blend_mode(blend)
+        self._wtab = None
+        if self.blend == 'gaussian':
+            self._wtab = torch.from_numpy(np.concatenate(blend_weight_tables(self.box, sigma_scale))).to(dev)
 
     # ---- control block ---------------------------------------------------------------------------------------------
     def _control_words(self, idx):
@@ -122,9 +196,18 @@ class SlidingWindowBatcher(object):
         return ctypes.c_void_p(self._ctl.data_ptr() + 4 * 3 * self.max_batch)
 
     # ---- kernels -----------------------------------------------------------------------------------------------------
-    def gather_current(self, out=None):
+    @staticmethod
+    def _flip_mask(flip):
+        flip = int(flip)
+        if not 0 <= flip <= 7:
+            raise ValueError('flip mask {} outside 0..7'.format(flip))
+        return flip
+
+    def gather_current(self, out=None, flip=0):
         """crop + normalise the max_batch patches described by the control block -> [P, 1, bz, by, bx]
-        ([P, M, bz, by, bx] view of NDHWC memory for a multi-modality volume)"""
+        ([P, M, bz, by, bx] view of NDHWC memory for a multi-modality volume).  flip: mirror mask (bit 0 = x, 1 = y,
+        2 = z); the result equals torch.flip of the plain gather along those axes, bit for bit"""
+        flip = self._flip_mask(flip)
         bx, by, bz = self.box
         P = self.max_batch
         if self.channels_last:
@@ -133,6 +216,11 @@ class SlidingWindowBatcher(object):
                                   device=self.volume.device).permute(0, 4, 1, 2, 3)
             elif tuple(out.shape) != (P, self.M, bz, by, bx) or not out.permute(0, 2, 3, 4, 1).is_contiguous():
                 raise ValueError('out must be the [P, M, bz, by, bx] view of a contiguous [P, bz, by, bx, M] batch')
+            if flip:
+                E.call('seg3d_patch_gather_normalize_mc_flip', E.ptr(self.volume), self._starts_ptr(), E.ptr(out),
+                       E.ptr(self._stat_ws), E.ptr(self._mean_std), self.Z, self.Y, self.X, bx, by, bz, P, self.M,
+                       self._norm_params, flip, E.stream_ptr())
+                return out
             E.call('seg3d_patch_gather_normalize_mc', E.ptr(self.volume), self._starts_ptr(), E.ptr(out),
                    E.ptr(self._stat_ws), E.ptr(self._mean_std), self.Z, self.Y, self.X, bx, by, bz, P, self.M,
                    self._norm_params, E.stream_ptr())
@@ -140,33 +228,46 @@ class SlidingWindowBatcher(object):
         if out is None:
             out = torch.empty((P, 1, bz, by, bx), dtype=torch.float32, device=self.volume.device)
         ntype, mean, std, clip, sigma = self._norm
+        if flip:
+            E.call('seg3d_patch_gather_normalize_flip', E.ptr(self.volume), self._starts_ptr(), E.ptr(out),
+                   E.ptr(self._stat_ws), E.ptr(self._mean_std), self.Z, self.Y, self.X, bx, by, bz, P, ntype, mean, std, clip,
+                   sigma, flip, E.stream_ptr())
+            return out
         E.call('seg3d_patch_gather_normalize', E.ptr(self.volume), self._starts_ptr(), E.ptr(out), E.ptr(self._stat_ws),
                E.ptr(self._mean_std), self.Z, self.Y, self.X, bx, by, bz, P, ntype, mean, std, clip, sigma, E.stream_ptr())
         return out
 
-    def scatter_current(self, probs):
-        """accumulate probs [P, C, bz, by, bx] of the control block's valid patches into acc / count"""
+    def scatter_current(self, probs, flip=0):
+        """accumulate probs [P, C, bz, by, bx] of the control block's valid patches into acc / count, each voxel with the
+        batcher's blend weight.  flip: the probabilities are stored mirrored by that mask (the net saw gather_current(flip=
+        flip)) and are accumulated un-mirrored"""
+        flip = self._flip_mask(flip)
         bx, by, bz = self.box
         P = self.max_batch
         if tuple(probs.shape) != (P, self.C, bz, by, bx) or not probs.is_contiguous():
             raise ValueError('probs must be contiguous [{}, {}, {}, {}, {}], got {}'.format(P, self.C, bz, by, bx,
                                                                                             tuple(probs.shape)))
         max_box = min(self.X * self.Y * self.Z, min(self.X, bx * P) * min(self.Y, by * P) * min(self.Z, bz * P))
+        if self._wtab is not None or flip:
+            E.call('seg3d_patch_scatter_blend', E.ptr(probs), self._starts_ptr(), self._ctl_ptr(),
+                   E.ptr(self._wtab) if self._wtab is not None else None, E.ptr(self.acc), E.ptr(self.count), self.Z, self.Y,
+                   self.X, bx, by, bz, self.C, flip, max_box, E.stream_ptr())
+            return
         E.call('seg3d_patch_scatter_accumulate', E.ptr(probs), self._starts_ptr(), self._ctl_ptr(), E.ptr(self.acc),
                E.ptr(self.count), self.Z, self.Y, self.X, bx, by, bz, self.C, max_box, E.stream_ptr())
 
     # convenience (eager) forms used by tests and the non-graph path
-    def gather(self, idx):
+    def gather(self, idx, flip=0):
         self.set_batch(idx)
-        return self.gather_current()[:len(idx)]
+        return self.gather_current(flip=flip)[:len(idx)]
 
-    def scatter(self, idx, probs):
+    def scatter(self, idx, probs, flip=0):
         self.set_batch(idx)
         P = self.max_batch
         if probs.shape[0] != P:
             pad = torch.zeros((P - probs.shape[0],) + tuple(probs.shape[1:]), dtype=probs.dtype, device=probs.device)
             probs = torch.cat((probs, pad), 0)
-        self.scatter_current(probs.contiguous())
+        self.scatter_current(probs.contiguous(), flip=flip)
 
     def finalize(self, z_range=None):
         """acc *= 1/count (in place) and arg-max -> (probs [C,Z,Y,X], mask int8 [Z,Y,X]).
@@ -323,8 +424,13 @@ def _forward_two_streams(net, batch, side):
 
 
 def sliding_window_inference(net, volume, starts, box, num_classes, normalizer, batch_size=8, use_graph=True,
-                             process_group=None, shard=False, two_streams=True, gather='all'):
+                             process_group=None, shard=False, two_streams=True, gather='all', blend='constant',
+                             sigma_scale=0.125, mirror_axes=()):
     """run `net` over all patches of a device-resident volume; returns (probs [C,Z,Y,X], mask int8 [Z,Y,X], batcher).
+    blend = 'gaussian' weights every patch voxel with blend_weight_tables(box, sigma_scale); mirror_axes (a subset of
+    'x', 'y', 'z') adds mirror test-time augmentation: every batch is gathered, predicted and accumulated once per mask of
+    mirror_flip_masks(mirror_axes), and the result is the weighted mean over patches and flips.  The flip sequence of a
+    batch is part of the captured graph: one replay per batch whatever the number of flips.
     With shard=True under an initialised torch.distributed group the patch list is cut into z-contiguous chunks, one per
     rank (SlabShardPlan); after the patch loop only the halo planes are exchanged (merge_slabs), every rank divides and
     arg-maxes the slab it owns, and the slabs are replicated (gather='all': probabilities and mask, 'mask': mask only,
@@ -332,7 +438,7 @@ def sliding_window_inference(net, volume, starts, box, num_classes, normalizer, 
     differs from the sequential reference loop by rounding only."""
     with torch.cuda.device(volume.device):
         return _sliding_window_inference(net, volume, starts, box, num_classes, normalizer, batch_size, use_graph,
-                                         process_group, shard, two_streams, gather)
+                                         process_group, shard, two_streams, gather, blend, sigma_scale, mirror_axes)
 
 
 # hipGraph capture for the per-volume graphs.  `with torch.cuda.graph(g)` empties the caching allocator before every capture
@@ -435,10 +541,12 @@ def release_graph_pool(device=None):
 
 
 def _sliding_window_inference(net, volume, starts, box, num_classes, normalizer, batch_size, use_graph, process_group,
-                              shard, two_streams, gather):
+                              shard, two_streams, gather, blend='constant', sigma_scale=0.125, mirror_axes=()):
     if gather not in ('all', 'mask', 'none'):
         raise ValueError("gather must be 'all', 'mask' or 'none'")
-    batcher = SlidingWindowBatcher(volume, starts, box, num_classes, normalizer, max_batch=batch_size)
+    flips = mirror_flip_masks(mirror_axes)
+    batcher = SlidingWindowBatcher(volume, starts, box, num_classes, normalizer, max_batch=batch_size, blend=blend,
+                                   sigma_scale=sigma_scale)
     P = batcher.max_batch
     sharded = shard and torch.distributed.is_available() and torch.distributed.is_initialized() and \
         torch.distributed.get_world_size(process_group) > 1
@@ -459,6 +567,14 @@ def _sliding_window_inference(net, volume, starts, box, num_classes, normalizer,
     # the eager batches nor the captured graph re-pack 26 tensors per forward
     cache_was_on = _ops.weight_cache(True)
     side = _job_stream(volume.device, 'side') if (two_streams and P >= 2) else None
+
+    def run_batch(buf=None):
+        """the current batch once per flip, in flip-set order: mirrored gather -> net -> un-mirroring scatter; returns the
+        gather buffer (reused by every flip, and by every replay when captured)"""
+        for f in flips:
+            buf = batcher.gather_current(out=buf, flip=f)
+            batcher.scatter_current(_forward_two_streams(net, buf, side), flip=f)
+        return buf
     try:
         with torch.no_grad():
             if use_graph and len(batches) > 2:
@@ -469,22 +585,19 @@ def _sliding_window_inference(net, volume, starts, box, num_classes, normalizer,
                 stream.wait_stream(torch.cuda.current_stream())
                 with torch.cuda.stream(stream):
                     batcher.select(0)
-                    static_in = batcher.gather_current()
-                    batcher.scatter_current(_forward_two_streams(net, static_in, side))
+                    static_in = run_batch()
                 torch.cuda.current_stream().wait_stream(stream)
                 first = 1
                 # capture with n_valid = 0 in the control block so the captured launch itself accumulates nothing
                 batcher._ctl.zero_()
                 torch.cuda.synchronize()
-                graph = _capture_in_shared_pool(
-                    lambda: batcher.scatter_current(_forward_two_streams(net, batcher.gather_current(out=static_in), side)),
-                    volume.device)
+                graph = _capture_in_shared_pool(lambda: run_batch(static_in), volume.device)
             for b in range(first, len(batches)):
                 batcher.select(b)
                 if graph is not None:
                     graph.replay()
                 else:
-                    batcher.scatter_current(_forward_two_streams(net, batcher.gather_current(), side))
+                    run_batch()
             if sharded:
                 merge_slabs(batcher.acc, batcher.count, plan, rank, process_group)
                 probs, mask = batcher.finalize(plan.owned(rank))
@@ -613,7 +726,8 @@ def _index_to_physical(frame, index):
     return origin + direction.reshape(3, 3) @ (spacing * np.asarray(index, dtype=np.float64))
 
 
-def segmentation_volume(model, cfg, image, bbox_start_voxel, bbox_end_voxel, use_gpu=True, batch_size=8):
+def segmentation_volume(model, cfg, image, bbox_start_voxel, bbox_end_voxel, use_gpu=True, batch_size=8, blend=None,
+                        mirror_axes=None):
     """segment a whole volume (reference: seg_infer.py:249-350), everything between the upload of the image and the
     download of the probability maps / mask on the device:
       resample to the model spacing, size up to a multiple of max_stride (image_tools.py:348-377)  -> seg3d_resample_affine
@@ -624,15 +738,22 @@ def segmentation_volume(model, cfg, image, bbox_start_voxel, bbox_end_voxel, use
     image: an Image3d, or a list of M co-registered Image3d (one per modality; the model must take in_channels = M):
     the M modalities are resampled to the model grid in one launch (seg3d_resample_affine_mc) and every patch is
     normalised with its modality's normaliser (seg3d_patch_gather_normalize_mc).
+    Patch blending and mirror TTA come from the optional stage keys cfg.blend_mode ('constant' | 'gaussian'),
+    cfg.blend_sigma_scale and cfg.tta_mirror_axes (blend_options: defaults 'constant', 0.125, []); `blend` / `mirror_axes`,
+    when not None, override the config.
     Returns (mean_probs: list of Image3d, mask: Image3d int8).
     """
     images, M = _case_images(model, image)
+    cfg_blend, sigma_scale, cfg_axes = blend_options(cfg)
+    blend = cfg_blend if blend is None else check_blend_mode(blend)
+    mirror_axes = cfg_axes if mirror_axes is None else check_mirror_axes(mirror_axes)
     with torch.cuda.device(model['device']):
         return _segmentation_volume(model, cfg, images[0] if M == 1 else images, bbox_start_voxel, bbox_end_voxel,
-                                    batch_size)
+                                    batch_size, blend, sigma_scale, mirror_axes)
 
 
-def _segmentation_volume(model, cfg, image, bbox_start_voxel, bbox_end_voxel, batch_size):
+def _segmentation_volume(model, cfg, image, bbox_start_voxel, bbox_end_voxel, batch_size, blend='constant',
+                         sigma_scale=0.125, mirror_axes=()):
     images = image if isinstance(image, list) else None
     if images is not None:
         image = images[0]
@@ -670,7 +791,8 @@ def _segmentation_volume(model, cfg, image, bbox_start_voxel, bbox_end_voxel, ba
         raise ValueError('Unsupported partition type!')
     norm = _model_normalizers(model, 1 if images is None else len(images))
     probs, _, batcher = sliding_window_inference(model['net'], vol, starts, box, num_classes, norm,
-                                                 batch_size=min(batch_size, max(1, len(starts))))
+                                                 batch_size=min(batch_size, max(1, len(starts))), blend=blend,
+                                                 sigma_scale=sigma_scale, mirror_axes=mirror_axes)
     # (voxels no patch covered -- bounding-box runs -- have count 0: their probabilities are 0 and the arg-max there is
     # class 0, as with ITK's division in the reference, see finalize_argmax_kernel)
     # back to the image grid (identity when the image already is at the model spacing and a stride multiple)
@@ -752,13 +874,20 @@ def read_test_folder(folder_path):
 
 
 def segmentation(input_path, model_folder, output_folder, seg_name, gpu_id, return_mask, save_mask, save_image,
-                 save_prob):
+                 save_prob, blend=None, mirror_axes=None):
     """volumetric image segmentation engine for image files (reference: seg_infer.py:353-493): single-scale
     ('coarse' / 'fine') or the coarse -> fine cascade ('DISABLE') through the coarse mask's bounding box.
     input_path: a list file (.txt, one or several co-registered modality paths per case), one image file, or a folder of
     image files; a 4-D NIfTI file is one case of M modalities.  Results go to `<output_folder>/<case name>/` with the
-    reference's file names (seg_name, org.mha -- org_<m>.mha per modality when M > 1 --, mean_prob_<c>.mha)."""
+    reference's file names (seg_name, org.mha -- org_<m>.mha per modality when M > 1 --, mean_prob_<c>.mha).
+    blend ('constant' | 'gaussian') and mirror_axes (e.g. ('x', 'y') or 'xy'): patch blending and mirror TTA of every
+    stage; None = what the stage's section of infer_config.py says."""
     from segmentation3d.utils.image_io import write_image
+    if blend is not None:
+        check_blend_mode(blend)
+    if mirror_axes is not None:
+        mirror_axes = check_mirror_axes(mirror_axes)
+    tta = dict(blend=blend, mirror_axes=mirror_axes)
     begin = time.time()
     models = load_models(model_folder, gpu_id)
     load_model_time = time.time() - begin
@@ -795,14 +924,14 @@ def segmentation(input_path, model_folder, output_folder, seg_name, gpu_id, retu
         read_image_time = time.time() - begin
         begin = time.time()
         if scale == 'coarse':
-            mean_probs, mask = segmentation_volume(models['coarse_model'], models['infer_cfg'].coarse, image, None, None, True)
+            mean_probs, mask = segmentation_volume(models['coarse_model'], models['infer_cfg'].coarse, image, None, None, True, **tta)
         elif scale == 'fine':
-            mean_probs, mask = segmentation_volume(models['fine_model'], models['infer_cfg'].fine, image, None, None, True)
+            mean_probs, mask = segmentation_volume(models['fine_model'], models['infer_cfg'].fine, image, None, None, True, **tta)
         else:
             # coarse -> fine cascade (seg_infer.py:428-444): the coarse mask's bounding box restricts the fine pass
             from segmentation3d.utils.image_tools import get_bounding_box
             print('Coarse segmentation: ')
-            _, mask = segmentation_volume(models['coarse_model'], models['infer_cfg'].coarse, image, None, None, True)
+            _, mask = segmentation_volume(models['coarse_model'], models['infer_cfg'].coarse, image, None, None, True, **tta)
             start_voxel, end_voxel = get_bounding_box(mask, None)
             if start_voxel is None:
                 start_voxel, end_voxel = [0, 0, 0], list(mask.GetSize())
@@ -811,7 +940,7 @@ def segmentation(input_path, model_folder, output_folder, seg_name, gpu_id, retu
                 bbox_ratio *= (end_voxel[idx] - start_voxel[idx]) / mask.GetSize()[idx]
             print('Fine segmentation (bbox ratio: {:.2f}%): '.format(bbox_ratio))
             mean_probs, mask = segmentation_volume(models['fine_model'], models['infer_cfg'].fine, image, start_voxel,
-                                                   end_voxel, True)
+                                                   end_voxel, True, **tta)
         torch.cuda.synchronize()
         inference_time = time.time() - begin
         total += inference_time

@@ -172,7 +172,8 @@ def train(train_config_file, data_iter_factory=None):
             imlist_file=cfg.general.imseg_list, num_classes=cfg.dataset.num_classes, spacing=cfg.dataset.spacing,
             crop_size=cfg.dataset.crop_size, sampling_method=cfg.dataset.sampling_method,
             random_translation=cfg.dataset.random_translation, random_scale=cfg.dataset.random_scale,
-            interpolation=cfg.dataset.interpolation, crop_normalizers=cfg.dataset.crop_normalizers, device=None)
+            interpolation=cfg.dataset.interpolation, crop_normalizers=cfg.dataset.crop_normalizers, device=None,
+            random_mirror_axes=getattr(cfg.dataset, 'random_mirror_axes', None) or ())
         num_modality = dataset.num_modality()
         configured = getattr(cfg.dataset, 'num_modality', None)
         if configured is not None and int(configured) != num_modality:

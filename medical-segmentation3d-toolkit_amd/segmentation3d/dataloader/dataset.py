@@ -154,7 +154,7 @@ class SegmentationDataset(Dataset):
     """training data set for volumetric segmentation (constructor as dataloader/dataset.py:58-100)"""
 
     def __init__(self, imlist_file, num_classes, spacing, crop_size, sampling_method, random_translation, random_scale,
-                 interpolation, crop_normalizers, device=None):
+                 interpolation, crop_normalizers, device=None, random_mirror_axes=()):
         if imlist_file.endswith('txt'):
             self.im_list, self.seg_list = read_train_txt(imlist_file)
         elif imlist_file.endswith('csv'):
@@ -177,6 +177,13 @@ class SegmentationDataset(Dataset):
         assert self.interpolation in ('LINEAR', 'NN'), 'interpolation must either be a LINEAR or NN'
         self.crop_normalizers = crop_normalizers
         assert isinstance(self.crop_normalizers, list), 'crop normalizers must be a list'
+        # mirror augmentation (not in the reference): every listed axis is mirrored with probability 1/2 per sample
+        self.random_mirror_axes = []
+        for a in (random_mirror_axes or ()):
+            if a not in ('x', 'y', 'z'):
+                raise ValueError("unknown mirror axis {!r}: 'x', 'y' or 'z'".format(a))
+            if a not in self.random_mirror_axes:
+                self.random_mirror_axes.append(a)
         # modalities per case from the list and the file headers (no volume is read here): every case must have the same M,
         # and there is one normaliser per modality (None: no normalisation, dataset.py:202)
         self._num_modality = 1
@@ -262,9 +269,21 @@ class SegmentationDataset(Dataset):
         crop_spacing = self.spacing * np.random.uniform(self.random_scale[0], self.random_scale[1])
         return center, crop_spacing
 
+    def sample_mirror(self):
+        """(x, y, z) mirror flags of the next sample: one randint(0, 2, size=k) over the k random_mirror_axes, drawn after
+        the scale draw; with no mirror axes nothing is drawn, so the RNG stream is the reference's"""
+        flags = [False, False, False]
+        if self.random_mirror_axes:
+            draw = np.random.randint(0, 2, size=len(self.random_mirror_axes))
+            for a, d in zip(self.random_mirror_axes, draw):
+                flags['xyz'.index(a)] = bool(d)
+        return tuple(flags)
+
     # ---- the sample ---------------------------------------------------------------------------------------------------
     def __getitem__(self, index):
         """-> (image crop [M, z, y, x], mask crop [1, z, y, x] float labels, frame (15 floats), case name); device tensors.
+        With random_mirror_axes image and mask are mirrored together inside their resampling launches (mirrored index
+        map, no extra pass) and the frame describes the mirrored grid.
         For M > 1 the image crop is a view of channels-last [z, y, x, M] memory (what the stem reads, without a copy)."""
         return self.sample(index)
 
@@ -274,19 +293,24 @@ class SegmentationDataset(Dataset):
         case = self.case(index)
         case_name = self.case_name(index)
         center, crop_spacing = self.sample_crop_geometry(index)
+        mirror = self.sample_mirror()
         if self._num_modality == 1:
             im = image_tools.crop_image_device(case.image, case.frame, center, self.crop_size, crop_spacing,
-                                               self.interpolation)
+                                               self.interpolation, mirror=mirror)
             if self.crop_normalizers[0] is not None:
                 im = image_tools.normalize_crop_device(im, self.crop_normalizers[0])
             im = im.unsqueeze(0)
         else:
             im = image_tools.crop_image_device_mc(case.image, case.frame, center, self.crop_size, crop_spacing,
-                                                  self.interpolation, out=out)
+                                                  self.interpolation, out=out, mirror=mirror)
             im = image_tools.normalize_crop_device_mc(im, self._norm_params, out=im).permute(3, 0, 1, 2)
-        seg = image_tools.crop_image_device(case.seg, case.seg_frame, center, self.crop_size, crop_spacing, 'NN')
+        seg = image_tools.crop_image_device(case.seg, case.seg_frame, center, self.crop_size, crop_spacing, 'NN',
+                                            mirror=mirror)
         origin = image_tools.crop_origin(center, self.crop_size, crop_spacing)
-        frame = np.array(list(crop_spacing) + list(origin) + list(case.seg_frame[2]), dtype=np.float32)
+        direction = list(case.seg_frame[2])
+        if any(mirror):
+            _, origin, direction = image_tools.mirror_frame((crop_spacing, origin, direction), self.crop_size, mirror)
+        frame = np.array(list(crop_spacing) + list(origin) + list(direction), dtype=np.float32)
         return im, seg.unsqueeze(0), frame, case_name
 
 

@@ -5,7 +5,7 @@ import argparse
 from segmentation3d.core.seg_infer import segmentation
 
 
-def main():
+def build_parser():
     parser = argparse.ArgumentParser(
         description='Sliding-window 3D medical image segmentation on an MI355X (HIP engine). Input: one MetaImage '
                     'volume (.mha/.mhd) or a text file listing volumes.')
@@ -19,11 +19,23 @@ def main():
     parser.add_argument('--dtype', default='fp32', choices=['fp32', 'bf16'],
                         help='fp32 = the reference arithmetic (default); bf16 = bf16 activations / packed weights with '
                              'fp32 accumulation (about 3x faster, probabilities within ~1e-2)')
-    args = parser.parse_args()
+    parser.add_argument('--blend', default=None, choices=['constant', 'gaussian'],
+                        help='patch blending: constant = every patch counts 1 (the reference), gaussian = centre-weighted '
+                             '(default: blend_mode of the stage in infer_config.py, else constant)')
+    parser.add_argument('--tta_mirror', default=None, metavar='AXES',
+                        help="mirror test-time augmentation along these axes, e.g. 'xy' (2^k forwards per patch); '' = "
+                             'none (default: tta_mirror_axes of the stage in infer_config.py, else none)')
+    return parser
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
     from segmentation3d import _ops
+    from segmentation3d.core.seg_infer import check_mirror_axes
+    mirror_axes = None if args.tta_mirror is None else check_mirror_axes(args.tta_mirror)
     _ops.set_activation_dtype(args.dtype)
     segmentation(args.input, args.model, args.output, args.seg_name, args.gpu_id, False, True, args.save_image,
-                 args.save_prob)
+                 args.save_prob, blend=args.blend, mirror_axes=mirror_axes)
 
 
 if __name__ == '__main__':

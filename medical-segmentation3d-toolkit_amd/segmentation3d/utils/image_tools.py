@@ -105,8 +105,33 @@ def index_affine(src_frame, dst_frame):
     return M
 
 
-def resample_device(src, src_frame, out_size, dst_frame, interp_method, padding_value=0.0):
-    """src: float32 device tensor [Z, Y, X]; returns the float32 device tensor [Zo, Yo, Xo] of the destination grid"""
+def mirror_index_affine(M, out_size, mirror):
+    """index map of the destination grid mirrored along the axes flagged in `mirror` = (x, y, z): destination index i of a
+    mirrored axis of n voxels reads what index n - 1 - i read before.  The axis column of the 3 x 4 matrix is negated and
+    (n - 1) times the column goes to the offset; a copy is returned."""
+    M = np.array(M, dtype=np.float64)
+    for a in range(3):
+        if mirror[a]:
+            M[:, 3] += (int(out_size[a]) - 1) * M[:, a]
+            M[:, a] = -M[:, a]
+    return M
+
+
+def mirror_frame(frame, out_size, mirror):
+    """(spacing, origin, direction) of the grid that mirror_index_affine samples: the origin moves to the last voxel of a
+    mirrored axis and that axis' direction column changes sign"""
+    spacing, origin, direction = (np.array(v, dtype=np.float64) for v in frame)
+    D = direction.reshape(3, 3).copy()
+    for a in range(3):
+        if mirror[a]:
+            origin = origin + D[:, a] * spacing[a] * (int(out_size[a]) - 1)
+            D[:, a] = -D[:, a]
+    return [float(v) for v in spacing], [float(v) for v in origin], [float(v) for v in D.reshape(-1)]
+
+
+def resample_device(src, src_frame, out_size, dst_frame, interp_method, padding_value=0.0, mirror=None):
+    """src: float32 device tensor [Z, Y, X]; returns the float32 device tensor [Zo, Yo, Xo] of the destination grid.
+    mirror = (x, y, z) flags: the destination grid is sampled mirrored along those axes (mirror_index_affine)"""
     if interp_method not in ('LINEAR', 'NN'):
         raise ValueError('Unsupported interpolation type.')
     E.require_device(src)
@@ -114,13 +139,16 @@ def resample_device(src, src_frame, out_size, dst_frame, interp_method, padding_
     Zi, Yi, Xi = src.shape
     Xo, Yo, Zo = (int(v) for v in out_size)
     dst = torch.empty((Zo, Yo, Xo), dtype=torch.float32, device=src.device)
-    M = np.ascontiguousarray(index_affine(src_frame, dst_frame), dtype=np.float64)
+    M = index_affine(src_frame, dst_frame)
+    if mirror is not None and any(mirror):
+        M = mirror_index_affine(M, (Xo, Yo, Zo), mirror)
+    M = np.ascontiguousarray(M, dtype=np.float64)
     E.call('seg3d_resample_affine', E.ptr(src), E.ptr(dst), Xi, Yi, Zi, Xo, Yo, Zo,
            M.ctypes.data_as(ctypes.c_void_p), int(interp_method == 'LINEAR'), float(padding_value), E.stream_ptr())
     return dst
 
 
-def resample_device_mc(src, src_frame, out_size, dst_frame, interp_method, padding_value=0.0, out=None):
+def resample_device_mc(src, src_frame, out_size, dst_frame, interp_method, padding_value=0.0, out=None, mirror=None):
     """M co-registered channels in one launch: src float32 device tensor [Z, Y, X, M] (channels-last) -> [Zo, Yo, Xo, M].
     `out`: a contiguous [Zo, Yo, Xo, M] destination, e.g. slot b of an NDHWC batch.  Channel m equals resample_device
     on src[..., m] bit for bit (seg3d_resample_affine_mc)."""
@@ -136,7 +164,10 @@ def resample_device_mc(src, src_frame, out_size, dst_frame, interp_method, paddi
         out = torch.empty((Zo, Yo, Xo, M), dtype=torch.float32, device=src.device)
     elif tuple(out.shape) != (Zo, Yo, Xo, M) or not out.is_contiguous() or out.dtype != torch.float32:
         raise ValueError('out must be a contiguous float32 [{}, {}, {}, {}] tensor'.format(Zo, Yo, Xo, M))
-    M_ = np.ascontiguousarray(index_affine(src_frame, dst_frame), dtype=np.float64)
+    M_ = index_affine(src_frame, dst_frame)
+    if mirror is not None and any(mirror):
+        M_ = mirror_index_affine(M_, (Xo, Yo, Zo), mirror)
+    M_ = np.ascontiguousarray(M_, dtype=np.float64)
     E.call('seg3d_resample_affine_mc', E.ptr(src), E.ptr(out), int(M), int(M), Xi, Yi, Zi, Xo, Yo, Zo,
            M_.ctypes.data_as(ctypes.c_void_p), int(interp_method == 'LINEAR'), float(padding_value), E.stream_ptr())
     return out
@@ -286,13 +317,14 @@ def crop_origin(cropping_center, cropping_size, cropping_spacing):
     return out
 
 
-def crop_image_device(volume, frame, cropping_center, cropping_size, cropping_spacing, interp_method):
+def crop_image_device(volume, frame, cropping_center, cropping_size, cropping_spacing, interp_method, mirror=None):
     """volume: float32 device tensor [Z, Y, X] with frame (spacing, origin, direction) -> crop [z, y, x] of
-    `cropping_size` voxels at `cropping_spacing`, centred at the world point `cropping_center`, zero outside"""
+    `cropping_size` voxels at `cropping_spacing`, centred at the world point `cropping_center`, zero outside;
+    mirror = (x, y, z) flags: the crop comes out mirrored along those axes (same launch, mirrored index map)"""
     size = [int(cropping_size[idx]) for idx in range(3)]
     spacing = [float(cropping_spacing[idx]) for idx in range(3)]
     dst_frame = (spacing, crop_origin(cropping_center, size, spacing), frame[2])
-    return resample_device(volume, frame, size, dst_frame, interp_method, 0.0)
+    return resample_device(volume, frame, size, dst_frame, interp_method, 0.0, mirror=mirror)
 
 
 def crop_image(image, cropping_center, cropping_size, cropping_spacing, interp_method):
@@ -326,12 +358,13 @@ def normalize_crop_device(crop, normalizer):
     return out[0, 0]
 
 
-def crop_image_device_mc(volume, frame, cropping_center, cropping_size, cropping_spacing, interp_method, out=None):
+def crop_image_device_mc(volume, frame, cropping_center, cropping_size, cropping_spacing, interp_method, out=None,
+                         mirror=None):
     """crop_image_device for a channels-last [Z, Y, X, M] volume: one launch for all modalities -> [z, y, x, M]"""
     size = [int(cropping_size[idx]) for idx in range(3)]
     spacing = [float(cropping_spacing[idx]) for idx in range(3)]
     dst_frame = (spacing, crop_origin(cropping_center, size, spacing), frame[2])
-    return resample_device_mc(volume, frame, size, dst_frame, interp_method, 0.0, out=out)
+    return resample_device_mc(volume, frame, size, dst_frame, interp_method, 0.0, out=out, mirror=mirror)
 
 
 def normalize_crop_device_mc(crop, params, out=None):
