@@ -328,6 +328,26 @@ int seg3d_focal_fwd(const float* probs, const float* target, const float* alpha,
 int seg3d_focal_bwd(const float* probs, const float* target, const float* alpha, const float* gout, float* dprobs, int N,
                     int C, long long S, long long sn, long long sc, long long ss, float gamma, int size_average,
                     void* stream);
+/* Compound loss (no counterpart in the reference): L = dice_weight * L_region + ce_weight * L_dist on probabilities
+ * [N][C][S] and a float class-id target [N][S].  A voxel counts iff 0 <= t < C and t != ignore_label (pass a value
+ * outside [0, C), e.g. -1, for "no ignore label"); every other voxel enters no sum and gets a zero gradient.
+ *   L_region = sum_c wdice_c (1 - mean_n d[n,c]),  d = (2 sum p_c t_c + 1e-5) / (sum p_c + sum t_c + 1e-5): soft Dice,
+ *              no gate, non-squared denominator; batch_dice != 0 sums over n before the ratio.  wdice: C floats, already
+ *              normalised over the included classes, 0 for an excluded class.
+ *   L_dist   = sum alpha_t (1 - pt)^gamma (-log pt) / sum alpha_t,  pt = max(p_t, 1e-12); 0 when no voxel counts.
+ * A term whose weight is 0 does not enter L.  One pass over probs and target, no atomics, fp64 finalize in fixed order.
+ * part: seg3d_compound_loss_part_floats(N, C, S) floats of workspace; loss: 3 floats (L, L_region, L_dist);
+ * coef: 2 * R * C + 1 floats kept for the backward, R = batch_dice ? 1 : N -- per (r, c) the pair (A, B) with
+ * dL_region/dp[n,c,s] = A t_c + B on counted voxels, then ce_weight / sum alpha_t (0 when that term is off or empty). */
+long long seg3d_compound_loss_part_floats(int N, int C, long long S);
+int seg3d_compound_loss_fwd(const float* probs, const float* target, const float* wdice, const float* alpha, float* part,
+                            float* coef, float* loss, int N, int C, long long S, float gamma, float dice_weight,
+                            float ce_weight, int batch_dice, float ignore_label, void* stream);
+/* dprobs[n][c][s] = gout[0] * dL/dp: all C planes in one pass, zeros on voxels that do not count; the distribution part
+ * sits on the plane c == t and is 0 where p_t < 1e-12 (the clamp's gradient). */
+int seg3d_compound_loss_bwd(const float* probs, const float* target, const float* coef, const float* alpha,
+                            const float* gout, float* dprobs, int N, int C, long long S, float gamma, int batch_dice,
+                            float ignore_label, void* stream);
 
 /* ---- optimizer: optim.Adam(...).step()  (core/seg_train.py:83,127) -------------------------------------------------- */
 int seg3d_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long long n, int step, float lr,

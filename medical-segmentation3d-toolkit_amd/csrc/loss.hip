@@ -1,4 +1,5 @@
-// loss.hip -- channel softmax (network head), multi-class Dice loss, Focal loss; forward + backward.
+// loss.hip -- channel softmax (network head), multi-class Dice loss, Focal loss, compound soft-Dice + CE / focal loss;
+// forward + backward.
 //
 // Reference semantics restated (file:line relative to /root/reference/segmentation3d):
 //   * nn.Softmax(dim=1) at the end of OutputBlock                     network/module/vnet_outblock.py:18,23
@@ -393,5 +394,349 @@ extern "C" int seg3d_focal_bwd(const float* probs, const float* target, const fl
                      alpha, gout, dprobs, C, (i64)S, total, (i64)sn, (i64)sc, (i64)ss, gamma,
                      size_average ? (float)(1.0 / (double)total) : 1.0f);
   SEG3D_LAUNCH_CHECK("seg3d_focal_bwd");
+  return SEG3D_OK;
+}
+
+// ---- compound loss: soft Dice (no gate, non-squared denominator) + cross-entropy / focal on probabilities --------------
+// (no counterpart in the reference; definitions in DESIGN.md section 7, row f7)
+//   valid voxel v = [t != ignore][0 <= t < C];  t_c = [t == c];  every sum below carries v
+//   region:        I[n,c] = sum p_c t_c,  U[n,c] = sum p_c + sum t_c,  d = (2 I + 1e-5) / (U + 1e-5),
+//                  L_region = sum_c w'_c (1 - mean_n d[n,c])      (batch_dice: I, U summed over n first, one d per class)
+//   distribution:  pt = max(p_t, 1e-12),  L_dist = sum a_t (1 - pt)^gamma (-log pt) / sum a_t      (0 when nothing is valid)
+//   L = dice_weight * L_region + ce_weight * L_dist; a term whose weight is 0 never enters L.
+// w' (normalised over the included classes, 0 for an excluded background) and a come from the host.
+// Forward: ONE pass reads target + all C planes and leaves 3C + 2 partial sums per workgroup; a one-workgroup fp64
+// finalize in fixed order writes the three loss figures and, instead of the raw sums, the coefficients the backward
+// multiplies with -- the region derivative does not depend on p (non-squared denominator):
+//   dL/dp[n,c,s] = v (A[r,c] t_c + B[r,c]) + [c == t] v coef_dist a_t d/dpt[(1 - pt)^gamma (-log pt)] [p_t >= 1e-12]
+//   A = -dice_weight w'_c k 2 / (U + eps),  B = dice_weight w'_c k (2 I + eps) / (U + eps)^2,  k = 1/N (r = n) or 1 (batch_dice, r = 0)
+//   coef_dist = ce_weight / sum a_t  (0 when nothing is valid or ce_weight is 0)
+// CT is the compile-time class count (1..5: exact, accumulators in registers; 16: generic, planes c >= C predicated
+// off); VEC: S % 4 == 0 and 16-byte aligned bases -> one 16-byte access per lane and plane, else a scalar path.
+#define COMPOUND_EPS 1e-5
+#define COMPOUND_PMIN 1e-12f
+
+template <int CT>
+struct CompoundAcc {
+  float r[3 * CT];   // (I, P, T) per class
+  float num, den;    // distribution numerator / denominator
+};
+
+// (1 - pt)^gamma (-log pt) for pt already clamped; q = max(1 - pt, 0)
+__device__ __forceinline__ float compound_dist(float pt, float gamma) {
+  const float nl = -logf(pt);
+  if (gamma == 0.0f) return nl;
+  return focal_pow(fmaxf(1.0f - pt, 0.0f), gamma) * nl;
+}
+
+// d/dpt of the above:  gamma q^(gamma-1) log pt - q^gamma / pt   (q = 0: the first product's limit is 0 for every gamma > 0)
+__device__ __forceinline__ float compound_dist_grad(float pt, float gamma) {
+  if (gamma == 0.0f) return -1.0f / pt;
+  const float q = fmaxf(1.0f - pt, 0.0f), lp = logf(pt);
+  float qg1;
+  if (gamma == 2.0f) qg1 = q;
+  else if (gamma == 1.0f) qg1 = 1.0f;
+  else qg1 = q > 0.0f ? powf(q, gamma - 1.0f) : 0.0f;
+  return gamma * qg1 * lp - focal_pow(q, gamma) / pt;
+}
+
+template <int CT>
+__device__ __forceinline__ void compound_voxel(CompoundAcc<CT>& a, float t, const float (&p)[CT], const float (&alpha)[CT],
+                                               int C, float ignore, float gamma) {
+  const bool valid = t >= 0.0f && t < (float)C && t != ignore;
+  if (!valid) return;
+  const int ti = (int)t;
+  float pt = 0.f, at = 0.f;
+#pragma unroll
+  for (int c = 0; c < CT; ++c)
+    if (CT <= 5 || c < C) {
+      const bool is = ti == c;
+      a.r[3 * c + 0] += is ? p[c] : 0.f;
+      a.r[3 * c + 1] += p[c];
+      a.r[3 * c + 2] += is ? 1.f : 0.f;
+      pt = is ? p[c] : pt;
+      at = is ? alpha[c] : at;
+    }
+  a.num += at * compound_dist(fmaxf(pt, COMPOUND_PMIN), gamma);
+  a.den += at;
+}
+
+// part[n][blk][3C + 2] = (I, P, T) x C, dist numerator, dist denominator over the block's voxels
+template <int CT, bool VEC>
+__global__ __launch_bounds__(256) void compound_partial_kernel(const float* __restrict__ probs,
+                                                                 const float* __restrict__ target,
+                                                                 const float* __restrict__ alpha_g, float* __restrict__ part,
+                                                                 int C, i64 S, int nblk, float ignore, float gamma) {
+  __shared__ float red[4 * 3];
+  const int n = blockIdx.y;
+  const i64 s0 = (i64)blockIdx.x * DICE_VPB;
+  i64 s1 = s0 + DICE_VPB;
+  if (s1 > S) s1 = S;
+  const float* tg = target + (i64)n * S;
+  const float* pb = probs + (i64)n * C * S;
+  float alpha[CT];
+#pragma unroll
+  for (int c = 0; c < CT; ++c) alpha[c] = (CT <= 5 || c < C) ? alpha_g[c] : 0.f;
+  CompoundAcc<CT> a;
+#pragma unroll
+  for (int k = 0; k < 3 * CT; ++k) a.r[k] = 0.f;
+  a.num = 0.f;
+  a.den = 0.f;
+  if constexpr (VEC) {
+    for (i64 s = s0 + (i64)threadIdx.x * 4; s < s1; s += 256 * 4) {   // s1 is a multiple of 4 here (S % 4 == 0)
+      const float4 t4 = *reinterpret_cast<const float4*>(tg + s);
+      float4 p4[CT];
+#pragma unroll
+      for (int c = 0; c < CT; ++c)
+        if (CT <= 5 || c < C) p4[c] = *reinterpret_cast<const float4*>(pb + (i64)c * S + s);
+      float p[CT];
+#pragma unroll
+      for (int c = 0; c < CT; ++c) p[c] = (CT <= 5 || c < C) ? p4[c].x : 0.f;
+      compound_voxel<CT>(a, t4.x, p, alpha, C, ignore, gamma);
+#pragma unroll
+      for (int c = 0; c < CT; ++c) p[c] = (CT <= 5 || c < C) ? p4[c].y : 0.f;
+      compound_voxel<CT>(a, t4.y, p, alpha, C, ignore, gamma);
+#pragma unroll
+      for (int c = 0; c < CT; ++c) p[c] = (CT <= 5 || c < C) ? p4[c].z : 0.f;
+      compound_voxel<CT>(a, t4.z, p, alpha, C, ignore, gamma);
+#pragma unroll
+      for (int c = 0; c < CT; ++c) p[c] = (CT <= 5 || c < C) ? p4[c].w : 0.f;
+      compound_voxel<CT>(a, t4.w, p, alpha, C, ignore, gamma);
+    }
+  } else {
+    for (i64 s = s0 + threadIdx.x; s < s1; s += 256) {
+      const float t = tg[s];
+      float p[CT];
+#pragma unroll
+      for (int c = 0; c < CT; ++c) p[c] = (CT <= 5 || c < C) ? pb[(i64)c * S + s] : 0.f;
+      compound_voxel<CT>(a, t, p, alpha, C, ignore, gamma);
+    }
+  }
+  float* dst = part + ((i64)n * nblk + blockIdx.x) * (3 * C + 2);
+#pragma unroll
+  for (int c = 0; c < CT; ++c)
+    if (CT <= 5 || c < C) {
+      float v[3] = {a.r[3 * c + 0], a.r[3 * c + 1], a.r[3 * c + 2]};
+      block_sum_256<3>(v, red);
+      if (threadIdx.x == 0) { dst[3 * c + 0] = v[0]; dst[3 * c + 1] = v[1]; dst[3 * c + 2] = v[2]; }
+    }
+  float v[2] = {a.num, a.den};
+  block_sum_256<2>(v, red);
+  if (threadIdx.x == 0) { dst[3 * C + 0] = v[0]; dst[3 * C + 1] = v[1]; }
+}
+
+// One workgroup, fp64, fixed order.  First all 256 threads stride over the N * nblk distribution pairs; then, as in
+// dice_finalize_kernel, 32 lanes per region item -- (n, c) over the sample's nblk blocks, or with batch_dice c over all
+// N * nblk blocks -- and a fixed-shape shuffle tree.  coef: [R][C][2] = (A, B) then one float coef_dist (R = batch_dice ? 1 : N);
+// loss[3] = (L, L_region, L_dist).
+__global__ __launch_bounds__(256) void compound_finalize_kernel(const float* __restrict__ part,
+                                                                  const float* __restrict__ wdice, float* __restrict__ coef,
+                                                                  float* __restrict__ loss, int N, int C, int nblk,
+                                                                  int batch_dice, float dice_weight, float ce_weight) {
+  __shared__ double red[8], redd[8];
+  const int NV = 3 * C + 2;
+  const i64 nent = (i64)N * nblk;
+  double num = 0.0, den = 0.0;
+  for (i64 m = threadIdx.x; m < nent; m += 256) {
+    num += (double)part[m * NV + 3 * C + 0];
+    den += (double)part[m * NV + 3 * C + 1];
+  }
+  num = wave_sum_d(num);
+  den = wave_sum_d(den);
+  if ((threadIdx.x & 63) == 0) {
+    red[threadIdx.x >> 6] = num;
+    redd[threadIdx.x >> 6] = den;
+  }
+  __syncthreads();
+  num = red[0] + red[1] + red[2] + red[3];   // every thread holds the same totals
+  den = redd[0] + redd[1] + redd[2] + redd[3];
+  __syncthreads();
+
+  const int grp = threadIdx.x >> 5, l32 = threadIdx.x & 31;
+  const int R = batch_dice ? 1 : N;
+  const i64 cnt = batch_dice ? nent : (i64)nblk;
+  const double k = batch_dice ? 1.0 : 1.0 / (double)N;
+  double acc = 0.0;
+  for (int idx0 = 0; idx0 < R * C; idx0 += 8) {   // uniform trip count: the shuffles below need whole waves
+    const int idx = idx0 + grp;
+    const bool ok = idx < R * C;
+    const int r = ok ? idx / C : 0, c = ok ? idx % C : 0;
+    double I = 0.0, P = 0.0, T = 0.0;
+    if (ok) {
+      const float* p = part + (i64)r * nblk * NV + 3 * c;
+      for (i64 m = l32; m < cnt; m += 32) {
+        I += (double)p[m * NV + 0];
+        P += (double)p[m * NV + 1];
+        T += (double)p[m * NV + 2];
+      }
+    }
+#pragma unroll
+    for (int off = 16; off > 0; off >>= 1) {   // within the 32-lane group
+      I += __shfl_down(I, off, 32);
+      P += __shfl_down(P, off, 32);
+      T += __shfl_down(T, off, 32);
+    }
+    if (ok && l32 == 0) {
+      const double w = (double)wdice[c];
+      const double U = P + T + COMPOUND_EPS, nu = 2.0 * I + COMPOUND_EPS;
+      acc += w * k * (1.0 - nu / U);
+      const bool on = dice_weight > 0.f && w > 0.0;
+      coef[2 * idx + 0] = on ? (float)(-(double)dice_weight * w * k * 2.0 / U) : 0.f;
+      coef[2 * idx + 1] = on ? (float)((double)dice_weight * w * k * nu / (U * U)) : 0.f;
+    }
+  }
+  if (l32 == 0) red[grp] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double lr = 0.0;
+    for (int g = 0; g < 8; ++g) lr += red[g];
+    const double ld = den > 0.0 ? num / den : 0.0;
+    double l = 0.0;
+    if (dice_weight > 0.f) l += (double)dice_weight * lr;
+    if (ce_weight > 0.f) l += (double)ce_weight * ld;
+    loss[0] = (float)l;
+    loss[1] = (float)lr;
+    loss[2] = (float)ld;
+    coef[2 * R * C] = (ce_weight > 0.f && den > 0.0) ? (float)((double)ce_weight / den) : 0.f;
+  }
+}
+
+// one voxel's C gradients; g[c] is written for every c < C
+template <int CT>
+__device__ __forceinline__ void compound_voxel_grad(float (&g)[CT], float t, float pt_in, const float (&A)[CT],
+                                                    const float (&B)[CT], const float (&alpha)[CT], int C, float ignore,
+                                                    float gamma, float cd, float go) {
+  const bool valid = t >= 0.0f && t < (float)C && t != ignore;
+  const int ti = valid ? (int)t : -1;
+  float dt = 0.f;
+  if (valid && cd != 0.f && pt_in >= COMPOUND_PMIN) dt = cd * compound_dist_grad(pt_in, gamma);
+#pragma unroll
+  for (int c = 0; c < CT; ++c)
+    if (CT <= 5 || c < C) {
+      const bool is = ti == c;
+      const float d = (is ? A[c] + B[c] : B[c]) + (is ? alpha[c] * dt : 0.f);
+      g[c] = valid ? go * d : 0.f;
+    }
+}
+
+// grid (blocks, N): the sample -- and with it the coefficient row -- is uniform per workgroup
+template <int CT, bool VEC>
+__global__ __launch_bounds__(256) void compound_bwd_kernel(const float* __restrict__ probs, const float* __restrict__ target,
+                                                             const float* __restrict__ coef, const float* __restrict__ alpha_g,
+                                                             const float* __restrict__ gout, float* __restrict__ dprobs,
+                                                             int C, i64 S, int R, float ignore, float gamma) {
+  const int n = blockIdx.y;
+  const int r = R == 1 ? 0 : n;
+  const float go = gout[0];
+  const float cd = coef[2 * R * C];
+  float A[CT], B[CT], alpha[CT];
+#pragma unroll
+  for (int c = 0; c < CT; ++c) {
+    const bool on = CT <= 5 || c < C;
+    A[c] = on ? coef[2 * (r * C + c) + 0] : 0.f;
+    B[c] = on ? coef[2 * (r * C + c) + 1] : 0.f;
+    alpha[c] = on ? alpha_g[c] : 0.f;
+  }
+  const float* tg = target + (i64)n * S;
+  const float* pb = probs + (i64)n * C * S;
+  float* db = dprobs + (i64)n * C * S;
+  if constexpr (VEC) {
+    for (i64 s = ((i64)blockIdx.x * 256 + threadIdx.x) * 4; s < S; s += (i64)gridDim.x * 256 * 4) {
+      const float4 t4 = *reinterpret_cast<const float4*>(tg + s);
+      const float tt[4] = {t4.x, t4.y, t4.z, t4.w};
+      float pt[4] = {0.f, 0.f, 0.f, 0.f};
+      if constexpr (CT <= 5) {   // all planes with 16-byte loads, p_t picked in registers
+#pragma unroll
+        for (int c = 0; c < CT; ++c) {
+          const float4 p4 = *reinterpret_cast<const float4*>(pb + (i64)c * S + s);
+          pt[0] = tt[0] == (float)c ? p4.x : pt[0];
+          pt[1] = tt[1] == (float)c ? p4.y : pt[1];
+          pt[2] = tt[2] == (float)c ? p4.z : pt[2];
+          pt[3] = tt[3] == (float)c ? p4.w : pt[3];
+        }
+      } else {                   // many planes: gather the one probability each voxel needs
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if (tt[j] >= 0.0f && tt[j] < (float)C) pt[j] = pb[(i64)(int)tt[j] * S + s + j];
+      }
+      float g[4][CT];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) compound_voxel_grad<CT>(g[j], tt[j], pt[j], A, B, alpha, C, ignore, gamma, cd, go);
+#pragma unroll
+      for (int c = 0; c < CT; ++c)
+        if (CT <= 5 || c < C)
+          *reinterpret_cast<float4*>(db + (i64)c * S + s) = make_float4(g[0][c], g[1][c], g[2][c], g[3][c]);
+    }
+  } else {
+    for (i64 s = (i64)blockIdx.x * 256 + threadIdx.x; s < S; s += (i64)gridDim.x * 256) {
+      const float t = tg[s];
+      float pt = 0.f;
+      if (t >= 0.0f && t < (float)C) pt = pb[(i64)(int)t * S + s];
+      float g[CT];
+      compound_voxel_grad<CT>(g, t, pt, A, B, alpha, C, ignore, gamma, cd, go);
+#pragma unroll
+      for (int c = 0; c < CT; ++c)
+        if (CT <= 5 || c < C) db[(i64)c * S + s] = g[c];
+    }
+  }
+}
+
+static inline bool compound_vec_ok(long long S, const void* a, const void* b, const void* c) {
+  return S % 4 == 0 && (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) == 0;
+}
+
+#define COMPOUND_DISPATCH(KERNEL, C, vec, ...)                                         \
+  do {                                                                                 \
+    switch (C) {                                                                       \
+      case 1: if (vec) KERNEL<1, true> __VA_ARGS__; else KERNEL<1, false> __VA_ARGS__; break;    \
+      case 2: if (vec) KERNEL<2, true> __VA_ARGS__; else KERNEL<2, false> __VA_ARGS__; break;    \
+      case 3: if (vec) KERNEL<3, true> __VA_ARGS__; else KERNEL<3, false> __VA_ARGS__; break;    \
+      case 4: if (vec) KERNEL<4, true> __VA_ARGS__; else KERNEL<4, false> __VA_ARGS__; break;    \
+      case 5: if (vec) KERNEL<5, true> __VA_ARGS__; else KERNEL<5, false> __VA_ARGS__; break;    \
+      default: if (vec) KERNEL<SEG3D_MAXC, true> __VA_ARGS__; else KERNEL<SEG3D_MAXC, false> __VA_ARGS__; break; \
+    }                                                                                  \
+  } while (0)
+
+extern "C" long long seg3d_compound_loss_part_floats(int N, int C, long long S) {
+  return (long long)N * seg3d_dice_blocks(S) * (3 * C + 2);
+}
+
+extern "C" int seg3d_compound_loss_fwd(const float* probs, const float* target, const float* wdice, const float* alpha,
+                                       float* part, float* coef, float* loss, int N, int C, long long S, float gamma,
+                                       float dice_weight, float ce_weight, int batch_dice, float ignore_label, void* stream) {
+  SEG3D_REQUIRE(probs && target && wdice && alpha && part && coef && loss && N > 0 && N <= 65535 && S > 0,
+                "seg3d_compound_loss_fwd: bad arguments");
+  SEG3D_REQUIRE(C >= 1 && C <= SEG3D_MAXC, "seg3d_compound_loss_fwd: num_class %d not in [1, %d]", C, SEG3D_MAXC);
+  SEG3D_REQUIRE(gamma >= 0.f && dice_weight >= 0.f && ce_weight >= 0.f && (dice_weight > 0.f || ce_weight > 0.f),
+                "seg3d_compound_loss_fwd: gamma and the term weights must be >= 0 and the weights not both 0");
+  const int nblk = (int)seg3d_dice_blocks(S);
+  const bool vec = compound_vec_ok(S, probs, target, probs);
+  hipStream_t s = (hipStream_t)stream;
+  COMPOUND_DISPATCH(compound_partial_kernel, C, vec,
+                    <<<dim3(nblk, N), dim3(256), 0, s>>>(probs, target, alpha, part, C, (i64)S, nblk, ignore_label, gamma));
+  SEG3D_LAUNCH_CHECK("seg3d_compound_loss_fwd(partial)");
+  compound_finalize_kernel<<<dim3(1), dim3(256), 0, s>>>(part, wdice, coef, loss, N, C, nblk, batch_dice ? 1 : 0,
+                                                         dice_weight, ce_weight);
+  SEG3D_LAUNCH_CHECK("seg3d_compound_loss_fwd(finalize)");
+  return SEG3D_OK;
+}
+
+extern "C" int seg3d_compound_loss_bwd(const float* probs, const float* target, const float* coef, const float* alpha,
+                                       const float* gout, float* dprobs, int N, int C, long long S, float gamma,
+                                       int batch_dice, float ignore_label, void* stream) {
+  SEG3D_REQUIRE(probs && target && coef && alpha && gout && dprobs && N > 0 && N <= 65535 && S > 0,
+                "seg3d_compound_loss_bwd: bad arguments");
+  SEG3D_REQUIRE(C >= 1 && C <= SEG3D_MAXC, "seg3d_compound_loss_bwd: num_class %d not in [1, %d]", C, SEG3D_MAXC);
+  SEG3D_REQUIRE(gamma >= 0.f, "seg3d_compound_loss_bwd: gamma must be >= 0");
+  const bool vec = compound_vec_ok(S, probs, target, dprobs);
+  const i64 items = vec ? S / 4 : S;
+  i64 gx = (items + 255) / 256, cap = 8192 / N;
+  if (cap < 1) cap = 1;
+  if (gx > cap) gx = cap;
+  const int R = batch_dice ? 1 : N;
+  COMPOUND_DISPATCH(compound_bwd_kernel, C, vec,
+                    <<<dim3((unsigned)gx, N), dim3(256), 0, (hipStream_t)stream>>>(probs, target, coef, alpha, gout, dprobs, C,
+                                                                                  (i64)S, R, ignore_label, gamma));
+  SEG3D_LAUNCH_CHECK("seg3d_compound_loss_bwd");
   return SEG3D_OK;
 }

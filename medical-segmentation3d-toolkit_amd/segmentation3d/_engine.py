@@ -149,6 +149,9 @@ _SIGNATURES = {
     'seg3d_focal_blocks': (_c_ll, [_c_ll]),
     'seg3d_focal_fwd': (_c_int, [_c_p] * 5 + [_c_int, _c_int, _c_ll, _c_ll, _c_ll, _c_ll, _c_f, _c_int, _c_p]),
     'seg3d_focal_bwd': (_c_int, [_c_p] * 5 + [_c_int, _c_int, _c_ll, _c_ll, _c_ll, _c_ll, _c_f, _c_int, _c_p]),
+    'seg3d_compound_loss_part_floats': (_c_ll, [_c_int, _c_int, _c_ll]),
+    'seg3d_compound_loss_fwd': (_c_int, [_c_p] * 7 + [_c_int, _c_int, _c_ll, _c_f, _c_f, _c_f, _c_int, _c_f, _c_p]),
+    'seg3d_compound_loss_bwd': (_c_int, [_c_p] * 6 + [_c_int, _c_int, _c_ll, _c_f, _c_int, _c_f, _c_p]),
     'seg3d_adam_step': (_c_int, [_c_p] * 4 + [_c_ll, _c_int] + [_c_f] * 6 + [_c_p]),
     'seg3d_adam_step_devstep': (_c_int, [_c_p] * 4 + [_c_ll, _c_p, _c_p] + [_c_f] * 6 + [_c_p]),
     'seg3d_patch_stats_blocks': (_c_ll, [_c_int] * 3),

@@ -1314,6 +1314,47 @@ class DiceLossFunction(torch.autograd.Function):
         return dp, None, None
 
 
+class CompoundLossFunction(torch.autograd.Function):
+    """DiceCELoss.forward (loss/compound_loss.py): soft Dice + cross-entropy / focal with an ignore label as one fused
+    reduction + one elementwise backward.  `wdice` are the region weights normalised over the included classes (0 for an
+    excluded class), `alpha` the cross-entropy class weights; `ignore` is a float outside [0, C) for "no ignore label".
+    Returns (loss, terms): the 0-dim loss and the device tensor (L, L_region, L_dist), which carries no gradient."""
+
+    @staticmethod
+    def forward(ctx, probs, target, wdice, alpha, gamma, dice_weight, ce_weight, batch_dice, ignore):
+        E.require_device(probs, target, wdice, alpha)
+        if probs.dtype != torch.float32:
+            raise ValueError('probabilities must be float32, got {}'.format(probs.dtype))
+        p = probs.contiguous()
+        t = target.contiguous().float()
+        N, C = p.shape[0], p.shape[1]
+        S = p[0, 0].numel()
+        if t.numel() != N * S:
+            raise ValueError('target shape {} does not match input {}'.format(tuple(target.shape), tuple(probs.shape)))
+        cfg = (float(gamma), int(bool(batch_dice)), float(ignore))
+        part = _empty((E.query('seg3d_compound_loss_part_floats', N, C, S),), p)
+        coef = _empty((2 * (1 if cfg[1] else N) * C + 1,), p)
+        terms = _empty((3,), p)
+        E.call('seg3d_compound_loss_fwd', E.ptr(p), E.ptr(t), E.ptr(wdice), E.ptr(alpha), E.ptr(part), E.ptr(coef),
+               E.ptr(terms), N, C, S, cfg[0], float(dice_weight), float(ce_weight), cfg[1], cfg[2], E.stream_ptr())
+        ctx.save_for_backward(p, t, coef, alpha)
+        ctx.cfg = cfg
+        ctx.mark_non_differentiable(terms)
+        return terms[0], terms
+
+    @staticmethod
+    def backward(ctx, gout, _gterms):
+        p, t, coef, alpha = ctx.saved_tensors
+        gamma, batch_dice, ignore = ctx.cfg
+        N, C = p.shape[0], p.shape[1]
+        S = p[0, 0].numel()
+        g = gout.contiguous().reshape(1).float()
+        dp = torch.empty_like(p)
+        E.call('seg3d_compound_loss_bwd', E.ptr(p), E.ptr(t), E.ptr(coef), E.ptr(alpha), E.ptr(g), E.ptr(dp), N, C, S,
+               gamma, batch_dice, ignore, E.stream_ptr())
+        return (dp,) + (None,) * 8
+
+
 class BinaryDiceLossFunction(torch.autograd.Function):
     """BinaryDiceLoss.forward called on its own (loss/binary_dice_loss.py:9-36): one fused reduction + one elementwise
     backward; probs [N, 2, ...], float target with N * S elements"""

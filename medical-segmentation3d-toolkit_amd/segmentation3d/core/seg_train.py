@@ -17,14 +17,21 @@ import torch.distributed as dist
 
 from segmentation3d import _ops
 from segmentation3d.core.ddp import GradientReducer
+from segmentation3d.loss.compound_loss import DiceCELoss
 from segmentation3d.loss.cross_entropy_loss import CrossEntropyLoss
 from segmentation3d.loss.focal_loss import FocalLoss
 from segmentation3d.loss.multi_dice_loss import MultiDiceLoss
 from segmentation3d.optim.fused_adam import FusedAdam
 
 
-def build_loss(name, num_classes, obj_weight=None, focal_gamma=2, use_gpu=True):
-    """loss selection of core/seg_train.py:91-102"""
+def build_loss(name, num_classes, obj_weight=None, focal_gamma=2, use_gpu=True, dice_weight=1.0, ce_weight=1.0,
+               include_background=True, batch_dice=False, ignore_label=None):
+    """loss selection of core/seg_train.py:91-102, plus the compound losses 'DiceCE' (soft Dice + cross-entropy) and
+    'DiceFocal' (soft Dice + focal with focal_gamma); the keyword options after use_gpu apply to those two only"""
+    if name in ('DiceCE', 'DiceFocal'):
+        return DiceCELoss(num_classes, weights=obj_weight, dice_weight=dice_weight, ce_weight=ce_weight,
+                          gamma=focal_gamma if name == 'DiceFocal' else 0.0, include_background=include_background,
+                          batch_dice=batch_dice, ignore_label=ignore_label, use_gpu=use_gpu)
     if name == 'Focal':
         return FocalLoss(class_num=num_classes, alpha=obj_weight, gamma=focal_gamma, use_gpu=use_gpu)
     if name == 'Dice':
@@ -35,11 +42,22 @@ def build_loss(name, num_classes, obj_weight=None, focal_gamma=2, use_gpu=True):
     raise ValueError('Unknown loss function')
 
 
+def loss_options_from_config(loss_cfg):
+    """the optional keys of the config's `loss` section that the compound losses read, with their defaults (a config
+    without them -- every reference config -- loads unchanged)"""
+    return {'dice_weight': getattr(loss_cfg, 'dice_weight', 1.0), 'ce_weight': getattr(loss_cfg, 'ce_weight', 1.0),
+            'include_background': getattr(loss_cfg, 'include_background', True),
+            'batch_dice': getattr(loss_cfg, 'batch_dice', False), 'ignore_label': getattr(loss_cfg, 'ignore_label', None)}
+
+
 class TrainStep(object):
-    """network + loss + FusedAdam (+ gradient reducer when distributed) on one device"""
+    """network + loss + FusedAdam (+ gradient reducer when distributed) on one device; `loss_options` is a dict of
+    build_loss's keyword options for the compound losses (dice_weight, ce_weight, include_background, batch_dice,
+    ignore_label)"""
 
     def __init__(self, net_name, in_channels, num_classes, loss_name='Dice', obj_weight=None, focal_gamma=2, lr=1e-4,
-                 betas=(0.9, 0.999), device=None, seed=0, distributed=None, num_buckets=4, use_graph=False):
+                 betas=(0.9, 0.999), device=None, seed=0, distributed=None, num_buckets=4, use_graph=False,
+                 loss_options=None):
         self.device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
         if self.device.type == 'cuda' and self.device.index is not None:
             torch.cuda.set_device(self.device)   # the engine launches on the current device's stream (_engine.stream_ptr)
@@ -51,7 +69,7 @@ class TrainStep(object):
         self.net = self.net.to(self.device)
         self.opt = FusedAdam(self.net.parameters(), lr=lr, betas=betas)                 # core/seg_train.py:83
         _ops.weight_cache(True)   # packed conv weights are refreshed by FusedAdam.step() with one launch per step
-        self.loss_func = build_loss(loss_name, num_classes, obj_weight, focal_gamma, use_gpu=True)
+        self.loss_func = build_loss(loss_name, num_classes, obj_weight, focal_gamma, use_gpu=True, **(loss_options or {}))
         if distributed is None:
             distributed = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
         self.reducer = None
@@ -184,7 +202,8 @@ def train(train_config_file, data_iter_factory=None):
     _ops.set_activation_dtype(str(getattr(cfg.train, 'compute_dtype', 'fp32')))
     step = TrainStep(cfg.net.name, num_modality, cfg.dataset.num_classes, cfg.loss.name, cfg.loss.obj_weight,
                      cfg.loss.focal_gamma, cfg.train.lr, tuple(cfg.train.betas), seed=cfg.general.seed,
-                     use_graph=bool(getattr(cfg.train, 'use_graph', False)))
+                     use_graph=bool(getattr(cfg.train, 'use_graph', False)),
+                     loss_options=loss_options_from_config(cfg.loss))
     assert np.all(np.array(cfg.dataset.crop_size) % step.max_stride == 0), 'crop size not divisible by max stride'
     last_save_epoch, batch_idx = 0, 0
     if cfg.general.resume_epoch >= 0:
