@@ -452,6 +452,52 @@ int seg3d_resample_affine(const float* src, float* dst, int Xi, int Yi, int Zi, 
  * seg3d_resample_affine on plane m.  1 <= M <= 8. */
 int seg3d_resample_affine_mc(const float* src, float* dst, int M, long long dst_stride, int Xi, int Yi, int Zi, int Xo,
                              int Yo, int Zo, const double* affine_host, int linear, float pad, void* stream);
+/* ---- training augmentation (not in the reference) -----------------------------------------
+ * The two resampling entries with an elastic deformation of the sampled point:
+ *   c = M (x, y, z, 1) + L u(x', y', z'),  L = l_host, 9 doubles on the HOST (row-major 3 x 3, diag(1 / s_src) D_src^-1),
+ * u a displacement in millimetres (world axes): the tensor-product cubic B-spline over the control grid
+ * ctrl [gz][gy][gx][3] (DEVICE, float32, components x, y, z) laid over the destination grid.  Per axis a of n voxels with
+ * t_host[a] = crop spacing / control spacing (3 doubles on the HOST, each in [0, 1]): t = i * t_host[a], k = floor(t),
+ * f = t - k, u = sum_{j = 0..3} B_j(f) ctrl[k + j] with the uniform cubic basis B_0 = (1 - f)^3 / 6,
+ * B_1 = (3 f^3 - 6 f^2 + 4) / 6, B_2 = (-3 f^3 + 3 f^2 + 3 f + 1) / 6, B_3 = f^3 / 6; at least
+ * floor((n - 1) t_host[a]) + 4 control points per axis (checked).  (x', y', z') is the destination index with the axes of
+ * mirror_mask (bit 0 = x, 1 = y, 2 = z) reversed, n - 1 - i: pass the mirrored affine map (image_tools.mirror_index_affine)
+ * and the mask, and the result is the flip of the un-mirrored deformed crop.  A rotation is part of M.  The field is
+ * evaluated in double; inside test, interpolation and padding are those of the affine entries, a zero control grid gives
+ * their result bit for bit, and channel m of the _mc entry equals the planar entry on plane m bit for bit.  Per-axis
+ * weights and the control grid are staged in LDS (at most 64 KB: crop-sized grids). */
+int seg3d_resample_deform(const float* src, float* dst, int Xi, int Yi, int Zi, int Xo, int Yo, int Zo,
+                          const double* affine_host, int linear, float pad, const double* l_host, const float* ctrl,
+                          int gx, int gy, int gz, const double* t_host, int mirror_mask, void* stream);
+int seg3d_resample_deform_mc(const float* src, float* dst, int M, long long dst_stride, int Xi, int Yi, int Zi, int Xo,
+                             int Yo, int Zo, const double* affine_host, int linear, float pad, const double* l_host,
+                             const float* ctrl, int gx, int gy, int gz, const double* t_host, int mirror_mask,
+                             void* stream);
+/* Intensity augmentation of a normalised crop [Z][Y][X][M] (M = 1..8, channels-last; M = 1 is the planar crop), IN PLACE.
+ * Per modality m, with (mn, mx, mean) of the crop's channel m (min / max exact, mean from an fp64 sum in a fixed order):
+ *   brightness  y = x * brightness
+ *   contrast    y = clamp(mean + contrast * (y - mean), mn, mx)     (statistics after the brightness step)
+ *   gamma       [lo, hi] = the range after the contrast step; hi - lo >= 1e-7: r = (y - lo) / (hi - lo), r = 1 - r if
+ *               invert, r = r^gamma, r = 1 - r if invert, y = lo + r (hi - lo); otherwise unchanged
+ *   noise       y += sigma * n, n = sqrt(-2 ln u1) cos(2 pi u2), u1 = (r0 + 1) 2^-32, u2 = r1 2^-32, (r0, r1) the first two
+ *               outputs of Philox4x32-10 with key (seed_lo, seed_hi) and counter (v_lo, v_hi, m, 0), v = (z Y + y) X + x
+ * brightness, contrast, gamma > 0, sigma >= 0 (checked); a neutral parameter (1, 1, 1, 0) skips its step exactly, the two
+ * statistics launches run only when some modality has contrast or gamma on, and nothing is launched when all is
+ * neutral.  workspace: seg3d_augment_intensity_workspace_doubles doubles (may be NULL without contrast / gamma).
+ * grid_blocks: workgroups of the apply pass, 0 = default; the result does not depend on it.  No atomics, no allocation,
+ * no host sync: two runs are bit-equal and the call is capturable. */
+typedef struct Seg3dIntensity {
+  float brightness, contrast, gamma;
+  int invert;
+  float sigma;
+} Seg3dIntensity;
+typedef struct Seg3dIntensityParams {
+  Seg3dIntensity m[8];
+  unsigned int seed_lo, seed_hi;
+} Seg3dIntensityParams;
+long long seg3d_augment_intensity_workspace_doubles(int X, int Y, int Z, int M);
+int seg3d_augment_intensity(float* crop, double* workspace, int X, int Y, int Z, int M, Seg3dIntensityParams params,
+                            int grid_blocks, void* stream);
 /* box_device[6] initialised to {INT_MAX x3, -1 x3} -> inclusive (xmin, ymin, zmin, xmax, ymax, zmax) of the voxels whose
  * value is in labels_host (nlabels == 0: every voxel > 0); untouched when nothing is selected */
 int seg3d_mask_bounding_box(const signed char* mask, int X, int Y, int Z, const int* labels_host, int nlabels,

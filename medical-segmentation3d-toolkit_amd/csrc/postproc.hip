@@ -19,17 +19,115 @@ struct Affine12 {
   double m[12];  // c = M[:, :3] * (x, y, z) + M[:, 3], rows = (cx, cy, cz)
 };
 
+// ---- elastic deformation of the sampled point (training augmentation) ----------------------
+// c_src = M (i, 1) + L u(i'): u is a tensor-product cubic B-spline (millimetres, world axes) over a coarse control grid
+// laid over the destination grid, i' the destination index with the axes of `mirror` reversed (so that a mirrored deformed
+// crop is the flip of the plain one), L = diag(1 / s_src) D_src^-1.  Per axis of n voxels: t = i * (sp / h), k = floor(t),
+// f = t - k, u = sum_j B_j(f) ctrl[k + j], uniform cubic basis.  Everything in double, like the affine map.
+// DEFORM = false: an empty argument and no code -- the kernels below compile to what they were without the parameter.
+template <bool DEFORM>
+struct DeformArgs {};
+template <>
+struct DeformArgs<true> {
+  double L[9];        // row-major 3 x 3
+  double t[3];        // sp / h per axis (x, y, z)
+  const float* ctrl;  // [gz][gy][gx][3] control displacements (x, y, z components), device
+  int g[3];           // gx, gy, gz
+  int mirror;         // bit 0 = x, 1 = y, 2 = z
+};
+
+// LDS image of a launch (dynamic shared memory): per destination index of every axis the four basis weights (doubles) and
+// the first control index (they are constant along the other two axes, so they are computed once per workgroup, not per
+// voxel), then the control grid, which every voxel of the launch shares.
+struct DeformLds {
+  const double* w;   // [Xo + Yo + Zo][4]
+  const int* k;      // [Xo + Yo + Zo]
+  const float* ctrl; // [gz][gy][gx][3]
+};
+
+static inline size_t deform_lds_bytes(int Xo, int Yo, int Zo, const int* g) {
+  const size_t n = (size_t)Xo + Yo + Zo;
+  return n * 4 * sizeof(double) + n * sizeof(int) + (size_t)g[0] * g[1] * g[2] * 3 * sizeof(float);
+}
+
+__device__ __forceinline__ DeformLds deform_stage(double* smem, const DeformArgs<true>& dfm, int Xo, int Yo, int Zo) {
+  const int n = Xo + Yo + Zo;
+  double* w = smem;
+  int* k = reinterpret_cast<int*>(smem + 4 * n);
+  float* c = reinterpret_cast<float*>(k + n);
+  for (int e = threadIdx.x; e < n; e += blockDim.x) {
+    const int a = e < Xo ? 0 : (e < Xo + Yo ? 1 : 2);
+    const int i = e - (a == 0 ? 0 : (a == 1 ? Xo : Xo + Yo));
+    const double t = i * dfm.t[a];
+    double fl = floor(t);
+    int kk = (int)fl;
+    if (kk > dfm.g[a] - 4) kk = dfm.g[a] - 4;   // never taken for a grid the launcher accepted; keeps k + 3 < g regardless
+    if (kk < 0) kk = 0;
+    const double f = t - fl, f2 = f * f, f3 = f2 * f, o = 1.0 - f;
+    w[4 * e + 0] = o * o * o / 6.0;
+    w[4 * e + 1] = (3.0 * f3 - 6.0 * f2 + 4.0) / 6.0;
+    w[4 * e + 2] = (-3.0 * f3 + 3.0 * f2 + 3.0 * f + 1.0) / 6.0;
+    w[4 * e + 3] = f3 / 6.0;
+    k[e] = kk;
+  }
+  const int nc = dfm.g[0] * dfm.g[1] * dfm.g[2] * 3;
+  for (int e = threadIdx.x; e < nc; e += blockDim.x) c[e] = dfm.ctrl[e];
+  __syncthreads();
+  DeformLds l;
+  l.w = w;
+  l.k = k;
+  l.ctrl = c;
+  return l;
+}
+
+// adds L u(x', y', z') to the continuous source index (cx, cy, cz) of destination voxel (x, y, z)
+__device__ __forceinline__ void deform_apply(const DeformLds& l, const DeformArgs<true>& dfm, int x, int y, int z, int Xo,
+                                             int Yo, int Zo, double& cx, double& cy, double& cz) {
+  const int ex = (dfm.mirror & 1) ? Xo - 1 - x : x;
+  const int ey = Xo + ((dfm.mirror & 2) ? Yo - 1 - y : y);
+  const int ez = Xo + Yo + ((dfm.mirror & 4) ? Zo - 1 - z : z);
+  const int kx = l.k[ex], ky = l.k[ey], kz = l.k[ez];
+  const double* wx = l.w + 4 * ex;
+  const double* wy = l.w + 4 * ey;
+  const double* wz = l.w + 4 * ez;
+  const int gx = dfm.g[0], gy = dfm.g[1];
+  double ux = 0.0, uy = 0.0, uz = 0.0;
+#pragma unroll
+  for (int jz = 0; jz < 4; ++jz) {
+#pragma unroll
+    for (int jy = 0; jy < 4; ++jy) {
+      const float* row = l.ctrl + (((kz + jz) * gy + (ky + jy)) * gx + kx) * 3;
+      const double wzy = wz[jz] * wy[jy];
+#pragma unroll
+      for (int jx = 0; jx < 4; ++jx) {
+        const double wgt = wzy * wx[jx];
+        ux += wgt * (double)row[3 * jx + 0];
+        uy += wgt * (double)row[3 * jx + 1];
+        uz += wgt * (double)row[3 * jx + 2];
+      }
+    }
+  }
+  cx += dfm.L[0] * ux + dfm.L[1] * uy + dfm.L[2] * uz;
+  cy += dfm.L[3] * ux + dfm.L[4] * uy + dfm.L[5] * uz;
+  cz += dfm.L[6] * ux + dfm.L[7] * uy + dfm.L[8] * uz;
+}
+
+template <bool DEFORM>
 __global__ __launch_bounds__(256) void resample_affine_kernel(const float* __restrict__ src, float* __restrict__ dst, int Xi,
                                                                 int Yi, int Zi, int Xo, int Yo, int Zo, Affine12 A,
-                                                                int linear, float pad) {
+                                                                int linear, float pad, DeformArgs<DEFORM> dfm) {
+  extern __shared__ double deform_smem[];
+  DeformLds lds;
+  if constexpr (DEFORM) lds = deform_stage(deform_smem, dfm, Xo, Yo, Zo);
   const i64 total = (i64)Xo * Yo * Zo;
   for (i64 idx = (i64)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (i64)gridDim.x * 256) {
     const int x = (int)(idx % Xo);
     const i64 t = idx / Xo;
     const int y = (int)(t % Yo), z = (int)(t / Yo);
-    const double cx = A.m[0] * x + A.m[1] * y + A.m[2] * z + A.m[3];
-    const double cy = A.m[4] * x + A.m[5] * y + A.m[6] * z + A.m[7];
-    const double cz = A.m[8] * x + A.m[9] * y + A.m[10] * z + A.m[11];
+    double cx = A.m[0] * x + A.m[1] * y + A.m[2] * z + A.m[3];
+    double cy = A.m[4] * x + A.m[5] * y + A.m[6] * z + A.m[7];
+    double cz = A.m[8] * x + A.m[9] * y + A.m[10] * z + A.m[11];
+    if constexpr (DEFORM) deform_apply(lds, dfm, x, y, z, Xo, Yo, Zo, cx, cy, cz);
     float out = pad;
     if (cx >= -0.5 && cx < Xi - 0.5 && cy >= -0.5 && cy < Yi - 0.5 && cz >= -0.5 && cz < Zi - 0.5) {
       if (linear) {
@@ -66,9 +164,54 @@ extern "C" int seg3d_resample_affine(const float* src, float* dst, int Xi, int Y
   Affine12 A;
   for (int k = 0; k < 12; ++k) A.m[k] = affine_host[k];
   const i64 total = (i64)Xo * Yo * Zo;
-  hipLaunchKernelGGL(resample_affine_kernel, dim3(seg3d_ew_grid(total, 256)), dim3(256), 0, (hipStream_t)stream, src, dst, Xi,
-                     Yi, Zi, Xo, Yo, Zo, A, linear, pad);
+  hipLaunchKernelGGL(resample_affine_kernel<false>, dim3(seg3d_ew_grid(total, 256)), dim3(256), 0, (hipStream_t)stream, src,
+                     dst, Xi, Yi, Zi, Xo, Yo, Zo, A, linear, pad, DeformArgs<false>());
   SEG3D_LAUNCH_CHECK("seg3d_resample_affine");
+  return SEG3D_OK;
+}
+
+// host side of the two deform entries: checks and the by-value argument.  The control grid must cover every index the
+// kernel reads (k + 3 with k = floor((n - 1) * sp / h), evaluated here with the device's own arithmetic) and the LDS image
+// must fit the 64 KB a workgroup gets without opting in -- a training crop needs a few KB.
+static int deform_args(const char* name, int Xo, int Yo, int Zo, const double* l_host, const float* ctrl, int gx, int gy,
+                       int gz, const double* t_host, int mirror_mask, DeformArgs<true>* out) {
+  SEG3D_REQUIRE(l_host && ctrl && t_host, "%s: null pointer", name);
+  SEG3D_REQUIRE(mirror_mask >= 0 && mirror_mask <= 7, "%s: mirror mask %d outside 0..7", name, mirror_mask);
+  const int n[3] = {Xo, Yo, Zo}, g[3] = {gx, gy, gz};
+  for (int a = 0; a < 3; ++a) {
+    SEG3D_REQUIRE(t_host[a] >= 0.0 && t_host[a] <= 1.0, "%s: spacing / grid factor %g of axis %d outside [0, 1]", name,
+                  t_host[a], a);
+    const double last = floor((n[a] - 1) * t_host[a]);
+    SEG3D_REQUIRE(g[a] >= 4 && (double)g[a] >= last + 4.0 && g[a] <= 1024,
+                  "%s: %d control points on axis %d, floor((n - 1) sp / h) + 4 = %.0f are needed", name, g[a], a, last + 4.0);
+    out->t[a] = t_host[a];
+    out->g[a] = g[a];
+  }
+  SEG3D_REQUIRE(deform_lds_bytes(Xo, Yo, Zo, g) <= 64 * 1024,
+                "%s: weight tables + control grid need %zu bytes of LDS, 65536 are available (crop-sized grids only)", name,
+                deform_lds_bytes(Xo, Yo, Zo, g));
+  for (int k = 0; k < 9; ++k) out->L[k] = l_host[k];
+  out->ctrl = ctrl;
+  out->mirror = mirror_mask;
+  return SEG3D_OK;
+}
+
+// seg3d_resample_affine with the sampled point displaced by a cubic B-spline field: c = M (x, y, z, 1) + L u(x', y', z')
+extern "C" int seg3d_resample_deform(const float* src, float* dst, int Xi, int Yi, int Zi, int Xo, int Yo, int Zo,
+                                     const double* affine_host, int linear, float pad, const double* l_host,
+                                     const float* ctrl, int gx, int gy, int gz, const double* t_host, int mirror_mask,
+                                     void* stream) {
+  SEG3D_REQUIRE(src && dst && affine_host, "seg3d_resample_deform: null pointer");
+  SEG3D_REQUIRE(Xi > 0 && Yi > 0 && Zi > 0 && Xo > 0 && Yo > 0 && Zo > 0, "seg3d_resample_deform: bad dims");
+  DeformArgs<true> D;
+  const int rc = deform_args("seg3d_resample_deform", Xo, Yo, Zo, l_host, ctrl, gx, gy, gz, t_host, mirror_mask, &D);
+  if (rc != SEG3D_OK) return rc;
+  Affine12 A;
+  for (int k = 0; k < 12; ++k) A.m[k] = affine_host[k];
+  const i64 total = (i64)Xo * Yo * Zo;
+  hipLaunchKernelGGL(resample_affine_kernel<true>, dim3(seg3d_ew_grid(total, 256)), dim3(256),
+                     deform_lds_bytes(Xo, Yo, Zo, D.g), (hipStream_t)stream, src, dst, Xi, Yi, Zi, Xo, Yo, Zo, A, linear, pad, D);
+  SEG3D_LAUNCH_CHECK("seg3d_resample_deform");
   return SEG3D_OK;
 }
 
@@ -90,20 +233,25 @@ __device__ __forceinline__ void resample_mc_lerp(const float* t000, const float*
   out[m] = (float)(b0 + (b1 - b0) * dz);
 }
 
-template <int MC, bool VEC>
+template <int MC, bool VEC, bool DEFORM>
 __global__ __launch_bounds__(256) void resample_affine_mc_kernel(const float* __restrict__ src, float* __restrict__ dst,
                                                                    int Mrt, i64 dst_stride, int Xi, int Yi, int Zi, int Xo,
-                                                                   int Yo, int Zo, Affine12 A, int linear, float pad) {
+                                                                   int Yo, int Zo, Affine12 A, int linear, float pad,
+                                                                   DeformArgs<DEFORM> dfm) {
   constexpr int MR = MC > 0 ? MC : 8;          // register rows: MC, or the generic path's bound
   const int M = MC > 0 ? MC : Mrt;
+  extern __shared__ double deform_smem[];
+  DeformLds lds;
+  if constexpr (DEFORM) lds = deform_stage(deform_smem, dfm, Xo, Yo, Zo);
   const i64 total = (i64)Xo * Yo * Zo;
   for (i64 idx = (i64)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (i64)gridDim.x * 256) {
     const int x = (int)(idx % Xo);
     const i64 t = idx / Xo;
     const int y = (int)(t % Yo), z = (int)(t / Yo);
-    const double cx = A.m[0] * x + A.m[1] * y + A.m[2] * z + A.m[3];
-    const double cy = A.m[4] * x + A.m[5] * y + A.m[6] * z + A.m[7];
-    const double cz = A.m[8] * x + A.m[9] * y + A.m[10] * z + A.m[11];
+    double cx = A.m[0] * x + A.m[1] * y + A.m[2] * z + A.m[3];
+    double cy = A.m[4] * x + A.m[5] * y + A.m[6] * z + A.m[7];
+    double cz = A.m[8] * x + A.m[9] * y + A.m[10] * z + A.m[11];
+    if constexpr (DEFORM) deform_apply(lds, dfm, x, y, z, Xo, Yo, Zo, cx, cy, cz);
     float out[MR];
 #pragma unroll
     for (int m = 0; m < MR; ++m) out[m] = pad;
@@ -163,6 +311,35 @@ __global__ __launch_bounds__(256) void resample_affine_mc_kernel(const float* __
   }
 }
 
+template <bool DEFORM>
+static void resample_mc_launch(const float* src, float* dst, int M, i64 dst_stride, int Xi, int Yi, int Zi, int Xo, int Yo,
+                               int Zo, const Affine12& A, int lin, float pad, const DeformArgs<DEFORM>& D, size_t lds,
+                               hipStream_t s) {
+  const i64 total = (i64)Xo * Yo * Zo;
+  const dim3 grid(seg3d_ew_grid(total, 256)), block(256);
+  // vector rows need the source base / destination base and stride aligned to the row width
+  const bool vec4 = M == 4 && ((uintptr_t)src & 15) == 0 && ((uintptr_t)dst & 15) == 0 && dst_stride % 4 == 0;
+  const bool vec2 = M == 2 && ((uintptr_t)src & 7) == 0 && ((uintptr_t)dst & 7) == 0 && dst_stride % 2 == 0;
+  if (vec4)
+    hipLaunchKernelGGL((resample_affine_mc_kernel<4, true, DEFORM>), grid, block, lds, s, src, dst, M, dst_stride, Xi, Yi, Zi,
+                       Xo, Yo, Zo, A, lin, pad, D);
+  else if (M == 4)
+    hipLaunchKernelGGL((resample_affine_mc_kernel<4, false, DEFORM>), grid, block, lds, s, src, dst, M, dst_stride, Xi, Yi,
+                       Zi, Xo, Yo, Zo, A, lin, pad, D);
+  else if (vec2)
+    hipLaunchKernelGGL((resample_affine_mc_kernel<2, true, DEFORM>), grid, block, lds, s, src, dst, M, dst_stride, Xi, Yi, Zi,
+                       Xo, Yo, Zo, A, lin, pad, D);
+  else if (M == 2)
+    hipLaunchKernelGGL((resample_affine_mc_kernel<2, false, DEFORM>), grid, block, lds, s, src, dst, M, dst_stride, Xi, Yi,
+                       Zi, Xo, Yo, Zo, A, lin, pad, D);
+  else if (M == 3)
+    hipLaunchKernelGGL((resample_affine_mc_kernel<3, false, DEFORM>), grid, block, lds, s, src, dst, M, dst_stride, Xi, Yi,
+                       Zi, Xo, Yo, Zo, A, lin, pad, D);
+  else
+    hipLaunchKernelGGL((resample_affine_mc_kernel<0, false, DEFORM>), grid, block, lds, s, src, dst, M, dst_stride, Xi, Yi,
+                       Zi, Xo, Yo, Zo, A, lin, pad, D);
+}
+
 // src [Zi][Yi][Xi][M] -> rows of M floats at dst + voxel * dst_stride (dst_stride >= M floats); affine_host as above
 extern "C" int seg3d_resample_affine_mc(const float* src, float* dst, int M, long long dst_stride, int Xi, int Yi, int Zi,
                                         int Xo, int Yo, int Zo, const double* affine_host, int linear, float pad,
@@ -173,32 +350,30 @@ extern "C" int seg3d_resample_affine_mc(const float* src, float* dst, int M, lon
   SEG3D_REQUIRE(Xi > 0 && Yi > 0 && Zi > 0 && Xo > 0 && Yo > 0 && Zo > 0, "seg3d_resample_affine_mc: bad dims");
   Affine12 A;
   for (int k = 0; k < 12; ++k) A.m[k] = affine_host[k];
-  const i64 total = (i64)Xo * Yo * Zo;
-  const dim3 grid(seg3d_ew_grid(total, 256)), block(256);
-  hipStream_t s = (hipStream_t)stream;
-  const int lin = linear ? 1 : 0;
-  // vector rows need the source base / destination base and stride aligned to the row width
-  const bool vec4 = M == 4 && ((uintptr_t)src & 15) == 0 && ((uintptr_t)dst & 15) == 0 && dst_stride % 4 == 0;
-  const bool vec2 = M == 2 && ((uintptr_t)src & 7) == 0 && ((uintptr_t)dst & 7) == 0 && dst_stride % 2 == 0;
-  if (vec4)
-    hipLaunchKernelGGL((resample_affine_mc_kernel<4, true>), grid, block, 0, s, src, dst, M, (i64)dst_stride, Xi, Yi, Zi, Xo,
-                       Yo, Zo, A, lin, pad);
-  else if (M == 4)
-    hipLaunchKernelGGL((resample_affine_mc_kernel<4, false>), grid, block, 0, s, src, dst, M, (i64)dst_stride, Xi, Yi, Zi,
-                       Xo, Yo, Zo, A, lin, pad);
-  else if (vec2)
-    hipLaunchKernelGGL((resample_affine_mc_kernel<2, true>), grid, block, 0, s, src, dst, M, (i64)dst_stride, Xi, Yi, Zi, Xo,
-                       Yo, Zo, A, lin, pad);
-  else if (M == 2)
-    hipLaunchKernelGGL((resample_affine_mc_kernel<2, false>), grid, block, 0, s, src, dst, M, (i64)dst_stride, Xi, Yi, Zi,
-                       Xo, Yo, Zo, A, lin, pad);
-  else if (M == 3)
-    hipLaunchKernelGGL((resample_affine_mc_kernel<3, false>), grid, block, 0, s, src, dst, M, (i64)dst_stride, Xi, Yi, Zi,
-                       Xo, Yo, Zo, A, lin, pad);
-  else
-    hipLaunchKernelGGL((resample_affine_mc_kernel<0, false>), grid, block, 0, s, src, dst, M, (i64)dst_stride, Xi, Yi, Zi,
-                       Xo, Yo, Zo, A, lin, pad);
+  resample_mc_launch<false>(src, dst, M, (i64)dst_stride, Xi, Yi, Zi, Xo, Yo, Zo, A, linear ? 1 : 0, pad, DeformArgs<false>(),
+                            0, (hipStream_t)stream);
   SEG3D_LAUNCH_CHECK("seg3d_resample_affine_mc");
+  return SEG3D_OK;
+}
+
+// seg3d_resample_affine_mc with the deformation of seg3d_resample_deform: one field for all M channels; channel m equals
+// seg3d_resample_deform on plane m bit for bit (same coordinate code, same per-channel arithmetic)
+extern "C" int seg3d_resample_deform_mc(const float* src, float* dst, int M, long long dst_stride, int Xi, int Yi, int Zi,
+                                        int Xo, int Yo, int Zo, const double* affine_host, int linear, float pad,
+                                        const double* l_host, const float* ctrl, int gx, int gy, int gz,
+                                        const double* t_host, int mirror_mask, void* stream) {
+  SEG3D_REQUIRE(src && dst && affine_host, "seg3d_resample_deform_mc: null pointer");
+  SEG3D_REQUIRE(M >= 1 && M <= 8, "seg3d_resample_deform_mc: M = %d channels, 1..8 are supported", M);
+  SEG3D_REQUIRE(dst_stride >= M, "seg3d_resample_deform_mc: voxel stride %lld below M = %d", dst_stride, M);
+  SEG3D_REQUIRE(Xi > 0 && Yi > 0 && Zi > 0 && Xo > 0 && Yo > 0 && Zo > 0, "seg3d_resample_deform_mc: bad dims");
+  DeformArgs<true> D;
+  const int rc = deform_args("seg3d_resample_deform_mc", Xo, Yo, Zo, l_host, ctrl, gx, gy, gz, t_host, mirror_mask, &D);
+  if (rc != SEG3D_OK) return rc;
+  Affine12 A;
+  for (int k = 0; k < 12; ++k) A.m[k] = affine_host[k];
+  resample_mc_launch<true>(src, dst, M, (i64)dst_stride, Xi, Yi, Zi, Xo, Yo, Zo, A, linear ? 1 : 0, pad, D,
+                           deform_lds_bytes(Xo, Yo, Zo, D.g), (hipStream_t)stream);
+  SEG3D_LAUNCH_CHECK("seg3d_resample_deform_mc");
   return SEG3D_OK;
 }
 

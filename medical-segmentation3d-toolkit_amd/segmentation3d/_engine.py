@@ -25,6 +25,17 @@ class Normalizers(ctypes.Structure):
     """Seg3dNormalizers: up to 8 per-modality normalisers, passed BY VALUE to seg3d_patch_gather_normalize_mc"""
     _fields_ = [('n', Normalizer * 8)]
 
+
+
+class Intensity(ctypes.Structure):
+    """Seg3dIntensity: one modality's intensity augmentation (neutral: 1, 1, 1, 0, 0)"""
+    _fields_ = [('brightness', _c_f), ('contrast', _c_f), ('gamma', _c_f), ('invert', _c_int), ('sigma', _c_f)]
+
+
+class IntensityParams(ctypes.Structure):
+    """Seg3dIntensityParams: up to 8 per-modality parameter sets + the Philox key, BY VALUE to seg3d_augment_intensity"""
+    _fields_ = [('m', Intensity * 8), ('seed_lo', ctypes.c_uint), ('seed_hi', ctypes.c_uint)]
+
 # name -> (restype, argtypes); keep in sync with include/seg3d_hip.h (tests/test_abi.py checks every symbol)
 _SIGNATURES = {
     'seg3d_last_error': (ctypes.c_char_p, []),
@@ -46,6 +57,12 @@ _SIGNATURES = {
     'seg3d_pack_weights_mfma_multi': (_c_int, [_c_p, _c_int, _c_ll, _c_p]),
     'seg3d_resample_affine': (_c_int, [_c_p, _c_p] + [_c_int] * 6 + [_c_p, _c_int, _c_f, _c_p]),
     'seg3d_resample_affine_mc': (_c_int, [_c_p, _c_p, _c_int, _c_ll] + [_c_int] * 6 + [_c_p, _c_int, _c_f, _c_p]),
+    'seg3d_resample_deform': (_c_int, [_c_p, _c_p] + [_c_int] * 6 + [_c_p, _c_int, _c_f, _c_p, _c_p] + [_c_int] * 3
+                              + [_c_p, _c_int, _c_p]),
+    'seg3d_resample_deform_mc': (_c_int, [_c_p, _c_p, _c_int, _c_ll] + [_c_int] * 6 + [_c_p, _c_int, _c_f, _c_p, _c_p]
+                                 + [_c_int] * 3 + [_c_p, _c_int, _c_p]),
+    'seg3d_augment_intensity_workspace_doubles': (_c_ll, [_c_int] * 4),
+    'seg3d_augment_intensity': (_c_int, [_c_p, _c_p] + [_c_int] * 4 + [IntensityParams, _c_int, _c_p]),
     'seg3d_mask_bounding_box': (_c_int, [_c_p, _c_int, _c_int, _c_int, _c_p, _c_int, _c_p, _c_p]),
     'seg3d_ccl_workspace_ints': (_c_ll, [_c_ll]),
     'seg3d_ccl26_select': (_c_int, [_c_p] + [_c_int] * 8 + [_c_p, _c_p, _c_p]),

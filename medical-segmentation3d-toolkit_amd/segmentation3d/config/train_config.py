@@ -23,6 +23,25 @@ __C.dataset.random_translation = [15, 15, 15]             # mm, uniform in [-t, 
 __C.dataset.random_scale = [0.9, 1.1]                     # crop spacing = spacing * uniform(lo, hi)
 __C.dataset.random_mirror_axes = []                       # e.g. ['x', 'y']: mirror each listed axis with probability 1/2
 __C.dataset.interpolation = 'LINEAR'                   # NN | LINEAR
+# on-device training augmentation (an extension of this build, everything off: the crops and the RNG stream are then
+# exactly those without the section).  Rotation and elastic deformation run inside the crop's resampling launch, the
+# intensity transforms in one fused pass over the normalised crop.  A transform is on when its probability is > 0 and
+# its range is not neutral; an nnU-Net-like setting is noted behind each key.
+__C.dataset.augmentation = {}
+__C.dataset.augmentation.rotation_deg = [0, 0, 0]         # per-axis max angle (x, y, z), uniform in [-a, a]   ([30, 30, 30])
+__C.dataset.augmentation.rotation_prob = 1.0              #                                                     (0.2)
+__C.dataset.augmentation.elastic_grid_mm = 32.0           # control-point spacing of the cubic B-spline field
+__C.dataset.augmentation.elastic_magnitude_mm = [0, 0]    # control displacements uniform in [-a, a], a in [lo, hi]; hi < grid / 6   ([0, 4])
+__C.dataset.augmentation.elastic_prob = 0.0               #                                                     (0.2)
+__C.dataset.augmentation.brightness = [1, 1]              # multiplicative, uniform in [lo, hi]                 ([0.75, 1.25])
+__C.dataset.augmentation.brightness_prob = 0.0            #                                                     (0.15)
+__C.dataset.augmentation.contrast = [1, 1]                # about the crop's mean, range preserved              ([0.75, 1.25])
+__C.dataset.augmentation.contrast_prob = 0.0              #                                                     (0.15)
+__C.dataset.augmentation.gamma = [1, 1]                   # on the crop's range                                 ([0.7, 1.5])
+__C.dataset.augmentation.gamma_prob = 0.0                 #                                                     (0.3)
+__C.dataset.augmentation.gamma_invert_prob = 0.0          # gamma on the inverted range                         (0.25)
+__C.dataset.augmentation.noise_sigma = [0, 0]             # additive Gaussian noise on the normalised crop      ([0, 0.1])
+__C.dataset.augmentation.noise_prob = 0.0                 #                                                     (0.1)
 __C.dataset.crop_normalizers = [AdaptiveNormalizer()]
 
 __C.loss = {}

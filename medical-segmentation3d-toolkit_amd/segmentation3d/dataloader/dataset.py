@@ -8,6 +8,9 @@ for every sample; at >150 patches/s per GPU four such workers cannot feed eight 
 processes, no host copies.  The random decisions (crop centre, translation, scale) stay on the host with numpy's
 global RNG in exactly the reference's order, so a seeded run draws the same crops.
 `DeviceCropLoader` batches the samples of a sampler into device tensors for core/seg_train.train().
+Optional augmentation beyond the reference (off by default): axis mirrors, rotation and
+elastic deformation inside the resampling launches, intensity transforms in one fused pass over the normalised crop
+(csrc/augment.hip); its random decisions are drawn after the reference's, and none is drawn while it is off.
 """
 import os
 
@@ -150,11 +153,101 @@ class _Case(object):
         return [int(yx[1]), int(yx[0]), z]
 
 
+# training augmentation (not in the reference): keys and defaults of the `augmentation`
+# section -- everything off
+AUGMENTATION_DEFAULTS = {
+    'rotation_deg': [0.0, 0.0, 0.0],        # per-axis max angle (x, y, z), uniform in [-a, a]
+    'rotation_prob': 1.0,
+    'elastic_grid_mm': 32.0,                # control-point spacing h of the cubic B-spline displacement field
+    'elastic_magnitude_mm': [0.0, 0.0],     # a ~ uniform in [lo, hi]; control displacements uniform in [-a, a] mm
+    'elastic_prob': 0.0,
+    'brightness': [1.0, 1.0],               # multiplicative, uniform in [lo, hi]
+    'brightness_prob': 0.0,
+    'contrast': [1.0, 1.0],
+    'contrast_prob': 0.0,
+    'gamma': [1.0, 1.0],
+    'gamma_prob': 0.0,
+    'gamma_invert_prob': 0.0,
+    'noise_sigma': [0.0, 0.0],
+    'noise_prob': 0.0,
+}
+
+
+def _range2(name, value, lowest, strict):
+    try:
+        lo, hi = (float(v) for v in value)
+    except (TypeError, ValueError):
+        raise ValueError('augmentation.{} must be a [lo, hi] pair, got {!r}'.format(name, value))
+    ok = np.isfinite(lo) and np.isfinite(hi) and lo <= hi and (lo > lowest if strict else lo >= lowest)
+    if not ok:
+        raise ValueError('augmentation.{} = {!r}: need {} {} lo <= hi'.format(name, value, lowest, '<' if strict else '<='))
+    return [lo, hi]
+
+
+def validate_augmentation(augmentation):
+    """the `augmentation` section (dict / EasyDict / None) -> a plain dict with every key of AUGMENTATION_DEFAULTS, or None
+    when the section is absent or switches nothing on.  Unknown keys, bad ranges, probabilities outside [0, 1] and an
+    elastic magnitude that does not satisfy the folding bound raise ValueError.
+    Folding: a partial derivative of a cubic B-spline field is a convex combination of differences of neighbouring
+    control values, so with control displacements in [-a, a] every entry of the Jacobian of u is at most 2a / h, its
+    Frobenius norm at most 6a / h, and id + u is injective when a < h / 6.  The bound is sufficient, not necessary."""
+    if augmentation is None:
+        return None
+    if not hasattr(augmentation, 'keys'):
+        raise ValueError('augmentation must be a dict, got {!r}'.format(type(augmentation)))
+    unknown = sorted(set(augmentation.keys()) - set(AUGMENTATION_DEFAULTS))
+    if unknown:
+        raise ValueError('unknown augmentation option(s) {}; known: {}'.format(unknown, sorted(AUGMENTATION_DEFAULTS)))
+    a = {k: augmentation[k] if k in augmentation else v for k, v in AUGMENTATION_DEFAULTS.items()}
+    for key in a:
+        if key.endswith('_prob'):
+            try:
+                pr = float(a[key])
+            except (TypeError, ValueError):
+                raise ValueError('augmentation.{} must be a number, got {!r}'.format(key, a[key]))
+            if not 0.0 <= pr <= 1.0:
+                raise ValueError('augmentation.{} = {!r} outside [0, 1]'.format(key, a[key]))
+            a[key] = pr
+    try:
+        rot = [float(v) for v in a['rotation_deg']]
+    except (TypeError, ValueError):
+        raise ValueError('augmentation.rotation_deg must be three angles, got {!r}'.format(a['rotation_deg']))
+    if len(rot) != 3 or not all(np.isfinite(v) and 0.0 <= v <= 180.0 for v in rot):
+        raise ValueError('augmentation.rotation_deg = {!r}: three angles in [0, 180]'.format(a['rotation_deg']))
+    a['rotation_deg'] = rot
+    try:
+        h = float(a['elastic_grid_mm'])
+    except (TypeError, ValueError):
+        raise ValueError('augmentation.elastic_grid_mm must be a number, got {!r}'.format(a['elastic_grid_mm']))
+    if not (np.isfinite(h) and h > 0.0):
+        raise ValueError('augmentation.elastic_grid_mm = {!r} must be positive'.format(a['elastic_grid_mm']))
+    a['elastic_grid_mm'] = h
+    a['elastic_magnitude_mm'] = _range2('elastic_magnitude_mm', a['elastic_magnitude_mm'], 0.0, False)
+    if not a['elastic_magnitude_mm'][1] < h / 6.0:
+        raise ValueError('augmentation.elastic_magnitude_mm = {!r}: the largest magnitude must be below elastic_grid_mm / 6 '
+                         '= {:g} mm, which keeps the deformation free of folds'.format(a['elastic_magnitude_mm'], h / 6.0))
+    for key in ('brightness', 'contrast', 'gamma'):
+        a[key] = _range2(key, a[key], 0.0, True)
+    a['noise_sigma'] = _range2('noise_sigma', a['noise_sigma'], 0.0, False)
+    on = {
+        'rotation': a['rotation_prob'] > 0.0 and any(v > 0.0 for v in rot),
+        'elastic': a['elastic_prob'] > 0.0 and a['elastic_magnitude_mm'][1] > 0.0,
+        'brightness': a['brightness_prob'] > 0.0 and a['brightness'] != [1.0, 1.0],
+        'contrast': a['contrast_prob'] > 0.0 and a['contrast'] != [1.0, 1.0],
+        'gamma': a['gamma_prob'] > 0.0 and a['gamma'] != [1.0, 1.0],
+        'noise': a['noise_prob'] > 0.0 and a['noise_sigma'][1] > 0.0,
+    }
+    if not any(on.values()):
+        return None
+    a['enabled'] = on
+    return a
+
+
 class SegmentationDataset(Dataset):
     """training data set for volumetric segmentation (constructor as dataloader/dataset.py:58-100)"""
 
     def __init__(self, imlist_file, num_classes, spacing, crop_size, sampling_method, random_translation, random_scale,
-                 interpolation, crop_normalizers, device=None, random_mirror_axes=()):
+                 interpolation, crop_normalizers, device=None, random_mirror_axes=(), augmentation=None):
         if imlist_file.endswith('txt'):
             self.im_list, self.seg_list = read_train_txt(imlist_file)
         elif imlist_file.endswith('csv'):
@@ -184,6 +277,20 @@ class SegmentationDataset(Dataset):
                 raise ValueError("unknown mirror axis {!r}: 'x', 'y' or 'z'".format(a))
             if a not in self.random_mirror_axes:
                 self.random_mirror_axes.append(a)
+        # rotation / elastic / intensity augmentation (not in the reference): None when the section is absent or all off,
+        # and then a sample takes the code path and draws the RNG stream it always did
+        self.augmentation = validate_augmentation(augmentation)
+        if self.augmentation is not None and self.augmentation['enabled']['elastic']:
+            # the kernel's per-axis factor sp / h must be <= 1, and its weight tables + control grid live in 64 KB of LDS
+            coarsest = self.spacing * self.random_scale[1]
+            if self.augmentation['elastic_grid_mm'] < float(np.max(coarsest)):
+                raise ValueError('augmentation.elastic_grid_mm = {:g} is below the coarsest crop spacing {:g} mm'.format(
+                    self.augmentation['elastic_grid_mm'], float(np.max(coarsest))))
+            dims = image_tools.bspline_control_dims(self.crop_size, coarsest, self.augmentation['elastic_grid_mm'])
+            if int(np.sum(self.crop_size)) * 36 + int(np.prod(dims)) * 12 > 65536:
+                raise ValueError('augmentation.elastic_grid_mm = {:g}: a control grid of {} points does not fit the 64 KB '
+                                 'of on-chip memory the resampling kernel keeps it in'.format(
+                                     self.augmentation['elastic_grid_mm'], dims))
         # modalities per case from the list and the file headers (no volume is read here): every case must have the same M,
         # and there is one normaliser per modality (None: no normalisation, dataset.py:202)
         self._num_modality = 1
@@ -279,11 +386,61 @@ class SegmentationDataset(Dataset):
                 flags['xyz'.index(a)] = bool(d)
         return tuple(flags)
 
+    def sample_augmentation(self, crop_spacing):
+        """the random decisions of the rotation / elastic / intensity augmentation of the next sample, drawn after the
+        mirror draw with numpy's global RNG in this fixed order; a transform that is disabled (probability 0 or a
+        neutral range) draws NOTHING, so with the section absent or all off the stream is the reference's plus the
+        mirror draw.  An enabled transform first draws its gate, uniform() < prob, then -- if the gate is open -- its
+        values:
+          1. rotation:  gate; uniform(-a, a, size=3) degrees, a = rotation_deg (x, y, z)
+          2. elastic:   gate; magnitude a = uniform(lo, hi); control tensor uniform(-a, a, size=(gz, gy, gx, 3)) with
+                        (gx, gy, gz) = bspline_control_dims(crop_size, crop_spacing, elastic_grid_mm)
+          3. per modality m = 0 .. M-1, each drawing independently:
+                brightness: gate; uniform(lo, hi)      contrast: gate; uniform(lo, hi)
+                gamma:      gate; uniform(lo, hi); then, if gamma_invert_prob > 0, uniform() < gamma_invert_prob
+                noise:      gate; sigma = uniform(lo, hi)
+          4. noise enabled: the noise seed, one randint(0, 2^63) (whether or not a gate opened)
+        -> dict(rotation = (gx, gy, gz) radians or None, control = float32 [gz, gy, gx, 3] mm or None, intensity = list of
+        M parameter dicts (image_tools.augment_intensity_device) or None, seed = int), or None without augmentation"""
+        a = self.augmentation
+        if a is None:
+            return None
+        on = a['enabled']
+        rotation = control = None
+        if on['rotation'] and np.random.uniform() < a['rotation_prob']:
+            lim = np.array(a['rotation_deg'], dtype=np.double)
+            deg = np.random.uniform(-lim, lim, size=[3])
+            rotation = tuple(float(v) for v in np.deg2rad(deg))
+        if on['elastic'] and np.random.uniform() < a['elastic_prob']:
+            mag = np.random.uniform(a['elastic_magnitude_mm'][0], a['elastic_magnitude_mm'][1])
+            gx, gy, gz = image_tools.bspline_control_dims(self.crop_size, crop_spacing, a['elastic_grid_mm'])
+            control = np.random.uniform(-mag, mag, size=(gz, gy, gx, 3)).astype(np.float32)
+        intensity, any_intensity = [], False
+        for m in range(self._num_modality):
+            p = {}
+            if on['brightness'] and np.random.uniform() < a['brightness_prob']:
+                p['brightness'] = float(np.random.uniform(a['brightness'][0], a['brightness'][1]))
+            if on['contrast'] and np.random.uniform() < a['contrast_prob']:
+                p['contrast'] = float(np.random.uniform(a['contrast'][0], a['contrast'][1]))
+            if on['gamma'] and np.random.uniform() < a['gamma_prob']:
+                p['gamma'] = float(np.random.uniform(a['gamma'][0], a['gamma'][1]))
+                if a['gamma_invert_prob'] > 0.0:
+                    p['invert'] = bool(np.random.uniform() < a['gamma_invert_prob'])
+            if on['noise'] and np.random.uniform() < a['noise_prob']:
+                p['sigma'] = float(np.random.uniform(a['noise_sigma'][0], a['noise_sigma'][1]))
+            any_intensity = any_intensity or bool(p)
+            intensity.append(p)
+        seed = int(np.random.randint(0, 2 ** 63, dtype=np.int64)) if on['noise'] else 0
+        return {'rotation': rotation, 'control': control, 'intensity': intensity if any_intensity else None, 'seed': seed}
+
     # ---- the sample ---------------------------------------------------------------------------------------------------
     def __getitem__(self, index):
         """-> (image crop [M, z, y, x], mask crop [1, z, y, x] float labels, frame (15 floats), case name); device tensors.
         With random_mirror_axes image and mask are mirrored together inside their resampling launches (mirrored index
         map, no extra pass) and the frame describes the mirrored grid.
+        With `augmentation` image and mask are rotated and elastically deformed together inside the same launches (one
+        rotation and one control tensor for both, each with its own source frame) and the normalised image crop gets the
+        intensity transforms in place; the frame stays the NOMINAL crop frame (un-rotated, un-deformed).
         For M > 1 the image crop is a view of channels-last [z, y, x, M] memory (what the stem reads, without a copy)."""
         return self.sample(index)
 
@@ -294,18 +451,30 @@ class SegmentationDataset(Dataset):
         case_name = self.case_name(index)
         center, crop_spacing = self.sample_crop_geometry(index)
         mirror = self.sample_mirror()
+        aug = self.sample_augmentation(crop_spacing)
+        spatial = {}
+        if aug is not None:
+            # one small host-to-device copy on the current stream; nothing is read back
+            deform = None if aug['control'] is None else (
+                torch.from_numpy(aug['control']).to(self.device, non_blocking=True), self.augmentation['elastic_grid_mm'])
+            spatial = {'rotation': aug['rotation'], 'deform': deform}
         if self._num_modality == 1:
             im = image_tools.crop_image_device(case.image, case.frame, center, self.crop_size, crop_spacing,
-                                               self.interpolation, mirror=mirror)
+                                               self.interpolation, mirror=mirror, **spatial)
             if self.crop_normalizers[0] is not None:
                 im = image_tools.normalize_crop_device(im, self.crop_normalizers[0])
+            if aug is not None and aug['intensity'] is not None:
+                im = image_tools.augment_intensity_device(im.contiguous(), aug['intensity'], aug['seed'])
             im = im.unsqueeze(0)
         else:
             im = image_tools.crop_image_device_mc(case.image, case.frame, center, self.crop_size, crop_spacing,
-                                                  self.interpolation, out=out, mirror=mirror)
-            im = image_tools.normalize_crop_device_mc(im, self._norm_params, out=im).permute(3, 0, 1, 2)
+                                                  self.interpolation, out=out, mirror=mirror, **spatial)
+            im = image_tools.normalize_crop_device_mc(im, self._norm_params, out=im)
+            if aug is not None and aug['intensity'] is not None:
+                image_tools.augment_intensity_device(im, aug['intensity'], aug['seed'])
+            im = im.permute(3, 0, 1, 2)
         seg = image_tools.crop_image_device(case.seg, case.seg_frame, center, self.crop_size, crop_spacing, 'NN',
-                                            mirror=mirror)
+                                            mirror=mirror, **spatial)
         origin = image_tools.crop_origin(center, self.crop_size, crop_spacing)
         direction = list(case.seg_frame[2])
         if any(mirror):

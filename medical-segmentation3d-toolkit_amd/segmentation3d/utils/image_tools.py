@@ -129,9 +129,83 @@ def mirror_frame(frame, out_size, mirror):
     return [float(v) for v in spacing], [float(v) for v in origin], [float(v) for v in D.reshape(-1)]
 
 
-def resample_device(src, src_frame, out_size, dst_frame, interp_method, padding_value=0.0, mirror=None):
+def rotation_matrix(angles):
+    """R = Rz(gz) Ry(gy) Rx(gx) for angles = (gx, gy, gz) in radians, float64"""
+    gx, gy, gz = (float(v) for v in angles)
+    cx, sx, cy, sy, cz, sz = np.cos(gx), np.sin(gx), np.cos(gy), np.sin(gy), np.cos(gz), np.sin(gz)
+    Rx = np.array([[1.0, 0.0, 0.0], [0.0, cx, -sx], [0.0, sx, cx]])
+    Ry = np.array([[cy, 0.0, sy], [0.0, 1.0, 0.0], [-sy, 0.0, cy]])
+    Rz = np.array([[cz, -sz, 0.0], [sz, cz, 0.0], [0.0, 0.0, 1.0]])
+    return Rz @ Ry @ Rx
+
+
+def rotate_index_affine(M, src_frame, dst_frame, out_size, angles):
+    """index map of the destination grid rotated in physical space about its geometric centre
+    c = origin + D diag(spacing) (n - 1) / 2: the sampled point p(i) of index i becomes p' = c + R (p(i) - c) with
+    R = Rz(gz) Ry(gy) Rx(gx), angles = (gx, gy, gz) in radians.  M is index_affine(src_frame, dst_frame); a copy is
+    returned, and with all angles zero it is M bit for bit.  Apply before mirror_index_affine."""
+    M = np.array(M, dtype=np.float64)
+    if not any(float(a) != 0.0 for a in angles):
+        return M
+    s_sp, s_or, s_dir = (np.asarray(v, dtype=np.float64) for v in src_frame)
+    d_sp, d_or, d_dir = (np.asarray(v, dtype=np.float64) for v in dst_frame)
+    to_src = np.diag(1.0 / s_sp) @ np.linalg.inv(s_dir.reshape(3, 3))
+    A = d_dir.reshape(3, 3) @ np.diag(d_sp)                       # index -> physical offset from the origin
+    n = np.array([int(v) for v in out_size], dtype=np.float64)
+    c = d_or + A @ ((n - 1.0) / 2.0)
+    R = rotation_matrix(angles)
+    out = np.zeros((3, 4))
+    out[:, :3] = to_src @ R @ A
+    out[:, 3] = to_src @ (c + R @ (d_or - c) - s_or)
+    return out
+
+
+def bspline_control_dims(out_size, spacing, grid_mm):
+    """(gx, gy, gz) control points of the cubic B-spline displacement field over a destination grid of `out_size` voxels
+    at `spacing` mm with control spacing `grid_mm`: floor((n - 1) sp / h) + 4 per axis"""
+    h = float(grid_mm)
+    return tuple(int(np.floor((int(out_size[a]) - 1) * (float(spacing[a]) / h))) + 4 for a in range(3))
+
+
+def _deform_call_args(src_frame, dst_frame, out_size, deform, mirror):
+    """host arguments of the seg3d_resample_deform entries: L (3 x 3 `to_src` of index_affine), the control tensor, its
+    dims, the per-axis spacing / grid factors and the mirror mask.  deform = (ctrl, grid_mm), ctrl a float32 device
+    tensor [gz, gy, gx, 3] of displacements in mm (world x, y, z)."""
+    ctrl, grid_mm = deform
+    E.require_device(ctrl)
+    if ctrl.dtype != torch.float32 or ctrl.dim() != 4 or ctrl.shape[3] != 3 or not ctrl.is_contiguous():
+        raise ValueError('control tensor must be a contiguous float32 [gz, gy, gx, 3] tensor')
+    h = float(grid_mm)
+    if not h > 0.0:
+        raise ValueError('control grid spacing must be positive, got {}'.format(grid_mm))
+    d_sp = [float(v) for v in dst_frame[0]]
+    want = bspline_control_dims(out_size, d_sp, h)
+    gz, gy, gx = (int(v) for v in ctrl.shape[:3])
+    if (gx, gy, gz) != want:
+        raise ValueError('control tensor has (gx, gy, gz) = {}, the grid needs {}'.format((gx, gy, gz), want))
+    s_sp, _, s_dir = (np.asarray(v, dtype=np.float64) for v in src_frame)
+    L = np.ascontiguousarray(np.diag(1.0 / s_sp) @ np.linalg.inv(s_dir.reshape(3, 3)), dtype=np.float64)
+    t = np.array([sp / h for sp in d_sp], dtype=np.float64)
+    mask = sum(1 << a for a in range(3) if mirror is not None and mirror[a])
+    return L, ctrl, (gx, gy, gz), t, mask
+
+
+def _crop_index_map(src_frame, dst_frame, out_size, rotation, mirror):
+    M = index_affine(src_frame, dst_frame)
+    if rotation is not None:
+        M = rotate_index_affine(M, src_frame, dst_frame, out_size, rotation)
+    if mirror is not None and any(mirror):
+        M = mirror_index_affine(M, out_size, mirror)
+    return np.ascontiguousarray(M, dtype=np.float64)
+
+
+def resample_device(src, src_frame, out_size, dst_frame, interp_method, padding_value=0.0, mirror=None, rotation=None,
+                    deform=None):
     """src: float32 device tensor [Z, Y, X]; returns the float32 device tensor [Zo, Yo, Xo] of the destination grid.
-    mirror = (x, y, z) flags: the destination grid is sampled mirrored along those axes (mirror_index_affine)"""
+    mirror = (x, y, z) flags: the destination grid is sampled mirrored along those axes (mirror_index_affine).
+    rotation = (gx, gy, gz) radians: the grid is rotated about its centre (rotate_index_affine).  deform = (ctrl, grid_mm):
+    the sampled points are displaced by a cubic B-spline field (seg3d_resample_deform; ctrl float32 device
+    [gz, gy, gx, 3] mm, bspline_control_dims points).  Without the last two this is the plain affine launch."""
     if interp_method not in ('LINEAR', 'NN'):
         raise ValueError('Unsupported interpolation type.')
     E.require_device(src)
@@ -139,19 +213,24 @@ def resample_device(src, src_frame, out_size, dst_frame, interp_method, padding_
     Zi, Yi, Xi = src.shape
     Xo, Yo, Zo = (int(v) for v in out_size)
     dst = torch.empty((Zo, Yo, Xo), dtype=torch.float32, device=src.device)
-    M = index_affine(src_frame, dst_frame)
-    if mirror is not None and any(mirror):
-        M = mirror_index_affine(M, (Xo, Yo, Zo), mirror)
-    M = np.ascontiguousarray(M, dtype=np.float64)
-    E.call('seg3d_resample_affine', E.ptr(src), E.ptr(dst), Xi, Yi, Zi, Xo, Yo, Zo,
-           M.ctypes.data_as(ctypes.c_void_p), int(interp_method == 'LINEAR'), float(padding_value), E.stream_ptr())
+    M = _crop_index_map(src_frame, dst_frame, (Xo, Yo, Zo), rotation, mirror)
+    if deform is None:
+        E.call('seg3d_resample_affine', E.ptr(src), E.ptr(dst), Xi, Yi, Zi, Xo, Yo, Zo,
+               M.ctypes.data_as(ctypes.c_void_p), int(interp_method == 'LINEAR'), float(padding_value), E.stream_ptr())
+        return dst
+    L, ctrl, g, t, mask = _deform_call_args(src_frame, dst_frame, (Xo, Yo, Zo), deform, mirror)
+    E.call('seg3d_resample_deform', E.ptr(src), E.ptr(dst), Xi, Yi, Zi, Xo, Yo, Zo, M.ctypes.data_as(ctypes.c_void_p),
+           int(interp_method == 'LINEAR'), float(padding_value), L.ctypes.data_as(ctypes.c_void_p), E.ptr(ctrl), g[0], g[1],
+           g[2], t.ctypes.data_as(ctypes.c_void_p), mask, E.stream_ptr())
     return dst
 
 
-def resample_device_mc(src, src_frame, out_size, dst_frame, interp_method, padding_value=0.0, out=None, mirror=None):
+def resample_device_mc(src, src_frame, out_size, dst_frame, interp_method, padding_value=0.0, out=None, mirror=None,
+                       rotation=None, deform=None):
     """M co-registered channels in one launch: src float32 device tensor [Z, Y, X, M] (channels-last) -> [Zo, Yo, Xo, M].
     `out`: a contiguous [Zo, Yo, Xo, M] destination, e.g. slot b of an NDHWC batch.  Channel m equals resample_device
-    on src[..., m] bit for bit (seg3d_resample_affine_mc)."""
+    on src[..., m] bit for bit (seg3d_resample_affine_mc; with `deform` seg3d_resample_deform_mc).  rotation / deform as
+    in resample_device."""
     if interp_method not in ('LINEAR', 'NN'):
         raise ValueError('Unsupported interpolation type.')
     E.require_device(src)
@@ -164,12 +243,16 @@ def resample_device_mc(src, src_frame, out_size, dst_frame, interp_method, paddi
         out = torch.empty((Zo, Yo, Xo, M), dtype=torch.float32, device=src.device)
     elif tuple(out.shape) != (Zo, Yo, Xo, M) or not out.is_contiguous() or out.dtype != torch.float32:
         raise ValueError('out must be a contiguous float32 [{}, {}, {}, {}] tensor'.format(Zo, Yo, Xo, M))
-    M_ = index_affine(src_frame, dst_frame)
-    if mirror is not None and any(mirror):
-        M_ = mirror_index_affine(M_, (Xo, Yo, Zo), mirror)
-    M_ = np.ascontiguousarray(M_, dtype=np.float64)
-    E.call('seg3d_resample_affine_mc', E.ptr(src), E.ptr(out), int(M), int(M), Xi, Yi, Zi, Xo, Yo, Zo,
-           M_.ctypes.data_as(ctypes.c_void_p), int(interp_method == 'LINEAR'), float(padding_value), E.stream_ptr())
+    M_ = _crop_index_map(src_frame, dst_frame, (Xo, Yo, Zo), rotation, mirror)
+    if deform is None:
+        E.call('seg3d_resample_affine_mc', E.ptr(src), E.ptr(out), int(M), int(M), Xi, Yi, Zi, Xo, Yo, Zo,
+               M_.ctypes.data_as(ctypes.c_void_p), int(interp_method == 'LINEAR'), float(padding_value), E.stream_ptr())
+        return out
+    L, ctrl, g, t, mask = _deform_call_args(src_frame, dst_frame, (Xo, Yo, Zo), deform, mirror)
+    E.call('seg3d_resample_deform_mc', E.ptr(src), E.ptr(out), int(M), int(M), Xi, Yi, Zi, Xo, Yo, Zo,
+           M_.ctypes.data_as(ctypes.c_void_p), int(interp_method == 'LINEAR'), float(padding_value),
+           L.ctypes.data_as(ctypes.c_void_p), E.ptr(ctrl), g[0], g[1], g[2], t.ctypes.data_as(ctypes.c_void_p), mask,
+           E.stream_ptr())
     return out
 
 
@@ -317,14 +400,17 @@ def crop_origin(cropping_center, cropping_size, cropping_spacing):
     return out
 
 
-def crop_image_device(volume, frame, cropping_center, cropping_size, cropping_spacing, interp_method, mirror=None):
+def crop_image_device(volume, frame, cropping_center, cropping_size, cropping_spacing, interp_method, mirror=None,
+                      rotation=None, deform=None):
     """volume: float32 device tensor [Z, Y, X] with frame (spacing, origin, direction) -> crop [z, y, x] of
     `cropping_size` voxels at `cropping_spacing`, centred at the world point `cropping_center`, zero outside;
-    mirror = (x, y, z) flags: the crop comes out mirrored along those axes (same launch, mirrored index map)"""
+    mirror = (x, y, z) flags: the crop comes out mirrored along those axes (same launch, mirrored index map);
+    rotation / deform: training augmentation inside the same launch, see resample_device"""
     size = [int(cropping_size[idx]) for idx in range(3)]
     spacing = [float(cropping_spacing[idx]) for idx in range(3)]
     dst_frame = (spacing, crop_origin(cropping_center, size, spacing), frame[2])
-    return resample_device(volume, frame, size, dst_frame, interp_method, 0.0, mirror=mirror)
+    return resample_device(volume, frame, size, dst_frame, interp_method, 0.0, mirror=mirror, rotation=rotation,
+                           deform=deform)
 
 
 def crop_image(image, cropping_center, cropping_size, cropping_spacing, interp_method):
@@ -359,12 +445,13 @@ def normalize_crop_device(crop, normalizer):
 
 
 def crop_image_device_mc(volume, frame, cropping_center, cropping_size, cropping_spacing, interp_method, out=None,
-                         mirror=None):
+                         mirror=None, rotation=None, deform=None):
     """crop_image_device for a channels-last [Z, Y, X, M] volume: one launch for all modalities -> [z, y, x, M]"""
     size = [int(cropping_size[idx]) for idx in range(3)]
     spacing = [float(cropping_spacing[idx]) for idx in range(3)]
     dst_frame = (spacing, crop_origin(cropping_center, size, spacing), frame[2])
-    return resample_device_mc(volume, frame, size, dst_frame, interp_method, 0.0, out=out, mirror=mirror)
+    return resample_device_mc(volume, frame, size, dst_frame, interp_method, 0.0, out=out, mirror=mirror,
+                              rotation=rotation, deform=deform)
 
 
 def normalize_crop_device_mc(crop, params, out=None):
@@ -383,6 +470,60 @@ def normalize_crop_device_mc(crop, params, out=None):
     E.call('seg3d_patch_gather_normalize_mc', E.ptr(crop), E.ptr(starts), E.ptr(out), E.ptr(ws), E.ptr(mean_std), bz, by,
            bx, bx, by, bz, 1, int(M), params, E.stream_ptr())
     return out
+
+
+INTENSITY_NEUTRAL = {'brightness': 1.0, 'contrast': 1.0, 'gamma': 1.0, 'invert': False, 'sigma': 0.0}
+
+
+def intensity_params(params, num_modality, seed=0):
+    """list of per-modality dicts (keys of INTENSITY_NEUTRAL, missing = neutral; None = all neutral) -> the
+    Seg3dIntensityParams struct passed by value to seg3d_augment_intensity; seed: the 64-bit Philox key"""
+    if len(params) != num_modality:
+        raise ValueError('{} intensity parameter sets for {} modalities'.format(len(params), num_modality))
+    out = E.IntensityParams()
+    for m in range(8):
+        d = dict(INTENSITY_NEUTRAL)
+        if m < num_modality and params[m] is not None:
+            unknown = set(params[m]) - set(d)
+            if unknown:
+                raise ValueError('unknown intensity parameter(s) {}'.format(sorted(unknown)))
+            d.update(params[m])
+        for key in ('brightness', 'contrast', 'gamma'):
+            if not (np.isfinite(d[key]) and d[key] > 0.0):
+                raise ValueError('{} must be positive, got {}'.format(key, d[key]))
+        if not (np.isfinite(d['sigma']) and d['sigma'] >= 0.0):
+            raise ValueError('sigma must be >= 0, got {}'.format(d['sigma']))
+        p = out.m[m]
+        p.brightness, p.contrast, p.gamma, p.invert, p.sigma = float(d['brightness']), float(d['contrast']), \
+            float(d['gamma']), int(bool(d['invert'])), float(d['sigma'])
+    seed = int(seed)
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError('seed must be in [0, 2^64), got {}'.format(seed))
+    out.seed_lo, out.seed_hi = seed & 0xffffffff, seed >> 32
+    return out
+
+
+def augment_intensity_device(crop, params, seed=0, grid_blocks=0):
+    """brightness, contrast, gamma and additive Gaussian noise on a normalised float32 device crop, IN PLACE
+    (csrc/augment.hip, seg3d_augment_intensity): crop [z, y, x] (one modality) or channels-last [z, y, x, M], contiguous;
+    params: one dict per modality with any of brightness, contrast, gamma (> 0), invert (bool), sigma (>= 0) -- missing
+    keys are neutral and a neutral transform is skipped exactly -- or a ready E.IntensityParams.  seed: the noise's 64-bit
+    Philox key; the noise of a voxel depends on (seed, voxel index, modality) alone.  Returns `crop`."""
+    E.require_device(crop)
+    if crop.dtype != torch.float32 or crop.dim() not in (3, 4) or not crop.is_contiguous():
+        raise ValueError('crop must be a contiguous float32 [z, y, x] or [z, y, x, M] tensor')
+    M = 1 if crop.dim() == 3 else int(crop.shape[3])
+    if not 1 <= M <= 8:
+        raise ValueError('{} modalities, 1..8 are supported'.format(M))
+    Z, Y, X = (int(v) for v in crop.shape[:3])
+    prm = params if isinstance(params, E.IntensityParams) else intensity_params(params, M, seed)
+    need_stats = any(prm.m[m].contrast != 1.0 or prm.m[m].gamma != 1.0 for m in range(M))
+    ws = None
+    if need_stats:
+        ws = torch.empty((E.query('seg3d_augment_intensity_workspace_doubles', X, Y, Z, M),), dtype=torch.float64,
+                         device=crop.device)
+    E.call('seg3d_augment_intensity', E.ptr(crop), E.ptr(ws), X, Y, Z, M, prm, int(grid_blocks), E.stream_ptr())
+    return crop
 
 
 def get_image_frame(image):
