@@ -291,6 +291,20 @@ int seg3d_gn_bwd_apply(const float* dout, const float* out /* NULL: recompute */
                        const float* s12, const float* gamma, const float* beta, float* dy, float* dres, int N, long long S,
                        int C, int relu, int ld_dout /* row stride of dout in floats, 0 = C */, void* stream);
 
+/* ReLU mask of a residual unit's output, out = relu(x_in + GN(conv(..))) (residual_block3.py:24,46): the backward pass needs
+ * only [out > 0] of the forward output once a residual was added, so the forward apply can write it as one byte per channel
+ * quad (bits 0-3 = out > 0 of the quad's four channels; layout [N][S][C/4] bytes, contiguous, 4-byte aligned) and the backward
+ * passes read that instead of `out`: g = bit ? dout : 0, everything else (arithmetic, summation order, ld_dout) as in the
+ * entries above, results bit-identical.  C % 4 == 0 with C/4 dividing 256 (seg3d_gn_mask_supported). */
+int seg3d_gn_mask_supported(int C);
+int seg3d_gn_apply_mask(const float* y, const float* mean_rstd, const float* gamma, const float* beta, const float* res,
+                        float* out, unsigned char* mask, int N, long long S, int C, int relu, int ld_out, void* stream);
+int seg3d_gn_bwd_reduce_mask(const float* dout, const unsigned char* mask, const float* y, const float* mean_rstd,
+                             float* part, int N, long long S, int C, int ld_dout, void* stream);
+int seg3d_gn_bwd_apply_mask(const float* dout, const unsigned char* mask, const float* y, const float* mean_rstd,
+                            const float* s12, const float* gamma, float* dy, float* dres /* optional: the masked dout */,
+                            int N, long long S, int C, int ld_dout, void* stream);
+
 /* bf16 mode GroupNorm: the conv output y, the statistics and all arithmetic stay fp32; the activation-side tensors
  * (residual, unit output, incoming gradient) are bf16 where flagged.  ld_out / ld_dout count elements of that tensor. */
 /* y_bf16: the conv output y itself is bf16 storage (the conv epilogue rounded it after taking the fp32 statistics) */

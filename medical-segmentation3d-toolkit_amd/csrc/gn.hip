@@ -179,13 +179,37 @@ struct GnWalker {
   }
 };
 
+// ---- ReLU mask of a residual unit: one byte per channel quad, bits 0-3 = [out > 0] of the quad's four channels, laid out
+// [N][S][C/4] contiguous (the order of the apply passes' quad index).  It is all the backward pass needs of `out` once a
+// residual was added (the mask cannot be recomputed from y then), at 1/16 of its bytes.
+__device__ __forceinline__ unsigned gn_quad_bits(float4 o) {
+  return (o.x > 0.f ? 1u : 0u) | (o.y > 0.f ? 2u : 0u) | (o.z > 0.f ? 4u : 0u) | (o.w > 0.f ? 8u : 0u);
+}
+// pack4 (C/4 a multiple of 4, so the four lanes of a quad of lanes are active together and hold four neighbouring bytes): the
+// bytes are combined across the lane quad by two DPP steps and lane 0 of the quad stores one dword instead of four byte stores
+__device__ __forceinline__ void gn_mask_store(unsigned char* __restrict__ mask, i64 idx, unsigned bits, bool pack4) {
+  if (pack4) {
+    int w = (int)(bits << (8 * (threadIdx.x & 3)));
+    w |= __builtin_amdgcn_update_dpp(0, w, 0xB1, 0xf, 0xf, false);   // quad_perm [1,0,3,2]
+    w |= __builtin_amdgcn_update_dpp(0, w, 0x4E, 0xf, 0xf, false);   // quad_perm [2,3,0,1]
+    if ((threadIdx.x & 3) == 0) __builtin_nontemporal_store(w, reinterpret_cast<int*>(mask + idx));
+  } else {
+    mask[idx] = (unsigned char)bits;
+  }
+}
+__device__ __forceinline__ float4 gn_mask_select(float4 g, unsigned bits) {
+  g.x = (bits & 1u) ? g.x : 0.f; g.y = (bits & 2u) ? g.y : 0.f; g.z = (bits & 4u) ? g.z : 0.f; g.w = (bits & 8u) ? g.w : 0.f;
+  return g;
+}
+
 // ---- apply: out = act(gamma*(y-mean)*rstd + beta (+ res)) -------------------------------------------------------
 // RES_BF / OUT_BF (bf16 mode): the residual / the output are bf16 activations; y, statistics and the arithmetic fp32
-template <bool VEC, bool RES_BF, bool OUT_BF, bool Y_BF = false>
+// MASK: additionally writes the ReLU mask of `out` (VEC only)
+template <bool VEC, bool RES_BF, bool OUT_BF, bool Y_BF = false, bool MASK = false>
 __device__ __forceinline__ void gn_apply_body(const float* __restrict__ y, const float* __restrict__ mean_rstd,
                                               const float* __restrict__ gamma, const float* __restrict__ beta,
                                               const void* __restrict__ res_v, void* __restrict__ out_v, i64 S, int C,
-                                              i64 total_vox, int relu, int ldo) {
+                                              i64 total_vox, int relu, int ldo, unsigned char* __restrict__ mask = nullptr) {
   const float* res = reinterpret_cast<const float*>(res_v);   // only dereferenced as float when !RES_BF
   float* out = reinterpret_cast<float*>(out_v);
   if (VEC) {
@@ -193,6 +217,7 @@ __device__ __forceinline__ void gn_apply_body(const float* __restrict__ y, const
     const i64 total = total_vox * CQ;
     const i64 stride = (i64)gridDim.x * 256;
     GnWalker wk((i64)blockIdx.x * 256 + threadIdx.x, stride, CQ, S);
+    const bool pack4 = MASK && (CQ & 3) == 0;
     // GN_U quads per trip, every load issued before the first store: a wave keeps GN_U x (1 or 2) 16-byte loads in flight
     // instead of one or two -- what counts when these passes share a CU with a weight-gradient kernel of the side stream and
     // get a fraction of the wave slots, and it keeps a trip's loads clear of the previous trip's stores
@@ -217,6 +242,7 @@ __device__ __forceinline__ void gn_apply_body(const float* __restrict__ y, const
       }
       const seg3d_f32x4 ov = {o.x, o.y, o.z, o.w};
       GnQuad<OUT_BF>::store(out_v, v * ldo + 4 * q, ov);
+      if (MASK) gn_mask_store(mask, idx, gn_quad_bits(o), pack4);
     };
     i64 idx = (i64)blockIdx.x * 256 + threadIdx.x;
     for (; idx + (GN_U - 1) * stride < total; idx += GN_U * stride) {
@@ -304,6 +330,14 @@ extern "C" int seg3d_gn_apply_mixed(const void* yv, const float* mean_rstd, cons
   return SEG3D_OK;
 }
 
+__global__ __launch_bounds__(256) void gn_apply_mask_kernel(const float* __restrict__ y, const float* __restrict__ mean_rstd,
+                                                              const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                              const float* __restrict__ res, float* __restrict__ out,
+                                                              unsigned char* __restrict__ mask, i64 S, int C, i64 total_vox,
+                                                              int relu, int ldo) {
+  gn_apply_body<true, false, false, false, true>(y, mean_rstd, gamma, beta, res, out, S, C, total_vox, relu, ldo, mask);
+}
+
 extern "C" int seg3d_gn_apply(const float* y, const float* mean_rstd, const float* gamma, const float* beta,
                               const float* res, float* out, int N, long long S, int C, int relu, int ld_out,
                               void* stream) {
@@ -323,6 +357,27 @@ extern "C" int seg3d_gn_apply(const float* y, const float* mean_rstd, const floa
   return SEG3D_OK;
 }
 
+static bool gn_vec_ok(int C);
+
+// can the ReLU-mask entries (seg3d_gn_apply_mask, seg3d_gn_bwd_reduce_mask, seg3d_gn_bwd_apply_mask) serve C channels
+extern "C" int seg3d_gn_mask_supported(int C) { return C > 0 && gn_vec_ok(C) ? 1 : 0; }
+
+// seg3d_gn_apply + the ReLU mask of `out` ([N][S][C/4] bytes, 4-byte aligned): same arithmetic, same `out`
+extern "C" int seg3d_gn_apply_mask(const float* y, const float* mean_rstd, const float* gamma, const float* beta,
+                                   const float* res, float* out, unsigned char* mask, int N, long long S, int C, int relu,
+                                   int ld_out, void* stream) {
+  SEG3D_REQUIRE(y && mean_rstd && gamma && beta && out && mask && N > 0 && S > 0 && C > 0, "seg3d_gn_apply_mask: bad arguments");
+  SEG3D_REQUIRE(seg3d_gn_mask_supported(C), "seg3d_gn_apply_mask: needs C %% 4 == 0 with C/4 dividing 256 (got %d)", C);
+  SEG3D_REQUIRE((reinterpret_cast<unsigned long long>(mask) & 3) == 0, "seg3d_gn_apply_mask: mask must be 4-byte aligned");
+  SEG3D_REQUIRE(ld_out == 0 || (ld_out >= C && (ld_out & 3) == 0), "seg3d_gn_apply_mask: ld_out must be 0 or a multiple of 4 >= C");
+  const int ldo = ld_out ? ld_out : C;
+  const i64 total_vox = (i64)N * S;
+  hipLaunchKernelGGL(gn_apply_mask_kernel, dim3(seg3d_ew_grid(total_vox * (C / 4), 256)), dim3(256), 0, (hipStream_t)stream, y,
+                     mean_rstd, gamma, beta, res, out, mask, (i64)S, C, total_vox, relu, ldo);
+  SEG3D_LAUNCH_CHECK("seg3d_gn_apply_mask");
+  return SEG3D_OK;
+}
+
 // ---- backward reduce: per (n, c) partial A = sum g, B = sum g*xhat, X = sum xhat ---------------------------------
 // voxels per workgroup of the backward reduce: <= 2048, but small levels are cut finer so that the pass still
 // spreads over >= ~128 workgroups per sample (a 12^3 x 256-channel tensor would otherwise run on 4 workgroups)
@@ -335,7 +390,8 @@ static inline int gn_bwd_vpb(i64 S) {
 
 // fast path: C % 4 == 0 and (C/4) divides 256: thread = (channel quad, voxel lane)
 // ACT_BF (bf16 mode): dout and out (activation-side tensors) are bf16
-template <bool ACT_BF, bool Y_BF = false>
+// MASK: `out` is the ReLU mask written by seg3d_gn_apply_mask (one byte per quad) instead of the forward output
+template <bool ACT_BF, bool Y_BF = false, bool MASK = false>
 __device__ __forceinline__ void gn_bwd_reduce_vec_body(const void* __restrict__ dout, const void* __restrict__ out,
                                                        const float* __restrict__ y, const float* __restrict__ mean_rstd,
                                                        const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -355,6 +411,7 @@ __device__ __forceinline__ void gn_bwd_reduce_vec_body(const void* __restrict__ 
     float4 g[4], yv[4], o[4];
     typename GnQuad<ACT_BF>::raw graw[4], oraw[4];
     typename GnQuad<Y_BF>::raw yraw[4];
+    unsigned mb[4];
     bool ok[4];
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
@@ -363,7 +420,8 @@ __device__ __forceinline__ void gn_bwd_reduce_vec_body(const void* __restrict__ 
       const i64 off = ((i64)n * S + (ok[u] ? svu : s0)) * C + 4 * q;
       graw[u] = GnQuad<ACT_BF>::load(dout, ((i64)n * S + (ok[u] ? svu : s0)) * ldd + 4 * q);
       yraw[u] = GnQuad<Y_BF>::load(y, off);
-      if (relu && out) oraw[u] = GnQuad<ACT_BF>::load(out, off);
+      if (MASK) mb[u] = __builtin_nontemporal_load(reinterpret_cast<const unsigned char*>(out) + (off >> 2));
+      else if (relu && out) oraw[u] = GnQuad<ACT_BF>::load(out, off);
     }
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
@@ -371,12 +429,12 @@ __device__ __forceinline__ void gn_bwd_reduce_vec_body(const void* __restrict__ 
       g[u] = make_float4(gv[0], gv[1], gv[2], gv[3]);
       const seg3d_f32x4 yq = GnQuad<Y_BF>::cvt(yraw[u]);
       yv[u] = make_float4(yq[0], yq[1], yq[2], yq[3]);
-      if (relu && out) {
+      if (!MASK && relu && out) {
         const seg3d_f32x4 ov = GnQuad<ACT_BF>::cvt(oraw[u]);
         o[u] = make_float4(ov[0], ov[1], ov[2], ov[3]);
       }
     }
-    if (relu && !out) {
+    if (!MASK && relu && !out) {
       // no residual: the forward output is a pure function of y -> recompute it (same expression as gn_apply_kernel)
       // instead of reading a third tensor
       const float4 gm = *reinterpret_cast<const float4*>(gamma + 4 * q);
@@ -391,7 +449,9 @@ __device__ __forceinline__ void gn_bwd_reduce_vec_body(const void* __restrict__ 
     for (int u = 0; u < 4; ++u) {
       if (!ok[u]) continue;
       float4 gg = g[u];
-      if (relu) {
+      if (MASK) {
+        gg = gn_mask_select(gg, mb[u]);
+      } else if (relu) {
         gg.x = o[u].x > 0.f ? gg.x : 0.f; gg.y = o[u].y > 0.f ? gg.y : 0.f;
         gg.z = o[u].z > 0.f ? gg.z : 0.f; gg.w = o[u].w > 0.f ? gg.w : 0.f;
       }
@@ -431,6 +491,15 @@ __global__ __launch_bounds__(256) void gn_bwd_reduce_vec_kernel(const float* __r
                                                                   float* __restrict__ part, i64 S, int C, int nblk,
                                                                   int relu, int vpb, int ldd) {
   gn_bwd_reduce_vec_body<false>(dout, out, y, mean_rstd, gamma, beta, part, S, C, nblk, relu, vpb, ldd);
+}
+
+__global__ __launch_bounds__(256) void gn_bwd_reduce_vec_mask_kernel(const float* __restrict__ dout,
+                                                                       const unsigned char* __restrict__ mask,
+                                                                       const float* __restrict__ y,
+                                                                       const float* __restrict__ mean_rstd,
+                                                                       float* __restrict__ part, i64 S, int C, int nblk,
+                                                                       int vpb, int ldd) {
+  gn_bwd_reduce_vec_body<false, false, true>(dout, mask, y, mean_rstd, nullptr, nullptr, part, S, C, nblk, 1, vpb, ldd);
 }
 
 template <bool Y_BF>
@@ -519,6 +588,21 @@ extern "C" int seg3d_gn_bwd_reduce(const float* dout, const float* out, const fl
     SEG3D_UNSUPPORTED("seg3d_gn_bwd_reduce: unsupported channel count %d (need C<=16 or C%%4==0 with C/4 | 256)", C);
   }
   SEG3D_LAUNCH_CHECK("seg3d_gn_bwd_reduce");
+  return SEG3D_OK;
+}
+
+// seg3d_gn_bwd_reduce of a ReLU unit with the mask of seg3d_gn_apply_mask in place of the forward output: g = bit ? dout : 0,
+// the same partial sums in the same order
+extern "C" int seg3d_gn_bwd_reduce_mask(const float* dout, const unsigned char* mask, const float* y, const float* mean_rstd,
+                                        float* part, int N, long long S, int C, int ld_dout, void* stream) {
+  SEG3D_REQUIRE(dout && mask && y && mean_rstd && part && N > 0 && S > 0 && C > 0, "seg3d_gn_bwd_reduce_mask: bad arguments");
+  SEG3D_REQUIRE(seg3d_gn_mask_supported(C), "seg3d_gn_bwd_reduce_mask: needs C %% 4 == 0 with C/4 dividing 256 (got %d)", C);
+  SEG3D_REQUIRE(ld_dout == 0 || (ld_dout >= C && (ld_dout & 3) == 0),
+                "seg3d_gn_bwd_reduce_mask: ld_dout must be 0 or a multiple of 4 >= C");
+  const int nblk = (int)seg3d_gn_bwd_blocks(S);
+  hipLaunchKernelGGL(gn_bwd_reduce_vec_mask_kernel, dim3(nblk, N), dim3(256), 0, (hipStream_t)stream, dout, mask, y, mean_rstd,
+                     part, (i64)S, C, nblk, gn_bwd_vpb(S), ld_dout ? ld_dout : C);
+  SEG3D_LAUNCH_CHECK("seg3d_gn_bwd_reduce_mask");
   return SEG3D_OK;
 }
 
@@ -704,7 +788,8 @@ extern "C" int seg3d_gn_bwd_finalize_fused(const float* part, const float* gamma
 // ---- backward apply: dy = rstd (gamma g - s1 - xhat s2),  dres = g -----------------------------------------------
 // ACT_BF: dout / out are bf16; DY_BF: dy (the gradient handed to the conv's dgrad / wgrad kernels) is written as bf16.
 // dres (gradient of the identity path, folded into a dgrad epilogue) stays fp32.
-template <bool VEC, bool ACT_BF, bool DY_BF, bool Y_BF = false>
+// MASK: out_v is the ReLU mask written by seg3d_gn_apply_mask (one byte per quad) instead of the forward output (VEC only)
+template <bool VEC, bool ACT_BF, bool DY_BF, bool Y_BF = false, bool MASK = false>
 __device__ __forceinline__ void gn_bwd_apply_body(const void* __restrict__ dout_v, const void* __restrict__ out_v,
                                                   const float* __restrict__ y, const float* __restrict__ mean_rstd,
                                                   const float* __restrict__ s12, const float* __restrict__ gamma,
@@ -719,10 +804,11 @@ __device__ __forceinline__ void gn_bwd_apply_body(const void* __restrict__ dout_
     const i64 total = total_vox * CQ;
     const i64 stride = (i64)gridDim.x * 256;
     GnWalker wk((i64)blockIdx.x * 256 + threadIdx.x, stride, CQ, S);
-    const bool need_out = relu && out;
+    const bool need_out = !MASK && relu && out;
+    const unsigned char* mask = reinterpret_cast<const unsigned char*>(out_v);
     // GN_U quads per trip, all loads ahead of the first store (see gn_apply_body)
     auto one = [&](i64 idx, int q, int n, typename GnQuad<ACT_BF>::raw graw, typename GnQuad<Y_BF>::raw yraw,
-                   typename GnQuad<ACT_BF>::raw oraw) {
+                   typename GnQuad<ACT_BF>::raw oraw, unsigned mb) {
       const float mean = mean_rstd[2 * n], rstd = mean_rstd[2 * n + 1];
       const float s1 = s12[2 * n], s2 = s12[2 * n + 1];
       const seg3d_f32x4 gq = GnQuad<ACT_BF>::cvt(graw);
@@ -730,7 +816,9 @@ __device__ __forceinline__ void gn_bwd_apply_body(const void* __restrict__ dout_
       const seg3d_f32x4 yq = GnQuad<Y_BF>::cvt(yraw);
       const float4 yv = make_float4(yq[0], yq[1], yq[2], yq[3]);
       const float4 gm = *reinterpret_cast<const float4*>(gamma + 4 * q);
-      if (relu) {
+      if (MASK) {
+        g = gn_mask_select(g, mb);
+      } else if (relu) {
         float4 o;
         if (out) {
           const seg3d_f32x4 oq = GnQuad<ACT_BF>::cvt(oraw);
@@ -756,6 +844,7 @@ __device__ __forceinline__ void gn_bwd_apply_body(const void* __restrict__ dout_
       int qq[GN_U], nn[GN_U];
       typename GnQuad<ACT_BF>::raw graw[GN_U], oraw[GN_U];
       typename GnQuad<Y_BF>::raw yraw[GN_U];
+      unsigned mb[GN_U];
 #pragma unroll
       for (int u = 0; u < GN_U; ++u) {
         qq[u] = wk.q, nn[u] = wk.n;
@@ -763,14 +852,16 @@ __device__ __forceinline__ void gn_bwd_apply_body(const void* __restrict__ dout_
         wk.step(CQ, S);
         yraw[u] = GnQuad<Y_BF>::load(y, (idx + u * stride) * 4);
         if (need_out) oraw[u] = GnQuad<ACT_BF>::load(out_v, (idx + u * stride) * 4);
+        mb[u] = MASK ? (unsigned)__builtin_nontemporal_load(mask + idx + u * stride) : 0u;
       }
 #pragma unroll
-      for (int u = 0; u < GN_U; ++u) one(idx + u * stride, qq[u], nn[u], graw[u], yraw[u], oraw[u]);
+      for (int u = 0; u < GN_U; ++u) one(idx + u * stride, qq[u], nn[u], graw[u], yraw[u], oraw[u], mb[u]);
     }
     for (; idx < total; idx += stride, wk.step(CQ, S)) {
       typename GnQuad<ACT_BF>::raw oraw = {};
       if (need_out) oraw = GnQuad<ACT_BF>::load(out_v, idx * 4);
-      one(idx, wk.q, wk.n, GnQuad<ACT_BF>::load(dout_v, wk.v * ldd + 4 * wk.q), GnQuad<Y_BF>::load(y, idx * 4), oraw);
+      const unsigned mb = MASK ? (unsigned)__builtin_nontemporal_load(mask + idx) : 0u;
+      one(idx, wk.q, wk.n, GnQuad<ACT_BF>::load(dout_v, wk.v * ldd + 4 * wk.q), GnQuad<Y_BF>::load(y, idx * 4), oraw, mb);
     }
   } else {
     const i64 total = total_vox * C;
@@ -798,6 +889,18 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const float* __restri
                                                              float* __restrict__ dres, i64 S, int C, i64 total_vox,
                                                              int relu, int ldd) {
   gn_bwd_apply_body<VEC, false, false>(dout, out, y, mean_rstd, s12, gamma, beta, dy, dres, S, C, total_vox, relu, ldd);
+}
+
+__global__ __launch_bounds__(256) void gn_bwd_apply_mask_kernel(const float* __restrict__ dout,
+                                                                  const unsigned char* __restrict__ mask,
+                                                                  const float* __restrict__ y,
+                                                                  const float* __restrict__ mean_rstd,
+                                                                  const float* __restrict__ s12,
+                                                                  const float* __restrict__ gamma, float* __restrict__ dy,
+                                                                  float* __restrict__ dres, i64 S, int C, i64 total_vox,
+                                                                  int ldd) {
+  gn_bwd_apply_body<true, false, false, false, true>(dout, mask, y, mean_rstd, s12, gamma, nullptr, dy, dres, S, C, total_vox, 1,
+                                                     ldd);
 }
 
 template <bool DY_BF, bool Y_BF>
@@ -859,5 +962,22 @@ extern "C" int seg3d_gn_bwd_apply(const float* dout, const float* out, const flo
                        mean_rstd, s12, gamma, beta, dy, dres, (i64)S, C, total_vox, relu, ldd);
   }
   SEG3D_LAUNCH_CHECK("seg3d_gn_bwd_apply");
+  return SEG3D_OK;
+}
+
+// seg3d_gn_bwd_apply of a ReLU unit with the mask of seg3d_gn_apply_mask in place of the forward output; dres (optional) = the
+// masked gradient g = bit ? dout : 0 of the identity path
+extern "C" int seg3d_gn_bwd_apply_mask(const float* dout, const unsigned char* mask, const float* y, const float* mean_rstd,
+                                       const float* s12, const float* gamma, float* dy, float* dres, int N, long long S, int C,
+                                       int ld_dout, void* stream) {
+  SEG3D_REQUIRE(dout && mask && y && mean_rstd && s12 && gamma && dy && N > 0 && S > 0 && C > 0,
+                "seg3d_gn_bwd_apply_mask: bad arguments");
+  SEG3D_REQUIRE(seg3d_gn_mask_supported(C), "seg3d_gn_bwd_apply_mask: needs C %% 4 == 0 with C/4 dividing 256 (got %d)", C);
+  SEG3D_REQUIRE(ld_dout == 0 || (ld_dout >= C && (ld_dout & 3) == 0),
+                "seg3d_gn_bwd_apply_mask: ld_dout must be 0 or a multiple of 4 >= C");
+  const i64 total_vox = (i64)N * S;
+  hipLaunchKernelGGL(gn_bwd_apply_mask_kernel, dim3(seg3d_ew_grid(total_vox * (C / 4), 256)), dim3(256), 0, (hipStream_t)stream,
+                     dout, mask, y, mean_rstd, s12, gamma, dy, dres, (i64)S, C, total_vox, ld_dout ? ld_dout : C);
+  SEG3D_LAUNCH_CHECK("seg3d_gn_bwd_apply_mask");
   return SEG3D_OK;
 }

@@ -28,6 +28,10 @@ WINOGRAD = True
 WINOGRAD2D = True    # F(2x2, 3x3) over (y, x) where it is preferred, else F(2, 3) along x
 STREAM_K = True      # F(2x2, 3x3) tile kernel: stream-K chunk ranges where whole items would fill the CUs' rounds badly (432 / 864 items)
 _TWO_FORWARDS = 0    # > 0 inside two_forwards(): see there
+# last unit of a residual block, out = relu(x_in + GN(conv(..))), fp32: the forward apply writes the ReLU mask [out > 0] as one
+# byte per channel quad and GroupNorm backward reads that instead of the saved forward output (1/16 of its bytes in each of the
+# two backward passes; False: the forward output is saved and read, as in bf16 mode)
+RELU_MASK = True
 
 
 @contextlib.contextmanager
@@ -711,10 +715,17 @@ def gn_stats(yn, stats_partial=None, eps=GN_EPS):
     return mean_rstd
 
 
-def gn_apply(yn, mean_rstd, gamma, beta, resn, relu, out=None, out_bf16=False):
+def relu_mask_usable(C):
+    """can a fp32 unit with C channels keep its ReLU mask instead of its forward output for backward"""
+    return RELU_MASK and not _ACT_BF16[0] and bool(E.query('seg3d_gn_mask_supported', C))
+
+
+def gn_apply(yn, mean_rstd, gamma, beta, resn, relu, out=None, out_bf16=False, mask=None):
     """out: optional destination -- a channel slice [..., c0:c0+C] of a wider contiguous NDHWC buffer (the up-branch
     half of a skip concatenation is normalised straight into the concatenated tensor).
-    bf16 mode: `resn` may be bf16; the output is bf16 when out_bf16 (or when `out` is a bf16 buffer)."""
+    bf16 mode: `resn` may be bf16; the output is bf16 when out_bf16 (or when `out` is a bf16 buffer).
+    mask (fp32 only): contiguous uint8 [N,D,H,W,C/4] the ReLU mask of the output is written to (bits 0-3 of a byte = out > 0 of
+    a channel quad), for gn_backward(..., mask=...)."""
     N, D, H, W_, C = yn.shape
     ld = 0
     if _is_bf16(yn) and C % 4:
@@ -726,6 +737,14 @@ def gn_apply(yn, mean_rstd, gamma, beta, resn, relu, out=None, out_bf16=False):
                 out.stride(2) != W_ * out.stride(3) or out.stride(1) != H * out.stride(2) or out.stride(0) != D * out.stride(1):
             raise ValueError('gn_apply destination must be a channel slice of a contiguous NDHWC buffer')
         ld = out.stride(3)
+    if mask is not None:
+        if _is_bf16(out) or _is_bf16(resn) or _is_bf16(yn):
+            raise TypeError('the ReLU mask is written by the fp32 GroupNorm apply only')
+        if mask.dtype != torch.uint8 or tuple(mask.shape) != (N, D, H, W_, C // 4) or not mask.is_contiguous():
+            raise ValueError('ReLU mask must be a contiguous uint8 [N,D,H,W,C/4] tensor')
+        E.call('seg3d_gn_apply_mask', E.ptr(yn), E.ptr(mean_rstd), E.ptr(gamma), E.ptr(beta), E.ptr(resn), E.ptr(out),
+               E.ptr(mask), N, D * H * W_, C, int(relu), ld, E.stream_ptr())
+        return out
     if _is_bf16(out) or _is_bf16(resn) or _is_bf16(yn):
         E.call('seg3d_gn_apply_mixed', E.ptr(yn), E.ptr(mean_rstd), E.ptr(gamma), E.ptr(beta), E.ptr(resn), E.ptr(out), N,
                D * H * W_, C, int(relu), ld, int(_is_bf16(resn)), int(_is_bf16(out)), int(_is_bf16(yn)), E.stream_ptr())
@@ -764,9 +783,10 @@ def _gn_ticket(device):
 
 
 def gn_backward(doutn, outn, yn, mean_rstd, gamma, beta, relu, want_dres, want_dbias=True, sinks=(None, None, None),
-                dy_bf16=False):
+                dy_bf16=False, mask=None):
     """returns (dy, dres or None, dgamma, dbeta, dbias or None).  `outn` (the unit's forward output) is only read when
     it cannot be recomputed from y, i.e. when a residual was added; pass None otherwise.
+    mask: the ReLU mask gn_apply(..., mask=...) wrote, in place of `outn` (fp32 ReLU unit).
     sinks = (dgamma, dbeta, dbias) destinations ([C] tensors) the finalize kernel ADDS into; the matching return
     value is then None."""
     N, D, H, W_, C = yn.shape
@@ -783,7 +803,13 @@ def gn_backward(doutn, outn, yn, mean_rstd, gamma, beta, relu, want_dres, want_d
     if _is_bf16(yn) and not act_bf16:
         yn = _to_f32(yn)              # (not produced by the fused units: a bf16 y always comes with a bf16 output)
     y16 = int(_is_bf16(yn))
-    if act_bf16:
+    if mask is not None:
+        if not relu or outn is not None or act_bf16 or y16 or mask.dtype != torch.uint8 or not mask.is_contiguous() or \
+                mask.numel() * 4 != yn.numel():
+            raise ValueError('GroupNorm backward: the ReLU mask belongs to a fp32 ReLU unit and stands in for its output')
+        E.call('seg3d_gn_bwd_reduce_mask', E.ptr(doutn), E.ptr(mask), E.ptr(yn), E.ptr(mean_rstd), E.ptr(part), N, S, C, ldd,
+               E.stream_ptr())
+    elif act_bf16:
         E.call('seg3d_gn_bwd_reduce_bf16', E.ptr(doutn), E.ptr(mask_src), E.ptr(yn), E.ptr(mean_rstd), E.ptr(gamma),
                E.ptr(beta), E.ptr(part), N, S, C, int(relu), ldd, y16, E.stream_ptr())
     else:
@@ -807,7 +833,10 @@ def gn_backward(doutn, outn, yn, mean_rstd, gamma, beta, relu, want_dres, want_d
                E.ptr(dbeta), E.ptr(dbias), N, S, C, acc_mask, E.stream_ptr())
     dy = torch.empty(yn.shape, dtype=torch.bfloat16 if dy_bf16 else torch.float32, device=yn.device)
     dres = torch.empty(yn.shape, dtype=torch.float32, device=yn.device) if want_dres else None
-    if act_bf16:
+    if mask is not None:
+        E.call('seg3d_gn_bwd_apply_mask', E.ptr(doutn), E.ptr(mask), E.ptr(yn), E.ptr(mean_rstd), E.ptr(s12), E.ptr(gamma),
+               E.ptr(dy), E.ptr(dres), N, S, C, ldd, E.stream_ptr())
+    elif act_bf16:
         E.call('seg3d_gn_bwd_apply_bf16', E.ptr(doutn), E.ptr(mask_src), E.ptr(yn), E.ptr(mean_rstd), E.ptr(s12),
                E.ptr(gamma), E.ptr(beta), E.ptr(dy), E.ptr(dres), N, S, C, int(relu), ldd, int(dy_bf16), y16,
                E.stream_ptr())
@@ -1010,7 +1039,12 @@ class ConvGnActFunction(torch.autograd.Function):
                 raise ValueError('residual shape {} does not match conv output {}'.format(tuple(residual.shape),
                                                                                           tuple(from_ndhwc(yn).shape)))
         C = yn.shape[4]
-        outn = gn_apply(yn, mean_rstd, gamma.detach(), beta.detach(), resn, relu, out=out_slot, out_bf16=_out_bf16(C))
+        # residual + ReLU with a backward pass to come: backward needs [out > 0] only, kept as a byte per channel quad
+        mask = None
+        if residual is not None and relu and not no_backward and relu_mask_usable(C) and not _is_bf16(yn) and \
+                not _is_bf16(resn) and not _out_bf16(C):
+            mask = torch.empty(yn.shape[:4] + (C // 4,), dtype=torch.uint8, device=yn.device)
+        outn = gn_apply(yn, mean_rstd, gamma.detach(), beta.detach(), resn, relu, out=out_slot, out_bf16=_out_bf16(C), mask=mask)
         # the gradient w.r.t. the conv output goes to the dgrad / wgrad kernels as bf16 when they take bf16 (same
         # condition as in forward: bf16 input activations and MFMA-shaped channel counts on both sides)
         ctx.dy_bf16 = _is_bf16(xn) and _is_bf16(outn) and xn.shape[4] % 16 == 0
@@ -1023,9 +1057,11 @@ class ConvGnActFunction(torch.autograd.Function):
         ctx.res_is_x = residual is not None and residual is x
         ctx.link_in, ctx.link_out = link_in, (link_out if residual is not None else None)
         ctx.sinks = (G.lookup(weight), G.lookup(bias), G.lookup(gamma), G.lookup(beta))
-        # the forward output is kept for backward only when a residual was added (otherwise the ReLU mask is
-        # recomputed from y, saving one full-tensor read in each of the two GroupNorm backward passes)
-        ctx.save_for_backward(xn, w, gamma.detach(), beta.detach(), yn, outn if residual is not None else None, mean_rstd)
+        # the forward output (or, in its place, its ReLU mask) is kept for backward only when a residual was added (otherwise
+        # the mask is recomputed from y, saving one full-tensor read in each of the two GroupNorm backward passes)
+        ctx.has_mask = mask is not None
+        ctx.save_for_backward(xn, w, gamma.detach(), beta.detach(), yn,
+                              mask if mask is not None else (outn if residual is not None else None), mean_rstd)
         return from_ndhwc(outn)
 
     @staticmethod
@@ -1033,10 +1069,13 @@ class ConvGnActFunction(torch.autograd.Function):
         xn, w, gamma, beta, yn, outn, mean_rstd = ctx.saved_tensors
         dn = to_ndhwc(dout)
         sw, sb_, sg, sbt = ctx.sinks
+        mask = None
+        if ctx.has_mask:
+            mask, outn = outn, None
         dy, dres, dgamma, dbeta, dbias = gn_backward(dn, outn, yn, mean_rstd, gamma, beta, ctx.relu,
                                                      want_dres=ctx.has_res and ctx.needs_input_grad[5],
                                                      want_dbias=ctx.has_bias, sinks=_views(sg, sbt, sb_),
-                                                     dy_bf16=ctx.dy_bf16)
+                                                     dy_bf16=ctx.dy_bf16, mask=mask)
         dx = None
         addend = None
         if ctx.res_is_x and dres is not None and ctx.needs_input_grad[0]:
