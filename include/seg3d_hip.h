@@ -372,6 +372,52 @@ int seg3d_adam_step_devstep(float* params, const float* grads, float* exp_avg, f
                             int* step_dev, float* bc_dev, float lr, float beta1, float beta2, float eps,
                             float weight_decay, float grad_scale, void* stream);
 
+/* ---- optimizer control block: gradient-norm clipping, learning-rate schedules, SGD (no counterpart in the reference) ---
+ * The per-step scalars live on the device so that a step captured in a hipGraph can change them and the gradient norm
+ * never travels to the host.  One step of a parameter group is
+ *     [seg3d_grad_sumsq_partial, only when clipping]  ->  seg3d_optim_prepare  ->  seg3d_sgd_step_ctl | seg3d_adam_step_ctl
+ * Control block: SEG3D_CTL_FLOATS floats, written by seg3d_optim_prepare, read by the *_ctl updates:
+ *   [SEG3D_CTL_LR]         learning rate of this step
+ *   [SEG3D_CTL_GRAD_MULT]  gradient multiplier grad_scale * coef (exactly grad_scale when coef == 1)
+ *   [SEG3D_CTL_BC1]        Adam: 1 - beta1^t
+ *   [SEG3D_CTL_BC2_SQRT]   Adam: sqrt(1 - beta2^t)
+ *   [SEG3D_CTL_NORM]       grad_scale * sqrt(sum of squares): the global gradient norm (0 when max_norm <= 0)
+ *   [SEG3D_CTL_COEF]       clip coefficient min(1, max_norm / (norm + 1e-6))  (1 when max_norm <= 0)
+ *   [6], [7]               reserved */
+#define SEG3D_CTL_LR 0
+#define SEG3D_CTL_GRAD_MULT 1
+#define SEG3D_CTL_BC1 2
+#define SEG3D_CTL_BC2_SQRT 3
+#define SEG3D_CTL_NORM 4
+#define SEG3D_CTL_COEF 5
+#define SEG3D_CTL_FLOATS 8
+#define SEG3D_SCHEDULE_CONSTANT 0
+#define SEG3D_SCHEDULE_POLY 1
+#define SEG3D_SCHEDULE_COSINE 2
+/* sum of squares of n floats (16-byte aligned): part[b] = fp64 partial of workgroup b, b < seg3d_grad_sumsq_part_count(n)
+ * (host arithmetic, at most 8192).  Exact fp64 products, fp64 accumulation, no atomics; the summation order depends on n
+ * only, so two calls on the same data are bit-equal. */
+long long seg3d_grad_sumsq_part_count(long long n);
+int seg3d_grad_sumsq_partial(const float* grads, long long n, double* part, void* stream);
+/* one workgroup: t = *step_dev + 1 (stored back); with max_norm > 0 the nparts slots (of all parameter groups, laid end
+ * to end) are added in a fixed order in fp64 and norm / coef follow the rule above -- torch.nn.utils.clip_grad_norm_'s,
+ * including that a non-finite norm is not skipped; with max_norm <= 0 the slots are not read (part may be NULL).
+ * Learning rate, with s = t - 1 completed steps, T = total_steps, in fp64 and rounded once to float:
+ *   lr = base_lr * w(s) * d(s),  w = warmup_steps ? min(1, (s + 1) / warmup_steps) : 1,
+ *   d = 1 (CONSTANT) | max(0, 1 - s / T)^power (POLY) | 0.5 (1 + cos(pi min(s, T) / T)) (COSINE)
+ * beta1 / beta2 feed Adam's bias corrections only (pass 0 for SGD). */
+int seg3d_optim_prepare(int* step_dev, float* ctl, const double* part, int nparts, float grad_scale, float max_norm,
+                        int schedule, float base_lr, int total_steps, int warmup_steps, float power, float beta1,
+                        float beta2, void* stream);
+/* torch.optim.SGD with dampening 0:  g = grads * ctl.mult + weight_decay * p;  buf = momentum * buf + g;
+ * d = nesterov ? g + momentum * buf : buf;  p -= ctl.lr * d.  A zero-initialised buf makes the first step torch's buf = g.
+ * momentum == 0: momentum_buf is neither read nor written (may be NULL). */
+int seg3d_sgd_step_ctl(float* params, const float* grads, float* momentum_buf, long long n, const float* ctl,
+                       float momentum, float weight_decay, int nesterov, void* stream);
+/* seg3d_adam_step with lr, the gradient multiplier and the bias corrections read from the control block */
+int seg3d_adam_step_ctl(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long long n,
+                        const float* ctl, float beta1, float beta2, float eps, float weight_decay, void* stream);
+
 /* ---- sliding-window batcher (core/seg_infer.py:208-246, 313-327, 336-339; utils/image_tools.py:435-469;
  *      utils/normalizer.py:6-81) ---------------------------------------------------------------------------------- */
 long long seg3d_patch_stats_blocks(int bx, int by, int bz);

@@ -175,6 +175,12 @@ _SIGNATURES = {
     'seg3d_compound_loss_bwd': (_c_int, [_c_p] * 6 + [_c_int, _c_int, _c_ll, _c_f, _c_int, _c_f, _c_p]),
     'seg3d_adam_step': (_c_int, [_c_p] * 4 + [_c_ll, _c_int] + [_c_f] * 6 + [_c_p]),
     'seg3d_adam_step_devstep': (_c_int, [_c_p] * 4 + [_c_ll, _c_p, _c_p] + [_c_f] * 6 + [_c_p]),
+    'seg3d_grad_sumsq_part_count': (_c_ll, [_c_ll]),
+    'seg3d_grad_sumsq_partial': (_c_int, [_c_p, _c_ll, _c_p, _c_p]),
+    'seg3d_optim_prepare': (_c_int, [_c_p, _c_p, _c_p, _c_int, _c_f, _c_f, _c_int, _c_f, _c_int, _c_int, _c_f, _c_f, _c_f,
+                                     _c_p]),
+    'seg3d_sgd_step_ctl': (_c_int, [_c_p, _c_p, _c_p, _c_ll, _c_p, _c_f, _c_f, _c_int, _c_p]),
+    'seg3d_adam_step_ctl': (_c_int, [_c_p] * 4 + [_c_ll, _c_p] + [_c_f] * 4 + [_c_p]),
     'seg3d_patch_stats_blocks': (_c_ll, [_c_int] * 3),
     'seg3d_patch_gather_normalize': (_c_int, [_c_p] * 5 + [_c_int] * 8 + [_c_f, _c_f, _c_int, _c_f, _c_p]),
     'seg3d_patch_stats_mc_doubles': (_c_ll, [_c_int] * 5),

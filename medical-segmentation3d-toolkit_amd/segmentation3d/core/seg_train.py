@@ -7,6 +7,7 @@ loss / Adam arithmetic in HIP kernels, gradients exchanged with a bucketed RCCL 
 """
 import importlib
 import gc
+import math
 import os
 import shutil
 import time
@@ -22,6 +23,7 @@ from segmentation3d.loss.cross_entropy_loss import CrossEntropyLoss
 from segmentation3d.loss.focal_loss import FocalLoss
 from segmentation3d.loss.multi_dice_loss import MultiDiceLoss
 from segmentation3d.optim.fused_adam import FusedAdam
+from segmentation3d.optim.fused_sgd import FusedSGD
 
 
 def build_loss(name, num_classes, obj_weight=None, focal_gamma=2, use_gpu=True, dice_weight=1.0, ce_weight=1.0,
@@ -50,14 +52,56 @@ def loss_options_from_config(loss_cfg):
             'batch_dice': getattr(loss_cfg, 'batch_dice', False), 'ignore_label': getattr(loss_cfg, 'ignore_label', None)}
 
 
+def optim_options_from_config(train_cfg, num_samples=None, world_size=1):
+    """the optional keys of the config's `train` section that select and configure the optimizer, with defaults that
+    reproduce the reference's run (Adam at one constant rate, no clipping: a config without them loads unchanged).
+    Returns {'optimizer': 'Adam' | 'SGD', + TrainStep's `optim_options`}; `momentum` / `nesterov` are read by SGD only.
+    `total_steps = None` means the whole run: ceil(epochs * num_samples / (batchsize * world_size))."""
+    name = getattr(train_cfg, 'optimizer', 'Adam')
+    if name not in ('Adam', 'SGD'):
+        raise ValueError('Unknown optimizer {!r} (Adam or SGD)'.format(name))
+    schedule = getattr(train_cfg, 'lr_schedule', 'constant')
+    warmup_steps = int(getattr(train_cfg, 'warmup_steps', 0))
+    lr_schedule = None
+    if schedule != 'constant' or warmup_steps > 0:
+        total_steps = getattr(train_cfg, 'total_steps', None)
+        if total_steps is None:
+            if num_samples is None:
+                raise ValueError('train.total_steps is not set and the number of samples is unknown')
+            total_steps = max(1, int(math.ceil(float(train_cfg.epochs) * num_samples /
+                                               (train_cfg.batchsize * max(1, int(world_size))))))
+        lr_schedule = {'name': schedule, 'total_steps': total_steps, 'warmup_steps': warmup_steps,
+                       'power': getattr(train_cfg, 'lr_power', 0.9)}
+    return {'optimizer': name, 'momentum': getattr(train_cfg, 'momentum', 0.99),
+            'nesterov': getattr(train_cfg, 'nesterov', True), 'weight_decay': getattr(train_cfg, 'weight_decay', 0.0),
+            'max_grad_norm': getattr(train_cfg, 'clip_grad_norm', None), 'lr_schedule': lr_schedule}
+
+
+def build_optimizer(name, params, lr, betas=(0.9, 0.999), optim_options=None):
+    """'Adam' -> FusedAdam(lr, betas), 'SGD' -> FusedSGD(lr); `optim_options`: weight_decay, max_grad_norm,
+    lr_schedule, and for SGD momentum, nesterov"""
+    opts = dict(optim_options or {})
+    opts.pop('optimizer', None)
+    unknown = set(opts) - {'momentum', 'nesterov', 'weight_decay', 'max_grad_norm', 'lr_schedule'}
+    if unknown:
+        raise ValueError('unknown optim_options: {}'.format(sorted(unknown)))
+    if name == 'Adam':
+        opts.pop('momentum', None)
+        opts.pop('nesterov', None)
+        return FusedAdam(params, lr=lr, betas=betas, **opts)
+    if name == 'SGD':
+        return FusedSGD(params, lr=lr, **opts)
+    raise ValueError('Unknown optimizer {!r} (Adam or SGD)'.format(name))
+
+
 class TrainStep(object):
-    """network + loss + FusedAdam (+ gradient reducer when distributed) on one device; `loss_options` is a dict of
-    build_loss's keyword options for the compound losses (dice_weight, ce_weight, include_background, batch_dice,
-    ignore_label)"""
+    """network + loss + FusedAdam or FusedSGD (+ gradient reducer when distributed) on one device; `loss_options` is a
+    dict of build_loss's keyword options for the compound losses (dice_weight, ce_weight, include_background, batch_dice,
+    ignore_label); `optimizer` / `optim_options` are build_optimizer's (gradient-norm clipping, lr schedule, SGD)"""
 
     def __init__(self, net_name, in_channels, num_classes, loss_name='Dice', obj_weight=None, focal_gamma=2, lr=1e-4,
                  betas=(0.9, 0.999), device=None, seed=0, distributed=None, num_buckets=4, use_graph=False,
-                 loss_options=None):
+                 loss_options=None, optimizer='Adam', optim_options=None):
         self.device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
         if self.device.type == 'cuda' and self.device.index is not None:
             torch.cuda.set_device(self.device)   # the engine launches on the current device's stream (_engine.stream_ptr)
@@ -67,8 +111,8 @@ class TrainStep(object):
         self.max_stride = self.net.max_stride()
         net_module.parameters_kaiming_init(self.net)                                    # core/seg_train.py:75
         self.net = self.net.to(self.device)
-        self.opt = FusedAdam(self.net.parameters(), lr=lr, betas=betas)                 # core/seg_train.py:83
-        _ops.weight_cache(True)   # packed conv weights are refreshed by FusedAdam.step() with one launch per step
+        self.opt = build_optimizer(optimizer, self.net.parameters(), lr, betas, optim_options)   # core/seg_train.py:83
+        _ops.weight_cache(True)   # packed conv weights are refreshed by the optimizer's step() with one launch per step
         self.loss_func = build_loss(loss_name, num_classes, obj_weight, focal_gamma, use_gpu=True, **(loss_options or {}))
         if distributed is None:
             distributed = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
@@ -139,7 +183,7 @@ class TrainStep(object):
         loss = self.loss_func(outputs, masks)
         loss.backward()
         if self.reducer is not None:
-            self.reducer.finish_step()
+            self.reducer.finish_step()   # the norm a clipping optimizer measures is that of the REDUCED buffer
         self.opt.step()
         return loss
 
@@ -201,10 +245,14 @@ def train(train_config_file, data_iter_factory=None):
     else:
         num_modality = int(getattr(cfg.dataset, 'num_modality', 1))
     _ops.set_activation_dtype(str(getattr(cfg.train, 'compute_dtype', 'fp32')))
+    num_samples = len(dataset) if dataset is not None else int(getattr(cfg.dataset, 'num_samples', cfg.train.batchsize))
+    optim_options = optim_options_from_config(cfg.train, num_samples, world_size)
+    show_lr = optim_options['lr_schedule'] is not None and optim_options['lr_schedule']['name'] != 'constant'
     step = TrainStep(cfg.net.name, num_modality, cfg.dataset.num_classes, cfg.loss.name, cfg.loss.obj_weight,
                      cfg.loss.focal_gamma, cfg.train.lr, tuple(cfg.train.betas), seed=cfg.general.seed,
                      use_graph=bool(getattr(cfg.train, 'use_graph', False)),
-                     loss_options=loss_options_from_config(cfg.loss))
+                     loss_options=loss_options_from_config(cfg.loss), optimizer=optim_options.pop('optimizer'),
+                     optim_options=optim_options)
     assert np.all(np.array(cfg.dataset.crop_size) % step.max_stride == 0), 'crop size not divisible by max stride'
     last_save_epoch, batch_idx = 0, 0
     if cfg.general.resume_epoch >= 0:
@@ -218,10 +266,8 @@ def train(train_config_file, data_iter_factory=None):
         else:
             sampler = EpochConcateSampler(dataset, cfg.train.epochs)
         batches = DeviceCropLoader(dataset, sampler, cfg.train.batchsize)
-        num_samples = len(dataset)
     else:
         batches = data_iter_factory(cfg)
-        num_samples = int(getattr(cfg.dataset, 'num_samples', cfg.train.batchsize))
     steps_this_run = 0
     for batch in batches:
         crops, masks = batch[0], batch[1]
@@ -240,8 +286,11 @@ def train(train_config_file, data_iter_factory=None):
         value = loss.item()
         sample_duration = (time.time() - begin_t) / cfg.train.batchsize
         if logger is not None:
-            logger.info('epoch: {}, batch: {}, train_loss: {:.4f}, time: {:.4f} s/vol'.format(epoch_idx, batch_idx, value,
-                                                                                             sample_duration))
+            line = 'epoch: {}, batch: {}, train_loss: {:.4f}, time: {:.4f} s/vol'.format(epoch_idx, batch_idx, value,
+                                                                                        sample_duration)
+            if show_lr:   # the reference's log format unless a schedule moves the rate
+                line += ', lr: {:.6e}'.format(step.opt.param_groups[0]['lr'])
+            logger.info(line)
         if rank == 0 and epoch_idx != 0 and epoch_idx % cfg.train.save_epochs == 0 and last_save_epoch != epoch_idx:
             save_checkpoint(step.net, step.opt, epoch_idx, batch_idx, cfg, step.max_stride, num_modality)
             last_save_epoch = epoch_idx
