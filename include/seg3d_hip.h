@@ -222,6 +222,29 @@ int seg3d_convT3d_k2s2_mfma_fwd(const float* x, const float* wp_mfma, const floa
 long long seg3d_k2_mfma_wgrad_workspace_floats(int N, int Dq, int Hq, int Wq, int CA, int CB);
 int seg3d_k2_mfma_wgrad(const float* P, const float* Q, float* dw, float* workspace, int N, int Dq, int Hq, int Wq, int CA,
                         int CB, long long sa, long long sb, int accumulate, void* stream);
+/* Which kernel instantiation of csrc/conv_k2_mfma.hip a call runs (pure host arithmetic: the launchers decide through the
+ * same functions).  Negative where the launcher would refuse the arguments.  x_mode: 0 fp32 x, 1 bf16 x with the fp32 weight
+ * image, 2 bf16 x with the bf16 weight image; out_bf16 needs x_mode 1 or 2.
+ * gather (seg3d_conv3d_k2s2_mfma_fwd / _fwd_ld / _bf16_fwd): 100 x_mode + 10 out_bf16 + k
+ *   k = 0  conv3d_k2s2_mfma_kernel<MODE, OUT_BF>                  LDS-staged: an odd count of 8-channel (mode 2: 16-channel) chunks
+ *   k = 1  conv3d_k2s2_direct_kernel<MODE, OUT_BF, NCOB 1, KSPLIT 1>
+ *   k = 2  conv3d_k2s2_direct_kernel<MODE, OUT_BF, 2, 1>          Cout % 64 == 0 and at least 16384 waves
+ *   k = 3  conv3d_k2s2_direct_kernel<MODE, OUT_BF, 1, 4>          chunk count % 4 == 0 and fewer than 3072 waves
+ * scatter (seg3d_convT3d_k2s2_mfma_fwd / _bf16_fwd, and with has_addend seg3d_convT3d_k2s2_scatter_addend):
+ *   100 x_mode + 10 out_bf16 + 4 direct + 2 ADD + PAIR
+ *   direct = 1  convT3d_k2s2_direct_kernel<MODE, ADD, PAIR>       (fp32 y only)
+ *   direct = 0  convT3d_k2s2_mfma_kernel<MODE, OUT_BF, ADD, PAIR>
+ *   ADD = has_addend; PAIR = two taps per MFMA (Cout 8 or 16)
+ * weight gradient (seg3d_k2_mfma_wgrad: bf16 = 0, seg3d_k2_bf16_wgrad: bf16 = 1): 10 k + r
+ *   k = 0  k2_wgrad_mfma_kernel<false>     fp32, CA > 16
+ *   k = 1  k2_wgrad_pair_kernel            fp32, CA <= 16
+ *   k = 2  k2_wgrad_bf16_mfma_kernel       bf16, CA % 8 == 0 and CB % 8 == 0
+ *   k = 3  k2_wgrad_mfma_kernel<true>      bf16, other channel counts
+ *   r = 1  k2_wgrad_reduce4_kernel<16> follows (32 or more partial slabs), r = 0  k2_wgrad_reduce_kernel */
+int seg3d_conv3d_k2s2_variant(int N, int Do, int Ho, int Wo, int Cin, int Cout, int x_mode, int out_bf16);
+int seg3d_convT3d_k2s2_variant(int N, int Di, int Hi, int Wi, int Cin, int Cout, int x_mode, int out_bf16, int has_addend,
+                               int ld_addend);
+int seg3d_k2_wgrad_variant(int N, int Dq, int Hq, int Wq, int CA, int CB, int bf16);
 
 /* thin 3x3x3 layers at full resolution (stem Cin <= 8 -> 16, head 32 -> num_classes <= 8): HBM-bound special cases
  * of Conv3d k3 p1 (vnet_inblock.py:9, vnet_outblock.py:13) and of their autograd adjoints */

@@ -487,42 +487,76 @@ extern "C" long long seg3d_conv3d_k2s2_mfma_stats_count(int Do, int Ho, int Wo, 
   return (long long)seg3d_cdiv(Do, t.tz) * seg3d_cdiv(Ho, t.ty) * seg3d_cdiv(Wo, t.tx) * 4 * ((Cout + 31) / 32);   // [tile][4][column block]
 }
 
-// x [N][2Do][2Ho][2Wo][Cin] -> y [N][Do][Ho][Wo][Cout];  wp = seg3d_pack_weights_mfma(A = Cin, B = Cout, T = 8)
-static int k2_gather_launch(const void* x, int x_bf16, const float* wp, const float* bias, float* y, float* stats, int N,
-                            int Do, int Ho, int Wo, int Cin, int Cout, void* stream, int out_bf16 = 0, int ldx = 0) {
-  if (ldx == 0) ldx = Cin;
+#ifndef K2_GATHER_DIRECT
+#define K2_GATHER_DIRECT 1   // 0: the LDS-staged kernel (kept for same-box A/B builds)
+#endif
+// The gather launch of a problem: tile, grid and WHICH kernel -- the one place that decides it, shared by the launcher and by
+// seg3d_conv3d_k2s2_variant (tests pin the variant a shape reaches, so a retuned threshold shows up as a failed lookup).
+// kernel: 0 = conv3d_k2s2_mfma_kernel (LDS-staged), 1 = conv3d_k2s2_direct_kernel<.., NCOB 1, KSPLIT 1>, 2 = <.., 2, 1>, 3 = <.., 1, 4>
+enum { K2G_STAGED = 0, K2G_DIRECT_1_1 = 1, K2G_DIRECT_2_1 = 2, K2G_DIRECT_1_4 = 3 };
+struct K2GatherPlan {
+  K2Tile t;
+  int ntz, nty, ntx;
+  unsigned gx, gy;   // the staged grid: (sample, tile) x 32-channel column block
+  int kernel;
+};
+// x_mode: 0 = fp32 input, 1 = bf16 input widened while staging (fp32 weight image), 2 = bf16 input + bf16 weight image
+static int k2_gather_plan(int x_mode, int out_bf16, int N, int Do, int Ho, int Wo, int Cin, int Cout, int ldx, K2GatherPlan* p) {
+  SEG3D_REQUIRE(x_mode >= 0 && x_mode <= 2 && (x_mode != 0 || !out_bf16),
+                "seg3d_conv3d_k2s2_mfma_fwd: x_mode must be 0, 1 or 2, and a bf16 output needs a bf16 input");
   SEG3D_REQUIRE(ldx >= Cin && (ldx % 4) == 0, "seg3d_conv3d_k2s2_mfma_fwd: ld_x must be a multiple of 4 >= Cin");
-  SEG3D_REQUIRE(x && wp && y, "seg3d_conv3d_k2s2_mfma_fwd: null pointer");
   SEG3D_REQUIRE(N > 0 && Do > 0 && Ho > 0 && Wo > 0 && Cin > 0 && Cout > 0, "seg3d_conv3d_k2s2_mfma_fwd: bad dims");
   SEG3D_REQUIRE((Cin % 4) == 0 && (Cout % 4) == 0,
                 "seg3d_conv3d_k2s2_mfma_fwd: Cin and Cout must be multiples of 4 (got %d, %d)", Cin, Cout);
   SEG3D_REQUIRE((i64)N * Do * Ho * Wo * 8 * ldx < (1ll << 31) && (i64)N * Do * Ho * Wo * Cout < (1ll << 31),
                 "seg3d_conv3d_k2s2_mfma_fwd: tensor exceeds 2^31 elements");
   SEG3D_REQUIRE((i64)Do * Ho * Wo * 8 * ldx * 4 < (1ll << 31), "seg3d_conv3d_k2s2_mfma_fwd: one sample of x exceeds 2^31 bytes");
-  K2Tile t = k2_pick_tile(Do, Ho, Wo);
-  const int ntz = seg3d_cdiv(Do, t.tz), nty = seg3d_cdiv(Ho, t.ty), ntx = seg3d_cdiv(Wo, t.tx);
-  const int mt = t.tz * t.ty * t.tx;
-  const size_t lds = (size_t)(8 * 8 * mt + K2_W_CHUNK + ((mt + 3) & ~3)) * 4;
-  SEG3D_REQUIRE((i64)N * ntz * nty * ntx < SEG3D_FDIV_MAX, "2x2x2 stride-2 MFMA kernels: more than 2^22 tiles");
-  dim3 grid((unsigned)(N * ntz * nty * ntx), (unsigned)((Cout + 31) / 32));
-  // x_bf16: 0 = fp32 input, 1 = bf16 input widened while staging (fp32 weight image), 2 = bf16 input + bf16 weight image
-  SEG3D_REQUIRE(x_bf16 != 2 || (Cin % 16) == 0, "seg3d_conv3d_k2s2_bf16_fwd: the bf16 weight image needs Cin %% 16 == 0");
-#ifndef K2_GATHER_DIRECT
-#define K2_GATHER_DIRECT 1   // 0: the LDS-staged kernel (kept for same-box A/B builds)
-#endif
+  p->t = k2_pick_tile(Do, Ho, Wo);
+  p->ntz = seg3d_cdiv(Do, p->t.tz), p->nty = seg3d_cdiv(Ho, p->t.ty), p->ntx = seg3d_cdiv(Wo, p->t.tx);
+  SEG3D_REQUIRE((i64)N * p->ntz * p->nty * p->ntx < SEG3D_FDIV_MAX, "2x2x2 stride-2 MFMA kernels: more than 2^22 tiles");
+  p->gx = (unsigned)(N * p->ntz * p->nty * p->ntx), p->gy = (unsigned)((Cout + 31) / 32);
+  SEG3D_REQUIRE(x_mode != 2 || (Cin % 16) == 0, "seg3d_conv3d_k2s2_bf16_fwd: the bf16 weight image needs Cin %% 16 == 0");
   // the direct kernel's variants: KSPLIT where 128-voxel tiles give fewer than two waves per SIMD and K is deep enough to deal
   // out ((kz, ky) runs of at least two steps: Cin >= 32 in fp32), two column blocks per wave where that still leaves three
-  const i64 waves1 = (i64)grid.x * grid.y * 4;
+  const i64 waves1 = (i64)p->gx * p->gy * 4;
+  const int cib = (Cin + (x_mode == 2 ? 15 : 7)) / (x_mode == 2 ? 16 : 8);   // 2 cib steps of four chunks
+  if (K2_GATHER_DIRECT && cib % 4 == 0 && waves1 < 3072) p->kernel = K2G_DIRECT_1_4;
+  else if (K2_GATHER_DIRECT && cib % 2 == 0 && Cout % 64 == 0 && waves1 >= 16384) p->kernel = K2G_DIRECT_2_1;
+  else if (K2_GATHER_DIRECT && cib % 2 == 0) p->kernel = K2G_DIRECT_1_1;
+  else p->kernel = K2G_STAGED;
+  return SEG3D_OK;
+}
+
+// which kernel instantiation a gather launch runs: 100 x_mode + 10 out_bf16 + kernel (see K2GatherPlan); negative where the
+// launcher refuses the arguments
+extern "C" int seg3d_conv3d_k2s2_variant(int N, int Do, int Ho, int Wo, int Cin, int Cout, int x_mode, int out_bf16) {
+  K2GatherPlan p;
+  const int rc = k2_gather_plan(x_mode, out_bf16, N, Do, Ho, Wo, Cin, Cout, Cin, &p);
+  return rc != SEG3D_OK ? rc : 100 * x_mode + 10 * (out_bf16 ? 1 : 0) + p.kernel;
+}
+
+// x [N][2Do][2Ho][2Wo][Cin] -> y [N][Do][Ho][Wo][Cout];  wp = seg3d_pack_weights_mfma(A = Cin, B = Cout, T = 8)
+static int k2_gather_launch(const void* x, int x_bf16, const float* wp, const float* bias, float* y, float* stats, int N,
+                            int Do, int Ho, int Wo, int Cin, int Cout, void* stream, int out_bf16 = 0, int ldx = 0) {
+  if (ldx == 0) ldx = Cin;
+  SEG3D_REQUIRE(x && wp && y, "seg3d_conv3d_k2s2_mfma_fwd: null pointer");
+  K2GatherPlan p;
+  const int rc = k2_gather_plan(x_bf16, out_bf16, N, Do, Ho, Wo, Cin, Cout, ldx, &p);
+  if (rc != SEG3D_OK) return rc;
+  const K2Tile t = p.t;
+  const int ntz = p.ntz, nty = p.nty, ntx = p.ntx;
+  const int mt = t.tz * t.ty * t.tx;
+  const size_t lds = (size_t)(8 * 8 * mt + K2_W_CHUNK + ((mt + 3) & ~3)) * 4;
+  const dim3 grid(p.gx, p.gy);
 #define K2_GATHER(MODE_, OB_)                                                                                        \
   do {                                                                                                               \
-    const int cib_ = (Cin + (MODE_ == 2 ? 15 : 7)) / (MODE_ == 2 ? 16 : 8);   /* 2 cib_ steps of four chunks */      \
-    if (K2_GATHER_DIRECT && cib_ % 4 == 0 && waves1 < 3072)                                                          \
+    if (p.kernel == K2G_DIRECT_1_4)                                                                                  \
       hipLaunchKernelGGL((conv3d_k2s2_direct_kernel<MODE_, OB_, 1, 4>), dim3(grid.x * 4, grid.y), dim3(256), 0,      \
                          (hipStream_t)stream, x, wp, bias, y, stats, N, Do, Ho, Wo, Cin, Cout, t.tz, t.ty, t.tx, ntz, nty, ntx, ldx); \
-    else if (K2_GATHER_DIRECT && cib_ % 2 == 0 && Cout % 64 == 0 && waves1 >= 16384)                                \
+    else if (p.kernel == K2G_DIRECT_2_1)                                                                             \
       hipLaunchKernelGGL((conv3d_k2s2_direct_kernel<MODE_, OB_, 2, 1>), dim3(grid.x, grid.y / 2), dim3(256), 0,      \
                          (hipStream_t)stream, x, wp, bias, y, stats, N, Do, Ho, Wo, Cin, Cout, t.tz, t.ty, t.tx, ntz, nty, ntx, ldx); \
-    else if (K2_GATHER_DIRECT && cib_ % 2 == 0)                                                                      \
+    else if (p.kernel == K2G_DIRECT_1_1)                                                                             \
       hipLaunchKernelGGL((conv3d_k2s2_direct_kernel<MODE_, OB_, 1, 1>), grid, dim3(256), 0, (hipStream_t)stream, x, wp, bias, y, \
                          stats, N, Do, Ho, Wo, Cin, Cout, t.tz, t.ty, t.tx, ntz, nty, ntx, ldx);                     \
     else                                                                                                             \
@@ -964,34 +998,66 @@ extern "C" long long seg3d_convT3d_k2s2_mfma_stats_count(int Di, int Hi, int Wi,
   return (long long)seg3d_cdiv(Di, t.tz) * seg3d_cdiv(Hi, t.ty) * seg3d_cdiv(Wi, t.tx) * 4 * ((Cout + 31) / 32);   // [tile][4][column block]
 }
 
-// x [N][Di][Hi][Wi][Cin] -> y [N][2Di][2Hi][2Wi][Cout];  wp = seg3d_pack_weights_mfma(A = Cin, B = Cout, T = 8)
-static int k2_scatter_launch(const void* x, int x_bf16, const float* wp, const float* bias, float* y, float* stats, int N,
-                             int Di, int Hi, int Wi, int Cin, int Cout, void* stream, int out_bf16 = 0,
-                             const void* addend = nullptr, int lda = 0) {
-  SEG3D_REQUIRE(x && wp && y, "seg3d_convT3d_k2s2_mfma_fwd: null pointer");
+#ifndef K2_SCATTER_DIRECT
+#define K2_SCATTER_DIRECT 1   // 0: the LDS-staged kernel (kept for same-box A/B builds)
+#endif
+// The scatter launch of a problem, decided in one place for the launcher and for seg3d_convT3d_k2s2_variant:
+//   direct  convT3d_k2s2_direct_kernel<MODE, ADD, PAIR> (else convT3d_k2s2_mfma_kernel<MODE, OUT_BF, ADD, PAIR>)
+//   pair    two taps per MFMA (rows (tap & 1) * 16 + co): Cout 8 or 16
+struct K2ScatterPlan {
+  K2Tile t;
+  int ntz, nty, ntx;
+  unsigned gx, gy;   // the staged grid: (sample, tile) x 32-channel column block
+  bool direct, pair;
+};
+static int k2_scatter_plan(int x_mode, int out_bf16, int N, int Di, int Hi, int Wi, int Cin, int Cout, bool addend, int lda,
+                           K2ScatterPlan* p) {
+  SEG3D_REQUIRE(x_mode >= 0 && x_mode <= 2 && (x_mode != 0 || !out_bf16),
+                "seg3d_convT3d_k2s2_mfma_fwd: x_mode must be 0, 1 or 2, and a bf16 output needs a bf16 input");
   SEG3D_REQUIRE(N > 0 && Di > 0 && Hi > 0 && Wi > 0 && Cin > 0 && Cout > 0, "seg3d_convT3d_k2s2_mfma_fwd: bad dims");
   SEG3D_REQUIRE((Cin % 4) == 0 && (Cout % 4) == 0,
                 "seg3d_convT3d_k2s2_mfma_fwd: Cin and Cout must be multiples of 4 (got %d, %d)", Cin, Cout);
   SEG3D_REQUIRE((i64)N * Di * Hi * Wi * 8 * Cout < (1ll << 31) && (i64)N * Di * Hi * Wi * Cin < (1ll << 31),
                 "seg3d_convT3d_k2s2_mfma_fwd: tensor exceeds 2^31 elements");
-  K2Tile t = k2_pick_tile(Di, Hi, Wi);
-  const int ntz = seg3d_cdiv(Di, t.tz), nty = seg3d_cdiv(Hi, t.ty), ntx = seg3d_cdiv(Wi, t.tx);
-  SEG3D_REQUIRE((i64)N * ntz * nty * ntx < SEG3D_FDIV_MAX, "2x2x2 stride-2 MFMA kernels: more than 2^22 tiles");
-  dim3 grid((unsigned)(N * ntz * nty * ntx), (unsigned)((Cout + 31) / 32));
-  SEG3D_REQUIRE(x_bf16 != 2 || (Cin % 16) == 0, "seg3d_convT3d_k2s2_bf16_fwd: the bf16 weight image needs Cin %% 16 == 0");
+  p->t = k2_pick_tile(Di, Hi, Wi);
+  p->ntz = seg3d_cdiv(Di, p->t.tz), p->nty = seg3d_cdiv(Hi, p->t.ty), p->ntx = seg3d_cdiv(Wi, p->t.tx);
+  SEG3D_REQUIRE((i64)N * p->ntz * p->nty * p->ntx < SEG3D_FDIV_MAX, "2x2x2 stride-2 MFMA kernels: more than 2^22 tiles");
+  p->gx = (unsigned)(N * p->ntz * p->nty * p->ntx), p->gy = (unsigned)((Cout + 31) / 32);
+  SEG3D_REQUIRE(x_mode != 2 || (Cin % 16) == 0, "seg3d_convT3d_k2s2_bf16_fwd: the bf16 weight image needs Cin %% 16 == 0");
   SEG3D_REQUIRE(!addend || ((Cout & 7) == 0 && lda >= Cout && (lda & 3) == 0),
                 "seg3d_convT3d_k2s2_scatter_addend: needs Cout %% 8 == 0 and a row stride >= Cout, multiple of 4");
-  const bool pair = Cout <= 16 && (Cout & 7) == 0;   // two taps per MFMA (rows (tap & 1) * 16 + co)
-#ifndef K2_SCATTER_DIRECT
-#define K2_SCATTER_DIRECT 1   // 0: the LDS-staged kernel (kept for same-box A/B builds)
-#endif
+  p->pair = Cout <= 16 && (Cout & 7) == 0;   // two taps per MFMA (rows (tap & 1) * 16 + co)
   // the direct kernel: fp32 outputs, whole steps (Cin a multiple of four chunks), whole 16-byte pieces of whole column blocks
   // -- and where it measured faster (tools/bench_k2.py, same box): every launch with a fused addend (its loads are coalesced too:
   // 168 -> 137 us at the top level, 50 -> 21 at 12^3) and the forward launches whose staged grid is under one workgroup per CU
   // (47 -> 21 us at 6^3, 49 -> 42 at 12^3); the forward at 24^3 / 48^3 is 4 % / 1.5 % faster staged (51 vs 56, 116 vs 118 us)
-  const bool direct = K2_SCATTER_DIRECT && !out_bf16 && (x_bf16 == 2 ? Cin % 64 == 0 : Cin % 32 == 0) &&
-                      (Cout == 16 || Cout % 32 == 0) && (!addend || (lda % 4) == 0) &&
-                      (addend || (i64)grid.x * grid.y < 256);
+  p->direct = K2_SCATTER_DIRECT && !out_bf16 && (x_mode == 2 ? Cin % 64 == 0 : Cin % 32 == 0) &&
+              (Cout == 16 || Cout % 32 == 0) && (!addend || (lda % 4) == 0) && (addend || (i64)p->gx * p->gy < 256);
+  return SEG3D_OK;
+}
+
+// which kernel instantiation a scatter launch runs: 100 x_mode + 10 out_bf16 + 4 direct + 2 ADD + PAIR (see K2ScatterPlan);
+// negative where the launcher (with an addend: seg3d_convT3d_k2s2_scatter_addend) refuses the arguments
+extern "C" int seg3d_convT3d_k2s2_variant(int N, int Di, int Hi, int Wi, int Cin, int Cout, int x_mode, int out_bf16,
+                                          int has_addend, int ld_addend) {
+  K2ScatterPlan p;
+  const int rc = k2_scatter_plan(x_mode, out_bf16, N, Di, Hi, Wi, Cin, Cout, has_addend != 0, ld_addend, &p);
+  if (rc != SEG3D_OK) return rc;
+  return 100 * x_mode + 10 * (out_bf16 ? 1 : 0) + 4 * (p.direct ? 1 : 0) + 2 * (has_addend ? 1 : 0) + (p.pair ? 1 : 0);
+}
+
+// x [N][Di][Hi][Wi][Cin] -> y [N][2Di][2Hi][2Wi][Cout];  wp = seg3d_pack_weights_mfma(A = Cin, B = Cout, T = 8)
+static int k2_scatter_launch(const void* x, int x_bf16, const float* wp, const float* bias, float* y, float* stats, int N,
+                             int Di, int Hi, int Wi, int Cin, int Cout, void* stream, int out_bf16 = 0,
+                             const void* addend = nullptr, int lda = 0) {
+  SEG3D_REQUIRE(x && wp && y, "seg3d_convT3d_k2s2_mfma_fwd: null pointer");
+  K2ScatterPlan p;
+  const int rc = k2_scatter_plan(x_bf16, out_bf16, N, Di, Hi, Wi, Cin, Cout, addend != nullptr, lda, &p);
+  if (rc != SEG3D_OK) return rc;
+  const K2Tile t = p.t;
+  const int ntz = p.ntz, nty = p.nty, ntx = p.ntx;
+  const dim3 grid(p.gx, p.gy);
+  const bool pair = p.pair, direct = p.direct;
 #define K2_SCATTER_D(MODE_)                                                                                          \
   do {                                                                                                               \
     const dim3 g4(grid.x * 4, grid.y);                                                                               \
@@ -1604,28 +1670,58 @@ extern "C" long long seg3d_k2_mfma_wgrad_workspace_floats(int N, int Dq, int Hq,
   return (long long)k2_wgrad_slabs(N, Dq, Hq, Wq, npairs, CA) * npairs * 8 * 1024;
 }
 
+// The weight-gradient launches of a problem, decided in one place for the launcher and for seg3d_k2_wgrad_variant.
+// kernel: 0 = k2_wgrad_mfma_kernel<false>, 1 = k2_wgrad_pair_kernel, 2 = k2_wgrad_bf16_mfma_kernel, 3 = k2_wgrad_mfma_kernel<true>;
+// reduce4: k2_wgrad_reduce4_kernel<16> follows (else k2_wgrad_reduce_kernel)
+enum { K2W_MFMA_F32 = 0, K2W_PAIR = 1, K2W_BF16_MFMA = 2, K2W_MFMA_BF16IN = 3 };
+struct K2WgradPlan {
+  int BB32, npairs, ntz, nty, ntx, ntiles, slabs;
+  int kernel;
+  bool reduce4;
+};
+static int k2_wgrad_plan(int bf16, int N, int Dq, int Hq, int Wq, int CA, int CB, K2WgradPlan* p) {
+  SEG3D_REQUIRE(N > 0 && Dq > 0 && Hq > 0 && Wq > 0 && CA > 0 && CB > 0, "seg3d_k2_mfma_wgrad: bad dims");
+  SEG3D_REQUIRE((CA % 4) == 0 && (CB % 4) == 0, "seg3d_k2_mfma_wgrad: channel counts must be multiples of 4 (got %d, %d)",
+                CA, CB);
+  const int AB32 = (CA + 31) / 32;
+  p->BB32 = (CB + 31) / 32;
+  p->npairs = AB32 * p->BB32;
+  p->ntz = seg3d_cdiv(Dq, K2W_TZ), p->nty = seg3d_cdiv(Hq, K2W_TY), p->ntx = seg3d_cdiv(Wq, K2W_TX);
+  p->ntiles = N * p->ntz * p->nty * p->ntx;
+  SEG3D_REQUIRE((i64)N * p->ntz * p->nty * p->ntx < SEG3D_FDIV_MAX, "seg3d_k2_mfma_wgrad: more than 2^22 tiles");
+  p->slabs = k2_wgrad_slabs(N, Dq, Hq, Wq, p->npairs, CA);
+  if (bf16 && (CA & 7) == 0 && (CB & 7) == 0) p->kernel = K2W_BF16_MFMA;
+  else if (bf16) p->kernel = K2W_MFMA_BF16IN;
+  else if (CA <= 16) p->kernel = K2W_PAIR;   // two taps per MFMA (rows (tap & 1) * 16 + a)
+  else p->kernel = K2W_MFMA_F32;
+  p->reduce4 = p->slabs >= 32;
+  return SEG3D_OK;
+}
+
+// which kernels a weight-gradient call runs: 10 kernel + reduce4 (see K2WgradPlan); negative where the launcher refuses
+extern "C" int seg3d_k2_wgrad_variant(int N, int Dq, int Hq, int Wq, int CA, int CB, int bf16) {
+  K2WgradPlan p;
+  const int rc = k2_wgrad_plan(bf16, N, Dq, Hq, Wq, CA, CB, &p);
+  return rc != SEG3D_OK ? rc : 10 * p.kernel + (p.reduce4 ? 1 : 0);
+}
+
 // P [N][2Dq][2Hq][2Wq][CA], Q [N][Dq][Hq][Wq][CB];  dw[a*sa + b*sb + t] (t < 8) receives the gradient
 static int k2_wgrad_launch(const void* P, const void* Q, int bf16, float* dw, float* workspace, int N, int Dq, int Hq,
                            int Wq, int CA, int CB, long long sa, long long sb, int accumulate, void* stream) {
   SEG3D_REQUIRE(P && Q && dw && workspace, "seg3d_k2_mfma_wgrad: null pointer");
-  SEG3D_REQUIRE(N > 0 && Dq > 0 && Hq > 0 && Wq > 0 && CA > 0 && CB > 0, "seg3d_k2_mfma_wgrad: bad dims");
-  SEG3D_REQUIRE((CA % 4) == 0 && (CB % 4) == 0, "seg3d_k2_mfma_wgrad: channel counts must be multiples of 4 (got %d, %d)",
-                CA, CB);
-  const int AB32 = (CA + 31) / 32, BB32 = (CB + 31) / 32;
-  const int npairs = AB32 * BB32;
-  const int ntz = seg3d_cdiv(Dq, K2W_TZ), nty = seg3d_cdiv(Hq, K2W_TY), ntx = seg3d_cdiv(Wq, K2W_TX);
-  const int ntiles = N * ntz * nty * ntx;
-  SEG3D_REQUIRE((i64)N * ntz * nty * ntx < SEG3D_FDIV_MAX, "seg3d_k2_mfma_wgrad: more than 2^22 tiles");
-  const int slabs = k2_wgrad_slabs(N, Dq, Hq, Wq, npairs, CA);
+  K2WgradPlan p;
+  const int rc = k2_wgrad_plan(bf16, N, Dq, Hq, Wq, CA, CB, &p);
+  if (rc != SEG3D_OK) return rc;
+  const int BB32 = p.BB32, npairs = p.npairs, ntz = p.ntz, nty = p.nty, ntx = p.ntx, ntiles = p.ntiles, slabs = p.slabs;
   hipStream_t s = (hipStream_t)stream;
-  if (bf16 && (CA & 7) == 0 && (CB & 7) == 0)
+  if (p.kernel == K2W_BF16_MFMA)
     hipLaunchKernelGGL(k2_wgrad_bf16_mfma_kernel, dim3(slabs, npairs), dim3(256), 0, s,
                        reinterpret_cast<const seg3d_bf16*>(P), reinterpret_cast<const seg3d_bf16*>(Q), workspace, N, Dq, Hq,
                        Wq, CA, CB, ntz, nty, ntx, ntiles, BB32);
-  else if (bf16)
+  else if (p.kernel == K2W_MFMA_BF16IN)
     hipLaunchKernelGGL(k2_wgrad_mfma_kernel<true>, dim3(slabs, npairs), dim3(256), 0, s, P, Q, workspace, N, Dq, Hq, Wq, CA,
                        CB, ntz, nty, ntx, ntiles, BB32);
-  else if (CA <= 16)   // two taps per MFMA (rows (tap & 1) * 16 + a)
+  else if (p.kernel == K2W_PAIR)
     hipLaunchKernelGGL(k2_wgrad_pair_kernel, dim3(slabs, npairs), dim3(256), 0, s, reinterpret_cast<const float*>(P),
                        reinterpret_cast<const float*>(Q), workspace, N, Dq, Hq, Wq, CA, CB, ntz, nty, ntx, ntiles, BB32);
   else
@@ -1633,7 +1729,7 @@ static int k2_wgrad_launch(const void* P, const void* Q, int bf16, float* dw, fl
                        CB, ntz, nty, ntx, ntiles, BB32);
   SEG3D_LAUNCH_CHECK("seg3d_k2_mfma_wgrad");
   const i64 total = (i64)npairs * 8 * 1024;
-  if (slabs >= 32)
+  if (p.reduce4)
     hipLaunchKernelGGL(k2_wgrad_reduce4_kernel<16>, dim3((unsigned)((total / 4 + 63) / 64)), dim3(1024), 0, s, workspace, dw, slabs,
                        CA, CB, BB32, npairs, (i64)sa, (i64)sb, accumulate);
   else

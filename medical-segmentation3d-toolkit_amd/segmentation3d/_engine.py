@@ -112,6 +112,9 @@ _SIGNATURES = {
     'seg3d_convT3d_k2s2_mfma_fwd': (_c_int, [_c_p] * 5 + [_c_int] * 6 + [_c_p]),
     'seg3d_k2_mfma_wgrad_workspace_floats': (_c_ll, [_c_int] * 6),
     'seg3d_k2_mfma_wgrad': (_c_int, [_c_p] * 4 + [_c_int] * 6 + [_c_ll, _c_ll, _c_int, _c_p]),
+    'seg3d_conv3d_k2s2_variant': (_c_int, [_c_int] * 8),
+    'seg3d_convT3d_k2s2_variant': (_c_int, [_c_int] * 10),
+    'seg3d_k2_wgrad_variant': (_c_int, [_c_int] * 7),
     'seg3d_packed_thin_in_floats': (_c_ll, [_c_int, _c_int]),
     'seg3d_pack_weights_thin_in': (_c_int, [_c_p, _c_p, _c_int, _c_int, _c_ll, _c_ll, _c_int, _c_p]),
     'seg3d_conv3d_k3_thin_stats_count': (_c_ll, [_c_int] * 4),

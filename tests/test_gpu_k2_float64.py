@@ -1,0 +1,355 @@
+"""Every kernel instantiation of csrc/conv_k2_mfma.hip (stride-2 2x2x2 gather, scatter and weight gradient), driven through the
+C ABI, against a plain float64 reference.  The cases are those of tests/k2_cases.py; each one first asserts through the
+seg3d_*k2*_variant queries that it reaches the instantiation it is named for.
+
+Layout: NDHWC activations; W(a, b, t) = w[a * sa + b * sb + t], t = (kz * 2 + ky) * 2 + kx, packed with T = 8.
+
+Reference: float64 einsums over the 2^3 cells (on the device), written from the three formulas of the kernel file's header:
+    gather   y[v][b]      = bias[b] + sum_{t,a} x[2v + t][a] W(a,b,t)
+    scatter  y[2i + t][b] = bias[b] + sum_a x[i][a] W(a,b,t)  (+ addend)
+    wgrad    dW(t,a,b)    = sum_v P[2v + t][a] Q[v][b]
+on operands rounded the way the mode rounds them (modes 1, 2: bf16 x; mode 2: bf16 W; bf16 weight gradient: bf16 P and Q; a
+bf16 addend).  The GroupNorm statistics slots are summed over the slot axis and compared with sum y and sum y^2 of the float64
+result (the kernels take them from the fp32 value in front of any bf16 rounding of y).
+
+Bars: nothing is pinned to what the kernels give.  Each case also runs the same operation in fp32 on the CPU (F.conv3d,
+F.conv_transpose3d, autograd for the weight gradient): the yardstick.  Element-wise outputs: err <= 4 * yardstick + 2e-6 * scale,
+scale = max|ref|; statistics sums and weight gradients: 4 * yardstick + 1e-5 * scale.  The bars of the existing stride-2 tests
+hold on top: 2e-6 * scale + 1e-6 for fp32 outputs, 1e-5 for the statistics (sum against sum|y|, squares relative), 2e-5
+relative for the bf16 weight gradient.  bf16-stored outputs, per element: |got - ref| <= 2^-8 |ref| + (the fp32 bar).
+
+Write discipline: outputs are NaN-filled (dw of an accumulating call: known values) inside NaN guard bands of at least a tile's
+rows on both sides; the guards must come back bit-identical and no NaN may survive inside.  Channel-slice operands (x of
+_fwd_ld, addends) live in wider buffers whose other channels are NaN.
+"""
+import pytest
+import torch
+import torch.nn.functional as F
+
+import k2_cases as K
+from gpu_util import report
+from oracle import detgen
+
+pytestmark = pytest.mark.gpu
+
+NAN = float('nan')
+FLOOR_EW, FLOOR_RED = 2e-6, 1e-5
+CAP_EW_REL, CAP_EW_ABS, CAP_STAT, CAP_WGRAD_BF16 = 2e-6, 1e-6, 1e-5, 2e-5
+BF16_REL = 2.0 ** -8
+SAMPLE_MEAN = (0.7, -0.4, 1.3)
+SAMPLE_STD = (2.0, 1.5, 2.5)
+_BASE_LEN = (1 << 20) - 3
+
+
+# ---- inputs --------------------------------------------------------------------------------------------------------------
+def _noise(seed, tag, shape):
+    """float32 N(0, 1) from oracle.detgen; large tensors are rotations of ONE 2^20-value draw (detgen costs ~0.15 s per million)"""
+    n = 1
+    for s in shape:
+        n *= s
+    if n <= _BASE_LEN:
+        return torch.from_numpy(detgen.normal(seed, tag, tuple(shape)))
+    base = torch.from_numpy(detgen.normal(seed, tag, (_BASE_LEN,)))
+    parts = [torch.roll(base, 7919 * k) for k in range((n + _BASE_LEN - 1) // _BASE_LEN)]
+    return torch.cat(parts)[:n].reshape(tuple(shape))
+
+
+def _activation(seed, tag, N, dims, C, offset=1.0):
+    """[N, d, h, w, C] with a different mean and spread per sample"""
+    x = _noise(seed, tag, (N,) + tuple(dims) + (C,))
+    view = (N, 1, 1, 1, 1)
+    return x * torch.tensor(SAMPLE_STD[:N]).view(view) + offset * torch.tensor(SAMPLE_MEAN[:N]).view(view)
+
+
+def _weight(seed, tag, shape, K_):
+    """N(0.5 / K, 1 / K): outputs of unit spread whose mean follows the sample's mean (sum y is not near zero)"""
+    return _noise(seed, tag, shape) * (1.0 / K_) ** 0.5 + 0.5 / K_
+
+
+def bf16_round(t):
+    return t.bfloat16().float()
+
+
+def _nan(n, device, dtype=torch.float32):
+    return torch.full((n,), NAN, dtype=dtype, device=device)
+
+
+class Guarded:
+    """`n` elements inside a NaN-filled buffer with `guard` elements in front and behind"""
+
+    def __init__(self, n, guard, device, dtype=torch.float32, fill=None):
+        assert guard > 0 and (guard * (2 if dtype == torch.bfloat16 else 4)) % 16 == 0
+        self.n, self.guard = n, guard
+        self.buf = _nan(n + 2 * guard, device, dtype)
+        self.before = self.buf.clone()
+        self.t = self.buf[guard:guard + n]
+        if fill is not None:
+            self.t.copy_(fill.reshape(-1))
+
+    def guards_untouched(self):
+        bits = torch.int16 if self.buf.dtype == torch.bfloat16 else torch.int32
+        a, b, g = self.buf.view(bits), self.before.view(bits), self.guard
+        return bool(torch.equal(a[:g], b[:g])) and bool(torch.equal(a[g + self.n:], b[g + self.n:]))
+
+    def all_nan(self):
+        return bool(torch.isnan(self.t).all())
+
+
+def _wide_slice(t, ld, device):
+    """t [.., C] as the LAST C channels of a [.., ld] device buffer whose other channels are NaN"""
+    C = t.shape[-1]
+    wide = torch.full(t.shape[:-1] + (ld,), NAN, dtype=t.dtype, device=device)
+    wide[..., ld - C:] = t.to(device)
+    return wide, wide[..., ld - C:]
+
+
+# ---- bookkeeping ---------------------------------------------------------------------------------------------------------
+class Figures:
+    """collects (device error, yardstick, scale, bar) per quantity of one case, reports them, then asserts"""
+
+    def __init__(self, name):
+        self.name, self.figs, self.fails = name, {}, []
+
+    def require(self, ok, msg):
+        if not ok:
+            self.fails.append(msg)
+
+    def check(self, key, dev, ref, yard, floor, cap=None, bf16_out=False):
+        """cap: an absolute bar that holds on top.  bf16_out: per element, 2^-8 |ref| is allowed beside the bar"""
+        dev = dev.detach().double().reshape(ref.shape)
+        if not bool(torch.isfinite(dev).all()):
+            self.fails.append('{}: {} elements were not written (or are not finite)'.format(key, int((~torch.isfinite(dev)).sum())))
+            return
+        scale = float(ref.abs().max())
+        ye = float((yard.double().to(ref.device).reshape(ref.shape) - ref).abs().max())
+        lim = 4.0 * ye + floor * scale
+        if not ye <= 1e-4 * scale:       # (a test of the test: the fp32 restatement and the float64 formula are the same operation)
+            self.fails.append('{}: the fp32 yardstick is {:.3e} away from the float64 reference (scale {:.3e})'.format(key, ye, scale))
+        if cap is not None:
+            lim = min(lim, cap)
+        d = (dev - ref).abs()
+        if bf16_out:
+            d = d - BF16_REL * ref.abs()
+        err = float(d.max())
+        self.figs.update({key + '_err': err, key + '_yard': ye, key + '_scale': scale, key + '_bar': lim})
+        if not err <= lim:
+            self.fails.append('{}: err {:.3e} > bar {:.3e} (yardstick {:.3e}, scale {:.3e})'.format(key, err, lim, ye, scale))
+
+    def done(self):
+        report(self.name, **self.figs)
+        assert not self.fails, '{}: {}'.format(self.name, '; '.join(self.fails))
+
+
+def _check_stats(fig, stats, ref_y, yard_y, N):
+    """slots summed per sample against sum y and sum y^2 of the float64 result"""
+    got = stats.t.reshape(N, -1, 2).double().sum(1)
+    r = ref_y.reshape(N, -1)
+    yd = yard_y.reshape(N, -1)
+    ref = torch.stack([r.sum(1), (r * r).sum(1)], 1)
+    yard = torch.stack([yd.sum(1), (yd * yd).sum(1)], 1)
+    fig.require(not bool(torch.isnan(stats.t).any()), 'stats: a slot was not written')
+    fig.require(stats.guards_untouched(), 'stats: the guard bands were written')
+    for j, key in enumerate(('stat_sum', 'stat_sq')):
+        fig.check(key, got[:, j], ref[:, j], yard[:, j], FLOOR_RED)
+    cap_sum = float(((got[:, 0] - ref[:, 0]).abs() / r.abs().sum(1)).max())
+    cap_sq = float((got[:, 1] - ref[:, 1]).abs().max() / ref[:, 1].abs().max())
+    fig.figs.update(stat_sum_vs_abs=cap_sum, stat_sq_rel=cap_sq)
+    fig.require(cap_sum < CAP_STAT and cap_sq < CAP_STAT, 'stats: above the existing 1e-5 bars ({:.3e}, {:.3e})'.format(cap_sum, cap_sq))
+
+
+def _check_output(fig, y, ref, yard, out_bf16):
+    fig.require(y.guards_untouched(), 'y: the guard bands were written')
+    scale = float(ref.abs().max())
+    fig.check('y', y.t, ref.reshape(-1), yard.reshape(-1), FLOOR_EW, cap=CAP_EW_REL * scale + CAP_EW_ABS, bf16_out=bool(out_bf16))
+
+
+def _pack(E, w, A, B, sa, sb, bf16):
+    if bf16:
+        wp = torch.empty(E.query('seg3d_packed_mfma_bf16_elems', A, B, 8), dtype=torch.bfloat16, device=w.device)
+        E.call('seg3d_pack_weights_mfma_bf16', E.ptr(w), E.ptr(wp), A, B, 8, sa, sb, 0, E.stream_ptr())
+    else:
+        wp = torch.empty(E.query('seg3d_packed_mfma_floats', A, B, 8), dtype=torch.float32, device=w.device)
+        E.call('seg3d_pack_weights_mfma', E.ptr(w), E.ptr(wp), A, B, 8, sa, sb, 0, E.stream_ptr())
+    return wp
+
+
+def _engine():
+    from segmentation3d import _engine as E
+    E.lib()
+    return E
+
+
+# ---- gather --------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('case', K.GATHER_CASES, ids=K.case_id)
+def test_gather(hip_device, case):
+    E, c, dev = _engine(), case, hip_device
+    assert E.query('seg3d_conv3d_k2s2_variant', c.N, c.D, c.H, c.W, c.Cin, c.Cout, c.mode, c.out_bf16) == K.gather_code(c)
+    fig = Figures(K.case_id(c))
+    A, B, fwd = c.Cin, c.Cout, c.role == 'fwd'
+    x = _activation(900, fig.name + '/x', c.N, (2 * c.D, 2 * c.H, 2 * c.W), A)
+    w = _weight(901, fig.name + '/w', (B, A, 2, 2, 2), 8 * A)              # w[b][a][t]: sa = 8, sb = 8 A
+    bias = (0.3 * _noise(902, fig.name + '/b', (B,)) + 0.2) if fwd else None
+    if c.mode:
+        x = bf16_round(x)
+    wr = bf16_round(w) if c.mode == 2 else w
+    # float64 reference (device) and fp32 yardstick (CPU)
+    cells = x.to(dev).double().reshape(c.N, c.D, 2, c.H, 2, c.W, 2, A)
+    ref = torch.einsum('nzaybxcq,oqabc->nzyxo', cells, wr.to(dev).double())
+    yard = F.conv3d(x.permute(0, 4, 1, 2, 3), wr, bias, stride=2).permute(0, 2, 3, 4, 1)
+    if fwd:
+        ref = ref + bias.to(dev).double()
+    del cells
+    # device operands
+    if c.ld_x:
+        wide, xd = _wide_slice(x, c.ld_x, dev)
+    else:
+        xd = x.to(dev).bfloat16() if c.mode else x.to(dev)
+    wd = w.to(dev)
+    wp = _pack(E, wd, A, B, 8, 8 * A, c.mode == 2)
+    bd = bias.to(dev) if fwd else None
+    y = Guarded(ref.numel(), 128 * B, dev, torch.bfloat16 if c.out_bf16 else torch.float32)
+    stats = None
+    if fwd:
+        cnt = E.query('seg3d_conv3d_k2s2_mfma_stats_count', c.D, c.H, c.W, B)
+        stats = Guarded(c.N * cnt * 2, 1024, dev)
+    dims = (c.N, c.D, c.H, c.W, A, B)
+    sp = E.ptr(stats.t) if fwd else None
+    if c.mode:
+        E.call('seg3d_conv3d_k2s2_bf16_fwd', E.ptr(xd), E.ptr(wp), E.ptr(bd), E.ptr(y.t), sp, *dims, c.out_bf16, int(c.mode == 2),
+               E.stream_ptr())
+    elif c.ld_x:
+        E.call('seg3d_conv3d_k2s2_mfma_fwd_ld', E.ptr(xd), c.ld_x, E.ptr(wp), E.ptr(bd), E.ptr(y.t), sp, *dims, E.stream_ptr())
+    else:
+        E.call('seg3d_conv3d_k2s2_mfma_fwd', E.ptr(xd), E.ptr(wp), E.ptr(bd), E.ptr(y.t), sp, *dims, E.stream_ptr())
+    torch.cuda.synchronize()
+    _check_output(fig, y, ref, yard, c.out_bf16)
+    if fwd:
+        _check_stats(fig, stats, ref, yard, c.N)
+    fig.done()
+
+
+# ---- scatter -------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('case', K.SCATTER_CASES, ids=K.case_id)
+def test_scatter(hip_device, case):
+    E, c, dev = _engine(), case, hip_device
+    assert E.query('seg3d_convT3d_k2s2_variant', c.N, c.D, c.H, c.W, c.Cin, c.Cout, c.mode, c.out_bf16, int(c.add),
+                   c.ld_addend) == K.scatter_code(c)
+    fig = Figures(K.case_id(c))
+    A, B, fwd = c.Cin, c.Cout, c.role == 'fwd'
+    x = _activation(910, fig.name + '/x', c.N, (c.D, c.H, c.W), A)
+    w = _weight(911, fig.name + '/w', (A, B, 2, 2, 2), A)                  # w[a][b][t]: sa = 8 B, sb = 8
+    bias = (0.3 * _noise(912, fig.name + '/b', (B,)) + 0.2) if fwd else None
+    if c.mode:
+        x = bf16_round(x)
+    wr = bf16_round(w) if c.mode == 2 else w
+    ref = torch.einsum('nzyxq,qoabc->nzaybxco', x.to(dev).double(), wr.to(dev).double()).reshape(c.N, 2 * c.D, 2 * c.H, 2 * c.W, B)
+    yard = F.conv_transpose3d(x.permute(0, 4, 1, 2, 3), wr, bias, stride=2).permute(0, 2, 3, 4, 1)
+    if fwd:
+        ref = ref + bias.to(dev).double()
+    addend = None
+    if c.add:
+        addend = _activation(913, fig.name + '/add', c.N, (2 * c.D, 2 * c.H, 2 * c.W), B, offset=0.5)
+        if c.out_bf16:
+            addend = bf16_round(addend)
+        ref = ref + addend.to(dev).double()
+        yard = yard + addend
+        wide, ad = _wide_slice(addend.bfloat16() if c.out_bf16 else addend, c.ld_addend, dev)
+    xd = x.to(dev).bfloat16() if c.mode else x.to(dev)
+    wp = _pack(E, w.to(dev), A, B, 8 * B, 8, c.mode == 2)
+    bd = bias.to(dev) if fwd else None
+    y = Guarded(ref.numel(), 1024 * B, dev, torch.bfloat16 if c.out_bf16 else torch.float32)
+    stats = None
+    if fwd:
+        cnt = E.query('seg3d_convT3d_k2s2_mfma_stats_count', c.D, c.H, c.W, B)
+        stats = Guarded(c.N * cnt * 2, 1024, dev)
+    dims = (c.N, c.D, c.H, c.W, A, B)
+    sp = E.ptr(stats.t) if fwd else None
+    if c.add:
+        E.call('seg3d_convT3d_k2s2_scatter_addend', E.ptr(xd), c.mode, E.ptr(wp), E.ptr(ad), c.ld_addend, E.ptr(y.t), *dims,
+               c.out_bf16, E.stream_ptr())
+    elif c.mode:
+        E.call('seg3d_convT3d_k2s2_bf16_fwd', E.ptr(xd), E.ptr(wp), E.ptr(bd), E.ptr(y.t), sp, *dims, c.out_bf16, int(c.mode == 2),
+               E.stream_ptr())
+    else:
+        E.call('seg3d_convT3d_k2s2_mfma_fwd', E.ptr(xd), E.ptr(wp), E.ptr(bd), E.ptr(y.t), sp, *dims, E.stream_ptr())
+    torch.cuda.synchronize()
+    _check_output(fig, y, ref, yard, c.out_bf16)
+    if fwd:
+        _check_stats(fig, stats, ref, yard, c.N)
+    fig.done()
+
+
+# ---- weight gradient -----------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('case', K.WGRAD_CASES, ids=K.case_id)
+def test_wgrad(hip_device, case):
+    E, c, dev = _engine(), case, hip_device
+    assert E.query('seg3d_k2_wgrad_variant', c.N, c.D, c.H, c.W, c.CA, c.CB, c.bf16) == K.wgrad_code(c)
+    fig = Figures(K.case_id(c))
+    CA, CB = c.CA, c.CB
+    P = _activation(920, fig.name + '/P', c.N, (2 * c.D, 2 * c.H, 2 * c.W), CA, offset=0.25)
+    Q = _activation(921, fig.name + '/Q', c.N, (c.D, c.H, c.W), CB, offset=0.0)
+    if c.bf16:
+        P, Q = bf16_round(P), bf16_round(Q)
+    cells = P.to(dev).double().reshape(c.N, c.D, 2, c.H, 2, c.W, 2, CA)
+    ref = torch.einsum('nzaybxcp,nzyxq->pqabc', cells, Q.to(dev).double()).reshape(CA, CB, 8)     # dW(a, b, t)
+    del cells
+    w0 = torch.zeros(CB, CA, 2, 2, 2, requires_grad=True)
+    yard = torch.autograd.grad(F.conv3d(P.permute(0, 4, 1, 2, 3), w0, stride=2), w0, Q.permute(0, 4, 1, 2, 3))[0]
+    yard = yard.reshape(CB, CA, 8).permute(1, 0, 2)
+    if c.swapped:
+        sa, sb = 8 * CB, 8                                                   # dw[a][b][t]
+    else:
+        sa, sb = 8, 8 * CA                                                   # dw[b][a][t], as the reference stores a Conv3d weight
+        ref, yard = ref.permute(1, 0, 2), yard.permute(1, 0, 2)
+    ref, yard = ref.contiguous(), yard.contiguous()
+    prior = None
+    if c.accumulate:
+        prior = _noise(922, fig.name + '/dw0', tuple(ref.shape)) * float(ref.abs().max()) * 0.5
+        ref = ref + prior.to(dev).double()
+        yard = yard + prior
+    dw = Guarded(ref.numel(), 8 * 1024, dev, fill=prior.to(dev) if c.accumulate else None)
+    nws = E.query('seg3d_k2_mfma_wgrad_workspace_floats', c.N, c.D, c.H, c.W, CA, CB)
+    ws = Guarded(nws, 8 * 1024, dev)
+    Pd, Qd = (P.to(dev).bfloat16(), Q.to(dev).bfloat16()) if c.bf16 else (P.to(dev), Q.to(dev))
+    E.call('seg3d_k2_bf16_wgrad' if c.bf16 else 'seg3d_k2_mfma_wgrad', E.ptr(Pd), E.ptr(Qd), E.ptr(dw.t), E.ptr(ws.t), c.N, c.D,
+           c.H, c.W, CA, CB, sa, sb, c.accumulate, E.stream_ptr())
+    torch.cuda.synchronize()
+    fig.require(dw.guards_untouched(), 'dw: the guard bands were written')
+    fig.require(ws.guards_untouched(), 'workspace: the guard bands were written')
+    scale = float(ref.abs().max())
+    fig.check('dw', dw.t, ref.reshape(-1), yard.reshape(-1), FLOOR_RED, cap=CAP_WGRAD_BF16 * scale if c.bf16 else None)
+    fig.done()
+
+
+# ---- refusals ------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('family,args,why', K.REFUSALS, ids=[r[2] for r in K.REFUSALS])
+def test_refusals_write_nothing(hip_device, family, args, why):
+    """arguments outside the kernels' contract: non-zero return with a message, y and the statistics stay NaN"""
+    E, dev = _engine(), hip_device
+    query = 'seg3d_conv3d_k2s2_variant' if family == 'gather' else 'seg3d_convT3d_k2s2_variant'
+    assert E.query(query, *args) < 0
+    N, D, H, W, A, B, mode, out_bf16 = args[:8]
+    has_addend, ld = (args[8], args[9]) if family == 'scatter' else (0, 0)
+    fine = family == 'gather'
+    xdt = torch.bfloat16 if mode else torch.float32
+    ydt = torch.bfloat16 if out_bf16 else torch.float32
+    x = torch.ones((N, D * (2 if fine else 1), H * (2 if fine else 1), W * (2 if fine else 1), A + 4), dtype=xdt, device=dev)
+    wp = torch.zeros(1 << 16, dtype=torch.float32, device=dev)              # ample for any image of these channel counts
+    bias = torch.zeros(B + 4, device=dev)
+    y = Guarded(N * D * H * W * (1 if fine else 8) * (B + 4), 1024 * 16, dev, ydt)
+    stats = Guarded(1 << 14, 1024, dev)
+    addend = torch.ones((N * D * H * W * 8, max(ld, B) + 4), dtype=ydt, device=dev)
+    dims = (N, D, H, W, A, B)
+    with pytest.raises(ValueError):
+        if has_addend:
+            E.call('seg3d_convT3d_k2s2_scatter_addend', E.ptr(x), mode, E.ptr(wp), E.ptr(addend), ld, E.ptr(y.t), *dims, out_bf16,
+                   E.stream_ptr())
+        elif mode:
+            E.call('seg3d_conv3d_k2s2_bf16_fwd' if fine else 'seg3d_convT3d_k2s2_bf16_fwd', E.ptr(x), E.ptr(wp), E.ptr(bias), E.ptr(y.t),
+                   E.ptr(stats.t), *dims, out_bf16, int(mode == 2), E.stream_ptr())
+        else:
+            E.call('seg3d_conv3d_k2s2_mfma_fwd' if fine else 'seg3d_convT3d_k2s2_mfma_fwd', E.ptr(x), E.ptr(wp), E.ptr(bias), E.ptr(y.t),
+                   E.ptr(stats.t), *dims, E.stream_ptr())
+    assert E.last_error(), why
+    torch.cuda.synchronize()
+    assert y.all_nan() and y.guards_untouched() and stats.all_nan() and stats.guards_untouched(), why
