@@ -386,6 +386,33 @@ int seg3d_compound_loss_bwd(const float* probs, const float* target, const float
                             const float* gout, float* dprobs, int N, int C, long long S, float gamma, int batch_dice,
                             float ignore_label, void* stream);
 
+/* ---- deep supervision (no counterpart in the reference): auxiliary heads on the lower decoder levels + label pyramid -- */
+/* Fused head: what nn.Conv3d(Cin, C, 1) + nn.Softmax(dim=1) compute on a decoder feature, in one streaming pass.
+ *   x: NDHWC fp32 rows [N * S][Cin] at a row stride of ldx floats (0 = Cin; else a multiple of 4 >= Cin: a channel slice of
+ *      a wider buffer is read in place), 16-byte aligned;  w: [C][Cin] (the Conv3d weight seen flat, no packing);  b: [C] or
+ *      NULL;  probs: contiguous NCDHW [N][C][S], p = softmax_c(w x + b) with the max subtracted as in seg3d_softmax_fwd.
+ * Supported (seg3d_ds_head_supported): Cin % 4 == 0, Cin <= 256, 1 <= C <= 8; anything else returns an error. */
+int seg3d_ds_head_supported(int Cin, int C);
+int seg3d_ds_head_fwd(const float* x, int ldx, const float* w, const float* b, float* probs, int N, long long S, int Cin,
+                      int C, void* stream);
+/* Backward of the fused head: g_c = p_c (dp_c - sum_k p_k dp_k);  dx[v][ci] = sum_c g_c w[c][ci] written as NDHWC rows at
+ * a row stride of ld_dx floats (0 = Cin);  per-workgroup partial sums of dw[c][ci] = sum_v g_c x[v][ci] and
+ * db[c] = sum_v g_c go to `workspace` (seg3d_ds_head_bwd_workspace_floats floats; a pure function of the shape).  x is
+ * read once, dx written once, no atomics. */
+long long seg3d_ds_head_bwd_workspace_floats(int N, long long S, int Cin, int C);
+int seg3d_ds_head_bwd(const float* probs, const float* dprobs, const float* x, int ldx, const float* w, float* dx, int ld_dx,
+                      float* workspace, int N, long long S, int Cin, int C, void* stream);
+/* Adds the partials of seg3d_ds_head_bwd (same N, S, Cin, C, same device) in a fixed order in fp64 and writes dw [C][Cin]
+ * and db [C] (either may be NULL); accumulate: bit 0 -- ADD into dw instead of overwriting it, bit 1 -- the same for db
+ * (the optimizer's gradient sinks).  Bit-reproducible. */
+int seg3d_ds_head_bwd_finalize(const float* workspace, float* dw, float* db, int N, long long S, int Cin, int C,
+                               int accumulate, void* stream);
+/* Label pyramid: one launch writes out_k[n][z][y][x] = mask[n][f z][f y][f x], f = 2^k, for k = 1..levels (levels <= 3;
+ * out_k contiguous [N][D/f][H/f][W/f], outputs past `levels` may be NULL).  Values are copied, not interpreted.  D, H, W
+ * must be divisible by 2^levels. */
+int seg3d_label_pyramid(const float* mask, float* out1, float* out2, float* out3, int N, int D, int H, int W, int levels,
+                        void* stream);
+
 /* ---- optimizer: optim.Adam(...).step()  (core/seg_train.py:83,127) -------------------------------------------------- */
 int seg3d_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long long n, int step, float lr,
                     float beta1, float beta2, float eps, float weight_decay, float grad_scale, void* stream);

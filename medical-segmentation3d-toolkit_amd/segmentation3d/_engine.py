@@ -176,6 +176,12 @@ _SIGNATURES = {
     'seg3d_compound_loss_part_floats': (_c_ll, [_c_int, _c_int, _c_ll]),
     'seg3d_compound_loss_fwd': (_c_int, [_c_p] * 7 + [_c_int, _c_int, _c_ll, _c_f, _c_f, _c_f, _c_int, _c_f, _c_p]),
     'seg3d_compound_loss_bwd': (_c_int, [_c_p] * 6 + [_c_int, _c_int, _c_ll, _c_f, _c_int, _c_f, _c_p]),
+    'seg3d_ds_head_supported': (_c_int, [_c_int] * 2),
+    'seg3d_ds_head_fwd': (_c_int, [_c_p, _c_int, _c_p, _c_p, _c_p, _c_int, _c_ll, _c_int, _c_int, _c_p]),
+    'seg3d_ds_head_bwd_workspace_floats': (_c_ll, [_c_int, _c_ll, _c_int, _c_int]),
+    'seg3d_ds_head_bwd': (_c_int, [_c_p] * 3 + [_c_int, _c_p, _c_p, _c_int, _c_p, _c_int, _c_ll, _c_int, _c_int, _c_p]),
+    'seg3d_ds_head_bwd_finalize': (_c_int, [_c_p] * 3 + [_c_int, _c_ll, _c_int, _c_int, _c_int, _c_p]),
+    'seg3d_label_pyramid': (_c_int, [_c_p] * 4 + [_c_int] * 5 + [_c_p]),
     'seg3d_adam_step': (_c_int, [_c_p] * 4 + [_c_ll, _c_int] + [_c_f] * 6 + [_c_p]),
     'seg3d_adam_step_devstep': (_c_int, [_c_p] * 4 + [_c_ll, _c_p, _c_p] + [_c_f] * 6 + [_c_p]),
     'seg3d_grad_sumsq_part_count': (_c_ll, [_c_ll]),

@@ -1458,3 +1458,93 @@ class FocalLossFunction(torch.autograd.Function):
         E.call('seg3d_focal_bwd', E.ptr(p), E.ptr(t), E.ptr(alpha), E.ptr(g), E.ptr(dp), N, C, S, sn, sc, ss, gamma,
                size_average, E.stream_ptr())
         return (dp,) + (None,) * 10
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# deep supervision: fused auxiliary head (1x1x1 conv + softmax) and the label pyramid (csrc/deep_supervision.hip)
+# ------------------------------------------------------------------------------------------------------------------
+def ds_head_supported(cin, num_classes):
+    """can the fused head take `cin` feature channels and `num_classes` outputs (Cin % 4 == 0, Cin <= 256, 1 <= C <= 8)"""
+    return bool(E.query('seg3d_ds_head_supported', int(cin), int(num_classes)))
+
+
+class DsHeadFunction(torch.autograd.Function):
+    """softmax_c(Conv3d(Cin, C, 1)(x)): decoder feature [N,Cin,D,H,W] -> contiguous NCDHW probabilities [N,C,D,H,W] in one
+    streaming pass (seg3d_ds_head_fwd; the logits are never stored), and one pass back (seg3d_ds_head_bwd + its finalize).
+    A feature that is a channel slice of a wider NDHWC buffer is read in place through its row stride.  weight
+    [C,Cin,1,1,1] is used as it lies in memory (no packed image, nothing in the pack cache); bias [C] or None."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        E.require_device(x, weight, bias)
+        if x.dim() != 5 or x.dtype != torch.float32:
+            raise TypeError('the deep-supervision head takes a float32 [N,Cin,D,H,W] feature (bf16 activations are not '
+                            'supported), got {} {}'.format(x.dtype, tuple(x.shape)))
+        xn = to_ndhwc(x, allow_slice=True)
+        N, D, H, W_, Cin = xn.shape
+        C = weight.shape[0]
+        _check_w(weight, (C, Cin, 1, 1, 1), 'k1')
+        if not ds_head_supported(Cin, C):
+            raise ValueError('the deep-supervision head needs Cin % 4 == 0, Cin <= 256 and 1 <= num_classes <= 8, got Cin = {} '
+                             'and {} classes'.format(Cin, C))
+        if bias is not None and (bias.numel() != C or not bias.is_contiguous()):
+            raise ValueError('head bias must be a contiguous [{}] tensor'.format(C))
+        w = weight.detach()
+        probs = _empty((N, C, D, H, W_), xn)
+        E.call('seg3d_ds_head_fwd', E.ptr(xn), _row_stride(xn, Cin), E.ptr(w), E.ptr(None if bias is None else bias.detach()),
+               E.ptr(probs), N, D * H * W_, Cin, C, E.stream_ptr())
+        ctx.has_bias = bias is not None
+        ctx.sinks = (G.lookup(weight), G.lookup(bias))
+        ctx.save_for_backward(xn, w, probs)
+        return probs
+
+    @staticmethod
+    def backward(ctx, dprobs):
+        xn, w, probs = ctx.saved_tensors
+        N, D, H, W_, Cin = xn.shape
+        C, S = w.shape[0], D * H * W_
+        dp = dprobs.contiguous()
+        ws = _empty((E.query('seg3d_ds_head_bwd_workspace_floats', N, S, Cin, C),), xn)
+        dxn = _empty((N, D, H, W_, Cin), xn)
+        E.call('seg3d_ds_head_bwd', E.ptr(probs), E.ptr(dp), E.ptr(xn), _row_stride(xn, Cin), E.ptr(w), E.ptr(dxn), 0, E.ptr(ws),
+               N, S, Cin, C, E.stream_ptr())
+        sw, sb_ = ctx.sinks
+        want_w = ctx.needs_input_grad[1]
+        want_b = ctx.has_bias and ctx.needs_input_grad[2]
+        dw = db = None
+        if want_w or want_b:
+            dw_dst = (sw.view if sw is not None else _empty(tuple(w.shape), xn)) if want_w else None
+            db_dst = (sb_.view if sb_ is not None else _empty((C,), xn)) if want_b else None
+            acc = (1 if (want_w and sw is not None) else 0) | (2 if (want_b and sb_ is not None) else 0)
+            E.call('seg3d_ds_head_bwd_finalize', E.ptr(ws), E.ptr(dw_dst), E.ptr(db_dst), N, S, Cin, C, acc, E.stream_ptr())
+            dw = dw_dst if (want_w and sw is None) else None
+            db = db_dst if (want_b and sb_ is None) else None
+        return (from_ndhwc(dxn) if ctx.needs_input_grad[0] else None), dw, db
+
+
+def ds_head(x, weight, bias):
+    return DsHeadFunction.apply(x, weight, bias)
+
+
+def label_pyramid(mask, levels):
+    """nearest-neighbour label pyramid: [mask[:, :, ::f, ::f, ::f] for f = 2, 4, .. 2^levels] from a float class-id map
+    [N,1,D,H,W] (or [N,D,H,W]) in ONE launch.  Values are copied, not interpreted: an ignore label or an out-of-range id
+    survives to every level.  D, H, W must be divisible by 2^levels."""
+    E.require_device(mask)
+    levels = int(levels)
+    if not 1 <= levels <= 3:
+        raise ValueError('label_pyramid: levels must be 1, 2 or 3, got {}'.format(levels))
+    if mask.dim() == 5 and mask.shape[1] == 1:
+        N, _, D, H, W_ = mask.shape
+    elif mask.dim() == 4:
+        N, D, H, W_ = mask.shape
+    else:
+        raise ValueError('label_pyramid: expected a [N,1,D,H,W] or [N,D,H,W] mask, got shape {}'.format(tuple(mask.shape)))
+    f = 2 ** levels
+    if D % f or H % f or W_ % f:
+        raise ValueError('label_pyramid: size {} is not divisible by 2^levels = {}'.format((D, H, W_), f))
+    m = mask.contiguous().float()
+    outs = [_empty((N, 1, D >> k, H >> k, W_ >> k), m) for k in range(1, levels + 1)]
+    ptrs = [E.ptr(o) for o in outs] + [None] * (3 - levels)
+    E.call('seg3d_label_pyramid', E.ptr(m), ptrs[0], ptrs[1], ptrs[2], N, D, H, W_, levels, E.stream_ptr())
+    return outs

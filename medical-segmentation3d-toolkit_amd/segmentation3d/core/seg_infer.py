@@ -26,7 +26,7 @@ from segmentation3d import _ops
 from segmentation3d.utils.image3d import Image3d
 from segmentation3d.utils import image_tools
 from segmentation3d.utils.image_tools import image_partition_by_fixed_size
-from segmentation3d.utils.model_io import get_checkpoint_folder, strip_module_prefix
+from segmentation3d.utils.model_io import get_checkpoint_folder, inference_state_dict
 from segmentation3d.utils.normalizer import normalizer_from_dict
 
 
@@ -635,7 +635,7 @@ def load_single_model(model_folder, gpu_id=0):
     state = torch.load(os.path.join(chk_dir, 'params.pth'), map_location='cpu', weights_only=True)
     net_module = importlib.import_module('segmentation3d.network.' + state['net'])
     net = net_module.SegmentationNet(state['in_channels'], state['out_channels'])
-    net.load_state_dict(strip_module_prefix(state['state_dict']))
+    net.load_state_dict(inference_state_dict(state['state_dict']))   # (the auxiliary heads of a deeply supervised run stay behind)
     net.eval()
     net = net.to(device)
     model = _Model()

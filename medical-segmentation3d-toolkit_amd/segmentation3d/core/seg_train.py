@@ -20,6 +20,7 @@ from segmentation3d import _ops
 from segmentation3d.core.ddp import GradientReducer
 from segmentation3d.loss.compound_loss import DiceCELoss
 from segmentation3d.loss.cross_entropy_loss import CrossEntropyLoss
+from segmentation3d.loss.deep_supervision_loss import DeepSupervisionLoss, normalise_level_weights
 from segmentation3d.loss.focal_loss import FocalLoss
 from segmentation3d.loss.multi_dice_loss import MultiDiceLoss
 from segmentation3d.optim.fused_adam import FusedAdam
@@ -77,6 +78,15 @@ def optim_options_from_config(train_cfg, num_samples=None, world_size=1):
             'max_grad_norm': getattr(train_cfg, 'clip_grad_norm', None), 'lr_schedule': lr_schedule}
 
 
+def deep_supervision_from_config(train_cfg):
+    """the optional keys `train.deep_supervision` (number of auxiliary decoder levels, 0..3; default 0 = the reference's
+    single full-resolution loss) and `train.deep_supervision_weights` (per-level weights, default None = halving per level)
+    as TrainStep's keyword arguments"""
+    weights = getattr(train_cfg, 'deep_supervision_weights', None)
+    return {'deep_supervision': int(getattr(train_cfg, 'deep_supervision', 0)),
+            'deep_supervision_weights': None if weights is None else list(weights)}
+
+
 def build_optimizer(name, params, lr, betas=(0.9, 0.999), optim_options=None):
     """'Adam' -> FusedAdam(lr, betas), 'SGD' -> FusedSGD(lr); `optim_options`: weight_decay, max_grad_norm,
     lr_schedule, and for SGD momentum, nesterov"""
@@ -97,23 +107,37 @@ def build_optimizer(name, params, lr, betas=(0.9, 0.999), optim_options=None):
 class TrainStep(object):
     """network + loss + FusedAdam or FusedSGD (+ gradient reducer when distributed) on one device; `loss_options` is a
     dict of build_loss's keyword options for the compound losses (dice_weight, ce_weight, include_background, batch_dice,
-    ignore_label); `optimizer` / `optim_options` are build_optimizer's (gradient-norm clipping, lr schedule, SGD)"""
+    ignore_label); `optimizer` / `optim_options` are build_optimizer's (gradient-norm clipping, lr schedule, SGD);
+    `deep_supervision` = L in 1..3 builds the network with L auxiliary heads and trains on the weighted per-level losses
+    (loss/deep_supervision_loss.py; `deep_supervision_weights`: L + 1 weights, None = halving per level)"""
 
     def __init__(self, net_name, in_channels, num_classes, loss_name='Dice', obj_weight=None, focal_gamma=2, lr=1e-4,
                  betas=(0.9, 0.999), device=None, seed=0, distributed=None, num_buckets=4, use_graph=False,
-                 loss_options=None, optimizer='Adam', optim_options=None):
+                 loss_options=None, optimizer='Adam', optim_options=None, deep_supervision=0, deep_supervision_weights=None):
         self.device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
         if self.device.type == 'cuda' and self.device.index is not None:
             torch.cuda.set_device(self.device)   # the engine launches on the current device's stream (_engine.stream_ptr)
         net_module = importlib.import_module('segmentation3d.network.' + net_name)      # core/seg_train.py:72
+        self.deep_supervision = int(deep_supervision)
+        if self.deep_supervision:
+            normalise_level_weights(self.deep_supervision, deep_supervision_weights)   # bad levels / weights raise before anything is built
+            if _ops.activation_dtype_name() != 'fp32':
+                raise ValueError('deep supervision runs in fp32 activation mode only')
+        elif deep_supervision_weights is not None:
+            raise ValueError('deep_supervision_weights given but deep_supervision is 0')
         torch.manual_seed(seed)
-        self.net = net_module.SegmentationNet(in_channels, num_classes)
+        if self.deep_supervision:
+            self.net = net_module.SegmentationNet(in_channels, num_classes, deep_supervision=self.deep_supervision)
+        else:
+            self.net = net_module.SegmentationNet(in_channels, num_classes)
         self.max_stride = self.net.max_stride()
         net_module.parameters_kaiming_init(self.net)                                    # core/seg_train.py:75
         self.net = self.net.to(self.device)
         self.opt = build_optimizer(optimizer, self.net.parameters(), lr, betas, optim_options)   # core/seg_train.py:83
         _ops.weight_cache(True)   # packed conv weights are refreshed by the optimizer's step() with one launch per step
         self.loss_func = build_loss(loss_name, num_classes, obj_weight, focal_gamma, use_gpu=True, **(loss_options or {}))
+        if self.deep_supervision:
+            self.loss_func = DeepSupervisionLoss(self.loss_func, self.deep_supervision, deep_supervision_weights)
         if distributed is None:
             distributed = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
         self.reducer = None
@@ -179,7 +203,7 @@ class TrainStep(object):
         self.opt.zero_grad()
         if self.reducer is not None:
             self.reducer.begin_step()
-        outputs = self.net(crops)
+        outputs = self.net.forward_deep(crops) if self.deep_supervision else self.net(crops)
         loss = self.loss_func(outputs, masks)
         loss.backward()
         if self.reducer is not None:
@@ -248,11 +272,15 @@ def train(train_config_file, data_iter_factory=None):
     num_samples = len(dataset) if dataset is not None else int(getattr(cfg.dataset, 'num_samples', cfg.train.batchsize))
     optim_options = optim_options_from_config(cfg.train, num_samples, world_size)
     show_lr = optim_options['lr_schedule'] is not None and optim_options['lr_schedule']['name'] != 'constant'
+    deep = deep_supervision_from_config(cfg.train)
+    if cfg.general.resume_epoch >= 0 and not hasattr(cfg.train, 'deep_supervision'):
+        from segmentation3d.utils.model_io import checkpoint_deep_supervision
+        deep['deep_supervision'] = checkpoint_deep_supervision(cfg.general.resume_epoch, model_folder)   # rebuild the same net
     step = TrainStep(cfg.net.name, num_modality, cfg.dataset.num_classes, cfg.loss.name, cfg.loss.obj_weight,
                      cfg.loss.focal_gamma, cfg.train.lr, tuple(cfg.train.betas), seed=cfg.general.seed,
                      use_graph=bool(getattr(cfg.train, 'use_graph', False)),
                      loss_options=loss_options_from_config(cfg.loss), optimizer=optim_options.pop('optimizer'),
-                     optim_options=optim_options)
+                     optim_options=optim_options, **deep)
     assert np.all(np.array(cfg.dataset.crop_size) % step.max_stride == 0), 'crop size not divisible by max stride'
     last_save_epoch, batch_idx = 0, 0
     if cfg.general.resume_epoch >= 0:

@@ -14,6 +14,7 @@ from segmentation3d.network.module.vnet_inblock import InputBlock
 from segmentation3d.network.module.vnet_outblock import OutputBlock
 from segmentation3d.network.module.vnet_upblock import UpBlock
 from segmentation3d.network.module.vnet_downblock import DownBlock
+from segmentation3d.network.module.layers import Conv3d
 
 STEM_WIDTH = 16
 # (attribute, input width, number of residual convs)
@@ -22,22 +23,65 @@ ENCODER_STAGES = (('down_32', 16, 1), ('down_64', 32, 2), ('down_128', 64, 3), (
 DECODER_STAGES = (('up_256', 256, 256, 3, 'down_128'), ('up_128', 256, 128, 3, 'down_64'),
                   ('up_64', 128, 64, 2, 'down_32'), ('up_32', 64, 32, 1, 'in_block'))
 MAX_STRIDE = 2 ** len(ENCODER_STAGES)
+# deep supervision: (head attribute, decoder stage it sits on, feature channels), finest first; level k works at 1 / 2^k resolution
+DEEP_SUPERVISION_HEADS = (('ds_out_64', 'up_64', 64), ('ds_out_128', 'up_128', 128), ('ds_out_256', 'up_256', 256))
 PREFILL_SKIP_SLOTS = True   # inference: encoder features written straight into the decoder's concatenated buffers (forward())
 
 
-class VNetBase(nn.Module):
-    """volumetric segmentation network; `bottleneck` lists the stage names that use BottResidualBlock3"""
+class DeepSupervisionHead(nn.Module):
+    """auxiliary segmentation output on a decoder feature: 1x1x1 conv to the classes + softmax, one fused HIP pass each way
+    (_ops.ds_head).  Training only; `conv` is an ordinary Conv3d holder, so the weight initialisers reach it."""
 
-    def __init__(self, in_channels, out_channels, bottleneck=()):
+    def __init__(self, in_channels, out_channels):
+        super(DeepSupervisionHead, self).__init__()
+        if not 1 <= out_channels <= 8 or in_channels % 4 or in_channels > 256:
+            raise ValueError('a deep-supervision head takes at most 256 feature channels (a multiple of 4) and 1..8 classes, got '
+                             '{} -> {}'.format(in_channels, out_channels))
+        self.conv = Conv3d(in_channels, out_channels, kernel_size=1)
+
+    def forward(self, input):
+        return _ops.ds_head(input, self.conv.weight, self.conv.bias)
+
+
+class VNetBase(nn.Module):
+    """volumetric segmentation network; `bottleneck` lists the stage names that use BottResidualBlock3;
+    `deep_supervision` = L in 0..3 registers L auxiliary heads (after `out_block`) on the lower decoder levels"""
+
+    def __init__(self, in_channels, out_channels, bottleneck=(), deep_supervision=0):
         super(VNetBase, self).__init__()
+        if isinstance(deep_supervision, bool) or not isinstance(deep_supervision, int) or \
+                not 0 <= deep_supervision <= len(DEEP_SUPERVISION_HEADS):
+            raise ValueError('deep_supervision must be an integer in 0..{}, got {!r}'.format(len(DEEP_SUPERVISION_HEADS),
+                                                                                           deep_supervision))
+        self.deep_supervision = deep_supervision
         self.in_block = InputBlock(in_channels, STEM_WIDTH)
         for name, width, convs in ENCODER_STAGES:
             setattr(self, name, DownBlock(width, convs, compression=name in bottleneck))
         for name, cin, cout, convs, _ in DECODER_STAGES:
             setattr(self, name, UpBlock(cin, cout, convs, compression=name in bottleneck))
         self.out_block = OutputBlock(DECODER_STAGES[-1][2], out_channels)
+        for name, _, width in DEEP_SUPERVISION_HEADS[:deep_supervision]:
+            setattr(self, name, DeepSupervisionHead(width, out_channels))
 
     def forward(self, input):
+        return self.out_block(self._decode(input, None))
+
+    def forward_deep(self, input):
+        """[p_full, p_1, .., p_L]: the full-resolution probabilities and those of the L auxiliary heads (level k at
+        1 / 2^k resolution), from ONE pass through the encoder / decoder"""
+        if self.deep_supervision == 0:
+            raise ValueError('forward_deep needs a network built with deep_supervision >= 1')
+        if _ops.activation_dtype_name() != 'fp32':
+            raise ValueError('deep supervision runs in fp32 activation mode only (the current mode is {})'.format(
+                _ops.activation_dtype_name()))
+        decoded = {}
+        outputs = [self.out_block(self._decode(input, decoded))]
+        for name, stage, _ in DEEP_SUPERVISION_HEADS[:self.deep_supervision]:
+            outputs.append(getattr(self, name)(decoded[stage]))
+        return outputs
+
+    def _decode(self, input, decoded):
+        """encoder + decoder: the feature `out_block` reads; `decoded` (a dict or None) receives every decoder stage's output"""
         if not isinstance(input, torch.Tensor):
             raise TypeError('input must be a torch.Tensor')
         if input.dim() != 5 or any(int(s) % MAX_STRIDE for s in input.shape[2:]):
@@ -74,7 +118,9 @@ class VNetBase(nn.Module):
             feats[name], source = x, name
         for name, _, _, _, skip in DECODER_STAGES:
             x = getattr(self, name)(x, feats[skip], skip_link=links.get(skip), cat_buf=slots.get(skip))
-        return self.out_block(x)
+            if decoded is not None:
+                decoded[name] = x
+        return x
 
     def max_stride(self):
         return MAX_STRIDE

@@ -10,8 +10,9 @@ BOTTLENECK_STAGES = ('down_64', 'down_128', 'down_256', 'up_256', 'up_128')  # v
 
 
 class SegmentationNet(VNetBase):
-    def __init__(self, in_channels, out_channels):
-        super(SegmentationNet, self).__init__(in_channels, out_channels, bottleneck=BOTTLENECK_STAGES)
+    def __init__(self, in_channels, out_channels, deep_supervision=0):
+        super(SegmentationNet, self).__init__(in_channels, out_channels, bottleneck=BOTTLENECK_STAGES,
+                                              deep_supervision=deep_supervision)
 
 
 def parameters_kaiming_init(net):

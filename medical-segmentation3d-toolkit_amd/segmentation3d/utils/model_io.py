@@ -27,6 +27,22 @@ def strip_module_prefix(state_dict):
     return OrderedDict((k[len('module.'):] if k.startswith('module.') else k, v) for k, v in state_dict.items())
 
 
+DEEP_SUPERVISION_PREFIX = 'ds_out_'   # the auxiliary heads of network/_vnet_base.py: training only
+
+
+def strip_deep_supervision(state_dict):
+    """a copy of `state_dict` without the deep-supervision heads' entries: inference runs the main output only, so a
+    deeply supervised checkpoint loads into a plain network"""
+    if not any(k.startswith(DEEP_SUPERVISION_PREFIX) for k in state_dict):
+        return state_dict
+    return OrderedDict((k, v) for k, v in state_dict.items() if not k.startswith(DEEP_SUPERVISION_PREFIX))
+
+
+def inference_state_dict(state_dict):
+    """what an inference network loads from a checkpoint's `state_dict`: no 'module.' prefix, no auxiliary heads"""
+    return strip_deep_supervision(strip_module_prefix(state_dict))
+
+
 def _chk_dir(model_folder, epoch_idx):
     return os.path.join(model_folder, 'checkpoints', 'chk_{}'.format(epoch_idx))
 
@@ -37,19 +53,38 @@ def _read(path, what):
 
 
 def load_checkpoint(epoch_idx, net, opt, save_dir):
-    """restore network + optimizer from `<save_dir>/checkpoints/chk_<epoch_idx>`; returns (epoch, batch)"""
+    """restore network + optimizer from `<save_dir>/checkpoints/chk_<epoch_idx>`; returns (epoch, batch).  opt = None loads the
+    network alone (inference): the auxiliary heads of a deeply supervised checkpoint are then dropped for a network without
+    them.  With an optimizer (a training resume) the network must have the checkpoint's `deep_supervision`: the optimizer
+    state covers exactly those parameters."""
     folder = _chk_dir(save_dir, epoch_idx)
     state = _read(os.path.join(folder, 'params.pth'), 'checkpoint')
-    getattr(net, 'module', net).load_state_dict(strip_module_prefix(state['state_dict']))
-    opt.load_state_dict(_read(os.path.join(folder, 'optimizer.pth'), 'optimizer'))
+    target = getattr(net, 'module', net)
+    weights = strip_module_prefix(state['state_dict'])
+    trained, built = int(state.get('deep_supervision', 0)), int(getattr(target, 'deep_supervision', 0))
+    if opt is None and built == 0:
+        weights = strip_deep_supervision(weights)     # inference: a network without the auxiliary heads takes the main path only
+    elif trained != built:
+        raise ValueError('the checkpoint was trained with deep_supervision = {} but the network was built with {}'.format(
+            trained, built))
+    target.load_state_dict(weights)
+    if opt is not None:
+        opt.load_state_dict(_read(os.path.join(folder, 'optimizer.pth'), 'optimizer'))
     return state['epoch'], state['batch']
+
+
+def checkpoint_deep_supervision(epoch_idx, save_dir):
+    """the `deep_supervision` a checkpoint was trained with (0 for checkpoints written before the key existed)"""
+    state = _read(os.path.join(_chk_dir(save_dir, epoch_idx), 'params.pth'), 'checkpoint')
+    return int(state.get('deep_supervision', 0))
 
 
 def checkpoint_state(net, epoch_idx, batch_idx, cfg, max_stride, num_modality):
     """the `params.pth` dictionary (fields of utils/model_io.py:75-84; tensors moved to the host)"""
     weights = OrderedDict((key, value.detach().cpu()) for key, value in net.state_dict().items())
     geometry = {'spacing': cfg.dataset.spacing, 'interpolation': cfg.dataset.interpolation, 'max_stride': max_stride}
-    channels = {'in_channels': num_modality, 'out_channels': cfg.dataset.num_classes}
+    channels = {'in_channels': num_modality, 'out_channels': cfg.dataset.num_classes,
+                'deep_supervision': int(getattr(getattr(net, 'module', net), 'deep_supervision', 0))}
     state = {'epoch': epoch_idx, 'batch': batch_idx, 'net': cfg.net.name, 'state_dict': weights,
              'crop_normalizers': [None if n is None else n.to_dict() for n in cfg.dataset.crop_normalizers]}
     state.update(geometry)
