@@ -386,6 +386,13 @@ int seg3d_compound_loss_bwd(const float* probs, const float* target, const float
                             const float* gout, float* dprobs, int N, int C, long long S, float gamma, int batch_dice,
                             float ignore_label, void* stream);
 
+/* ---- region-based models (no counterpart in the reference) -----------------------------
+ * Head sigmoid: the counterparts of the soft-max pair above, same layouts (NDHWC in, contiguous NCDHW out), 1 <= C <= 16.
+ * p = 1 / (1 + exp(-x)) evaluated through exp(-|x|): finite and inside [0, 1] for every x.  Backward: din = dp p (1 - p). */
+int seg3d_sigmoid_fwd(const float* in_ndhwc, float* probs_ncdhw, int N, int C, long long S, void* stream);
+int seg3d_sigmoid_bwd(const float* probs_ncdhw, const float* dprobs_ncdhw, float* din_ndhwc, int N, int C, long long S,
+                      void* stream);
+
 /* ---- deep supervision (no counterpart in the reference): auxiliary heads on the lower decoder levels + label pyramid -- */
 /* Fused head: what nn.Conv3d(Cin, C, 1) + nn.Softmax(dim=1) compute on a decoder feature, in one streaming pass.
  *   x: NDHWC fp32 rows [N * S][Cin] at a row stride of ldx floats (0 = Cin; else a multiple of 4 >= Cin: a channel slice of
@@ -500,6 +507,12 @@ int seg3d_patch_scatter_accumulate(const float* probs, const int* starts_xyz, co
                                    long long max_box_voxels, void* stream);
 int seg3d_finalize_argmax(float* acc, const float* count, signed char* mask, int C, long long voxels,
                           long long class_stride, void* stream);
+/* Region-based inference: acc[r][v] *= 1 / count[v] in place (R region planes, class_stride and z-slab convention as
+ * above), then mask = 0 and for r = 0 .. R-1 in order: p_r > 0.5 (strictly) sets mask = order_host[r] -- the sequential
+ * overwrite rule, so regions are listed from the largest to the smallest.  order_host: R host ints in 1..127.  A voxel
+ * with count 0 gets probabilities 0 and mask 0.  mask may be NULL. */
+int seg3d_finalize_regions(float* acc, const float* count, signed char* mask, int R, const int* order_host,
+                           long long voxels, long long class_stride, void* stream);
 /* ---- Gaussian patch blending and mirror test-time augmentation ---------------------------
  * flip_mask: bit 0 = x, bit 1 = y, bit 2 = z, 0..7.
  * The _flip gathers are the gathers above with every patch mirrored: batch element (lz, ly, lx) of patch p is the
@@ -529,6 +542,12 @@ int seg3d_patch_scatter_blend(const float* probs, const int* starts_xyz, const i
  * the caller zeroes counts first.  dtype: 0 int8, 1 uint8, 2 int16, 3 int32, 4 float32.  1..16 labels per call. */
 int seg3d_label_overlap_counts(const void* gt, const void* seg, int dtype, long long n, const int* labels_host, int nlabels,
                                unsigned long long* counts, void* stream);
+
+/* The same with set membership: counts[3r..3r+2] += (|gt in region r|, |seg in region r|, |both|).  lut_host: 256 host
+ * words, bit r of lut_host[l] set iff label l is in region r; a value that is no integer in [0, 256) is in no region.
+ * 1..16 regions per call, the same five dtypes, integer counting. */
+int seg3d_region_overlap_counts(const void* gt, const void* seg, int dtype, long long n, const unsigned* lut_host,
+                                int nregions, unsigned long long* counts, void* stream);
 
 /* ---- surface-distance metrics: HD, HD95, ASSD of one label --------------------------------
  * seg3d_label_surface: surface[i] = 1 on the voxels of (labels == label) that have a 6-neighbour outside the label

@@ -740,3 +740,66 @@ extern "C" int seg3d_compound_loss_bwd(const float* probs, const float* target, 
   SEG3D_LAUNCH_CHECK("seg3d_compound_loss_bwd");
   return SEG3D_OK;
 }
+
+// ---- region-based models: sigmoid head -------------------------------------------------
+// (no counterpart in the reference)
+// sigmoid over channels: in NDHWC [V][C] -> out NCDHW [N][C][S], the layout contract of softmax_fwd_kernel.  The exponential
+// is always taken of -|x|, so it never overflows: p = 1 / (1 + e) for x >= 0 and e / (1 + e) for x < 0, in [0, 1] for every x.
+__device__ __forceinline__ float sigmoid_stable(float x) {
+  const float e = expf(-fabsf(x));
+  return (x >= 0.f ? 1.0f : e) / (1.0f + e);
+}
+
+__global__ __launch_bounds__(256) void sigmoid_fwd_kernel(const float* __restrict__ in, float* __restrict__ out, int C,
+                                                            i64 S, i64 total_vox) {
+  for (i64 v = (i64)blockIdx.x * 256 + threadIdx.x; v < total_vox; v += (i64)gridDim.x * 256) {
+    const i64 n = v / S, s = v - n * S;
+    float x[SEG3D_MAXC];
+#pragma unroll
+    for (int c = 0; c < SEG3D_MAXC; ++c)
+      if (c < C) x[c] = in[v * C + c];
+#pragma unroll
+    for (int c = 0; c < SEG3D_MAXC; ++c)
+      if (c < C) out[(n * C + c) * S + s] = sigmoid_stable(x[c]);
+  }
+}
+
+// din[v][c] = dp_c p_c (1 - p_c);  probs, dprobs NCDHW planar, din NDHWC
+__global__ __launch_bounds__(256) void sigmoid_bwd_kernel(const float* __restrict__ probs,
+                                                            const float* __restrict__ dprobs, float* __restrict__ din,
+                                                            int C, i64 S, i64 total_vox) {
+  for (i64 v = (i64)blockIdx.x * 256 + threadIdx.x; v < total_vox; v += (i64)gridDim.x * 256) {
+    const i64 n = v / S, s = v - n * S;
+    float g[SEG3D_MAXC];
+#pragma unroll
+    for (int c = 0; c < SEG3D_MAXC; ++c)
+      if (c < C) {
+        const float p = probs[(n * C + c) * S + s];
+        g[c] = dprobs[(n * C + c) * S + s] * p * (1.0f - p);
+      }
+#pragma unroll
+    for (int c = 0; c < SEG3D_MAXC; ++c)
+      if (c < C) din[v * C + c] = g[c];
+  }
+}
+
+extern "C" int seg3d_sigmoid_fwd(const float* in_ndhwc, float* probs_ncdhw, int N, int C, long long S, void* stream) {
+  SEG3D_REQUIRE(in_ndhwc && probs_ncdhw && N > 0 && S > 0, "seg3d_sigmoid_fwd: bad arguments");
+  SEG3D_REQUIRE(C >= 1 && C <= SEG3D_MAXC, "seg3d_sigmoid_fwd: channels %d not in [1, %d]", C, SEG3D_MAXC);
+  const i64 total = (i64)N * S;
+  hipLaunchKernelGGL(sigmoid_fwd_kernel, dim3(seg3d_ew_grid(total, 256)), dim3(256), 0, (hipStream_t)stream, in_ndhwc,
+                     probs_ncdhw, C, (i64)S, total);
+  SEG3D_LAUNCH_CHECK("seg3d_sigmoid_fwd");
+  return SEG3D_OK;
+}
+
+extern "C" int seg3d_sigmoid_bwd(const float* probs_ncdhw, const float* dprobs_ncdhw, float* din_ndhwc, int N, int C,
+                                 long long S, void* stream) {
+  SEG3D_REQUIRE(probs_ncdhw && dprobs_ncdhw && din_ndhwc && N > 0 && S > 0, "seg3d_sigmoid_bwd: bad arguments");
+  SEG3D_REQUIRE(C >= 1 && C <= SEG3D_MAXC, "seg3d_sigmoid_bwd: channels %d not in [1, %d]", C, SEG3D_MAXC);
+  const i64 total = (i64)N * S;
+  hipLaunchKernelGGL(sigmoid_bwd_kernel, dim3(seg3d_ew_grid(total, 256)), dim3(256), 0, (hipStream_t)stream, probs_ncdhw,
+                     dprobs_ncdhw, din_ndhwc, C, (i64)S, total);
+  SEG3D_LAUNCH_CHECK("seg3d_sigmoid_bwd");
+  return SEG3D_OK;
+}

@@ -551,3 +551,46 @@ extern "C" int seg3d_finalize_argmax(float* acc, const float* count, signed char
   SEG3D_LAUNCH_CHECK("seg3d_finalize_argmax");
   return SEG3D_OK;
 }
+
+// Region-based inference: acc[r][v] *= 1/count[v] (in place), then the sequential overwrite
+// rule -- mask = 0; for r = 0 .. R-1 in order: p_r > 0.5 (strictly) sets mask = order[r] -- so regions are listed from the
+// largest to the smallest.  count 0: probabilities 0 and mask 0, as in finalize_argmax_kernel.
+struct RegionOrder {
+  signed char v[16];
+};
+
+__global__ __launch_bounds__(256) void finalize_regions_kernel(float* __restrict__ acc, const float* __restrict__ count,
+                                                                 signed char* __restrict__ mask, int R, RegionOrder order,
+                                                                 i64 vol, i64 cstride) {
+  for (i64 v = (i64)blockIdx.x * 256 + threadIdx.x; v < vol; v += (i64)gridDim.x * 256) {
+    const float cnt = count[v];
+    const float rc = cnt > 0.f ? 1.0f / cnt : 0.f;
+    signed char m = 0;
+#pragma unroll
+    for (int r = 0; r < 16; ++r)
+      if (r < R) {
+        const float p = acc[(i64)r * cstride + v] * rc;
+        acc[(i64)r * cstride + v] = p;
+        m = p > 0.5f ? order.v[r] : m;
+      }
+    if (mask) mask[v] = m;
+  }
+}
+
+// order_host: R host ints in 1..127 (the mask is int8); class_stride as in seg3d_finalize_argmax
+extern "C" int seg3d_finalize_regions(float* acc, const float* count, signed char* mask, int R, const int* order_host,
+                                      long long voxels, long long class_stride, void* stream) {
+  SEG3D_REQUIRE(acc && count && order_host && voxels > 0 && (class_stride == 0 || class_stride >= voxels),
+                "seg3d_finalize_regions: bad arguments");
+  SEG3D_REQUIRE(R >= 1 && R <= 16, "seg3d_finalize_regions: %d regions not in [1, 16]", R);
+  RegionOrder order;
+  for (int r = 0; r < 16; ++r) {
+    const int o = r < R ? order_host[r] : 0;
+    SEG3D_REQUIRE(r >= R || (o >= 1 && o <= 127), "seg3d_finalize_regions: region_class_order[%d] = %d not in [1, 127]", r, o);
+    order.v[r] = (signed char)o;
+  }
+  hipLaunchKernelGGL(finalize_regions_kernel, dim3(seg3d_ew_grid(voxels, 256)), dim3(256), 0, (hipStream_t)stream, acc, count,
+                     mask, R, order, (i64)voxels, (i64)(class_stride ? class_stride : voxels));
+  SEG3D_LAUNCH_CHECK("seg3d_finalize_regions");
+  return SEG3D_OK;
+}

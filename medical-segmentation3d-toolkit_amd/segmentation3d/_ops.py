@@ -1320,6 +1320,37 @@ def softmax_channels(x):
     return SoftmaxFunction.apply(x)
 
 
+class SigmoidFunction(torch.autograd.Function):
+    """element-wise sigmoid of the head's logits (region-based models); layouts as SoftmaxFunction: emits a contiguous
+    NCDHW tensor"""
+
+    @staticmethod
+    def forward(ctx, x):
+        E.require_device(x)
+        if x.dtype != torch.float32:   # bf16 mode keeps heads below 16 channels in fp32; a 16-region head would arrive as bf16
+            raise ValueError('the sigmoid head takes float32 logits, got {} (bf16 activation mode supports up to 15 '
+                             'regions)'.format(x.dtype))
+        xn = to_ndhwc(x)
+        N, D, H, W_, C = xn.shape
+        probs = _empty((N, C, D, H, W_), xn)
+        E.call('seg3d_sigmoid_fwd', E.ptr(xn), E.ptr(probs), N, C, D * H * W_, E.stream_ptr())
+        ctx.save_for_backward(probs)
+        return probs
+
+    @staticmethod
+    def backward(ctx, dprobs):
+        (probs,) = ctx.saved_tensors
+        N, C, D, H, W_ = probs.shape
+        dp = dprobs.contiguous()
+        din = _empty((N, D, H, W_, C), probs)
+        E.call('seg3d_sigmoid_bwd', E.ptr(probs), E.ptr(dp), E.ptr(din), N, C, D * H * W_, E.stream_ptr())
+        return from_ndhwc(din)
+
+
+def sigmoid_channels(x):
+    return SigmoidFunction.apply(x)
+
+
 class DiceLossFunction(torch.autograd.Function):
     """MultiDiceLoss.forward (loss/multi_dice_loss.py:24-43) as one fused reduction + one elementwise backward"""
 

@@ -26,7 +26,8 @@ from segmentation3d import _ops
 from segmentation3d.utils.image3d import Image3d
 from segmentation3d.utils import image_tools
 from segmentation3d.utils.image_tools import image_partition_by_fixed_size
-from segmentation3d.utils.model_io import get_checkpoint_folder, inference_state_dict
+from segmentation3d.loss.region_loss import check_region_class_order
+from segmentation3d.utils.model_io import get_checkpoint_folder, inference_state_dict, region_keys
 from segmentation3d.utils.normalizer import normalizer_from_dict
 
 
@@ -269,11 +270,16 @@ class SlidingWindowBatcher(object):
             probs = torch.cat((probs, pad), 0)
         self.scatter_current(probs.contiguous(), flip=flip)
 
-    def finalize(self, z_range=None):
+    def finalize(self, z_range=None, regions_order=None):
         """acc *= 1/count (in place) and arg-max -> (probs [C,Z,Y,X], mask int8 [Z,Y,X]).
         z_range = (z0, z1): only that slab of planes (a rank of the sharded sliding window finalizes the slab it owns);
-        the mask is zero outside it"""
+        the mask is zero outside it.
+        regions_order (C labels in 1..127, region-based models): the C planes are region probabilities and the mask is
+        composed by the sequential overwrite rule instead -- 0, then for r = 0 .. C-1 in order p_r > 0.5 writes
+        regions_order[r] (seg3d_finalize_regions)"""
         import ctypes
+        if regions_order is not None:
+            regions_order = check_region_class_order(regions_order, self.C)
         plane = self.Y * self.X
         if z_range is None:
             mask = torch.empty((self.Z, self.Y, self.X), dtype=torch.int8, device=self.volume.device)
@@ -283,7 +289,11 @@ class SlidingWindowBatcher(object):
             z0, z1 = int(z_range[0]), int(z_range[1])
             if not 0 <= z0 <= z1 <= self.Z:
                 raise ValueError('z range {} outside the volume'.format(z_range))
-        if z1 > z0:
+        if z1 > z0 and regions_order is not None:
+            E.call('seg3d_finalize_regions', ctypes.c_void_p(self.acc.data_ptr() + 4 * z0 * plane),
+                   ctypes.c_void_p(self.count.data_ptr() + 4 * z0 * plane), ctypes.c_void_p(mask.data_ptr() + z0 * plane),
+                   self.C, (ctypes.c_int * self.C)(*regions_order), (z1 - z0) * plane, self.Z * plane, E.stream_ptr())
+        elif z1 > z0:
             E.call('seg3d_finalize_argmax', ctypes.c_void_p(self.acc.data_ptr() + 4 * z0 * plane),
                    ctypes.c_void_p(self.count.data_ptr() + 4 * z0 * plane), ctypes.c_void_p(mask.data_ptr() + z0 * plane),
                    self.C, (z1 - z0) * plane, self.Z * plane, E.stream_ptr())
@@ -425,7 +435,7 @@ def _forward_two_streams(net, batch, side):
 
 def sliding_window_inference(net, volume, starts, box, num_classes, normalizer, batch_size=8, use_graph=True,
                              process_group=None, shard=False, two_streams=True, gather='all', blend='constant',
-                             sigma_scale=0.125, mirror_axes=()):
+                             sigma_scale=0.125, mirror_axes=(), regions_order=None):
     """run `net` over all patches of a device-resident volume; returns (probs [C,Z,Y,X], mask int8 [Z,Y,X], batcher).
     blend = 'gaussian' weights every patch voxel with blend_weight_tables(box, sigma_scale); mirror_axes (a subset of
     'x', 'y', 'z') adds mirror test-time augmentation: every batch is gathered, predicted and accumulated once per mask of
@@ -435,10 +445,14 @@ def sliding_window_inference(net, volume, starts, box, num_classes, normalizer, 
     rank (SlabShardPlan); after the patch loop only the halo planes are exchanged (merge_slabs), every rank divides and
     arg-maxes the slab it owns, and the slabs are replicated (gather='all': probabilities and mask, 'mask': mask only,
     'none': each rank keeps just its slab; batcher.shard_plan tells which).  Float summation order inside a halo then
-    differs from the sequential reference loop by rounding only."""
+    differs from the sequential reference loop by rounding only.
+    regions_order (num_classes labels in 1..127): `net` is a region-based (sigmoid) network; the accumulated planes are
+    region probabilities and the mask is composed from them by SlidingWindowBatcher.finalize's overwrite rule.  Nothing
+    else changes: gather, scatter, blending, mirror TTA and the slab merge are sums of num_classes planes either way."""
     with torch.cuda.device(volume.device):
         return _sliding_window_inference(net, volume, starts, box, num_classes, normalizer, batch_size, use_graph,
-                                         process_group, shard, two_streams, gather, blend, sigma_scale, mirror_axes)
+                                         process_group, shard, two_streams, gather, blend, sigma_scale, mirror_axes,
+                                         regions_order)
 
 
 # hipGraph capture for the per-volume graphs.  `with torch.cuda.graph(g)` empties the caching allocator before every capture
@@ -541,9 +555,12 @@ def release_graph_pool(device=None):
 
 
 def _sliding_window_inference(net, volume, starts, box, num_classes, normalizer, batch_size, use_graph, process_group,
-                              shard, two_streams, gather, blend='constant', sigma_scale=0.125, mirror_axes=()):
+                              shard, two_streams, gather, blend='constant', sigma_scale=0.125, mirror_axes=(),
+                              regions_order=None):
     if gather not in ('all', 'mask', 'none'):
         raise ValueError("gather must be 'all', 'mask' or 'none'")
+    if regions_order is not None:
+        regions_order = check_region_class_order(regions_order, int(num_classes))
     flips = mirror_flip_masks(mirror_axes)
     batcher = SlidingWindowBatcher(volume, starts, box, num_classes, normalizer, max_batch=batch_size, blend=blend,
                                    sigma_scale=sigma_scale)
@@ -600,11 +617,11 @@ def _sliding_window_inference(net, volume, starts, box, num_classes, normalizer,
                     run_batch()
             if sharded:
                 merge_slabs(batcher.acc, batcher.count, plan, rank, process_group)
-                probs, mask = batcher.finalize(plan.owned(rank))
+                probs, mask = batcher.finalize(plan.owned(rank), regions_order=regions_order)
                 if gather != 'none':
                     gather_slabs(probs, mask, plan, process_group, with_probs=(gather == 'all'))
             else:
-                probs, mask = batcher.finalize()
+                probs, mask = batcher.finalize(regions_order=regions_order)
     finally:
         if not cache_was_on:
             torch.cuda.synchronize()   # the images were allocated on the warm-up stream: nothing may still read them
@@ -634,7 +651,16 @@ def load_single_model(model_folder, gpu_id=0):
     chk_dir = get_checkpoint_folder(os.path.join(model_folder, 'checkpoints'), -1)
     state = torch.load(os.path.join(chk_dir, 'params.pth'), map_location='cpu', weights_only=True)
     net_module = importlib.import_module('segmentation3d.network.' + state['net'])
-    net = net_module.SegmentationNet(state['in_channels'], state['out_channels'])
+    # region-based checkpoints carry their regions and the head's activation; one without
+    # the keys is an exclusive-class (soft-max) model
+    regions, region_class_order, activation = region_keys(state)
+    if activation == 'sigmoid':
+        if region_class_order is None:
+            raise ValueError('region-based checkpoint {} has no region_class_order'.format(chk_dir))
+        region_class_order = check_region_class_order(region_class_order, int(state['out_channels']))
+        net = net_module.SegmentationNet(state['in_channels'], state['out_channels'], output_activation='sigmoid')
+    else:
+        net = net_module.SegmentationNet(state['in_channels'], state['out_channels'])
     net.load_state_dict(inference_state_dict(state['state_dict']))   # (the auxiliary heads of a deeply supervised run stay behind)
     net.eval()
     net = net.to(device)
@@ -643,6 +669,8 @@ def load_single_model(model_folder, gpu_id=0):
     model.device = device
     model.spacing, model.max_stride, model.interpolation = state['spacing'], state['max_stride'], state['interpolation']
     model.in_channels, model.out_channels = state['in_channels'], state['out_channels']
+    model.output_activation, model.regions = activation, regions
+    model.region_class_order = region_class_order if activation == 'sigmoid' else None
     model.crop_normalizers = [None if d is None else normalizer_from_dict(d) for d in state['crop_normalizers']]
     model.crop_normalizer_dicts = list(state['crop_normalizers'])
     return model
@@ -790,9 +818,11 @@ def _segmentation_volume(model, cfg, image, bbox_start_voxel, bbox_end_voxel, ba
     else:
         raise ValueError('Unsupported partition type!')
     norm = _model_normalizers(model, 1 if images is None else len(images))
-    probs, _, batcher = sliding_window_inference(model['net'], vol, starts, box, num_classes, norm,
-                                                 batch_size=min(batch_size, max(1, len(starts))), blend=blend,
-                                                 sigma_scale=sigma_scale, mirror_axes=mirror_axes)
+    order = model.get('region_class_order')     # region-based model: one sigmoid plane per region, composed label map
+    probs, net_mask, batcher = sliding_window_inference(model['net'], vol, starts, box, num_classes, norm,
+                                                        batch_size=min(batch_size, max(1, len(starts))), blend=blend,
+                                                        sigma_scale=sigma_scale, mirror_axes=mirror_axes,
+                                                        regions_order=order)
     # (voxels no patch covered -- bounding-box runs -- have count 0: their probabilities are 0 and the arg-max there is
     # class 0, as with ITK's division in the reference, see finalize_argmax_kernel)
     # back to the image grid (identity when the image already is at the model spacing and a stride multiple)
@@ -800,17 +830,32 @@ def _segmentation_volume(model, cfg, image, bbox_start_voxel, bbox_end_voxel, ba
                                                  for a, b in zip(image.GetSpacing(), spacing))
     if same_grid:
         out_probs = probs
-    else:
+    else:       # (region planes are all foreground: outside the model grid every one of them is 0)
         out_probs = torch.stack([image_tools.resample_device(probs[c], iso_frame, (X, Y, Z), img_frame, 'LINEAR',
-                                                              1.0 if c == 0 else 0.0) for c in range(num_classes)])
-    mask = out_probs.argmax(0).to(torch.int8)       # first maximum wins, like tensor.max(0) in the reference
-    labels = list(range(1, num_classes))
+                                                              1.0 if c == 0 and order is None else 0.0)
+                                 for c in range(num_classes)])
+    if order is None:
+        mask = out_probs.argmax(0).to(torch.int8)       # first maximum wins, like tensor.max(0) in the reference
+        labels = list(range(1, num_classes))
+    else:
+        mask = net_mask if same_grid else compose_region_mask(out_probs, order)
+        labels = sorted(set(order))
     if getattr(cfg, 'pick_largest_cc', False) and labels:
         mask = image_tools.connected_component_filter_device(mask, labels, 'largest')
     if getattr(cfg, 'remove_small_cc', 0) and cfg.remove_small_cc > 0 and labels:
         mask = image_tools.connected_component_filter_device(mask, labels, 'min_size', int(cfg.remove_small_cc))
     mean_probs = [Image3d(out_probs[c].cpu().numpy(), *img_frame) for c in range(num_classes)]
     return mean_probs, Image3d(mask.cpu().numpy(), *img_frame)
+
+
+def compose_region_mask(probs, regions_order):
+    """the label map of region probabilities [R, Z, Y, X] that are already means (the image-grid resampling of the
+    finalized planes): 0, then for r = 0 .. R-1 in order p_r > 0.5 writes regions_order[r] -- the rule of
+    seg3d_finalize_regions, as plain device plumbing off the patch path"""
+    mask = torch.zeros(probs.shape[1:], dtype=torch.int8, device=probs.device)
+    for r, label in enumerate(regions_order):
+        mask[probs[r] > 0.5] = int(label)
+    return mask
 
 
 _IMAGE_SUFFIXES = ('.mhd', '.nii', '.hdr', '.nii.gz', '.mha', '.image3d')     # core/seg_infer.py:80, 375-376

@@ -11,7 +11,7 @@ import torch.nn as nn
 from segmentation3d import _ops
 
 from segmentation3d.network.module.vnet_inblock import InputBlock
-from segmentation3d.network.module.vnet_outblock import OutputBlock
+from segmentation3d.network.module.vnet_outblock import OutputBlock, check_activation
 from segmentation3d.network.module.vnet_upblock import UpBlock
 from segmentation3d.network.module.vnet_downblock import DownBlock
 from segmentation3d.network.module.layers import Conv3d
@@ -45,21 +45,26 @@ class DeepSupervisionHead(nn.Module):
 
 class VNetBase(nn.Module):
     """volumetric segmentation network; `bottleneck` lists the stage names that use BottResidualBlock3;
-    `deep_supervision` = L in 0..3 registers L auxiliary heads (after `out_block`) on the lower decoder levels"""
+    `deep_supervision` = L in 0..3 registers L auxiliary heads (after `out_block`) on the lower decoder levels;
+    `output_activation` = 'sigmoid' ends the head in one sigmoid per output (region-based training) instead of the soft-max"""
 
-    def __init__(self, in_channels, out_channels, bottleneck=(), deep_supervision=0):
+    def __init__(self, in_channels, out_channels, bottleneck=(), deep_supervision=0, output_activation='softmax'):
         super(VNetBase, self).__init__()
         if isinstance(deep_supervision, bool) or not isinstance(deep_supervision, int) or \
                 not 0 <= deep_supervision <= len(DEEP_SUPERVISION_HEADS):
             raise ValueError('deep_supervision must be an integer in 0..{}, got {!r}'.format(len(DEEP_SUPERVISION_HEADS),
                                                                                            deep_supervision))
+        if check_activation(output_activation) == 'sigmoid' and deep_supervision > 0:
+            raise ValueError("output_activation='sigmoid' cannot be combined with deep supervision: the fused auxiliary "
+                             'head bakes in the soft-max')
         self.deep_supervision = deep_supervision
+        self.output_activation = output_activation
         self.in_block = InputBlock(in_channels, STEM_WIDTH)
         for name, width, convs in ENCODER_STAGES:
             setattr(self, name, DownBlock(width, convs, compression=name in bottleneck))
         for name, cin, cout, convs, _ in DECODER_STAGES:
             setattr(self, name, UpBlock(cin, cout, convs, compression=name in bottleneck))
-        self.out_block = OutputBlock(DECODER_STAGES[-1][2], out_channels)
+        self.out_block = OutputBlock(DECODER_STAGES[-1][2], out_channels, activation=output_activation)
         for name, _, width in DEEP_SUPERVISION_HEADS[:deep_supervision]:
             setattr(self, name, DeepSupervisionHead(width, out_channels))
 

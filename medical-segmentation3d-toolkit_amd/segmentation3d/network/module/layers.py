@@ -126,6 +126,13 @@ class Softmax(nn.Module):
         return _ops.softmax_channels(input)
 
 
+class Sigmoid(nn.Module):
+    """element-wise sigmoid over the channels (one output per region, region-based training); output is contiguous NCDHW"""
+
+    def forward(self, input):
+        return _ops.sigmoid_channels(input)
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # fused conv + GroupNorm (+ ReLU) units
 # ---------------------------------------------------------------------------------------------------------------------

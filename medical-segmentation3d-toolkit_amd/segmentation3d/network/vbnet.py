@@ -10,9 +10,9 @@ BOTTLENECK_STAGES = ('down_64', 'down_128', 'down_256', 'up_256', 'up_128')  # v
 
 
 class SegmentationNet(VNetBase):
-    def __init__(self, in_channels, out_channels, deep_supervision=0):
+    def __init__(self, in_channels, out_channels, deep_supervision=0, output_activation='softmax'):
         super(SegmentationNet, self).__init__(in_channels, out_channels, bottleneck=BOTTLENECK_STAGES,
-                                              deep_supervision=deep_supervision)
+                                              deep_supervision=deep_supervision, output_activation=output_activation)
 
 
 def parameters_kaiming_init(net):

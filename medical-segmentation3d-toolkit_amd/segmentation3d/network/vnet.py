@@ -10,8 +10,9 @@ from segmentation3d.network.module.weight_init import kaiming_weight_init, gauss
 
 
 class SegmentationNet(VNetBase):
-    def __init__(self, in_channels, out_channels, deep_supervision=0):
-        super(SegmentationNet, self).__init__(in_channels, out_channels, bottleneck=(), deep_supervision=deep_supervision)
+    def __init__(self, in_channels, out_channels, deep_supervision=0, output_activation='softmax'):
+        super(SegmentationNet, self).__init__(in_channels, out_channels, bottleneck=(), deep_supervision=deep_supervision,
+                                              output_activation=output_activation)
 
 
 def parameters_kaiming_init(net):

@@ -2,6 +2,7 @@
 a test list against its ground truth with `cal_dsc_batch` and write the CSV.
 
     python -m segmentation3d.seg_eval -i test.txt --gt_folder GT --seg_folder SEG -l 1 2 -o results.csv [--surface]
+                                   [--regions "1,2,3;1,3;3"]
 
 Case names come from a list file (read_test_txt) or from the image files of a folder (read_test_folder); case <name> is
 scored as <gt_folder>/<name>/<gt_name> against <seg_folder>/<name>/<seg_name>."""
@@ -25,7 +26,20 @@ def build_parser():
     parser.add_argument('--surface', action='store_true',
                         help='also report the Hausdorff distance, its 95th percentile and the average symmetric '
                              'surface distance (physical units) of every TP label')
+    parser.add_argument('--regions', default=None,
+                        help='overlapping regions to score as well, sets of label ids: "1,2,3;1,3;3" (BraTS whole tumour, '
+                             'tumour core, enhancing tumour) adds region<k>_score / region<k>_type columns')
     return parser
+
+
+def parse_regions(text):
+    """'1,2,3;1,3;3' -> [[1, 2, 3], [1, 3], [3]]; None / '' -> None"""
+    if not text:
+        return None
+    try:
+        return [[int(l) for l in part.split(',')] for part in text.split(';')]
+    except ValueError:
+        raise ValueError('--regions must look like "1,2,3;1,3;3", got {!r}'.format(text))
 
 
 def case_names(input_path):
@@ -46,7 +60,7 @@ def main(argv=None):
     gt_files = [os.path.join(args.gt_folder, name, args.gt_name) for name in names]
     seg_files = [os.path.join(args.seg_folder, name, args.seg_name) for name in names]
     return cal_dsc_batch(gt_files, seg_files, args.labels, args.threshold, args.output,
-                         surface_metrics=args.surface)
+                         surface_metrics=args.surface, regions=parse_regions(args.regions))
 
 
 if __name__ == '__main__':

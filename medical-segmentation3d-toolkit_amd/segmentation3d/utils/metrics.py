@@ -43,8 +43,7 @@ def _as_device_labels(vol, device):
     return vol.to(device).contiguous()
 
 
-def label_overlap_counts(gt, seg, labels, device=None):
-    """[(area_gt, area_seg, intersection)] per label, as Python ints, from one device pass per 16 labels"""
+def _device_pair(gt, seg, device):
     if device is None:
         device = gt.device if isinstance(gt, torch.Tensor) and gt.is_cuda else torch.device('cuda', torch.cuda.current_device())
     g, s = _as_device_labels(gt, device), _as_device_labels(seg, device)
@@ -54,6 +53,12 @@ def label_overlap_counts(gt, seg, labels, device=None):
     if g.numel() != s.numel():
         raise ValueError('ground truth and segmentation differ in size: {} vs {}'.format(tuple(g.shape), tuple(s.shape)))
     E.require_device(g, s)
+    return g, s, device
+
+
+def label_overlap_counts(gt, seg, labels, device=None):
+    """[(area_gt, area_seg, intersection)] per label, as Python ints, from one device pass per 16 labels"""
+    g, s, device = _device_pair(gt, seg, device)
     labels = [int(l) for l in labels]
     out = []
     for k0 in range(0, len(labels), MAX_LABELS_PER_PASS):
@@ -88,6 +93,28 @@ def cal_dsc(gt_npy, seg_npy, label, threshold):
 def cal_dsc_labels(gt, seg, labels, threshold):
     """[(dsc, seg_type)] for several labels from a single pass over the volumes"""
     return [_classify(a, b, c, threshold) for a, b, c in label_overlap_counts(gt, seg, labels)]
+
+
+def region_overlap_counts(gt, seg, regions, device=None):
+    """[(area_gt, area_seg, intersection)] per region (a set of label ids: a voxel is in the region when its label is in the
+    set), as Python ints, from one device pass per 16 regions (seg3d_region_overlap_counts)"""
+    from segmentation3d.loss.region_loss import region_lut
+    g, s, device = _device_pair(gt, seg, device)
+    out = []
+    for k0 in range(0, len(regions), MAX_LABELS_PER_PASS):
+        chunk = list(regions[k0:k0 + MAX_LABELS_PER_PASS])
+        counts = torch.zeros(3 * len(chunk), dtype=torch.int64, device=device)
+        lut = (ctypes.c_uint * 256)(*region_lut(chunk))
+        E.call('seg3d_region_overlap_counts', E.ptr(g), E.ptr(s), _DTYPE_CODES[g.dtype], g.numel(), lut, len(chunk),
+               E.ptr(counts), E.stream_ptr())
+        c = counts.cpu().tolist()
+        out.extend((c[3 * k], c[3 * k + 1], c[3 * k + 2]) for k in range(len(chunk)))
+    return out
+
+
+def cal_region_dsc(gt, seg, regions, threshold):
+    """[(dsc, seg_type)] per region -- cal_dsc with set membership (BraTS-style overlapping regions), one pass"""
+    return [_classify(a, b, c, threshold) for a, b, c in region_overlap_counts(gt, seg, regions)]
 
 
 # ---- surface-distance metrics (csrc/surface.hip; DESIGN.md section 7 row f5) -------------------------------------------

@@ -67,6 +67,10 @@ def load_checkpoint(epoch_idx, net, opt, save_dir):
     elif trained != built:
         raise ValueError('the checkpoint was trained with deep_supervision = {} but the network was built with {}'.format(
             trained, built))
+    trained_act, built_act = state.get('output_activation', 'softmax'), getattr(target, 'output_activation', 'softmax')
+    if trained_act != built_act:
+        raise ValueError('the checkpoint was trained with output_activation = {!r} but the network was built with {!r}'.format(
+            trained_act, built_act))
     target.load_state_dict(weights)
     if opt is not None:
         opt.load_state_dict(_read(os.path.join(folder, 'optimizer.pth'), 'optimizer'))
@@ -79,8 +83,20 @@ def checkpoint_deep_supervision(epoch_idx, save_dir):
     return int(state.get('deep_supervision', 0))
 
 
-def checkpoint_state(net, epoch_idx, batch_idx, cfg, max_stride, num_modality):
-    """the `params.pth` dictionary (fields of utils/model_io.py:75-84; tensors moved to the host)"""
+def region_keys(state):
+    """(regions, region_class_order, output_activation) of a `params.pth` dictionary; a checkpoint written before the keys
+    existed is an exclusive-class one: (None, None, 'softmax')"""
+    return state.get('regions'), state.get('region_class_order'), state.get('output_activation', 'softmax')
+
+
+def checkpoint_regions(epoch_idx, save_dir):
+    """region_keys of the checkpoint `<save_dir>/checkpoints/chk_<epoch_idx>`"""
+    return region_keys(_read(os.path.join(_chk_dir(save_dir, epoch_idx), 'params.pth'), 'checkpoint'))
+
+
+def checkpoint_state(net, epoch_idx, batch_idx, cfg, max_stride, num_modality, regions=None, region_class_order=None):
+    """the `params.pth` dictionary (fields of utils/model_io.py:75-84; tensors moved to the host); `regions` /
+    `region_class_order` of a region-based run are stored next to the channel counts with the head's activation"""
     weights = OrderedDict((key, value.detach().cpu()) for key, value in net.state_dict().items())
     geometry = {'spacing': cfg.dataset.spacing, 'interpolation': cfg.dataset.interpolation, 'max_stride': max_stride}
     channels = {'in_channels': num_modality, 'out_channels': cfg.dataset.num_classes,
@@ -89,15 +105,19 @@ def checkpoint_state(net, epoch_idx, batch_idx, cfg, max_stride, num_modality):
              'crop_normalizers': [None if n is None else n.to_dict() for n in cfg.dataset.crop_normalizers]}
     state.update(geometry)
     state.update(channels)
+    state['regions'] = None if regions is None else [[int(l) for l in r] for r in regions]
+    state['region_class_order'] = None if region_class_order is None else [int(l) for l in region_class_order]
+    state['output_activation'] = str(getattr(getattr(net, 'module', net), 'output_activation', 'softmax'))
     return state
 
 
-def save_checkpoint(net, opt, epoch_idx, batch_idx, cfg, max_stride, num_modality):
+def save_checkpoint(net, opt, epoch_idx, batch_idx, cfg, max_stride, num_modality, regions=None, region_class_order=None):
     """write params.pth / optimizer.pth (+ a copy of train_config.py) for `epoch_idx`"""
     model_folder = os.path.join(cfg.general.save_dir, cfg.general.model_scale)
     folder = _chk_dir(model_folder, epoch_idx)
     os.makedirs(folder, exist_ok=True)
-    torch.save(checkpoint_state(net, epoch_idx, batch_idx, cfg, max_stride, num_modality), os.path.join(folder, 'params.pth'))
+    torch.save(checkpoint_state(net, epoch_idx, batch_idx, cfg, max_stride, num_modality, regions, region_class_order),
+               os.path.join(folder, 'params.pth'))
     torch.save(opt.state_dict(), os.path.join(folder, 'optimizer.pth'))
     config_copy = os.path.join(model_folder, 'train_config.py')
     if os.path.isfile(config_copy):
