@@ -549,6 +549,17 @@ int seg3d_label_overlap_counts(const void* gt, const void* seg, int dtype, long 
 int seg3d_region_overlap_counts(const void* gt, const void* seg, int dtype, long long n, const unsigned* lut_host,
                                 int nregions, unsigned long long* counts, void* stream);
 
+/* ---- online validation: arg-max + per-class confusion counts in one pass ---------------
+ * Replaces nothing in the reference (its core/seg_train.py has no validation); the stock-torch chain it stands for is
+ * probs.argmax(1) followed by 3 C masked sums.  probs [N][C][S] planar fp32, target [N][S] float class ids, 1 <= C <= 16.
+ * A voxel counts iff t >= 0 && t < C && t != ignore_label (the rule of seg3d_compound_loss_fwd; any value outside [0, C)
+ * means "no ignore label"); its prediction is the FIRST maximum over the classes (class 0, replaced only by a strictly
+ * greater value).  counts[3c..3c+2] += (tp, fp, fn) of class c: the caller owns and zeroes the 3 * C device int64 words, so
+ * a whole validation pass accumulates on the device.  Integer arithmetic only (bit-exact in any order); no allocation and
+ * no synchronisation, so the call can be captured into a hipGraph. */
+int seg3d_confusion_counts(const float* probs, const float* target, long long* counts, int N, int C, long long S,
+                           float ignore_label, void* stream);
+
 /* ---- surface-distance metrics: HD, HD95, ASSD of one label --------------------------------
  * seg3d_label_surface: surface[i] = 1 on the voxels of (labels == label) that have a 6-neighbour outside the label
  * (voxels outside the volume count as outside), else 0, over an X x Y x Z volume ([Z][Y][X], < 2^31 voxels, dtype as

@@ -1,0 +1,147 @@
+// validation.hip -- arg-max + per-class confusion counts of a probability map against a label map, for the validation pass
+// that runs between training epochs.
+//
+// Replaces nothing in the reference: its core/seg_train.py never measures the model while it trains.  The stock-torch chain
+// this stands for is `pred = probs.argmax(1)` followed by 3 C masked sums (C + 1 reads of the label-sized tensors each).
+// Here ONE streaming pass over probs [N][C][S] (planar fp32, what the soft-max head writes) and target [N][S] (float class
+// ids, what the losses take) adds, for every valid voxel,
+//     tp[c] += [pred == c && t == c]      fp[c] += [pred == c && t != c]      fn[c] += [pred != c && t == c]
+// into counts[c] = (tp, fp, fn).  valid is the compound loss's rule (loss.hip compound_voxel): t >= 0 && t < C && t != ignore,
+// class (int)t.  pred is the FIRST maximum: class 0, replaced only by a strictly greater value (finalize_argmax_kernel,
+// tensor.max(0)).  NaN probabilities are outside the contract: every comparison with a NaN is false, so a NaN in a class
+// above 0 never becomes the maximum and a NaN in class 0 is never replaced (np.argmax would return the NaN's index in both
+// cases).  Integer counting only: per-thread 32-bit counters, a wave64
+// shuffle sum, one LDS row per wave, then 3 C 64-bit integer atomics per workgroup -- bit-exact in any order.
+// HBM-bound: algorithmic bytes = (C + 1) * 4 per voxel.
+#include "seg3d_common.h"
+#include "seg3d_hip.h"
+
+#define CONF_MAXC 16      // SEG3D_MAXC of loss.hip
+#define CONF_THREADS 1024
+#define CONF_WAVES (CONF_THREADS / 64)
+
+// CT = C for C <= 5 (fully unrolled, no guards); CT = 16 serves 6..16 classes with `c < C` guards, as in loss.hip
+template <int CT>
+struct ConfAcc {
+  unsigned tp[CT], fp[CT], fn[CT];
+};
+
+template <int CT>
+__device__ __forceinline__ void conf_voxel(ConfAcc<CT>& a, float t, int pred, int C, float ignore) {
+  const bool valid = t >= 0.0f && t < (float)C && t != ignore;
+  if (!valid) return;
+  const int ti = (int)t;
+#pragma unroll
+  for (int c = 0; c < CT; ++c)
+    if (CT <= 5 || c < C) {
+      const bool p = pred == c, g = ti == c;
+      a.tp[c] += (p && g) ? 1u : 0u;
+      a.fp[c] += (p && !g) ? 1u : 0u;
+      a.fn[c] += (!p && g) ? 1u : 0u;
+    }
+}
+
+// grid (gx, N): workgroup (bx, n) strides over sample n's voxels.  counts: 3 * C u64, ADDED to.
+template <int CT, bool VEC>
+__global__ __launch_bounds__(CONF_THREADS) void confusion_counts_kernel(const float* __restrict__ probs,
+                                                                         const float* __restrict__ target,
+                                                                         unsigned long long* __restrict__ counts, int C, i64 S,
+                                                                         float ignore) {
+  __shared__ unsigned red[CONF_WAVES][3 * CT];
+  const int n = blockIdx.y;
+  const float* tg = target + (i64)n * S;
+  const float* pb = probs + (i64)n * C * S;
+  ConfAcc<CT> a;
+#pragma unroll
+  for (int c = 0; c < CT; ++c) a.tp[c] = a.fp[c] = a.fn[c] = 0u;
+  if constexpr (VEC) {   // S % 4 == 0 and 16-byte aligned bases: every plane row starts aligned
+    for (i64 s = ((i64)blockIdx.x * CONF_THREADS + threadIdx.x) * 4; s < S; s += (i64)gridDim.x * CONF_THREADS * 4) {
+      const float4 t4 = *reinterpret_cast<const float4*>(tg + s);
+      float4 best = *reinterpret_cast<const float4*>(pb + s);
+      int ix = 0, iy = 0, iz = 0, iw = 0;
+#pragma unroll
+      for (int c = 1; c < CT; ++c)
+        if (CT <= 5 || c < C) {
+          const float4 p = *reinterpret_cast<const float4*>(pb + (i64)c * S + s);
+          if (p.x > best.x) { best.x = p.x; ix = c; }
+          if (p.y > best.y) { best.y = p.y; iy = c; }
+          if (p.z > best.z) { best.z = p.z; iz = c; }
+          if (p.w > best.w) { best.w = p.w; iw = c; }
+        }
+      conf_voxel<CT>(a, t4.x, ix, C, ignore);
+      conf_voxel<CT>(a, t4.y, iy, C, ignore);
+      conf_voxel<CT>(a, t4.z, iz, C, ignore);
+      conf_voxel<CT>(a, t4.w, iw, C, ignore);
+    }
+  } else {
+    for (i64 s = (i64)blockIdx.x * CONF_THREADS + threadIdx.x; s < S; s += (i64)gridDim.x * CONF_THREADS) {
+      const float t = tg[s];
+      float best = pb[s];
+      int idx = 0;
+#pragma unroll
+      for (int c = 1; c < CT; ++c)
+        if (CT <= 5 || c < C) {
+          const float p = pb[(i64)c * S + s];
+          if (p > best) { best = p; idx = c; }
+        }
+      conf_voxel<CT>(a, t, idx, C, ignore);
+    }
+  }
+  // a thread counts at most S / 1024 + 4 voxels and a wave 64 times that: 32 bits hold both for S < 2^33 (checked by the entry)
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int c = 0; c < CT; ++c)
+    if (CT <= 5 || c < C) {
+      unsigned x = a.tp[c], y = a.fp[c], z = a.fn[c];
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) {
+        x += __shfl_down(x, off, 64);
+        y += __shfl_down(y, off, 64);
+        z += __shfl_down(z, off, 64);
+      }
+      if (lane == 0) {
+        red[wave][3 * c + 0] = x;
+        red[wave][3 * c + 1] = y;
+        red[wave][3 * c + 2] = z;
+      }
+    }
+  __syncthreads();
+  if ((int)threadIdx.x < 3 * C) {
+    unsigned long long v = 0ull;
+#pragma unroll
+    for (int w = 0; w < CONF_WAVES; ++w) v += red[w][threadIdx.x];
+    if (v) atomicAdd(counts + threadIdx.x, v);   // integer atomics: the result does not depend on the order
+  }
+}
+
+#define CONF_LAUNCH(CT, VEC) \
+  confusion_counts_kernel<CT, VEC><<<grid, dim3(CONF_THREADS), 0, s>>>(probs, target, out, C, (i64)S, ignore_label)
+
+// counts[3c..3c+2] += (tp, fp, fn) of class c over probs [N][C][S] / target [N][S]; `counts` (3 * C int64, device) is owned
+// and zeroed by the caller, so that a whole validation pass accumulates on the device.  No allocation, no synchronisation.
+extern "C" int seg3d_confusion_counts(const float* probs, const float* target, long long* counts, int N, int C, long long S,
+                                      float ignore_label, void* stream) {
+  SEG3D_REQUIRE(probs && target && counts, "seg3d_confusion_counts: null pointer");
+  SEG3D_REQUIRE(N > 0 && N <= 65535 && S > 0 && S < (1ll << 33), "seg3d_confusion_counts: bad sizes (N = %d, S = %lld)", N, S);
+  SEG3D_REQUIRE(C >= 1 && C <= CONF_MAXC, "seg3d_confusion_counts: num_class %d not in [1, %d]", C, CONF_MAXC);
+  const bool vec = S % 4 == 0 && (((uintptr_t)probs | (uintptr_t)target) & 15) == 0;
+  const i64 items = vec ? S / 4 : S;
+  // two workgroups of 16 waves per compute unit over the whole batch; the grid-stride loop takes the rest
+  i64 gx = (items + CONF_THREADS - 1) / CONF_THREADS;
+  i64 cap = (2 * (i64)seg3d_device_cus() + N - 1) / N;
+  if (cap < 1) cap = 1;
+  if (gx > cap) gx = cap;
+  const dim3 grid((unsigned)gx, (unsigned)N);
+  unsigned long long* out = reinterpret_cast<unsigned long long*>(counts);
+  hipStream_t s = (hipStream_t)stream;
+  switch (C) {
+    case 1: if (vec) CONF_LAUNCH(1, true); else CONF_LAUNCH(1, false); break;
+    case 2: if (vec) CONF_LAUNCH(2, true); else CONF_LAUNCH(2, false); break;
+    case 3: if (vec) CONF_LAUNCH(3, true); else CONF_LAUNCH(3, false); break;
+    case 4: if (vec) CONF_LAUNCH(4, true); else CONF_LAUNCH(4, false); break;
+    case 5: if (vec) CONF_LAUNCH(5, true); else CONF_LAUNCH(5, false); break;
+    default: if (vec) CONF_LAUNCH(CONF_MAXC, true); else CONF_LAUNCH(CONF_MAXC, false); break;
+  }
+  SEG3D_LAUNCH_CHECK("seg3d_confusion_counts");
+  return SEG3D_OK;
+}

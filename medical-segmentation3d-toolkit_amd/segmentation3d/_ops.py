@@ -180,6 +180,10 @@ class PackedWeightCache(object):
         hipGraph stay valid;
       * an in-place torch update of a parameter (torch.optim.*) bumps `tensor._version`, which is part of the check.
     The cache is OFF by default: code that edits `param.data` in place (no version bump) must call `invalidate()`.
+    A captured train step holds raw pointers to the images AND to the job table of `repack_all()`; registering a new image
+    drops that table.  Code that runs forwards next to a captured step (the validation pass) therefore does so inside
+    `frozen()`: a current image is used as it is, anything else is packed into a buffer of the caller's own, and neither the
+    entries nor the table change.
     """
 
     def __init__(self):
@@ -187,6 +191,16 @@ class PackedWeightCache(object):
         self.entries = {}     # key -> dict(w, wp, args, epoch, version)
         self.epoch = 0
         self._table = None    # (device uint8 tensor, njobs, total_blocks), rebuilt when entries change
+        self.read_only = 0    # > 0 inside frozen()
+
+    @contextlib.contextmanager
+    def frozen(self):
+        """inside: lookups only (see the class docstring); nests"""
+        self.read_only += 1
+        try:
+            yield
+        finally:
+            self.read_only -= 1
 
     def invalidate(self):
         self.epoch += 1
@@ -254,9 +268,9 @@ def weight_cache(enabled):
 
 
 def _pack_mfma(w, A, B, T, sa, sb, flip=0, bf16=False):
-    if PACK_CACHE.enabled and not torch.cuda.is_current_stream_capturing():
+    if PACK_CACHE.enabled and not PACK_CACHE.read_only and not torch.cuda.is_current_stream_capturing():
         return PACK_CACHE.get(w, A, B, T, sa, sb, flip, bf16)
-    if PACK_CACHE.enabled:   # inside a hipGraph capture: only a current image may be used (no allocation, no launch)
+    if PACK_CACHE.enabled:   # inside a hipGraph capture or frozen(): only a current image may be used, the cache stays as it is
         key = (w.data_ptr(), w.device.index, A, B, T, sa, sb, flip, bf16)
         e = PACK_CACHE.entries.get(key)
         if e is not None and e['epoch'] == PACK_CACHE.epoch and e['version'] == w._version:
@@ -1579,3 +1593,31 @@ def label_pyramid(mask, levels):
     ptrs = [E.ptr(o) for o in outs] + [None] * (3 - levels)
     E.call('seg3d_label_pyramid', E.ptr(m), ptrs[0], ptrs[1], ptrs[2], N, D, H, W_, levels, E.stream_ptr())
     return outs
+
+
+def confusion_counts(probs, target, ignore_label=None, out=None):
+    """per-class (tp, fp, fn) of the arg-max of `probs` [N, C, *spatial] (float32 probabilities) against `target` (float
+    class ids, N * spatial elements) in ONE pass: device int64 [C, 3].  A voxel counts iff 0 <= t < C and t != ignore_label
+    (the compound loss's rule); its prediction is the first maximum over the classes.  `out` (int64 [C, 3], contiguous) is
+    ADDED to and returned, so a validation pass accumulates on the device; without it a zeroed tensor is made.  Nothing is
+    synchronised or read back."""
+    E.require_device(probs, target, out)
+    if probs.dtype != torch.float32:
+        raise ValueError('probabilities must be float32, got {}'.format(probs.dtype))
+    if probs.dim() < 2:
+        raise ValueError('probabilities must be [N, C, *spatial], got shape {}'.format(tuple(probs.shape)))
+    N, C = int(probs.shape[0]), int(probs.shape[1])
+    if not 1 <= C <= 16:
+        raise ValueError('confusion_counts: {} classes, 1..16 are supported'.format(C))
+    S = probs[0, 0].numel()
+    if target.numel() != N * S:
+        raise ValueError('target shape {} does not match input {}'.format(tuple(target.shape), tuple(probs.shape)))
+    if out is None:
+        out = torch.zeros((C, 3), dtype=torch.int64, device=probs.device)
+    elif out.dtype != torch.int64 or tuple(out.shape) != (C, 3) or not out.is_contiguous():
+        raise ValueError('out must be a contiguous int64 [{}, 3] tensor, got {} {}'.format(C, out.dtype, tuple(out.shape)))
+    p = probs.contiguous()
+    t = target.contiguous().float()
+    ignore = -1.0 if ignore_label is None else float(ignore_label)   # any value outside [0, C): no ignore label
+    E.call('seg3d_confusion_counts', E.ptr(p), E.ptr(t), E.ptr(out), N, C, S, ignore, E.stream_ptr())
+    return out

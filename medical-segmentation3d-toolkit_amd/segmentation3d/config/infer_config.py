@@ -6,6 +6,7 @@
 #   blend_mode = 'constant'        'constant' | 'gaussian': weight of a patch voxel when overlapping patches are averaged
 #   blend_sigma_scale = 0.125      Gaussian sigma as a fraction of the patch edge
 #   tta_mirror_axes = []           e.g. ['x', 'y']: mirror test-time augmentation, 2^k forwards per patch
+#   checkpoint = 'latest'          'latest' (largest chk_<n>) | 'best' (checkpoints/best of a run with validation) | an epoch
 from easydict import EasyDict as edict
 
 __C = edict()

@@ -27,7 +27,7 @@ from segmentation3d.utils.image3d import Image3d
 from segmentation3d.utils import image_tools
 from segmentation3d.utils.image_tools import image_partition_by_fixed_size
 from segmentation3d.loss.region_loss import check_region_class_order
-from segmentation3d.utils.model_io import get_checkpoint_folder, inference_state_dict, region_keys
+from segmentation3d.utils.model_io import inference_state_dict, region_keys, select_checkpoint_folder
 from segmentation3d.utils.normalizer import normalizer_from_dict
 
 
@@ -638,8 +638,9 @@ class _Model(dict):
     __setattr__ = dict.__setitem__
 
 
-def load_single_model(model_folder, gpu_id=0):
-    """load one model folder `<folder>/checkpoints/chk_<latest>/params.pth` (reference: seg_infer.py:99-164).
+def load_single_model(model_folder, gpu_id=0, checkpoint='latest'):
+    """load one model folder `<folder>/checkpoints/chk_<latest>/params.pth` (reference: seg_infer.py:99-164); `checkpoint`
+    = 'best' loads `checkpoints/best` (written by a training run with validation), an integer that epoch's `chk_<n>`.
     gpu_id must be >= 0: this engine has no CPU path (the reference's gpu_id = -1 branch is served by stock torch)."""
     assert os.path.isdir(model_folder), 'Model folder does not exist: {}'.format(model_folder)
     if gpu_id is None or int(gpu_id) < 0:
@@ -648,7 +649,7 @@ def load_single_model(model_folder, gpu_id=0):
     # the reference pins the GPU with CUDA_VISIBLE_DEVICES (seg_infer.py:104-105); here the chosen device becomes the
     # CURRENT device: every kernel of this engine is launched on the current device's stream
     torch.cuda.set_device(device)
-    chk_dir = get_checkpoint_folder(os.path.join(model_folder, 'checkpoints'), -1)
+    chk_dir = select_checkpoint_folder(os.path.join(model_folder, 'checkpoints'), checkpoint)
     state = torch.load(os.path.join(chk_dir, 'params.pth'), map_location='cpu', weights_only=True)
     net_module = importlib.import_module('segmentation3d.network.' + state['net'])
     # region-based checkpoints carry their regions and the head's activation; one without
@@ -688,9 +689,11 @@ def load_models(model_folder, gpu_id=0):
         raise ValueError('Unsupported single scale type!')
     models.coarse_model = models.fine_model = None
     if scale in ('coarse', 'DISABLE'):
-        models.coarse_model = load_single_model(os.path.join(model_folder, infer_cfg.coarse.model_name), gpu_id)
+        models.coarse_model = load_single_model(os.path.join(model_folder, infer_cfg.coarse.model_name), gpu_id,
+                                                getattr(infer_cfg.coarse, 'checkpoint', 'latest'))
     if scale in ('fine', 'DISABLE'):
-        models.fine_model = load_single_model(os.path.join(model_folder, infer_cfg.fine.model_name), gpu_id)
+        models.fine_model = load_single_model(os.path.join(model_folder, infer_cfg.fine.model_name), gpu_id,
+                                              getattr(infer_cfg.fine, 'checkpoint', 'latest'))
     return models
 
 

@@ -7,6 +7,7 @@ loss / Adam arithmetic in HIP kernels, gradients exchanged with a bucketed RCCL 
 """
 import importlib
 import gc
+import json
 import math
 import os
 import shutil
@@ -85,6 +86,36 @@ def deep_supervision_from_config(train_cfg):
     weights = getattr(train_cfg, 'deep_supervision_weights', None)
     return {'deep_supervision': int(getattr(train_cfg, 'deep_supervision', 0)),
             'deep_supervision_weights': None if weights is None else list(weights)}
+
+
+def build_validator(cfg, val_cfg, step, num_modality):
+    """the Validator of a run whose config has a `validation` section (`val_cfg`: validate_validation's dict): the held-out
+    cases go through a SegmentationDataset with the run's geometry and normalisers but no random translation, scale, mirror
+    or augmentation; `validation.crops_per_case` crops of each are drawn once with `validation.seed` and stay on the device"""
+    from segmentation3d.core.seg_validate import Validator
+    from segmentation3d.dataloader.dataset import SegmentationDataset, collect_fixed_crops
+    held_out = SegmentationDataset(
+        imlist_file=val_cfg['imseg_list'], num_classes=cfg.dataset.num_classes, spacing=cfg.dataset.spacing,
+        crop_size=cfg.dataset.crop_size, sampling_method=cfg.dataset.sampling_method, random_translation=[0, 0, 0],
+        random_scale=[1, 1], interpolation=cfg.dataset.interpolation, crop_normalizers=cfg.dataset.crop_normalizers,
+        device=step.device)
+    if held_out.num_modality() != num_modality:
+        raise ValueError('the validation cases of {} have {} modalities, the training set has {}'.format(
+            val_cfg['imseg_list'], held_out.num_modality(), num_modality))
+    crops, masks = collect_fixed_crops(held_out, val_cfg['crops_per_case'], val_cfg['seed'])
+    loss_options = loss_options_from_config(cfg.loss)
+    loss_func = build_loss(cfg.loss.name, cfg.dataset.num_classes, cfg.loss.obj_weight, cfg.loss.focal_gamma, use_gpu=True,
+                           **loss_options)   # a second object: the training loss's .last_terms stays the train step's
+    batchsize = val_cfg['batchsize'] if val_cfg['batchsize'] is not None else cfg.train.batchsize
+    return Validator(step.net, loss_func, crops, masks, batchsize, ignore_label=loss_options['ignore_label'],
+                     ema=val_cfg['ema'])
+
+
+def validation_log_line(epoch_idx, result):
+    """'epoch: 3, val_loss: 0.2134, val_dice: 0.8123, val_dice_ema: 0.7990, val_dice_per_class: [0.9912, 0.8123]'"""
+    ema = float('nan') if result['ema_dice'] is None else result['ema_dice']
+    return 'epoch: {}, val_loss: {:.4f}, val_dice: {:.4f}, val_dice_ema: {:.4f}, val_dice_per_class: [{}]'.format(
+        epoch_idx, result['val_loss'], result['mean_dice'], ema, ', '.join('{:.4f}'.format(d) for d in result['dice']))
 
 
 def build_optimizer(name, params, lr, betas=(0.9, 0.999), optim_options=None):
@@ -228,11 +259,19 @@ def train(train_config_file, data_iter_factory=None):
     exactly as core/seg_train.py:56-70 wires the reference's dataset; alternatively pass
     `data_iter_factory(cfg) -> iterator of (crops, masks[, frames, names])`.  Model folder, config copies, seeding,
     loss selection, logging format and checkpoint cadence follow core/seg_train.py:22-152.
+
+    An optional `validation` section (core/seg_validate.py; not in the reference) scores the network on fixed held-out crops
+    whenever the epoch index reaches a new multiple of `validation.epochs`: one `val_` log line, the checkpoint with the
+    best moving-average Dice in `checkpoints/best`, and the average's state in every `chk_<epoch>/params.pth`.
     """
     from segmentation3d.utils.file_io import load_config, setup_logger
-    from segmentation3d.utils.model_io import load_checkpoint, save_checkpoint
+    from segmentation3d.utils.model_io import BEST_FOLDER, checkpoint_validation, load_checkpoint, save_checkpoint
+    from segmentation3d.core.seg_validate import validate_validation
     assert os.path.isfile(train_config_file), 'Config not found: {}'.format(train_config_file)
     cfg = load_config(train_config_file)
+    # optional `validation` section (None: off, and then nothing below differs from a run without it); bad keys / values
+    # raise before anything is built
+    val_cfg = validate_validation(getattr(cfg, 'validation', None), cfg.dataset.num_classes)
     model_folder = os.path.join(cfg.general.save_dir, cfg.general.model_scale)
     distributed = dist.is_available() and dist.is_initialized()
     rank = dist.get_rank() if distributed else 0
@@ -296,6 +335,14 @@ def train(train_config_file, data_iter_factory=None):
         batches = DeviceCropLoader(dataset, sampler, cfg.train.batchsize)
     else:
         batches = data_iter_factory(cfg)
+    validator, last_val_epoch = None, last_save_epoch
+    if val_cfg is not None:
+        validator = build_validator(cfg, val_cfg, step, num_modality)
+        if cfg.general.resume_epoch >= 0:
+            stored = checkpoint_validation(cfg.general.resume_epoch, model_folder)
+            if stored is not None:
+                validator.load_state_dict(stored)   # the moving average and the best value continue
+        step.validator = validator
     steps_this_run = 0
     for batch in batches:
         crops, masks = batch[0], batch[1]
@@ -319,7 +366,18 @@ def train(train_config_file, data_iter_factory=None):
             if show_lr:   # the reference's log format unless a schedule moves the rate
                 line += ', lr: {:.6e}'.format(step.opt.param_groups[0]['lr'])
             logger.info(line)
+        if validator is not None and epoch_idx != 0 and epoch_idx % val_cfg['epochs'] == 0 and last_val_epoch != epoch_idx:
+            result = validator.run(epoch_idx)     # every rank: the counts are all-reduced
+            last_val_epoch = epoch_idx
+            if logger is not None:
+                logger.info(validation_log_line(epoch_idx, result))
+            if rank == 0 and result['improved'] and val_cfg['save_best']:
+                folder = save_checkpoint(step.net, step.opt, epoch_idx, batch_idx, cfg, step.max_stride, num_modality,
+                                         validation=validator.state_dict(), folder_name=BEST_FOLDER)
+                with open(os.path.join(folder, 'validation.json'), 'w') as f:
+                    json.dump(dict(result, epoch=epoch_idx, batch=batch_idx), f, indent=1)
         if rank == 0 and epoch_idx != 0 and epoch_idx % cfg.train.save_epochs == 0 and last_save_epoch != epoch_idx:
-            save_checkpoint(step.net, step.opt, epoch_idx, batch_idx, cfg, step.max_stride, num_modality)
+            save_checkpoint(step.net, step.opt, epoch_idx, batch_idx, cfg, step.max_stride, num_modality,
+                            validation=None if validator is None else validator.state_dict())
             last_save_epoch = epoch_idx
     return step

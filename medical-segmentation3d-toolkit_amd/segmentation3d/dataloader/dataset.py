@@ -529,3 +529,28 @@ class DeviceCropLoader(object):
                 batch, segs, frames, names = None, [], [], []
         if segs and not self.drop_last:
             yield batch[:len(segs)].permute(0, 4, 1, 2, 3), torch.stack(segs), np.stack(frames), names
+
+
+def collect_fixed_crops(dataset, crops_per_case, seed):
+    """`crops_per_case` crops of every case of a SegmentationDataset, in case order: device tensors
+    (crops [V, M, z, y, x], masks [V, 1, z, y, x]), V = len(dataset) * crops_per_case -- the fixed held-out set of the
+    validation pass (core/seg_validate.py).  The dataset draws from numpy's GLOBAL stream, which the training run depends
+    on: the state is saved, the stream seeded with `seed` for the draws, and the state restored whatever happens, so the
+    caller's stream is exactly what it was and the same seed gives the same crops."""
+    crops_per_case = int(crops_per_case)
+    if crops_per_case < 1:
+        raise ValueError('crops_per_case must be >= 1, got {}'.format(crops_per_case))
+    state = np.random.get_state()
+    crops, masks = [], []
+    try:
+        np.random.seed(int(seed))
+        for index in range(len(dataset)):
+            for _ in range(crops_per_case):
+                sample = dataset[index]
+                crops.append(sample[0].contiguous())
+                masks.append(sample[1])
+    finally:
+        np.random.set_state(state)
+    if not crops:
+        raise ValueError('the data set has no cases')
+    return torch.stack(crops), torch.stack(masks)

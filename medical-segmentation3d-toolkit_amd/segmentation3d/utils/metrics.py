@@ -268,3 +268,31 @@ def cal_surface_distances(gt, seg, labels, spacing=None):
             directed.append((int(count), mx, total, percentile_from_order_stats(a, b, ranks[direction])))
         results.append(combine_directed(directed[0], directed[1]))
     return results
+
+
+def _counts_rows(counts):
+    """[C, 3] confusion counts (device / host tensor, numpy array or nested list) -> list of (tp, fp, fn) Python ints"""
+    if isinstance(counts, torch.Tensor):
+        counts = counts.detach().cpu().tolist()
+    elif isinstance(counts, np.ndarray):
+        counts = counts.tolist()
+    rows = [tuple(int(v) for v in row) for row in counts]
+    if not rows or any(len(r) != 3 for r in rows):
+        raise ValueError('confusion counts must be [C, 3] = (tp, fp, fn) per class')
+    return rows
+
+
+def dice_from_counts(counts):
+    """per-class Dice 2 tp / (2 tp + fp + fn) from [C, 3] confusion counts (_ops.confusion_counts) as Python floats, in
+    doubles on the host; a class that neither the labels nor the prediction contain (denominator 0) gives nan"""
+    dice = []
+    for tp, fp, fn in _counts_rows(counts):
+        den = 2 * tp + fp + fn
+        dice.append(float('nan') if den == 0 else (2.0 * tp) / float(den))
+    return dice
+
+
+def mean_foreground_dice(counts):
+    """nan-mean of dice_from_counts over the foreground classes 1 .. C-1; nan when every foreground class is empty"""
+    fg = [d for d in dice_from_counts(counts)[1:] if not math.isnan(d)]
+    return sum(fg) / len(fg) if fg else float('nan')

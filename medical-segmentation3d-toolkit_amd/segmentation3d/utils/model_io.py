@@ -20,6 +20,25 @@ def get_checkpoint_folder(chk_root, epoch):
     return os.path.join(chk_root, 'chk_{}'.format(epoch))
 
 
+BEST_FOLDER = 'best'   # checkpoint of the best validation score (core/seg_validate.py); not `chk_*`: "latest" globs that
+
+
+def select_checkpoint_folder(chk_root, selection='latest'):
+    """folder named by the `checkpoint` key of an inference stage: 'latest' (or None; the largest `chk_<n>`), 'best'
+    (`<chk_root>/best`, written by a run with validation) or an integer epoch; a folder that is not there raises with its path"""
+    if selection is None or selection == 'latest':
+        folder = get_checkpoint_folder(chk_root, -1)
+    elif selection == BEST_FOLDER:
+        folder = os.path.join(chk_root, BEST_FOLDER)
+    elif isinstance(selection, int) and not isinstance(selection, bool) and selection >= 0:
+        folder = get_checkpoint_folder(chk_root, selection)
+    else:
+        raise ValueError("checkpoint must be 'latest', 'best' or an epoch >= 0, got {!r}".format(selection))
+    if not os.path.isdir(folder):
+        raise FileNotFoundError('checkpoint folder not found: {}'.format(folder))
+    return folder
+
+
 def strip_module_prefix(state_dict):
     """DataParallel-trained checkpoints prefix every key with 'module.' (core/seg_infer.py:130-142)"""
     if not any(k.startswith('module.') for k in state_dict):
@@ -94,9 +113,11 @@ def checkpoint_regions(epoch_idx, save_dir):
     return region_keys(_read(os.path.join(_chk_dir(save_dir, epoch_idx), 'params.pth'), 'checkpoint'))
 
 
-def checkpoint_state(net, epoch_idx, batch_idx, cfg, max_stride, num_modality, regions=None, region_class_order=None):
+def checkpoint_state(net, epoch_idx, batch_idx, cfg, max_stride, num_modality, regions=None, region_class_order=None,
+                     validation=None):
     """the `params.pth` dictionary (fields of utils/model_io.py:75-84; tensors moved to the host); `regions` /
-    `region_class_order` of a region-based run are stored next to the channel counts with the head's activation"""
+    `region_class_order` of a region-based run are stored next to the channel counts with the head's activation;
+    `validation` (a Validator's state dict) adds the key of that name, a run without validation keeps the key set"""
     weights = OrderedDict((key, value.detach().cpu()) for key, value in net.state_dict().items())
     geometry = {'spacing': cfg.dataset.spacing, 'interpolation': cfg.dataset.interpolation, 'max_stride': max_stride}
     channels = {'in_channels': num_modality, 'out_channels': cfg.dataset.num_classes,
@@ -108,17 +129,28 @@ def checkpoint_state(net, epoch_idx, batch_idx, cfg, max_stride, num_modality, r
     state['regions'] = None if regions is None else [[int(l) for l in r] for r in regions]
     state['region_class_order'] = None if region_class_order is None else [int(l) for l in region_class_order]
     state['output_activation'] = str(getattr(getattr(net, 'module', net), 'output_activation', 'softmax'))
+    if validation is not None:
+        state['validation'] = dict(validation)
     return state
 
 
-def save_checkpoint(net, opt, epoch_idx, batch_idx, cfg, max_stride, num_modality, regions=None, region_class_order=None):
-    """write params.pth / optimizer.pth (+ a copy of train_config.py) for `epoch_idx`"""
+def save_checkpoint(net, opt, epoch_idx, batch_idx, cfg, max_stride, num_modality, regions=None, region_class_order=None,
+                    validation=None, folder_name=None):
+    """write params.pth / optimizer.pth (+ a copy of train_config.py) for `epoch_idx` into `chk_<epoch_idx>`, or into
+    `checkpoints/<folder_name>` (the best-validation checkpoint); returns the folder"""
     model_folder = os.path.join(cfg.general.save_dir, cfg.general.model_scale)
-    folder = _chk_dir(model_folder, epoch_idx)
+    folder = _chk_dir(model_folder, epoch_idx) if folder_name is None else os.path.join(model_folder, 'checkpoints',
+                                                                                        folder_name)
     os.makedirs(folder, exist_ok=True)
-    torch.save(checkpoint_state(net, epoch_idx, batch_idx, cfg, max_stride, num_modality, regions, region_class_order),
-               os.path.join(folder, 'params.pth'))
+    torch.save(checkpoint_state(net, epoch_idx, batch_idx, cfg, max_stride, num_modality, regions, region_class_order,
+                                validation), os.path.join(folder, 'params.pth'))
     torch.save(opt.state_dict(), os.path.join(folder, 'optimizer.pth'))
     config_copy = os.path.join(model_folder, 'train_config.py')
     if os.path.isfile(config_copy):
         shutil.copy(config_copy, os.path.join(folder, 'train_config.py'))
+    return folder
+
+
+def checkpoint_validation(epoch_idx, save_dir):
+    """the Validator state dict stored in `chk_<epoch_idx>/params.pth`, None for a run without validation"""
+    return _read(os.path.join(_chk_dir(save_dir, epoch_idx), 'params.pth'), 'checkpoint').get('validation')
