@@ -638,6 +638,30 @@ typedef struct Seg3dIntensityParams {
 long long seg3d_augment_intensity_workspace_doubles(int X, int Y, int Z, int M);
 int seg3d_augment_intensity(float* crop, double* workspace, int X, int Y, int Z, int M, Seg3dIntensityParams params,
                             int grid_blocks, void* stream);
+/* Gaussian blur and low-resolution simulation of a normalised crop [Z][Y][X][M] (M = 1..8, channels-last; M = 1 is the
+ * planar crop), OUT OF PLACE src -> dst, buffers must not overlap (csrc/augment_filter.hip).
+ * One launch for all modalities; no allocation, no host sync, no atomics: two runs are bit-equal and the calls are
+ * capturable.  A voxel's value is a function of the crop and the parameters alone (not of tiling, M or alignment).
+ *   blur    per modality m: radius[m] = R in 0..6 and the 2R + 1 taps w[-R..R] in taps[m][0..R] (taps[m][k] = w[+-k], the
+ *           host computes them in double: exp(-k^2 / (2 s^2)) normalised over -R..R).  Separable x, then y, then z, fp32,
+ *           taps added in the order -R..R, no FMA contraction.  Border: half-sample reflection (d c b a | a b c d | d c b a),
+ *           i' = i mod 2n, i' >= n -> 2n - 1 - i', valid for any n and R.  radius[m] = 0 copies the modality bit for bit.
+ *   lowres  per modality the low-grid sizes 1 <= n' <= n of the three axes.  Down-sampling is nearest, centre-aligned:
+ *           low voxel j takes source voxel s(j) = min(n - 1, ((2 j + 1) n) / (2 n')).  Up-sampling is Keys cubic convolution
+ *           (a = -0.5), separable: t = (2 i + 1) n' - n, k = floor(t / 2n), f = (t - 2 n k) / 2n, output voxel i takes the low
+ *           voxels k-1 .. k+2 clamped to [0, n' - 1] with the weights -0.5 f^3 + f^2 - 0.5 f, 1.5 f^3 - 2.5 f^2 + 1,
+ *           -1.5 f^3 + 2 f^2 + 0.5 f, 0.5 f^3 - 0.5 f^2; x innermost, then y, then z, taps added in the order k-1 .. k+2.
+ *           The low grid is never stored.  An axis with n' = n has weights (0, 1, 0, 0); all three equal: bit-exact copy.
+ * When every modality is off, one copy kernel is launched. */
+typedef struct Seg3dBlurParams {
+  int radius[8];
+  float taps[8][7];
+} Seg3dBlurParams;
+typedef struct Seg3dLowresParams {
+  int nx[8], ny[8], nz[8];
+} Seg3dLowresParams;
+int seg3d_augment_blur(const float* src, float* dst, int X, int Y, int Z, int M, Seg3dBlurParams params, void* stream);
+int seg3d_augment_lowres(const float* src, float* dst, int X, int Y, int Z, int M, Seg3dLowresParams params, void* stream);
 /* box_device[6] initialised to {INT_MAX x3, -1 x3} -> inclusive (xmin, ymin, zmin, xmax, ymax, zmax) of the voxels whose
  * value is in labels_host (nlabels == 0: every voxel > 0); untouched when nothing is selected */
 int seg3d_mask_bounding_box(const signed char* mask, int X, int Y, int Z, const int* labels_host, int nlabels,

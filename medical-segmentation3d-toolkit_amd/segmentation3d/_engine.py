@@ -36,6 +36,17 @@ class IntensityParams(ctypes.Structure):
     """Seg3dIntensityParams: up to 8 per-modality parameter sets + the Philox key, BY VALUE to seg3d_augment_intensity"""
     _fields_ = [('m', Intensity * 8), ('seed_lo', ctypes.c_uint), ('seed_hi', ctypes.c_uint)]
 
+
+
+class BlurParams(ctypes.Structure):
+    """Seg3dBlurParams: per-modality radius (0 = copy) and taps w[|k|], k = 0..radius, BY VALUE to seg3d_augment_blur"""
+    _fields_ = [('radius', _c_int * 8), ('taps', (_c_f * 7) * 8)]
+
+
+class LowresParams(ctypes.Structure):
+    """Seg3dLowresParams: per-modality low-grid sizes (n' = n on all axes = copy), BY VALUE to seg3d_augment_lowres"""
+    _fields_ = [('nx', _c_int * 8), ('ny', _c_int * 8), ('nz', _c_int * 8)]
+
 # name -> (restype, argtypes); keep in sync with include/seg3d_hip.h (tests/test_abi.py checks every symbol)
 _SIGNATURES = {
     'seg3d_last_error': (ctypes.c_char_p, []),
@@ -63,6 +74,8 @@ _SIGNATURES = {
                                  + [_c_int] * 3 + [_c_p, _c_int, _c_p]),
     'seg3d_augment_intensity_workspace_doubles': (_c_ll, [_c_int] * 4),
     'seg3d_augment_intensity': (_c_int, [_c_p, _c_p] + [_c_int] * 4 + [IntensityParams, _c_int, _c_p]),
+    'seg3d_augment_blur': (_c_int, [_c_p, _c_p] + [_c_int] * 4 + [BlurParams, _c_p]),
+    'seg3d_augment_lowres': (_c_int, [_c_p, _c_p] + [_c_int] * 4 + [LowresParams, _c_p]),
     'seg3d_mask_bounding_box': (_c_int, [_c_p, _c_int, _c_int, _c_int, _c_p, _c_int, _c_p, _c_p]),
     'seg3d_ccl_workspace_ints': (_c_ll, [_c_ll]),
     'seg3d_ccl26_select': (_c_int, [_c_p] + [_c_int] * 8 + [_c_p, _c_p, _c_p]),

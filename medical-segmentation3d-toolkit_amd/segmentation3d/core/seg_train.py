@@ -299,7 +299,8 @@ def train(train_config_file, data_iter_factory=None):
             random_translation=cfg.dataset.random_translation, random_scale=cfg.dataset.random_scale,
             interpolation=cfg.dataset.interpolation, crop_normalizers=cfg.dataset.crop_normalizers, device=None,
             random_mirror_axes=getattr(cfg.dataset, 'random_mirror_axes', None) or (),
-            augmentation=getattr(cfg.dataset, 'augmentation', None))
+            augmentation=getattr(cfg.dataset, 'augmentation', None),
+            resolution_augmentation=getattr(cfg.dataset, 'resolution_augmentation', None))
         num_modality = dataset.num_modality()
         configured = getattr(cfg.dataset, 'num_modality', None)
         if configured is not None and int(configured) != num_modality:

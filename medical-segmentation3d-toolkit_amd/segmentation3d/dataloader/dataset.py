@@ -11,6 +11,8 @@ global RNG in exactly the reference's order, so a seeded run draws the same crop
 Optional augmentation beyond the reference (off by default): axis mirrors, rotation and
 elastic deformation inside the resampling launches, intensity transforms in one fused pass over the normalised crop
 (csrc/augment.hip); its random decisions are drawn after the reference's, and none is drawn while it is off.
+A second optional section, `resolution_augmentation` (row f13): Gaussian blur and low-resolution simulation of the
+normalised crop (csrc/augment_filter.hip), drawn after every other decision of the sample and before the intensity pass.
 """
 import os
 
@@ -243,11 +245,74 @@ def validate_augmentation(augmentation):
     return a
 
 
+# blur / low-resolution simulation (not in the reference): keys and defaults of the
+# `resolution_augmentation` section -- everything off.  A section of its own: AUGMENTATION_DEFAULTS stays as it is.
+RESOLUTION_AUGMENTATION_DEFAULTS = {
+    'blur_sigma_vox': [0.0, 0.0],           # sigma in voxels of the crop grid, uniform in [lo, hi], hi <= 2
+    'blur_prob': 0.0,                       # per modality
+    'lowres_zoom': [1.0, 1.0],              # zoom of the low grid, uniform in [lo, hi], 0 < lo <= hi <= 1
+    'lowres_prob': 0.0,                     # per modality
+}
+
+
+def validate_resolution_augmentation(section):
+    """the `resolution_augmentation` section (dict / EasyDict / None) -> a plain dict with every key of
+    RESOLUTION_AUGMENTATION_DEFAULTS plus `enabled` = {'blur', 'lowres'}, or None when the section is absent or switches
+    nothing on.  Raises ValueError for a section that is not a dict, unknown keys, a probability outside [0, 1], a
+    blur_sigma_vox pair that breaks 0 <= lo <= hi <= 2 and a lowres_zoom pair that breaks 0 < lo <= hi <= 1.
+    Blur is on iff blur_prob > 0 and hi > 0 (then lo > 0 is required: a drawn sigma of 0 has no taps); the low-resolution
+    simulation is on iff lowres_prob > 0 and lo < 1."""
+    if section is None:
+        return None
+    if not hasattr(section, 'keys'):
+        raise ValueError('resolution_augmentation must be a dict, got {!r}'.format(type(section)))
+    unknown = sorted(set(section.keys()) - set(RESOLUTION_AUGMENTATION_DEFAULTS))
+    if unknown:
+        raise ValueError('unknown resolution_augmentation option(s) {}; known: {}'.format(
+            unknown, sorted(RESOLUTION_AUGMENTATION_DEFAULTS)))
+    a = {k: section[k] if k in section else v for k, v in RESOLUTION_AUGMENTATION_DEFAULTS.items()}
+    for key in ('blur_prob', 'lowres_prob'):
+        try:
+            pr = float(a[key])
+        except (TypeError, ValueError):
+            raise ValueError('resolution_augmentation.{} must be a number, got {!r}'.format(key, a[key]))
+        if not 0.0 <= pr <= 1.0:
+            raise ValueError('resolution_augmentation.{} = {!r} outside [0, 1]'.format(key, a[key]))
+        a[key] = pr
+    pairs = {}
+    for key in ('blur_sigma_vox', 'lowres_zoom'):
+        try:
+            lo, hi = (float(v) for v in a[key])
+        except (TypeError, ValueError):
+            raise ValueError('resolution_augmentation.{} must be a [lo, hi] pair, got {!r}'.format(key, a[key]))
+        pairs[key] = [lo, hi]
+    lo, hi = pairs['blur_sigma_vox']
+    if not (np.isfinite(lo) and np.isfinite(hi) and 0.0 <= lo <= hi <= image_tools.BLUR_MAX_SIGMA):
+        raise ValueError('resolution_augmentation.blur_sigma_vox = {!r}: need 0 <= lo <= hi <= {:g}'.format(
+            a['blur_sigma_vox'], image_tools.BLUR_MAX_SIGMA))
+    lo, hi = pairs['lowres_zoom']
+    if not (np.isfinite(lo) and np.isfinite(hi) and 0.0 < lo <= hi <= 1.0):
+        raise ValueError('resolution_augmentation.lowres_zoom = {!r}: need 0 < lo <= hi <= 1'.format(a['lowres_zoom']))
+    a.update(pairs)
+    on = {
+        'blur': a['blur_prob'] > 0.0 and a['blur_sigma_vox'][1] > 0.0,
+        'lowres': a['lowres_prob'] > 0.0 and a['lowres_zoom'][0] < 1.0,
+    }
+    if on['blur'] and not a['blur_sigma_vox'][0] > 0.0:
+        raise ValueError('resolution_augmentation.blur_sigma_vox = {!r}: an enabled blur needs lo > 0'.format(
+            a['blur_sigma_vox']))
+    if not any(on.values()):
+        return None
+    a['enabled'] = on
+    return a
+
+
 class SegmentationDataset(Dataset):
     """training data set for volumetric segmentation (constructor as dataloader/dataset.py:58-100)"""
 
     def __init__(self, imlist_file, num_classes, spacing, crop_size, sampling_method, random_translation, random_scale,
-                 interpolation, crop_normalizers, device=None, random_mirror_axes=(), augmentation=None):
+                 interpolation, crop_normalizers, device=None, random_mirror_axes=(), augmentation=None,
+                 resolution_augmentation=None):
         if imlist_file.endswith('txt'):
             self.im_list, self.seg_list = read_train_txt(imlist_file)
         elif imlist_file.endswith('csv'):
@@ -291,6 +356,9 @@ class SegmentationDataset(Dataset):
                 raise ValueError('augmentation.elastic_grid_mm = {:g}: a control grid of {} points does not fit the 64 KB '
                                  'of on-chip memory the resampling kernel keeps it in'.format(
                                      self.augmentation['elastic_grid_mm'], dims))
+        # blur / low-resolution simulation (not in the reference): None when the section is absent or off -- no draw, no
+        # launch, the same tensors
+        self.resolution_augmentation = validate_resolution_augmentation(resolution_augmentation)
         # modalities per case from the list and the file headers (no volume is read here): every case must have the same M,
         # and there is one normaliser per modality (None: no normalisation, dataset.py:202)
         self._num_modality = 1
@@ -433,6 +501,46 @@ class SegmentationDataset(Dataset):
         seed = int(np.random.randint(0, 2 ** 63, dtype=np.int64)) if on['noise'] else 0
         return {'rotation': rotation, 'control': control, 'intensity': intensity if any_intensity else None, 'seed': seed}
 
+    def sample_resolution_augmentation(self):
+        """the random decisions of the blur / low-resolution simulation of the next sample, drawn after
+        sample_augmentation -- after every other draw of the sample -- with numpy's global RNG in this fixed order; a
+        transform that is off (validate_resolution_augmentation) draws NOTHING, so with the section absent or off the
+        stream is what it was.  Per modality m = 0 .. M-1, each drawing independently:
+          1. blur:    gate uniform() < blur_prob; if open, sigma = uniform(lo, hi) voxels
+          2. lowres:  gate uniform() < lowres_prob; if open, zoom = uniform(lo, hi)
+        -> dict(blur = list of M sigmas (0.0 = off for that modality) or None when no gate opened, lowres = list of M
+        low-grid sizes (nx', ny', nz') (None = off for that modality) or None when no modality has a size below the
+        crop's), or None without the section"""
+        a = self.resolution_augmentation
+        if a is None:
+            return None
+        on = a['enabled']
+        size = tuple(int(v) for v in self.crop_size)
+        sigmas, sizes = [], []
+        for m in range(self._num_modality):
+            sigma, low = 0.0, None
+            if on['blur'] and np.random.uniform() < a['blur_prob']:
+                sigma = float(np.random.uniform(a['blur_sigma_vox'][0], a['blur_sigma_vox'][1]))
+            if on['lowres'] and np.random.uniform() < a['lowres_prob']:
+                low = image_tools.lowres_sizes(size, float(np.random.uniform(a['lowres_zoom'][0], a['lowres_zoom'][1])))
+                if low == size:
+                    low = None
+            sigmas.append(sigma)
+            sizes.append(low)
+        return {'blur': sigmas if any(s > 0.0 for s in sigmas) else None,
+                'lowres': sizes if any(s is not None for s in sizes) else None}
+
+    def _resolution_filters(self, res):
+        """the out-of-place filters of one sample in their order -> list of callables (src, dst) -> dst"""
+        filters = []
+        if res is not None and res['blur'] is not None:
+            filters.append(lambda src, dst, p=res['blur']: image_tools.blur_device(src, p, out=dst))
+        if res is not None and res['lowres'] is not None:
+            size = tuple(int(v) for v in self.crop_size)
+            prm = image_tools.lowres_params(res['lowres'], self._num_modality, size)
+            filters.append(lambda src, dst, p=prm: image_tools.lowres_device(src, p, out=dst))
+        return filters
+
     # ---- the sample ---------------------------------------------------------------------------------------------------
     def __getitem__(self, index):
         """-> (image crop [M, z, y, x], mask crop [1, z, y, x] float labels, frame (15 floats), case name); device tensors.
@@ -441,6 +549,9 @@ class SegmentationDataset(Dataset):
         With `augmentation` image and mask are rotated and elastically deformed together inside the same launches (one
         rotation and one control tensor for both, each with its own source frame) and the normalised image crop gets the
         intensity transforms in place; the frame stays the NOMINAL crop frame (un-rotated, un-deformed).
+        With `resolution_augmentation` the normalised image crop is blurred and / or passed through the low-resolution
+        simulation (out of place, one launch each for all modalities) before the intensity transforms; mask and frame
+        are untouched.
         For M > 1 the image crop is a view of channels-last [z, y, x, M] memory (what the stem reads, without a copy)."""
         return self.sample(index)
 
@@ -452,6 +563,7 @@ class SegmentationDataset(Dataset):
         center, crop_spacing = self.sample_crop_geometry(index)
         mirror = self.sample_mirror()
         aug = self.sample_augmentation(crop_spacing)
+        filters = self._resolution_filters(self.sample_resolution_augmentation())
         spatial = {}
         if aug is not None:
             # one small host-to-device copy on the current stream; nothing is read back
@@ -463,13 +575,28 @@ class SegmentationDataset(Dataset):
                                                self.interpolation, mirror=mirror, **spatial)
             if self.crop_normalizers[0] is not None:
                 im = image_tools.normalize_crop_device(im, self.crop_normalizers[0])
+            for f in filters:                      # blur, then low resolution: each into a fresh tensor
+                im = f(im.contiguous(), None)
             if aug is not None and aug['intensity'] is not None:
                 im = image_tools.augment_intensity_device(im.contiguous(), aug['intensity'], aug['seed'])
             im = im.unsqueeze(0)
         else:
+            # the k filters of this sample run out of place and the last one must write the destination, so the
+            # resampling launch writes the destination for even k and a scratch buffer for odd k: no copy pass
+            if filters:
+                cz, cy, cx = (int(v) for v in self.crop_size[::-1])
+                shape = (cz, cy, cx, self._num_modality)
+                if out is None:
+                    out = torch.empty(shape, dtype=torch.float32, device=self.device)
+                scratch = torch.empty(shape, dtype=torch.float32, device=self.device)
+                first, other = (out, scratch) if len(filters) % 2 == 0 else (scratch, out)
+            else:
+                first = out
             im = image_tools.crop_image_device_mc(case.image, case.frame, center, self.crop_size, crop_spacing,
-                                                  self.interpolation, out=out, mirror=mirror, **spatial)
+                                                  self.interpolation, out=first, mirror=mirror, **spatial)
             im = image_tools.normalize_crop_device_mc(im, self._norm_params, out=im)
+            for f in filters:
+                im, other = f(im, other), im
             if aug is not None and aug['intensity'] is not None:
                 image_tools.augment_intensity_device(im, aug['intensity'], aug['seed'])
             im = im.permute(3, 0, 1, 2)

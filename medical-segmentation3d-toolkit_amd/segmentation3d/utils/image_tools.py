@@ -526,6 +526,118 @@ def augment_intensity_device(crop, params, seed=0, grid_blocks=0):
     return crop
 
 
+BLUR_MAX_SIGMA = 2.0     # radius ceil(3 sigma) <= 6: the halo the blur kernel stages in LDS
+
+
+def gaussian_taps(sigma):
+    """(R, taps) of the Gaussian blur: R = ceil(3 sigma) and the 2R + 1 taps w[-R..R] as float64,
+    w[k] = exp(-k^2 / (2 sigma^2)) / sum_j exp(-j^2 / (2 sigma^2)); 0 < sigma <= 2 voxels"""
+    sigma = float(sigma)
+    if not (np.isfinite(sigma) and 0.0 < sigma <= BLUR_MAX_SIGMA):
+        raise ValueError('blur sigma must be in (0, {}] voxels, got {}'.format(BLUR_MAX_SIGMA, sigma))
+    R = int(np.ceil(3.0 * sigma))
+    k = np.arange(-R, R + 1, dtype=np.float64)
+    w = np.exp(-(k * k) / (2.0 * sigma * sigma))
+    return R, w / w.sum()
+
+
+def lowres_sizes(size, zoom):
+    """low-grid sizes of the low-resolution simulation: n' = max(1, floor(n zoom + 0.5)) per axis of `size`, zoom in
+    (0, 1]; zoom 1 is the identity"""
+    zoom = float(zoom)
+    if not (np.isfinite(zoom) and 0.0 < zoom <= 1.0):
+        raise ValueError('low-resolution zoom must be in (0, 1], got {}'.format(zoom))
+    return tuple(max(1, int(np.floor(int(n) * zoom + 0.5))) for n in size)
+
+
+def blur_params(sigmas, num_modality):
+    """per-modality sigma in voxels (0 or None = off) -> the Seg3dBlurParams struct passed by value to seg3d_augment_blur:
+    radius and the taps w[|k|], k = 0..R, computed in double and rounded to float32"""
+    if len(sigmas) != num_modality:
+        raise ValueError('{} blur sigmas for {} modalities'.format(len(sigmas), num_modality))
+    if not 1 <= num_modality <= 8:
+        raise ValueError('{} modalities, 1..8 are supported'.format(num_modality))
+    out = E.BlurParams()
+    for m in range(num_modality):
+        s = 0.0 if sigmas[m] is None else float(sigmas[m])
+        if s == 0.0:
+            continue
+        R, w = gaussian_taps(s)
+        out.radius[m] = R
+        for k in range(R + 1):
+            out.taps[m][k] = float(w[R + k])
+    return out
+
+
+def lowres_params(sizes, num_modality, crop_size=None):
+    """per-modality low-grid sizes (nx', ny', nz') -> the Seg3dLowresParams struct passed by value to
+    seg3d_augment_lowres; with crop_size = (nx, ny, nz), None stands for "off" and 1 <= n' <= n is checked"""
+    if len(sizes) != num_modality:
+        raise ValueError('{} low-grid sizes for {} modalities'.format(len(sizes), num_modality))
+    if not 1 <= num_modality <= 8:
+        raise ValueError('{} modalities, 1..8 are supported'.format(num_modality))
+    out = E.LowresParams()
+    for m in range(num_modality):
+        sz = sizes[m]
+        if sz is None:
+            if crop_size is None:
+                raise ValueError('low-grid size None (off) needs the crop size')
+            sz = crop_size
+        if len(sz) != 3 or any(int(v) != v or int(v) < 1 for v in sz):
+            raise ValueError('low-grid size must be three positive integers, got {!r}'.format(sizes[m]))
+        if crop_size is not None and any(int(v) > int(n) for v, n in zip(sz, crop_size)):
+            raise ValueError('low-grid size {!r} exceeds the crop {!r}'.format(tuple(sz), tuple(crop_size)))
+        out.nx[m], out.ny[m], out.nz[m] = (int(v) for v in sz)
+    return out
+
+
+def _filter_buffers(crop, out):
+    E.require_device(crop, out)
+    if crop.dtype != torch.float32 or crop.dim() not in (3, 4) or not crop.is_contiguous():
+        raise ValueError('crop must be a contiguous float32 [z, y, x] or [z, y, x, M] tensor')
+    M = 1 if crop.dim() == 3 else int(crop.shape[3])
+    if not 1 <= M <= 8:
+        raise ValueError('{} modalities, 1..8 are supported'.format(M))
+    if out is None:
+        out = torch.empty_like(crop)
+    else:
+        if out.shape != crop.shape or out.dtype != torch.float32 or not out.is_contiguous():
+            raise ValueError('out must be a contiguous float32 tensor of the crop\'s shape')
+        nbytes = crop.numel() * 4
+        if out.data_ptr() < crop.data_ptr() + nbytes and crop.data_ptr() < out.data_ptr() + nbytes:
+            raise ValueError('out overlaps crop: the filters run out of place')
+    return M, out
+
+
+def blur_device(crop, sigmas, out=None):
+    """Gaussian blur of a normalised float32 device crop, OUT OF PLACE (csrc/augment_filter.hip, seg3d_augment_blur):
+    crop [z, y, x] (one modality) or channels-last [z, y, x, M], contiguous; sigmas: one sigma in voxels per modality
+    (0 or None = that modality is copied), or a ready E.BlurParams.  Separable, half-sample reflection at the border,
+    radius ceil(3 sigma) <= 6.  Returns `out` (allocated when None; it must not overlap `crop`)."""
+    M, out = _filter_buffers(crop, out)
+    Z, Y, X = (int(v) for v in crop.shape[:3])
+    prm = sigmas if isinstance(sigmas, E.BlurParams) else blur_params(sigmas, M)
+    E.call('seg3d_augment_blur', E.ptr(crop), E.ptr(out), X, Y, Z, M, prm, E.stream_ptr())
+    return out
+
+
+def lowres_device(crop, zooms, out=None):
+    """low-resolution simulation of a normalised float32 device crop, OUT OF PLACE (seg3d_augment_lowres): nearest
+    down-sampling to the low grid of lowres_sizes(crop size, zoom), Keys cubic (a = -0.5) up-sampling back; the low grid
+    is never stored.  zooms: one zoom in (0, 1] per modality (1 or None = that modality is copied), or a ready
+    E.LowresParams.  Returns `out` (allocated when None; it must not overlap `crop`)."""
+    M, out = _filter_buffers(crop, out)
+    Z, Y, X = (int(v) for v in crop.shape[:3])
+    if isinstance(zooms, E.LowresParams):
+        prm = zooms
+    else:
+        if len(zooms) != M:
+            raise ValueError('{} low-resolution zooms for {} modalities'.format(len(zooms), M))
+        prm = lowres_params([None if z is None else lowres_sizes((X, Y, Z), z) for z in zooms], M, (X, Y, Z))
+    E.call('seg3d_augment_lowres', E.ptr(crop), E.ptr(out), X, Y, Z, M, prm, E.stream_ptr())
+    return out
+
+
 def get_image_frame(image):
     """spacing, origin, direction packed into 15 float32 (image_tools.py:26-41)"""
     return np.array(list(image.GetSpacing()) + list(image.GetOrigin()) + list(image.GetDirection()), dtype=np.float32)
