@@ -478,6 +478,10 @@ int seg3d_adam_step_ctl(float* params, const float* grads, float* exp_avg, float
 /* ---- sliding-window batcher (core/seg_infer.py:208-246, 313-327, 336-339; utils/image_tools.py:435-469;
  *      utils/normalizer.py:6-81) ---------------------------------------------------------------------------------- */
 long long seg3d_patch_stats_blocks(int bx, int by, int bz);
+/* the M = 1 case of seg3d_patch_gather_normalize_mc below: volume [Z][Y][X] -> batch [P][1][bz][by][bx], the same memory as
+ * [Z][Y][X][1] -> [P][bz][by][bx][1].  normalizer_type 0 = fixed (mean, stddev, clip to [-1, 1] when clip != 0),
+ * 1 = adaptive (clip to +-clip_sigma, clip_sigma > 0), -1 = none.  workspace: P * seg3d_patch_stats_blocks * 2 doubles,
+ * mean_std: P * 2 floats (adaptive only) -- the M = 1 sizes of the _mc entry. */
 int seg3d_patch_gather_normalize(const float* volume, const int* starts_xyz, float* batch, double* workspace,
                                  float* mean_std, int Z, int Y, int X, int bx, int by, int bz, int P, int normalizer_type,
                                  float mean, float stddev, int clip, float clip_sigma, void* stream);
@@ -486,7 +490,7 @@ int seg3d_patch_gather_normalize(const float* volume, const int* starts_xyz, flo
  * crop_normalizers[0]-only ROI normalisation of core/seg_infer.py:221-224.  One normaliser per modality, passed by
  * value: type 0 = fixed ((x - mean) / stddev, clipped to [clip_lo, clip_hi] when clip != 0), 1 = adaptive (the patch's
  * own fp64 mean / population std floored at 1e-6, clipped to [clip_lo, clip_hi]), -1 = none.  Channel m is
- * bit-identical to seg3d_patch_gather_normalize on plane m with normaliser m.  Same starts / control-block contract;
+ * bit-identical to the M = 1 gather of plane m with normaliser m.  starts / control-block contract of the scatter below;
  * no host sync, no allocation (capturable).  workspace: seg3d_patch_stats_mc_doubles doubles; mean_std: P * M * 2
  * floats (adaptive only). */
 typedef struct Seg3dNormalizer {
@@ -502,6 +506,8 @@ long long seg3d_patch_stats_mc_doubles(int bx, int by, int bz, int P, int M);
 int seg3d_patch_gather_normalize_mc(const float* volume, const int* starts_xyz, float* batch, double* workspace,
                                     float* mean_std, int Z, int Y, int X, int bx, int by, int bz, int P, int M,
                                     Seg3dNormalizers norms, void* stream);
+/* the wtab = NULL, flip_mask = 0 case of seg3d_patch_scatter_blend below: probs [P][C][bz][by][bx] of the ctl[6] valid
+ * patches are added to acc [C][Z][Y][X] in list order and count [Z][Y][X] grows by 1.0f per covering patch */
 int seg3d_patch_scatter_accumulate(const float* probs, const int* starts_xyz, const int* ctl /* device int32[7] */,
                                    float* acc, float* count, int Z, int Y, int X, int bx, int by, int bz, int C,
                                    long long max_box_voxels, void* stream);
@@ -518,13 +524,15 @@ int seg3d_finalize_regions(float* acc, const float* count, signed char* mask, in
  * The _flip gathers are the gathers above with every patch mirrored: batch element (lz, ly, lx) of patch p is the
  * normalised volume voxel at start_p + (fx ? bx-1-lx : lx, fy ? by-1-ly : ly, fz ? bz-1-lz : lz).  The adaptive
  * normaliser's mean / std are those of the un-mirrored patch bit for bit, so the result equals the flipped plain gather
- * exactly.  The mirrored multi-modality gather cannot run in place.
- * seg3d_patch_scatter_blend: seg3d_patch_scatter_accumulate with a weight per local voxel and mirrored inputs.
+ * exactly.  A mirrored gather cannot run in place.  seg3d_patch_gather_normalize_flip is the M = 1 case of
+ * seg3d_patch_gather_normalize_mc_flip, and flip_mask = 0 is the plain gather.
+ * seg3d_patch_scatter_blend: the accumulation with a weight per local voxel and mirrored inputs.
  * wtab: device, bx + by + bz floats = the x, y and z tables one after the other (NULL = weight 1); the weight of local
  * voxel (lx, ly, lz) is the float32 w = (g_z[lz] * g_y[ly]) * g_x[lx]; acc[c][v] = acc[c][v] + (w * prob) and
  * count[v] = count[v] + w with a rounded multiply and a rounded add (no FMA), patches in list order, no atomics.  The
  * probabilities of patch p are stored mirrored by flip_mask (the output of a net that was fed the _flip gather) and are
- * accumulated un-mirrored.  wtab = NULL and flip_mask = 0 gives seg3d_patch_scatter_accumulate bit for bit.
+ * accumulated un-mirrored.  wtab = NULL and flip_mask = 0 is seg3d_patch_scatter_accumulate (w = 1: the product is the
+ * probability itself).
  * All three: no allocation, no host sync, control block on the device (capturable). */
 int seg3d_patch_gather_normalize_flip(const float* volume, const int* starts_xyz, float* batch, double* workspace,
                                       float* mean_std, int Z, int Y, int X, int bx, int by, int bz, int P,
@@ -582,14 +590,15 @@ int seg3d_surface_distance(const unsigned char* feature_surface, const unsigned 
 /* ---- pre/post-processing around the patch path: utils/image_tools.py:329-432, 481-510 ----------
  * resample: dst[z][y][x] (Xo, Yo, Zo) = src sampled at the continuous index c = M * (x, y, z, 1), M = 12 doubles on the
  * HOST (row-major 3 x 4); ITK semantics: inside iff -0.5 <= c < size - 0.5, else `pad`; linear (clamped 8-neighbourhood)
- * or nearest neighbour (round half up). */
+ * or nearest neighbour (round half up).  seg3d_resample_affine is the M = 1, dst_stride = 1 case of
+ * seg3d_resample_affine_mc. */
 int seg3d_resample_affine(const float* src, float* dst, int Xi, int Yi, int Zi, int Xo, int Yo, int Zo,
                           const double* affine_host, int linear, float pad, void* stream);
 /* the same resampling for M co-registered channels sharing one geometry (dataset.py:199-203 crops every modality at
  * one centre and spacing; core/seg_infer.py:221-224 + image_tools.py:348-377 resample the case to the model spacing):
  * src [Zi][Yi][Xi][M], output voxel (x, y, z) written as M floats at dst + ((z * Yo + y) * Xo + x) * dst_stride
- * (dst_stride >= M; a crop goes straight into slot b of an NDHWC batch).  Channel m is bit-identical to
- * seg3d_resample_affine on plane m.  1 <= M <= 8. */
+ * (dst_stride >= M; a crop goes straight into slot b of an NDHWC batch).  Channel m is bit-identical to the M = 1
+ * resampling of plane m.  1 <= M <= 8. */
 int seg3d_resample_affine_mc(const float* src, float* dst, int M, long long dst_stride, int Xi, int Yi, int Zi, int Xo,
                              int Yo, int Zo, const double* affine_host, int linear, float pad, void* stream);
 /* ---- training augmentation (not in the reference) -----------------------------------------
@@ -604,7 +613,8 @@ int seg3d_resample_affine_mc(const float* src, float* dst, int M, long long dst_
  * mirror_mask (bit 0 = x, 1 = y, 2 = z) reversed, n - 1 - i: pass the mirrored affine map (image_tools.mirror_index_affine)
  * and the mask, and the result is the flip of the un-mirrored deformed crop.  A rotation is part of M.  The field is
  * evaluated in double; inside test, interpolation and padding are those of the affine entries, a zero control grid gives
- * their result bit for bit, and channel m of the _mc entry equals the planar entry on plane m bit for bit.  Per-axis
+ * their result bit for bit, and channel m of the _mc entry equals its M = 1 case -- seg3d_resample_deform -- on plane m
+ * bit for bit.  Per-axis
  * weights and the control grid are staged in LDS (at most 64 KB: crop-sized grids). */
 int seg3d_resample_deform(const float* src, float* dst, int Xi, int Yi, int Zi, int Xo, int Yo, int Zo,
                           const double* affine_host, int linear, float pad, const double* l_host, const float* ctrl,

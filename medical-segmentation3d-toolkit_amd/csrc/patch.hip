@@ -15,41 +15,17 @@
 
 #define PATCH_STAT_CHUNK 8192
 
-// partial[p][blk][2] = (sum, sum of squares) in fp64 over a chunk of patch p's voxels
-__global__ __launch_bounds__(256) void patch_stats_partial_kernel(const float* __restrict__ vol,
-                                                                    const int* __restrict__ starts,
-                                                                    double* __restrict__ partial, int Y, int X, int bx,
-                                                                    int by, int bz, int nblk) {
-  __shared__ double red[8];
-  const int p = blockIdx.y;
-  const int sx = starts[3 * p], sy = starts[3 * p + 1], sz = starts[3 * p + 2];
-  const i64 nv = (i64)bx * by * bz;
-  const i64 e0 = (i64)blockIdx.x * PATCH_STAT_CHUNK;
-  i64 e1 = e0 + PATCH_STAT_CHUNK;
-  if (e1 > nv) e1 = nv;
-  double s = 0.0, ss = 0.0;
-  for (i64 e = e0 + threadIdx.x; e < e1; e += 256) {
-    const int lx = (int)(e % bx);
-    const i64 t = e / bx;
-    const int ly = (int)(t % by), lz = (int)(t / by);
-    const double v = (double)vol[((i64)(sz + lz) * Y + (sy + ly)) * X + (sx + lx)];
-    s += v;
-    ss += v * v;
-  }
-  s = wave_sum_d(s);
-  ss = wave_sum_d(ss);
-  if ((threadIdx.x & 63) == 0) {
-    red[threadIdx.x >> 6] = s;
-    red[4 + (threadIdx.x >> 6)] = ss;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    partial[((i64)p * nblk + blockIdx.x) * 2 + 0] = red[0] + red[1] + red[2] + red[3];
-    partial[((i64)p * nblk + blockIdx.x) * 2 + 1] = red[4] + red[5] + red[6] + red[7];
-  }
-}
+// SEG3D_LAUNCH_CHECK for a launch chain entered under several names: "<entry><stage>: kernel launch failed: ..."
+#define PATCH_LAUNCH_CHECK(name, stage)                                                           \
+  do {                                                                                            \
+    hipError_t e__ = hipGetLastError();                                                           \
+    if (e__ != hipSuccess) {                                                                      \
+      seg3d_set_error("%s%s: kernel launch failed: %s", name, stage, hipGetErrorString(e__));     \
+      return SEG3D_ERR_LAUNCH;                                                                    \
+    }                                                                                             \
+  } while (0)
 
-// mean_std[p] = (mean, max(population std, 1e-6)) as float32
+// mean_std[row] = (mean, max(population std, 1e-6)) as float32, one row of nblk partials per (patch, modality)
 __global__ __launch_bounds__(64) void patch_stats_finalize_kernel(const double* __restrict__ partial,
                                                                     float* __restrict__ mean_std, int nblk, double nv) {
   const int p = blockIdx.x;
@@ -71,123 +47,18 @@ __global__ __launch_bounds__(64) void patch_stats_finalize_kernel(const double* 
   }
 }
 
-// batch[p][0][lz][ly][lx] = clip((vol[...] - mean_p) / std_p).  FLIP: the volume voxel is read at the local position
-// mirrored along the axes of `flip` (bit 0 = x, 1 = y, 2 = z); the stores stay in batch order, the loads of a wave run
-// backwards through one contiguous row when x is mirrored.
-template <bool FLIP>
-__global__ __launch_bounds__(256) void patch_gather_normalize_kernel(const float* __restrict__ vol,
-                                                                       const int* __restrict__ starts,
-                                                                       const float* __restrict__ mean_std,
-                                                                       float* __restrict__ batch, int Y, int X, int bx,
-                                                                       int by, int bz, int P, float fixed_mean,
-                                                                       float fixed_std, int clip, float clip_lo,
-                                                                       float clip_hi, int flip) {
-  const i64 nv = (i64)bx * by * bz;
-  const i64 total = nv * P;
-  for (i64 idx = (i64)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (i64)gridDim.x * 256) {
-    const int p = (int)(idx / nv);
-    const i64 e = idx - (i64)p * nv;
-    int lx = (int)(e % bx);
-    const i64 t = e / bx;
-    int ly = (int)(t % by), lz = (int)(t / by);
-    if constexpr (FLIP) {
-      if (flip & 1) lx = bx - 1 - lx;
-      if (flip & 2) ly = by - 1 - ly;
-      if (flip & 4) lz = bz - 1 - lz;
-    }
-    const int sx = starts[3 * p], sy = starts[3 * p + 1], sz = starts[3 * p + 2];
-    const float mean = mean_std ? mean_std[2 * p] : fixed_mean;
-    const float sd = mean_std ? mean_std[2 * p + 1] : fixed_std;
-    float v = (vol[((i64)(sz + lz) * Y + (sy + ly)) * X + (sx + lx)] - mean) / sd;
-    if (clip) {
-      if (v < clip_lo) v = clip_lo;
-      if (v > clip_hi) v = clip_hi;
-    }
-    batch[idx] = v;
-  }
-}
-
 extern "C" long long seg3d_patch_stats_blocks(int bx, int by, int bz) {
   return ((long long)bx * by * bz + PATCH_STAT_CHUNK - 1) / PATCH_STAT_CHUNK;
 }
 
-// normalizer_type: 0 = fixed (mean, stddev, clip to [-1,1] when clip != 0), 1 = adaptive (clip to +-clip_sigma),
-// -1 = none.  starts: device int32 [P][3] as (x, y, z).  workspace: P * seg3d_patch_stats_blocks * 2 doubles and
-// mean_std: P * 2 floats (adaptive only).
-// flip: mirror mask of the gathered patches (bit 0 = x, 1 = y, 2 = z; 0 = the plain gather).  The statistics of the
-// adaptive normaliser are taken over the same voxels in the same order whatever the mask, so mean / std are those of the
-// un-mirrored patch bit for bit and a mirrored gather equals the flipped plain gather exactly.
-static int patch_gather_normalize_impl(const float* volume, const int* starts, float* batch, double* workspace,
-                                       float* mean_std, int Z, int Y, int X, int bx, int by, int bz, int P,
-                                       int normalizer_type, float mean, float stddev, int clip, float clip_sigma, int flip,
-                                       void* stream) {
-  SEG3D_REQUIRE(volume && starts && batch && P > 0, "seg3d_patch_gather_normalize: bad arguments");
-  SEG3D_REQUIRE(bx > 0 && by > 0 && bz > 0 && bx <= X && by <= Y && bz <= Z,
-                "seg3d_patch_gather_normalize: box (%d,%d,%d) does not fit volume (%d,%d,%d)", bx, by, bz, X, Y, Z);
-  hipStream_t s = (hipStream_t)stream;
-  const float* ms = nullptr;
-  float fm = 0.f, fs = 1.f, lo = -1.f, hi = 1.f;
-  int do_clip = 0;
-  if (normalizer_type == 1) {
-    SEG3D_REQUIRE(workspace && mean_std, "seg3d_patch_gather_normalize: adaptive normaliser needs workspace");
-    SEG3D_REQUIRE(clip_sigma > 0.f, "seg3d_patch_gather_normalize: clip_sigma must be positive");
-    const int nblk = (int)seg3d_patch_stats_blocks(bx, by, bz);
-    hipLaunchKernelGGL(patch_stats_partial_kernel, dim3(nblk, P), dim3(256), 0, s, volume, starts, workspace, Y, X, bx, by,
-                       bz, nblk);
-    SEG3D_LAUNCH_CHECK("seg3d_patch_gather_normalize(stats)");
-    hipLaunchKernelGGL(patch_stats_finalize_kernel, dim3(P), dim3(64), 0, s, workspace, mean_std, nblk,
-                       (double)bx * by * bz);
-    SEG3D_LAUNCH_CHECK("seg3d_patch_gather_normalize(finalize)");
-    ms = mean_std;
-    do_clip = 1;
-    lo = -clip_sigma;
-    hi = clip_sigma;
-  } else if (normalizer_type == 0) {
-    SEG3D_REQUIRE(stddev > 0.f, "seg3d_patch_gather_normalize: stddev must be positive");
-    fm = mean;
-    fs = stddev;
-    do_clip = clip;
-  } else if (normalizer_type != -1) {
-    SEG3D_UNSUPPORTED("seg3d_patch_gather_normalize: unsupported normalization type %d", normalizer_type);
-  }
-  const i64 total = (i64)bx * by * bz * P;
-  if (flip)
-    hipLaunchKernelGGL(patch_gather_normalize_kernel<true>, dim3(seg3d_ew_grid(total, 256)), dim3(256), 0, s, volume, starts,
-                       ms, batch, Y, X, bx, by, bz, P, fm, fs, do_clip, lo, hi, flip);
-  else
-    hipLaunchKernelGGL(patch_gather_normalize_kernel<false>, dim3(seg3d_ew_grid(total, 256)), dim3(256), 0, s, volume,
-                       starts, ms, batch, Y, X, bx, by, bz, P, fm, fs, do_clip, lo, hi, 0);
-  SEG3D_LAUNCH_CHECK("seg3d_patch_gather_normalize");
-  return SEG3D_OK;
-}
-
-extern "C" int seg3d_patch_gather_normalize(const float* volume, const int* starts, float* batch, double* workspace,
-                                            float* mean_std, int Z, int Y, int X, int bx, int by, int bz, int P,
-                                            int normalizer_type, float mean, float stddev, int clip, float clip_sigma,
-                                            void* stream) {
-  return patch_gather_normalize_impl(volume, starts, batch, workspace, mean_std, Z, Y, X, bx, by, bz, P, normalizer_type,
-                                     mean, stddev, clip, clip_sigma, 0, stream);
-}
-
-// the same gather with every patch mirrored by flip_mask (0..7): batch[p][0][lz][ly][lx] is the normalised voxel at
-// start_p + (fx ? bx-1-lx : lx, fy ? by-1-ly : ly, fz ? bz-1-lz : lz), i.e. torch.flip of the plain gather
-extern "C" int seg3d_patch_gather_normalize_flip(const float* volume, const int* starts, float* batch, double* workspace,
-                                                 float* mean_std, int Z, int Y, int X, int bx, int by, int bz, int P,
-                                                 int normalizer_type, float mean, float stddev, int clip, float clip_sigma,
-                                                 int flip_mask, void* stream) {
-  SEG3D_REQUIRE(flip_mask >= 0 && flip_mask <= 7, "seg3d_patch_gather_normalize_flip: flip mask %d outside 0..7", flip_mask);
-  return patch_gather_normalize_impl(volume, starts, batch, workspace, mean_std, Z, Y, X, bx, by, bz, P, normalizer_type,
-                                     mean, stddev, clip, clip_sigma, flip_mask, stream);
-}
-
-// ---- M co-registered modalities in one launch chain (dataset.py:199-203 crops and normalises a list of images with
-// crop_normalizers[idx]; core/seg_infer.py:221-224 applies crop_normalizers[0] to the single one).  The volume is
+// ---- gather: M co-registered modalities in one launch chain (dataset.py:199-203 crops and normalises a list of images
+// with crop_normalizers[idx]; core/seg_infer.py:221-224 applies crop_normalizers[0] to the single one).  The volume is
 // channels-last [Z][Y][X][M]; the batch is [P][bz][by][bx][M] (NDHWC).  ONE stats pass reads each patch once for all
-// modalities; per (patch, modality) the chunking, the fp64 summation order and the finalisation are those of
-// patch_stats_partial_kernel / patch_stats_finalize_kernel (the latter is reused as is over P * M rows), and every
-// voxel is normalised with patch_gather_normalize_kernel's float expression, so channel m is bit-identical to
-// seg3d_patch_gather_normalize on plane m with normaliser m.
-// MC = 2, 3, 4: compile-time width (VEC: 8- / 16-byte rows); MC = 0: runtime M <= 8.
+// modalities; the chunking, the fp64 summation order, the finalisation and the float expression of the normalisation are
+// per (patch, modality) and do not depend on M, so channel m of an M-modality gather is bit-identical to the M = 1 gather
+// of plane m with normaliser m.  A single-modality volume [Z][Y][X] is the M = 1 case of the same memory, and so is its
+// batch [P][1][bz][by][bx]: seg3d_patch_gather_normalize(_flip) are the M = 1 entries.
+// MC = 1, 2, 3, 4: compile-time width (VEC: 8- / 16-byte rows); MC = 0: runtime M <= 8.
 
 // partial[(p * M + m)][blk][2] = (sum, sum of squares) in fp64 of modality m over a chunk of patch p's voxels
 template <int MC, bool VEC>
@@ -309,17 +180,18 @@ extern "C" long long seg3d_patch_stats_mc_doubles(int bx, int by, int bz, int P,
 }
 
 template <int MC, bool VEC>
-static int patch_gather_normalize_mc_launch(const float* volume, const int* starts, float* batch, double* workspace,
-                                            float* mean_std, int M, int Y, int X, int bx, int by, int bz, int P,
-                                            const Seg3dNormalizers& nrm, bool any_adaptive, int flip, hipStream_t s) {
+static int patch_gather_normalize_mc_launch(const char* name, const float* volume, const int* starts, float* batch,
+                                            double* workspace, float* mean_std, int M, int Y, int X, int bx, int by, int bz,
+                                            int P, const Seg3dNormalizers& nrm, bool any_adaptive, int flip,
+                                            hipStream_t s) {
   if (any_adaptive) {
     const int nblk = (int)seg3d_patch_stats_blocks(bx, by, bz);
     hipLaunchKernelGGL((patch_stats_partial_mc_kernel<MC, VEC>), dim3(nblk, P), dim3(256), 0, s, volume, starts, workspace,
                        M, Y, X, bx, by, bz, nblk);
-    SEG3D_LAUNCH_CHECK("seg3d_patch_gather_normalize_mc(stats)");
+    PATCH_LAUNCH_CHECK(name, "(stats)");
     hipLaunchKernelGGL(patch_stats_finalize_kernel, dim3(P * M), dim3(64), 0, s, workspace, mean_std, nblk,
                        (double)bx * by * bz);
-    SEG3D_LAUNCH_CHECK("seg3d_patch_gather_normalize_mc(finalize)");
+    PATCH_LAUNCH_CHECK(name, "(finalize)");
   }
   const i64 total = (i64)bx * by * bz * P;
   if (flip)
@@ -328,7 +200,7 @@ static int patch_gather_normalize_mc_launch(const float* volume, const int* star
   else
     hipLaunchKernelGGL((patch_gather_normalize_mc_kernel<MC, VEC, false>), dim3(seg3d_ew_grid(total, 256)), dim3(256), 0, s,
                        volume, starts, mean_std, batch, M, Y, X, bx, by, bz, P, nrm, 0);
-  SEG3D_LAUNCH_CHECK("seg3d_patch_gather_normalize_mc");
+  PATCH_LAUNCH_CHECK(name, "");
   return SEG3D_OK;
 }
 
@@ -336,14 +208,20 @@ static int patch_gather_normalize_mc_launch(const float* volume, const int* star
 // block).  norms.n[m] for m < M: type 0 = fixed (mean, stddev, clip to [clip_lo, clip_hi] when clip != 0), 1 = adaptive
 // (the patch's own mean / std, clip to [clip_lo, clip_hi]), -1 = none.  workspace: seg3d_patch_stats_mc_doubles doubles,
 // mean_std: P * M * 2 floats (both used only when a modality is adaptive).  batch may be volume itself when P = 1, the
-// start is 0 and the box is the whole volume (a training crop normalised in place).
-static int patch_gather_normalize_mc_impl(const float* volume, const int* starts, float* batch, double* workspace,
-                                          float* mean_std, int Z, int Y, int X, int bx, int by, int bz, int P, int M,
-                                          const Seg3dNormalizers& norms, int flip, void* stream) {
-  SEG3D_REQUIRE(volume && starts && batch && P > 0, "seg3d_patch_gather_normalize_mc: bad arguments");
-  SEG3D_REQUIRE(M >= 1 && M <= 8, "seg3d_patch_gather_normalize_mc: M = %d modalities, 1..8 are supported", M);
+// start is 0 and the box is the whole volume (a training crop normalised in place), but never for a mirrored gather.
+// flip: mirror mask of the gathered patches (bit 0 = x, 1 = y, 2 = z; 0 = the plain gather).  The statistics of the
+// adaptive normaliser are taken over the same voxels in the same order whatever the mask, so mean / std are those of the
+// un-mirrored patch bit for bit and a mirrored gather equals the flipped plain gather exactly.
+// name: the entry the caller used, for the messages.
+static int patch_gather_normalize_mc_impl(const char* name, const float* volume, const int* starts, float* batch,
+                                          double* workspace, float* mean_std, int Z, int Y, int X, int bx, int by, int bz,
+                                          int P, int M, const Seg3dNormalizers& norms, int flip, void* stream) {
+  SEG3D_REQUIRE(flip >= 0 && flip <= 7, "%s: flip mask %d outside 0..7", name, flip);
+  SEG3D_REQUIRE(volume && starts && batch && P > 0, "%s: bad arguments", name);
+  SEG3D_REQUIRE(M >= 1 && M <= 8, "%s: M = %d modalities, 1..8 are supported", name, M);
   SEG3D_REQUIRE(bx > 0 && by > 0 && bz > 0 && bx <= X && by <= Y && bz <= Z,
-                "seg3d_patch_gather_normalize_mc: box (%d,%d,%d) does not fit volume (%d,%d,%d)", bx, by, bz, X, Y, Z);
+                "%s: box (%d,%d,%d) does not fit volume (%d,%d,%d)", name, bx, by, bz, X, Y, Z);
+  SEG3D_REQUIRE(flip == 0 || volume != batch, "%s: a mirrored gather cannot run in place", name);
   Seg3dNormalizers nrm = {};
   bool any_adaptive = false;
   for (int m = 0; m < 8; ++m) {
@@ -351,108 +229,107 @@ static int patch_gather_normalize_mc_impl(const float* volume, const int* starts
     if (m < M) {
       n = norms.n[m];
       if (n.type == 1) {
-        SEG3D_REQUIRE(n.clip_hi > n.clip_lo, "seg3d_patch_gather_normalize_mc: modality %d: empty clip range", m);
+        SEG3D_REQUIRE(n.clip_hi > n.clip_lo, "%s: modality %d: empty clip range", name, m);
         n.mean = 0.f;
         n.stddev = 1.f;
         n.clip = 1;
         any_adaptive = true;
       } else if (n.type == 0) {
-        SEG3D_REQUIRE(n.stddev > 0.f, "seg3d_patch_gather_normalize_mc: modality %d: stddev must be positive", m);
+        SEG3D_REQUIRE(n.stddev > 0.f, "%s: modality %d: stddev must be positive", name, m);
         n.clip = n.clip ? 1 : 0;
       } else if (n.type == -1) {
         n = Seg3dNormalizer{-1, 0.f, 1.f, 0, -1.f, 1.f};
       } else {
-        SEG3D_UNSUPPORTED("seg3d_patch_gather_normalize_mc: modality %d: unsupported normalization type %d", m, n.type);
+        SEG3D_UNSUPPORTED("%s: modality %d: unsupported normalization type %d", name, m, n.type);
       }
     }
     nrm.n[m] = n;
   }
-  SEG3D_REQUIRE(!any_adaptive || (workspace && mean_std),
-                "seg3d_patch_gather_normalize_mc: adaptive normaliser needs workspace and mean_std");
+  SEG3D_REQUIRE(!any_adaptive || (workspace && mean_std), "%s: adaptive normaliser needs workspace and mean_std", name);
   hipStream_t s = (hipStream_t)stream;
   const bool vec4 = M == 4 && ((uintptr_t)volume & 15) == 0 && ((uintptr_t)batch & 15) == 0;
   const bool vec2 = M == 2 && ((uintptr_t)volume & 7) == 0 && ((uintptr_t)batch & 7) == 0;
-  if (vec4) return patch_gather_normalize_mc_launch<4, true>(volume, starts, batch, workspace, mean_std, M, Y, X, bx, by, bz, P, nrm, any_adaptive, flip, s);
-  if (M == 4) return patch_gather_normalize_mc_launch<4, false>(volume, starts, batch, workspace, mean_std, M, Y, X, bx, by, bz, P, nrm, any_adaptive, flip, s);
-  if (vec2) return patch_gather_normalize_mc_launch<2, true>(volume, starts, batch, workspace, mean_std, M, Y, X, bx, by, bz, P, nrm, any_adaptive, flip, s);
-  if (M == 2) return patch_gather_normalize_mc_launch<2, false>(volume, starts, batch, workspace, mean_std, M, Y, X, bx, by, bz, P, nrm, any_adaptive, flip, s);
-  if (M == 3) return patch_gather_normalize_mc_launch<3, false>(volume, starts, batch, workspace, mean_std, M, Y, X, bx, by, bz, P, nrm, any_adaptive, flip, s);
-  return patch_gather_normalize_mc_launch<0, false>(volume, starts, batch, workspace, mean_std, M, Y, X, bx, by, bz, P, nrm, any_adaptive, flip, s);
+  if (M == 1) return patch_gather_normalize_mc_launch<1, false>(name, volume, starts, batch, workspace, mean_std, M, Y, X, bx, by, bz, P, nrm, any_adaptive, flip, s);
+  if (vec4) return patch_gather_normalize_mc_launch<4, true>(name, volume, starts, batch, workspace, mean_std, M, Y, X, bx, by, bz, P, nrm, any_adaptive, flip, s);
+  if (M == 4) return patch_gather_normalize_mc_launch<4, false>(name, volume, starts, batch, workspace, mean_std, M, Y, X, bx, by, bz, P, nrm, any_adaptive, flip, s);
+  if (vec2) return patch_gather_normalize_mc_launch<2, true>(name, volume, starts, batch, workspace, mean_std, M, Y, X, bx, by, bz, P, nrm, any_adaptive, flip, s);
+  if (M == 2) return patch_gather_normalize_mc_launch<2, false>(name, volume, starts, batch, workspace, mean_std, M, Y, X, bx, by, bz, P, nrm, any_adaptive, flip, s);
+  if (M == 3) return patch_gather_normalize_mc_launch<3, false>(name, volume, starts, batch, workspace, mean_std, M, Y, X, bx, by, bz, P, nrm, any_adaptive, flip, s);
+  return patch_gather_normalize_mc_launch<0, false>(name, volume, starts, batch, workspace, mean_std, M, Y, X, bx, by, bz, P, nrm, any_adaptive, flip, s);
 }
 
 extern "C" int seg3d_patch_gather_normalize_mc(const float* volume, const int* starts, float* batch, double* workspace,
                                                float* mean_std, int Z, int Y, int X, int bx, int by, int bz, int P, int M,
                                                Seg3dNormalizers norms, void* stream) {
-  return patch_gather_normalize_mc_impl(volume, starts, batch, workspace, mean_std, Z, Y, X, bx, by, bz, P, M, norms, 0,
-                                        stream);
+  return patch_gather_normalize_mc_impl("seg3d_patch_gather_normalize_mc", volume, starts, batch, workspace, mean_std, Z, Y,
+                                        X, bx, by, bz, P, M, norms, 0, stream);
 }
 
-// the multi-modality gather with every patch mirrored by flip_mask (0..7), see seg3d_patch_gather_normalize_flip; batch
-// must not alias volume
+// the multi-modality gather with every patch mirrored by flip_mask (0..7): batch[p][lz][ly][lx][m] is the normalised
+// voxel at start_p + (fx ? bx-1-lx : lx, fy ? by-1-ly : ly, fz ? bz-1-lz : lz), i.e. torch.flip of the plain gather;
+// batch must not alias volume unless flip_mask is 0
 extern "C" int seg3d_patch_gather_normalize_mc_flip(const float* volume, const int* starts, float* batch, double* workspace,
                                                     float* mean_std, int Z, int Y, int X, int bx, int by, int bz, int P,
                                                     int M, Seg3dNormalizers norms, int flip_mask, void* stream) {
-  SEG3D_REQUIRE(flip_mask >= 0 && flip_mask <= 7, "seg3d_patch_gather_normalize_mc_flip: flip mask %d outside 0..7",
-                flip_mask);
-  SEG3D_REQUIRE(flip_mask == 0 || volume != batch, "seg3d_patch_gather_normalize_mc_flip: a mirrored gather cannot run in place");
-  return patch_gather_normalize_mc_impl(volume, starts, batch, workspace, mean_std, Z, Y, X, bx, by, bz, P, M, norms,
-                                        flip_mask, stream);
+  return patch_gather_normalize_mc_impl("seg3d_patch_gather_normalize_mc_flip", volume, starts, batch, workspace, mean_std,
+                                        Z, Y, X, bx, by, bz, P, M, norms, flip_mask, stream);
 }
 
-// One thread per volume voxel of the batch's bounding box; patches are applied in list order so the float summation
-// order per voxel equals the reference's sequential loop (no atomics, reproducible).  The bounding box and the number
-// of valid patches come from a small DEVICE control block so that a captured hipGraph can be replayed for every
-// batch with unchanged kernel arguments:  ctl = {lo_x, lo_y, lo_z, extent_x, extent_y, extent_z, n_valid}.
-__global__ __launch_bounds__(256) void patch_scatter_accumulate_kernel(const float* __restrict__ probs,
-                                                                         const int* __restrict__ starts,
-                                                                         const int* __restrict__ ctl,
-                                                                         float* __restrict__ acc, float* __restrict__ count,
-                                                                         int Z, int Y, int X, int bx, int by, int bz,
-                                                                         int C) {
-  const int lox = ctl[0], loy = ctl[1], loz = ctl[2], ex = ctl[3], ey = ctl[4], ez = ctl[5], P = ctl[6];
-  const i64 total = (i64)ex * ey * ez;
-  const i64 vol = (i64)Z * Y * X;
-  const i64 nv = (i64)bx * by * bz;
-  for (i64 idx = (i64)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (i64)gridDim.x * 256) {
-    const int x = lox + (int)(idx % ex);
-    const i64 t = idx / ex;
-    const int y = loy + (int)(t % ey), z = loz + (int)(t / ey);
-    if (x >= X || y >= Y || z >= Z) continue;
-    const i64 v = ((i64)z * Y + y) * X + x;
-    for (int p = 0; p < P; ++p) {
-      const int lx = x - starts[3 * p], ly = y - starts[3 * p + 1], lz = z - starts[3 * p + 2];
-      if (lx >= 0 && lx < bx && ly >= 0 && ly < by && lz >= 0 && lz < bz) {
-        const i64 e = ((i64)lz * by + ly) * bx + lx;
-        for (int c = 0; c < C; ++c) acc[(i64)c * vol + v] += probs[((i64)p * C + c) * nv + e];
-        count[v] += 1.0f;
-      }
-    }
+// The single-modality entries are the M = 1 case: volume [Z][Y][X], batch [P][1][bz][by][bx], workspace
+// P * seg3d_patch_stats_blocks * 2 doubles and mean_std P * 2 floats (adaptive only) -- the M = 1 layouts.
+// normalizer_type: 0 = fixed (mean, stddev, clip to [-1,1] when clip != 0), 1 = adaptive (clip to +-clip_sigma), -1 = none.
+static int patch_gather_normalize_single(const char* name, const float* volume, const int* starts, float* batch,
+                                         double* workspace, float* mean_std, int Z, int Y, int X, int bx, int by, int bz,
+                                         int P, int normalizer_type, float mean, float stddev, int clip, float clip_sigma,
+                                         int flip, void* stream) {
+  Seg3dNormalizers norms = {};
+  if (normalizer_type == 1) {
+    SEG3D_REQUIRE(clip_sigma > 0.f, "%s: clip_sigma must be positive", name);
+    norms.n[0] = Seg3dNormalizer{1, 0.f, 1.f, 1, -clip_sigma, clip_sigma};
+  } else if (normalizer_type == 0) {
+    SEG3D_REQUIRE(stddev > 0.f, "%s: stddev must be positive", name);
+    norms.n[0] = Seg3dNormalizer{0, mean, stddev, clip, -1.f, 1.f};
+  } else if (normalizer_type == -1) {
+    norms.n[0] = Seg3dNormalizer{-1, 0.f, 1.f, 0, -1.f, 1.f};
+  } else {
+    SEG3D_UNSUPPORTED("%s: unsupported normalization type %d", name, normalizer_type);
   }
+  return patch_gather_normalize_mc_impl(name, volume, starts, batch, workspace, mean_std, Z, Y, X, bx, by, bz, P, 1, norms,
+                                        flip, stream);
 }
 
-// probs [P][C][bz][by][bx] -> acc [C][Z][Y][X] +=, count [Z][Y][X] += 1.  starts_xyz: device int32 [P][3];
-// ctl: device int32 [7] (see kernel); max_box_voxels: host upper bound of the bounding-box volume (sizes the grid).
-extern "C" int seg3d_patch_scatter_accumulate(const float* probs, const int* starts, const int* ctl, float* acc,
-                                              float* count, int Z, int Y, int X, int bx, int by, int bz, int C,
-                                              long long max_box_voxels, void* stream) {
-  SEG3D_REQUIRE(probs && starts && ctl && acc && count && C > 0, "seg3d_patch_scatter_accumulate: bad arguments");
-  SEG3D_REQUIRE(bx > 0 && by > 0 && bz > 0 && bx <= X && by <= Y && bz <= Z && max_box_voxels > 0,
-                "seg3d_patch_scatter_accumulate: bad box");
-  hipLaunchKernelGGL(patch_scatter_accumulate_kernel, dim3(seg3d_ew_grid(max_box_voxels, 256)), dim3(256), 0,
-                     (hipStream_t)stream, probs, starts, ctl, acc, count, Z, Y, X, bx, by, bz, C);
-  SEG3D_LAUNCH_CHECK("seg3d_patch_scatter_accumulate");
-  return SEG3D_OK;
+extern "C" int seg3d_patch_gather_normalize(const float* volume, const int* starts, float* batch, double* workspace,
+                                            float* mean_std, int Z, int Y, int X, int bx, int by, int bz, int P,
+                                            int normalizer_type, float mean, float stddev, int clip, float clip_sigma,
+                                            void* stream) {
+  return patch_gather_normalize_single("seg3d_patch_gather_normalize", volume, starts, batch, workspace, mean_std, Z, Y, X,
+                                       bx, by, bz, P, normalizer_type, mean, stddev, clip, clip_sigma, 0, stream);
 }
 
-// Weighted and / or mirrored accumulation, same thread mapping and patch order as patch_scatter_accumulate_kernel:
+// the same gather with every patch mirrored by flip_mask (0..7), see seg3d_patch_gather_normalize_mc_flip
+extern "C" int seg3d_patch_gather_normalize_flip(const float* volume, const int* starts, float* batch, double* workspace,
+                                                 float* mean_std, int Z, int Y, int X, int bx, int by, int bz, int P,
+                                                 int normalizer_type, float mean, float stddev, int clip, float clip_sigma,
+                                                 int flip_mask, void* stream) {
+  return patch_gather_normalize_single("seg3d_patch_gather_normalize_flip", volume, starts, batch, workspace, mean_std, Z, Y,
+                                       X, bx, by, bz, P, normalizer_type, mean, stddev, clip, clip_sigma, flip_mask, stream);
+}
+
+// ---- scatter.  One thread per volume voxel of the batch's bounding box; patches are applied in list order so the float
+// summation order per voxel equals the reference's sequential loop (no atomics, reproducible).  The bounding box and the
+// number of valid patches come from a small DEVICE control block so that a captured hipGraph can be replayed for every
+// batch with unchanged kernel arguments:  ctl = {lo_x, lo_y, lo_z, extent_x, extent_y, extent_z, n_valid}.
+// Weighted and / or mirrored accumulation:
 //   w = (g_z[lz] * g_y[ly]) * g_x[lx]   (wtab = x table, y table, z table: bx + by + bz floats; WEIGHTED = false: w = 1)
 //   acc[c][v] = acc[c][v] + (w * prob),  count[v] = count[v] + w     -- a rounded multiply, then a rounded add
 // (the file is built with -ffp-contract=off and the pragma below pins it, so no FMA is formed and the result is bit-equal
-// to a float32 loop on the host).  The probabilities of a patch are stored mirrored by `flip`: the value that belongs to
-// local voxel (lx, ly, lz) is read at the mirrored position; the tables are symmetric, so the weight needs no mirror, but
-// it is indexed with the un-mirrored position all the same.  A mirror along x reverses the lanes' addresses inside one
-// contiguous row.  The table reads are L1 / L2 hits (a few hundred bytes shared by every thread).
-template <bool WEIGHTED>
+// to a float32 loop on the host; with w = 1 the product is the probability itself and the count grows by 1.0f per patch,
+// the reference's plain accumulation).  The probabilities of a patch are stored mirrored by `flip`: the value that belongs
+// to local voxel (lx, ly, lz) is read at the mirrored position (FLIP = false: flip is 0, no mirror code is compiled); the
+// tables are symmetric, so the weight needs no mirror, but it is indexed with the un-mirrored position all the same.  A
+// mirror along x reverses the lanes' addresses inside one contiguous row.  The table reads are L1 / L2 hits (a few
+// hundred bytes shared by every thread).
+template <bool WEIGHTED, bool FLIP>
 __global__ __launch_bounds__(256) void patch_scatter_blend_kernel(const float* __restrict__ probs,
                                                                     const int* __restrict__ starts,
                                                                     const int* __restrict__ ctl,
@@ -477,9 +354,12 @@ __global__ __launch_bounds__(256) void patch_scatter_blend_kernel(const float* _
       if (lx >= 0 && lx < bx && ly >= 0 && ly < by && lz >= 0 && lz < bz) {
         float w = 1.0f;
         if constexpr (WEIGHTED) w = (wtab[bx + by + lz] * wtab[bx + ly]) * wtab[lx];
-        const int mx = (flip & 1) ? bx - 1 - lx : lx;
-        const int my = (flip & 2) ? by - 1 - ly : ly;
-        const int mz = (flip & 4) ? bz - 1 - lz : lz;
+        int mx = lx, my = ly, mz = lz;
+        if constexpr (FLIP) {
+          if (flip & 1) mx = bx - 1 - lx;
+          if (flip & 2) my = by - 1 - ly;
+          if (flip & 4) mz = bz - 1 - lz;
+        }
         const i64 e = ((i64)mz * by + my) * bx + mx;
         for (int c = 0; c < C; ++c) {
           const float wp = w * probs[((i64)p * C + c) * nv + e];
@@ -493,27 +373,39 @@ __global__ __launch_bounds__(256) void patch_scatter_blend_kernel(const float* _
   }
 }
 
-// seg3d_patch_scatter_accumulate with Gaussian importance weights and mirrored inputs.  wtab: device, bx + by + bz floats
-// (x table, y table, z table), NULL = constant weight 1; flip_mask (0..7): probs of every patch are stored mirrored by it.
-// wtab = NULL and flip_mask = 0 is seg3d_patch_scatter_accumulate itself.
+// probs [P][C][bz][by][bx] -> acc [C][Z][Y][X] += w * prob, count [Z][Y][X] += w.  starts_xyz: device int32 [P][3];
+// ctl: device int32 [7] (see kernel); max_box_voxels: host upper bound of the bounding-box volume (sizes the grid).
+// wtab: device, bx + by + bz floats (x table, y table, z table), NULL = constant weight 1; flip (0..7): probs of every patch
+// are stored mirrored by it.
+static int patch_scatter(const char* name, const float* probs, const int* starts, const int* ctl, const float* wtab,
+                         float* acc, float* count, int Z, int Y, int X, int bx, int by, int bz, int C, int flip,
+                         long long max_box_voxels, void* stream) {
+  SEG3D_REQUIRE(flip >= 0 && flip <= 7, "%s: flip mask %d outside 0..7", name, flip);
+  SEG3D_REQUIRE(probs && starts && ctl && acc && count && C > 0, "%s: bad arguments", name);
+  SEG3D_REQUIRE(bx > 0 && by > 0 && bz > 0 && bx <= X && by <= Y && bz <= Z && max_box_voxels > 0, "%s: bad box", name);
+  auto kernel = wtab ? (flip ? patch_scatter_blend_kernel<true, true> : patch_scatter_blend_kernel<true, false>)
+                     : (flip ? patch_scatter_blend_kernel<false, true> : patch_scatter_blend_kernel<false, false>);
+  hipLaunchKernelGGL(kernel, dim3(seg3d_ew_grid(max_box_voxels, 256)), dim3(256), 0, (hipStream_t)stream, probs, starts, ctl,
+                     wtab, acc, count, Z, Y, X, bx, by, bz, C, flip);
+  SEG3D_LAUNCH_CHECK(name);
+  return SEG3D_OK;
+}
+
+// the reference's accumulation: every patch counts 1, nothing is mirrored -- seg3d_patch_scatter_blend with wtab = NULL and
+// flip_mask = 0
+extern "C" int seg3d_patch_scatter_accumulate(const float* probs, const int* starts, const int* ctl, float* acc,
+                                              float* count, int Z, int Y, int X, int bx, int by, int bz, int C,
+                                              long long max_box_voxels, void* stream) {
+  return patch_scatter("seg3d_patch_scatter_accumulate", probs, starts, ctl, nullptr, acc, count, Z, Y, X, bx, by, bz, C, 0,
+                       max_box_voxels, stream);
+}
+
+// Gaussian importance weights and / or mirrored inputs
 extern "C" int seg3d_patch_scatter_blend(const float* probs, const int* starts, const int* ctl, const float* wtab,
                                          float* acc, float* count, int Z, int Y, int X, int bx, int by, int bz, int C,
                                          int flip_mask, long long max_box_voxels, void* stream) {
-  SEG3D_REQUIRE(flip_mask >= 0 && flip_mask <= 7, "seg3d_patch_scatter_blend: flip mask %d outside 0..7", flip_mask);
-  if (!wtab && flip_mask == 0)
-    return seg3d_patch_scatter_accumulate(probs, starts, ctl, acc, count, Z, Y, X, bx, by, bz, C, max_box_voxels, stream);
-  SEG3D_REQUIRE(probs && starts && ctl && acc && count && C > 0, "seg3d_patch_scatter_blend: bad arguments");
-  SEG3D_REQUIRE(bx > 0 && by > 0 && bz > 0 && bx <= X && by <= Y && bz <= Z && max_box_voxels > 0,
-                "seg3d_patch_scatter_blend: bad box");
-  const dim3 grid(seg3d_ew_grid(max_box_voxels, 256));
-  if (wtab)
-    hipLaunchKernelGGL(patch_scatter_blend_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, probs, starts, ctl, wtab,
-                       acc, count, Z, Y, X, bx, by, bz, C, flip_mask);
-  else
-    hipLaunchKernelGGL(patch_scatter_blend_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, probs, starts, ctl, wtab,
-                       acc, count, Z, Y, X, bx, by, bz, C, flip_mask);
-  SEG3D_LAUNCH_CHECK("seg3d_patch_scatter_blend");
-  return SEG3D_OK;
+  return patch_scatter("seg3d_patch_scatter_blend", probs, starts, ctl, wtab, acc, count, Z, Y, X, bx, by, bz, C, flip_mask,
+                       max_box_voxels, stream);
 }
 
 // acc[c][v] *= 1/count[v] (in place);  mask[v] = argmax_c (first maximum), int8.

@@ -112,65 +112,7 @@ __device__ __forceinline__ void deform_apply(const DeformLds& l, const DeformArg
   cz += dfm.L[6] * ux + dfm.L[7] * uy + dfm.L[8] * uz;
 }
 
-template <bool DEFORM>
-__global__ __launch_bounds__(256) void resample_affine_kernel(const float* __restrict__ src, float* __restrict__ dst, int Xi,
-                                                                int Yi, int Zi, int Xo, int Yo, int Zo, Affine12 A,
-                                                                int linear, float pad, DeformArgs<DEFORM> dfm) {
-  extern __shared__ double deform_smem[];
-  DeformLds lds;
-  if constexpr (DEFORM) lds = deform_stage(deform_smem, dfm, Xo, Yo, Zo);
-  const i64 total = (i64)Xo * Yo * Zo;
-  for (i64 idx = (i64)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (i64)gridDim.x * 256) {
-    const int x = (int)(idx % Xo);
-    const i64 t = idx / Xo;
-    const int y = (int)(t % Yo), z = (int)(t / Yo);
-    double cx = A.m[0] * x + A.m[1] * y + A.m[2] * z + A.m[3];
-    double cy = A.m[4] * x + A.m[5] * y + A.m[6] * z + A.m[7];
-    double cz = A.m[8] * x + A.m[9] * y + A.m[10] * z + A.m[11];
-    if constexpr (DEFORM) deform_apply(lds, dfm, x, y, z, Xo, Yo, Zo, cx, cy, cz);
-    float out = pad;
-    if (cx >= -0.5 && cx < Xi - 0.5 && cy >= -0.5 && cy < Yi - 0.5 && cz >= -0.5 && cz < Zi - 0.5) {
-      if (linear) {
-        const double fx = fmin(fmax(cx, 0.0), (double)(Xi - 1)), fy = fmin(fmax(cy, 0.0), (double)(Yi - 1)),
-                     fz = fmin(fmax(cz, 0.0), (double)(Zi - 1));
-        const int x0 = (int)floor(fx), y0 = (int)floor(fy), z0 = (int)floor(fz);
-        const int x1 = x0 + 1 < Xi ? x0 + 1 : x0, y1 = y0 + 1 < Yi ? y0 + 1 : y0, z1 = z0 + 1 < Zi ? z0 + 1 : z0;
-        const double dx = fx - x0, dy = fy - y0, dz = fz - z0;
-        const i64 r00 = ((i64)z0 * Yi + y0) * Xi, r01 = ((i64)z0 * Yi + y1) * Xi, r10 = ((i64)z1 * Yi + y0) * Xi,
-                  r11 = ((i64)z1 * Yi + y1) * Xi;
-        const double v000 = src[r00 + x0], v100 = src[r00 + x1], v010 = src[r01 + x0], v110 = src[r01 + x1];
-        const double v001 = src[r10 + x0], v101 = src[r10 + x1], v011 = src[r11 + x0], v111 = src[r11 + x1];
-        const double a00 = v000 + (v100 - v000) * dx, a01 = v010 + (v110 - v010) * dx;
-        const double a10 = v001 + (v101 - v001) * dx, a11 = v011 + (v111 - v011) * dx;
-        const double b0 = a00 + (a01 - a00) * dy, b1 = a10 + (a11 - a10) * dy;
-        out = (float)(b0 + (b1 - b0) * dz);
-      } else {
-        int xn = (int)floor(cx + 0.5), yn = (int)floor(cy + 0.5), zn = (int)floor(cz + 0.5);
-        xn = xn < 0 ? 0 : (xn >= Xi ? Xi - 1 : xn);
-        yn = yn < 0 ? 0 : (yn >= Yi ? Yi - 1 : yn);
-        zn = zn < 0 ? 0 : (zn >= Zi ? Zi - 1 : zn);
-        out = src[((i64)zn * Yi + yn) * Xi + xn];
-      }
-    }
-    dst[idx] = out;
-  }
-}
-
-// dst[z][y][x] (Xo, Yo, Zo) = src sampled at c = M * (x, y, z, 1); affine_host: 12 doubles, row-major 3 x 4
-extern "C" int seg3d_resample_affine(const float* src, float* dst, int Xi, int Yi, int Zi, int Xo, int Yo, int Zo,
-                                     const double* affine_host, int linear, float pad, void* stream) {
-  SEG3D_REQUIRE(src && dst && affine_host, "seg3d_resample_affine: null pointer");
-  SEG3D_REQUIRE(Xi > 0 && Yi > 0 && Zi > 0 && Xo > 0 && Yo > 0 && Zo > 0, "seg3d_resample_affine: bad dims");
-  Affine12 A;
-  for (int k = 0; k < 12; ++k) A.m[k] = affine_host[k];
-  const i64 total = (i64)Xo * Yo * Zo;
-  hipLaunchKernelGGL(resample_affine_kernel<false>, dim3(seg3d_ew_grid(total, 256)), dim3(256), 0, (hipStream_t)stream, src,
-                     dst, Xi, Yi, Zi, Xo, Yo, Zo, A, linear, pad, DeformArgs<false>());
-  SEG3D_LAUNCH_CHECK("seg3d_resample_affine");
-  return SEG3D_OK;
-}
-
-// host side of the two deform entries: checks and the by-value argument.  The control grid must cover every index the
+// host side of the deform entries: checks and the by-value argument.  The control grid must cover every index the
 // kernel reads (k + 3 with k = floor((n - 1) * sp / h), evaluated here with the device's own arithmetic) and the LDS image
 // must fit the 64 KB a workgroup gets without opting in -- a training crop needs a few KB.
 static int deform_args(const char* name, int Xo, int Yo, int Zo, const double* l_host, const float* ctrl, int gx, int gy,
@@ -196,31 +138,14 @@ static int deform_args(const char* name, int Xo, int Yo, int Zo, const double* l
   return SEG3D_OK;
 }
 
-// seg3d_resample_affine with the sampled point displaced by a cubic B-spline field: c = M (x, y, z, 1) + L u(x', y', z')
-extern "C" int seg3d_resample_deform(const float* src, float* dst, int Xi, int Yi, int Zi, int Xo, int Yo, int Zo,
-                                     const double* affine_host, int linear, float pad, const double* l_host,
-                                     const float* ctrl, int gx, int gy, int gz, const double* t_host, int mirror_mask,
-                                     void* stream) {
-  SEG3D_REQUIRE(src && dst && affine_host, "seg3d_resample_deform: null pointer");
-  SEG3D_REQUIRE(Xi > 0 && Yi > 0 && Zi > 0 && Xo > 0 && Yo > 0 && Zo > 0, "seg3d_resample_deform: bad dims");
-  DeformArgs<true> D;
-  const int rc = deform_args("seg3d_resample_deform", Xo, Yo, Zo, l_host, ctrl, gx, gy, gz, t_host, mirror_mask, &D);
-  if (rc != SEG3D_OK) return rc;
-  Affine12 A;
-  for (int k = 0; k < 12; ++k) A.m[k] = affine_host[k];
-  const i64 total = (i64)Xo * Yo * Zo;
-  hipLaunchKernelGGL(resample_affine_kernel<true>, dim3(seg3d_ew_grid(total, 256)), dim3(256),
-                     deform_lds_bytes(Xo, Yo, Zo, D.g), (hipStream_t)stream, src, dst, Xi, Yi, Zi, Xo, Yo, Zo, A, linear, pad, D);
-  SEG3D_LAUNCH_CHECK("seg3d_resample_deform");
-  return SEG3D_OK;
-}
-
-// ---- M co-registered channels in one pass (multi-modality training crops and inference resampling) ------------------
+// ---- resampling: M co-registered channels in one pass (multi-modality training crops and inference resampling) --------
 // src [Zi][Yi][Xi][M] (channels-last), dst: voxel (x, y, z) of the output grid at dst + ((z * Yo + y) * Xo + x) * dst_stride,
 // M floats.  The affine coordinate, the inside test and the trilinear weights (or the NN index) are computed once per
-// output voxel; each of the 8 taps is one contiguous M-float row.  Per channel the arithmetic is resample_affine_kernel's
-// (double, same operation order, same clamping / padding), so channel m equals seg3d_resample_affine on plane m bit for
-// bit.  MC = 2, 3, 4: compile-time width (VEC: the rows are 8- / 16-byte aligned); MC = 0: runtime M <= 8.
+// output voxel; each of the 8 taps is one contiguous M-float row.  Per channel the arithmetic is in double with one fixed
+// operation order, clamping and padding whatever M is, so channel m of an M-channel launch equals the M = 1 launch on
+// plane m bit for bit.  A single volume [Zi][Yi][Xi] is the M = 1, dst_stride = 1 case of the same memory:
+// seg3d_resample_affine / seg3d_resample_deform are those entries.
+// MC = 1, 2, 3, 4: compile-time width (VEC: the rows are 8- / 16-byte aligned); MC = 0: runtime M <= 8.
 template <int MC>
 __device__ __forceinline__ void resample_mc_lerp(const float* t000, const float* t100, const float* t010, const float* t110,
                                                  const float* t001, const float* t101, const float* t011, const float* t111,
@@ -320,7 +245,10 @@ static void resample_mc_launch(const float* src, float* dst, int M, i64 dst_stri
   // vector rows need the source base / destination base and stride aligned to the row width
   const bool vec4 = M == 4 && ((uintptr_t)src & 15) == 0 && ((uintptr_t)dst & 15) == 0 && dst_stride % 4 == 0;
   const bool vec2 = M == 2 && ((uintptr_t)src & 7) == 0 && ((uintptr_t)dst & 7) == 0 && dst_stride % 2 == 0;
-  if (vec4)
+  if (M == 1)
+    hipLaunchKernelGGL((resample_affine_mc_kernel<1, false, DEFORM>), grid, block, lds, s, src, dst, M, dst_stride, Xi, Yi,
+                       Zi, Xo, Yo, Zo, A, lin, pad, D);
+  else if (vec4)
     hipLaunchKernelGGL((resample_affine_mc_kernel<4, true, DEFORM>), grid, block, lds, s, src, dst, M, dst_stride, Xi, Yi, Zi,
                        Xo, Yo, Zo, A, lin, pad, D);
   else if (M == 4)
@@ -340,41 +268,75 @@ static void resample_mc_launch(const float* src, float* dst, int M, i64 dst_stri
                        Zi, Xo, Yo, Zo, A, lin, pad, D);
 }
 
-// src [Zi][Yi][Xi][M] -> rows of M floats at dst + voxel * dst_stride (dst_stride >= M floats); affine_host as above
-extern "C" int seg3d_resample_affine_mc(const float* src, float* dst, int M, long long dst_stride, int Xi, int Yi, int Zi,
-                                        int Xo, int Yo, int Zo, const double* affine_host, int linear, float pad,
-                                        void* stream) {
-  SEG3D_REQUIRE(src && dst && affine_host, "seg3d_resample_affine_mc: null pointer");
-  SEG3D_REQUIRE(M >= 1 && M <= 8, "seg3d_resample_affine_mc: M = %d channels, 1..8 are supported", M);
-  SEG3D_REQUIRE(dst_stride >= M, "seg3d_resample_affine_mc: voxel stride %lld below M = %d", dst_stride, M);
-  SEG3D_REQUIRE(Xi > 0 && Yi > 0 && Zi > 0 && Xo > 0 && Yo > 0 && Zo > 0, "seg3d_resample_affine_mc: bad dims");
-  Affine12 A;
-  for (int k = 0; k < 12; ++k) A.m[k] = affine_host[k];
-  resample_mc_launch<false>(src, dst, M, (i64)dst_stride, Xi, Yi, Zi, Xo, Yo, Zo, A, linear ? 1 : 0, pad, DeformArgs<false>(),
-                            0, (hipStream_t)stream);
-  SEG3D_LAUNCH_CHECK("seg3d_resample_affine_mc");
+// the four entries' common checks and the by-value affine argument
+static int resample_args(const char* name, const float* src, const float* dst, int M, long long dst_stride, int Xi, int Yi,
+                         int Zi, int Xo, int Yo, int Zo, const double* affine_host, Affine12* A) {
+  SEG3D_REQUIRE(src && dst && affine_host, "%s: null pointer", name);
+  SEG3D_REQUIRE(M >= 1 && M <= 8, "%s: M = %d channels, 1..8 are supported", name, M);
+  SEG3D_REQUIRE(dst_stride >= M, "%s: voxel stride %lld below M = %d", name, dst_stride, M);
+  SEG3D_REQUIRE(Xi > 0 && Yi > 0 && Zi > 0 && Xo > 0 && Yo > 0 && Zo > 0, "%s: bad dims", name);
+  for (int k = 0; k < 12; ++k) A->m[k] = affine_host[k];
   return SEG3D_OK;
 }
 
-// seg3d_resample_affine_mc with the deformation of seg3d_resample_deform: one field for all M channels; channel m equals
-// seg3d_resample_deform on plane m bit for bit (same coordinate code, same per-channel arithmetic)
+static int resample_affine(const char* name, const float* src, float* dst, int M, long long dst_stride, int Xi, int Yi,
+                           int Zi, int Xo, int Yo, int Zo, const double* affine_host, int linear, float pad, void* stream) {
+  Affine12 A;
+  const int rc = resample_args(name, src, dst, M, dst_stride, Xi, Yi, Zi, Xo, Yo, Zo, affine_host, &A);
+  if (rc != SEG3D_OK) return rc;
+  resample_mc_launch<false>(src, dst, M, (i64)dst_stride, Xi, Yi, Zi, Xo, Yo, Zo, A, linear ? 1 : 0, pad, DeformArgs<false>(),
+                            0, (hipStream_t)stream);
+  SEG3D_LAUNCH_CHECK(name);
+  return SEG3D_OK;
+}
+
+static int resample_deform(const char* name, const float* src, float* dst, int M, long long dst_stride, int Xi, int Yi,
+                           int Zi, int Xo, int Yo, int Zo, const double* affine_host, int linear, float pad,
+                           const double* l_host, const float* ctrl, int gx, int gy, int gz, const double* t_host,
+                           int mirror_mask, void* stream) {
+  Affine12 A;
+  int rc = resample_args(name, src, dst, M, dst_stride, Xi, Yi, Zi, Xo, Yo, Zo, affine_host, &A);
+  if (rc != SEG3D_OK) return rc;
+  DeformArgs<true> D;
+  rc = deform_args(name, Xo, Yo, Zo, l_host, ctrl, gx, gy, gz, t_host, mirror_mask, &D);
+  if (rc != SEG3D_OK) return rc;
+  resample_mc_launch<true>(src, dst, M, (i64)dst_stride, Xi, Yi, Zi, Xo, Yo, Zo, A, linear ? 1 : 0, pad, D,
+                           deform_lds_bytes(Xo, Yo, Zo, D.g), (hipStream_t)stream);
+  SEG3D_LAUNCH_CHECK(name);
+  return SEG3D_OK;
+}
+
+// src [Zi][Yi][Xi][M] -> rows of M floats at dst + voxel * dst_stride (dst_stride >= M floats): dst = src sampled at
+// c = M * (x, y, z, 1); affine_host: 12 doubles, row-major 3 x 4
+extern "C" int seg3d_resample_affine_mc(const float* src, float* dst, int M, long long dst_stride, int Xi, int Yi, int Zi,
+                                        int Xo, int Yo, int Zo, const double* affine_host, int linear, float pad,
+                                        void* stream) {
+  return resample_affine("seg3d_resample_affine_mc", src, dst, M, dst_stride, Xi, Yi, Zi, Xo, Yo, Zo, affine_host, linear,
+                         pad, stream);
+}
+
+// seg3d_resample_affine_mc with the sampled point displaced by a cubic B-spline field, one field for all M channels:
+// c = M (x, y, z, 1) + L u(x', y', z')
 extern "C" int seg3d_resample_deform_mc(const float* src, float* dst, int M, long long dst_stride, int Xi, int Yi, int Zi,
                                         int Xo, int Yo, int Zo, const double* affine_host, int linear, float pad,
                                         const double* l_host, const float* ctrl, int gx, int gy, int gz,
                                         const double* t_host, int mirror_mask, void* stream) {
-  SEG3D_REQUIRE(src && dst && affine_host, "seg3d_resample_deform_mc: null pointer");
-  SEG3D_REQUIRE(M >= 1 && M <= 8, "seg3d_resample_deform_mc: M = %d channels, 1..8 are supported", M);
-  SEG3D_REQUIRE(dst_stride >= M, "seg3d_resample_deform_mc: voxel stride %lld below M = %d", dst_stride, M);
-  SEG3D_REQUIRE(Xi > 0 && Yi > 0 && Zi > 0 && Xo > 0 && Yo > 0 && Zo > 0, "seg3d_resample_deform_mc: bad dims");
-  DeformArgs<true> D;
-  const int rc = deform_args("seg3d_resample_deform_mc", Xo, Yo, Zo, l_host, ctrl, gx, gy, gz, t_host, mirror_mask, &D);
-  if (rc != SEG3D_OK) return rc;
-  Affine12 A;
-  for (int k = 0; k < 12; ++k) A.m[k] = affine_host[k];
-  resample_mc_launch<true>(src, dst, M, (i64)dst_stride, Xi, Yi, Zi, Xo, Yo, Zo, A, linear ? 1 : 0, pad, D,
-                           deform_lds_bytes(Xo, Yo, Zo, D.g), (hipStream_t)stream);
-  SEG3D_LAUNCH_CHECK("seg3d_resample_deform_mc");
-  return SEG3D_OK;
+  return resample_deform("seg3d_resample_deform_mc", src, dst, M, dst_stride, Xi, Yi, Zi, Xo, Yo, Zo, affine_host, linear, pad,
+                         l_host, ctrl, gx, gy, gz, t_host, mirror_mask, stream);
+}
+
+// the M = 1 case of the two entries above: src [Zi][Yi][Xi] -> dst [Zo][Yo][Xo]
+extern "C" int seg3d_resample_affine(const float* src, float* dst, int Xi, int Yi, int Zi, int Xo, int Yo, int Zo,
+                                     const double* affine_host, int linear, float pad, void* stream) {
+  return resample_affine("seg3d_resample_affine", src, dst, 1, 1, Xi, Yi, Zi, Xo, Yo, Zo, affine_host, linear, pad, stream);
+}
+
+extern "C" int seg3d_resample_deform(const float* src, float* dst, int Xi, int Yi, int Zi, int Xo, int Yo, int Zo,
+                                     const double* affine_host, int linear, float pad, const double* l_host,
+                                     const float* ctrl, int gx, int gy, int gz, const double* t_host, int mirror_mask,
+                                     void* stream) {
+  return resample_deform("seg3d_resample_deform", src, dst, 1, 1, Xi, Yi, Zi, Xo, Yo, Zo, affine_host, linear, pad, l_host,
+                         ctrl, gx, gy, gz, t_host, mirror_mask, stream);
 }
 
 // ---- bounding box -----------------------------------------------------------------------------------------------------

@@ -7,9 +7,10 @@ of one, copy every class map back to the host and `+=` it into a SimpleITK volum
 trips (utils/image_tools.py:446-450); finally multiply by 1/count and arg-max.
 
 Here the volume stays resident in HBM.  `SlidingWindowBatcher` crops + normalises P patches per launch
-(seg3d_patch_gather_normalize), the net runs ONCE per patch (the reference's two forwards are identical in eval mode,
-so their mean is the single result bit for bit), and the class maps are accumulated on the device in list order
-(seg3d_patch_scatter_accumulate, no atomics => the same float summation order as the reference's sequential loop).
+(seg3d_patch_gather_normalize_mc_flip; one modality is its M = 1 case), the net runs ONCE per patch (the reference's two
+forwards are identical in eval mode, so their mean is the single result bit for bit), and the class maps are accumulated
+on the device in list order (seg3d_patch_scatter_blend, no atomics => the same float summation order as the reference's
+sequential loop).
 gather -> net -> scatter is captured once into a hipGraph (torch.cuda.CUDAGraph drives hipStreamBeginCapture) and
 replayed per batch; only a 4*(3P+7)-byte control block changes between replays.
 """
@@ -116,11 +117,10 @@ class SlidingWindowBatcher(object):
         E.require_device(volume)
         if volume.dim() not in (3, 4) or volume.dtype != torch.float32:
             raise ValueError('volume must be a float32 [Z, Y, X] or [Z, Y, X, M] tensor')
-        self.volume = volume.contiguous()
-        self.Z, self.Y, self.X = (int(s) for s in volume.shape[:3])
-        # M > 1: seg3d_patch_gather_normalize_mc, batches [P, bz, by, bx, M] handed out as [P, M, bz, by, bx] views
-        self.M = int(volume.shape[3]) if volume.dim() == 4 else 1
-        self.channels_last = volume.dim() == 4
+        # a [Z, Y, X] volume is the same memory as [Z, Y, X, 1]: one modality is the M = 1 case, with a list of one normaliser
+        single = volume.dim() == 3
+        self.volume = (volume.unsqueeze(3) if single else volume).contiguous()
+        self.Z, self.Y, self.X, self.M = (int(s) for s in self.volume.shape)
         self.box = tuple(int(b) for b in box)
         self.C = int(num_classes)
         self.starts = [[int(v) for v in s] for s in starts]
@@ -129,28 +129,14 @@ class SlidingWindowBatcher(object):
             if s[0] < 0 or s[1] < 0 or s[2] < 0 or s[0] + bx > self.X or s[1] + by > self.Y or s[2] + bz > self.Z:
                 raise ValueError('patch {} with box {} leaves the volume {}'.format(s, self.box, (self.X, self.Y, self.Z)))
         self.normalizer = normalizer
-        if self.channels_last:
-            self._norm_params = image_tools.normalizer_params(list(normalizer), self.M)
-        elif normalizer is None:
-            self._norm = (-1, 0.0, 1.0, 0, 1.0)
-        elif normalizer['type'] == 0:
-            self._norm = (0, float(normalizer['mean']), float(normalizer['stddev']), int(bool(normalizer['clip'])), 1.0)
-        elif normalizer['type'] == 1:
-            self._norm = (1, 0.0, 1.0, 1, float(normalizer['clip_sigma']))
-        else:
-            raise ValueError('Unsupported normalization type.')
+        self._norm_params = image_tools.normalizer_params([normalizer] if single else list(normalizer), self.M)
         dev = volume.device
         self.acc = torch.zeros((self.C, self.Z, self.Y, self.X), dtype=torch.float32, device=dev)
         self.count = torch.zeros((self.Z, self.Y, self.X), dtype=torch.float32, device=dev)
         self.max_batch = int(max_batch)
-        if self.channels_last:
-            nws = E.query('seg3d_patch_stats_mc_doubles', bx, by, bz, self.max_batch, self.M)
-            self._stat_ws = torch.empty((nws,), dtype=torch.float64, device=dev)
-            self._mean_std = torch.empty((self.max_batch, self.M, 2), dtype=torch.float32, device=dev)
-        else:
-            nblk = E.query('seg3d_patch_stats_blocks', bx, by, bz)
-            self._stat_ws = torch.empty((self.max_batch * nblk * 2,), dtype=torch.float64, device=dev)
-            self._mean_std = torch.empty((self.max_batch, 2), dtype=torch.float32, device=dev)
+        nws = E.query('seg3d_patch_stats_mc_doubles', bx, by, bz, self.max_batch, self.M)
+        self._stat_ws = torch.empty((nws,), dtype=torch.float64, device=dev)
+        self._mean_std = torch.empty((self.max_batch, self.M, 2), dtype=torch.float32, device=dev)
         # control block on the device: [P][3] starts then {lo xyz, extent xyz, n_valid}
         self._ctl = torch.zeros((3 * self.max_batch + 7,), dtype=torch.int32, device=dev)
         self._plan = None
@@ -205,37 +191,20 @@ class SlidingWindowBatcher(object):
         return flip
 
     def gather_current(self, out=None, flip=0):
-        """crop + normalise the max_batch patches described by the control block -> [P, 1, bz, by, bx]
-        ([P, M, bz, by, bx] view of NDHWC memory for a multi-modality volume).  flip: mirror mask (bit 0 = x, 1 = y,
-        2 = z); the result equals torch.flip of the plain gather along those axes, bit for bit"""
+        """crop + normalise the max_batch patches described by the control block -> [P, M, bz, by, bx] view of NDHWC
+        memory (for one modality that is a contiguous [P, 1, bz, by, bx] tensor).  flip: mirror mask (bit 0 = x, 1 = y,
+        2 = z; 0 = the plain gather); the result equals torch.flip of the plain gather along those axes, bit for bit"""
         flip = self._flip_mask(flip)
         bx, by, bz = self.box
         P = self.max_batch
-        if self.channels_last:
-            if out is None:
-                out = torch.empty((P, bz, by, bx, self.M), dtype=torch.float32,
-                                  device=self.volume.device).permute(0, 4, 1, 2, 3)
-            elif tuple(out.shape) != (P, self.M, bz, by, bx) or not out.permute(0, 2, 3, 4, 1).is_contiguous():
-                raise ValueError('out must be the [P, M, bz, by, bx] view of a contiguous [P, bz, by, bx, M] batch')
-            if flip:
-                E.call('seg3d_patch_gather_normalize_mc_flip', E.ptr(self.volume), self._starts_ptr(), E.ptr(out),
-                       E.ptr(self._stat_ws), E.ptr(self._mean_std), self.Z, self.Y, self.X, bx, by, bz, P, self.M,
-                       self._norm_params, flip, E.stream_ptr())
-                return out
-            E.call('seg3d_patch_gather_normalize_mc', E.ptr(self.volume), self._starts_ptr(), E.ptr(out),
-                   E.ptr(self._stat_ws), E.ptr(self._mean_std), self.Z, self.Y, self.X, bx, by, bz, P, self.M,
-                   self._norm_params, E.stream_ptr())
-            return out
         if out is None:
-            out = torch.empty((P, 1, bz, by, bx), dtype=torch.float32, device=self.volume.device)
-        ntype, mean, std, clip, sigma = self._norm
-        if flip:
-            E.call('seg3d_patch_gather_normalize_flip', E.ptr(self.volume), self._starts_ptr(), E.ptr(out),
-                   E.ptr(self._stat_ws), E.ptr(self._mean_std), self.Z, self.Y, self.X, bx, by, bz, P, ntype, mean, std, clip,
-                   sigma, flip, E.stream_ptr())
-            return out
-        E.call('seg3d_patch_gather_normalize', E.ptr(self.volume), self._starts_ptr(), E.ptr(out), E.ptr(self._stat_ws),
-               E.ptr(self._mean_std), self.Z, self.Y, self.X, bx, by, bz, P, ntype, mean, std, clip, sigma, E.stream_ptr())
+            out = torch.empty((P, bz, by, bx, self.M), dtype=torch.float32,
+                              device=self.volume.device).permute(0, 4, 1, 2, 3)
+        elif tuple(out.shape) != (P, self.M, bz, by, bx) or not out.permute(0, 2, 3, 4, 1).is_contiguous():
+            raise ValueError('out must be the [P, M, bz, by, bx] view of a contiguous [P, bz, by, bx, M] batch')
+        E.call('seg3d_patch_gather_normalize_mc_flip', E.ptr(self.volume), self._starts_ptr(), E.ptr(out),
+               E.ptr(self._stat_ws), E.ptr(self._mean_std), self.Z, self.Y, self.X, bx, by, bz, P, self.M,
+               self._norm_params, flip, E.stream_ptr())
         return out
 
     def scatter_current(self, probs, flip=0):
@@ -249,13 +218,9 @@ class SlidingWindowBatcher(object):
             raise ValueError('probs must be contiguous [{}, {}, {}, {}, {}], got {}'.format(P, self.C, bz, by, bx,
                                                                                             tuple(probs.shape)))
         max_box = min(self.X * self.Y * self.Z, min(self.X, bx * P) * min(self.Y, by * P) * min(self.Z, bz * P))
-        if self._wtab is not None or flip:
-            E.call('seg3d_patch_scatter_blend', E.ptr(probs), self._starts_ptr(), self._ctl_ptr(),
-                   E.ptr(self._wtab) if self._wtab is not None else None, E.ptr(self.acc), E.ptr(self.count), self.Z, self.Y,
-                   self.X, bx, by, bz, self.C, flip, max_box, E.stream_ptr())
-            return
-        E.call('seg3d_patch_scatter_accumulate', E.ptr(probs), self._starts_ptr(), self._ctl_ptr(), E.ptr(self.acc),
-               E.ptr(self.count), self.Z, self.Y, self.X, bx, by, bz, self.C, max_box, E.stream_ptr())
+        E.call('seg3d_patch_scatter_blend', E.ptr(probs), self._starts_ptr(), self._ctl_ptr(), E.ptr(self._wtab),
+               E.ptr(self.acc), E.ptr(self.count), self.Z, self.Y, self.X, bx, by, bz, self.C, flip, max_box,
+               E.stream_ptr())
 
     # convenience (eager) forms used by tests and the non-graph path
     def gather(self, idx, flip=0):
@@ -715,8 +680,8 @@ def _case_images(model, image, case=None):
 
 def _model_normalizers(model, M):
     dicts = list(model['crop_normalizer_dicts'] or [])
-    if M == 1:
-        return dicts[0] if dicts else None
+    if M == 1:                  # the reference applies crop_normalizers[0] (core/seg_infer.py:221-224); none = no normalisation
+        return dicts[:1] or [None]
     if len(dicts) != M:
         raise ValueError('model has {} crop normalizers for {} modalities'.format(len(dicts), M))
     return dicts
@@ -728,11 +693,8 @@ def segmentation_voi(model, iso_image, start_voxel, end_voxel, use_gpu=True):
     Kept for API parity; whole volumes should go through segmentation_volume, which batches patches on the device."""
     images, M = _case_images(model, iso_image)
     iso_image = images[0]
-    if M == 1:
-        vol = torch.from_numpy(np.ascontiguousarray(iso_image.array, dtype=np.float32)).to(model['device'])
-    else:
-        with torch.cuda.device(model['device']):
-            vol = image_tools.images_to_device(images, model['device'])
+    with torch.cuda.device(model['device']):
+        vol = image_tools.images_to_device(images, model['device'])
     box = [int(end_voxel[d] - start_voxel[d]) for d in range(3)]
     norm = _model_normalizers(model, M)
     probs, _, _ = sliding_window_inference(model['net'], vol, [list(start_voxel)], box, model['out_channels'], norm,
@@ -761,7 +723,7 @@ def segmentation_volume(model, cfg, image, bbox_start_voxel, bbox_end_voxel, use
                         mirror_axes=None):
     """segment a whole volume (reference: seg_infer.py:249-350), everything between the upload of the image and the
     download of the probability maps / mask on the device:
-      resample to the model spacing, size up to a multiple of max_stride (image_tools.py:348-377)  -> seg3d_resample_affine
+      resample to the model spacing, size up to a multiple of max_stride (image_tools.py:348-377)  -> seg3d_resample_affine_mc
       partition (host index arithmetic), one batched gather -> net -> scatter per hipGraph replay, divide by overlap
       resample the class probabilities back onto the image grid, padding 1.0 for class 0 and 0.0 otherwise (:330-333)
       arg-max -> int8 mask (:336-339); largest component / small-component removal (:342-348)
@@ -779,15 +741,13 @@ def segmentation_volume(model, cfg, image, bbox_start_voxel, bbox_end_voxel, use
     blend = cfg_blend if blend is None else check_blend_mode(blend)
     mirror_axes = cfg_axes if mirror_axes is None else check_mirror_axes(mirror_axes)
     with torch.cuda.device(model['device']):
-        return _segmentation_volume(model, cfg, images[0] if M == 1 else images, bbox_start_voxel, bbox_end_voxel,
-                                    batch_size, blend, sigma_scale, mirror_axes)
+        return _segmentation_volume(model, cfg, images, bbox_start_voxel, bbox_end_voxel, batch_size, blend, sigma_scale,
+                                    mirror_axes)
 
 
-def _segmentation_volume(model, cfg, image, bbox_start_voxel, bbox_end_voxel, batch_size, blend='constant',
+def _segmentation_volume(model, cfg, images, bbox_start_voxel, bbox_end_voxel, batch_size, blend='constant',
                          sigma_scale=0.125, mirror_axes=()):
-    images = image if isinstance(image, list) else None
-    if images is not None:
-        image = images[0]
+    image = images[0]
     dev = model['device']
     ms = int(model['max_stride'])
     num_classes = int(model['out_channels'])
@@ -797,13 +757,10 @@ def _segmentation_volume(model, cfg, image, bbox_start_voxel, bbox_end_voxel, ba
     X, Y, Z = image.GetSize()
     Xp, Yp, Zp = image_tools.resampled_size((X, Y, Z), image.GetSpacing(), spacing, ms)
     interp = model.get('interpolation', 'LINEAR') or 'LINEAR'
-    if images is None:
-        src = torch.from_numpy(np.array(image.array, dtype=np.float32, order='C')).to(dev)
-        vol = image_tools.resample_device(src, img_frame, (Xp, Yp, Zp), iso_frame, interp, 0.0)
-    else:                       # all modalities to the model grid in one launch: [Zp, Yp, Xp, M]
-        src = image_tools.images_to_device(images, dev)
-        vol = image_tools.resample_device_mc(src, img_frame, (Xp, Yp, Zp), iso_frame, interp, 0.0)
-        del src
+    # all modalities to the model grid in one launch: [Zp, Yp, Xp, M]
+    src = image_tools.images_to_device(images, dev)
+    vol = image_tools.resample_device_mc(src, img_frame, (Xp, Yp, Zp), iso_frame, interp, 0.0)
+    del src
     if cfg.partition_type == 'DISABLE':
         starts, box = [[0, 0, 0]], (Xp, Yp, Zp)
     elif cfg.partition_type == 'SIZE':
@@ -820,7 +777,7 @@ def _segmentation_volume(model, cfg, image, bbox_start_voxel, bbox_end_voxel, ba
         box = tuple(ends[0][d] - starts[0][d] for d in range(3))
     else:
         raise ValueError('Unsupported partition type!')
-    norm = _model_normalizers(model, 1 if images is None else len(images))
+    norm = _model_normalizers(model, len(images))
     order = model.get('region_class_order')     # region-based model: one sigmoid plane per region, composed label map
     probs, net_mask, batcher = sliding_window_inference(model['net'], vol, starts, box, num_classes, norm,
                                                         batch_size=min(batch_size, max(1, len(starts))), blend=blend,

@@ -118,9 +118,10 @@ def read_case_modalities(entry, case):
 
 class _Case(object):
     """one case resident on the device, plus the host-side per-slice label histogram that lets MASK sampling pick the k-th
-    voxel of a label (in np.argwhere order) without scanning the volume.  `image` is one modality as a [Z, Y, X] tensor,
-    or a list of M co-registered modalities, kept as ONE channels-last [Z, Y, X, M] fp32 tensor (a BraTS case of
-    240 x 240 x 155 x 4 is 143 MB resident); the mask and the histogram are the same for any M."""
+    voxel of a label (in np.argwhere order) without scanning the volume.  `image` is one modality or a list of M
+    co-registered modalities, kept as ONE channels-last [Z, Y, X, M] fp32 tensor `volume` (a BraTS case of
+    240 x 240 x 155 x 4 is 143 MB resident); the attribute `image` is that tensor, or its [Z, Y, X] view for one
+    modality.  The mask and the histogram are the same for any M."""
 
     def __init__(self, image, seg, device):
         images = image if isinstance(image, (list, tuple)) else [image]
@@ -130,10 +131,8 @@ class _Case(object):
         self.seg_frame = (seg.GetSpacing(), seg.GetOrigin(), seg.GetDirection())
         self.size = image.GetSize()
         self.seg_size = seg.GetSize()
-        if self.num_modality == 1:
-            self.image = torch.from_numpy(np.array(image.array, dtype=np.float32, order='C')).to(device)
-        else:
-            self.image = image_tools.images_to_device(images, device)       # [Z, Y, X, M]
+        self.volume = image_tools.images_to_device(images, device)          # [Z, Y, X, M]
+        self.image = self.volume[..., 0] if self.num_modality == 1 else self.volume
         self.seg_host = np.array(seg.array, order='C')                       # [z, y, x], label values as stored
         self.seg = torch.from_numpy(self.seg_host.astype(np.float32)).to(device)
         self._slice_counts = {}
@@ -371,11 +370,12 @@ class SegmentationDataset(Dataset):
                                                                                  self._num_modality))
         if not 1 <= self._num_modality <= 8:
             raise ValueError('case {}: {} modalities, 1..8 are supported'.format(self.case_name(0), self._num_modality))
-        if self._num_modality > 1:
-            if len(self.crop_normalizers) != self._num_modality:
-                raise ValueError('case {}: {} modalities but {} crop normalizers (one per modality, None for none)'.format(
-                    self.case_name(0), self._num_modality, len(self.crop_normalizers)))
-            self._norm_params = image_tools.normalizer_params(self.crop_normalizers, self._num_modality)
+        # (a single-modality case takes crop_normalizers[0], as dataset.py:199-203 does)
+        norms = self.crop_normalizers[:1] if self._num_modality == 1 else self.crop_normalizers
+        if len(norms) != self._num_modality:
+            raise ValueError('case {}: {} modalities but {} crop normalizers (one per modality, None for none)'.format(
+                self.case_name(0), self._num_modality, len(self.crop_normalizers)))
+        self._norm_params = image_tools.normalizer_params(norms, self._num_modality)
         self.device = device if device is not None else torch.device('cuda', torch.cuda.current_device())
         self._cases = {}
 
@@ -394,10 +394,7 @@ class SegmentationDataset(Dataset):
     def case(self, index):
         c = self._cases.get(index)
         if c is None:
-            if self._num_modality == 1:
-                image = read_image(self.im_list[index])
-            else:
-                image = read_case_modalities(self.im_list[index], self.case_name(index))
+            image = read_case_modalities(self.im_list[index], self.case_name(index))
             c = _Case(image, read_image(self.seg_list[index], dtype=None), self.device)
             self._cases[index] = c
         return c
@@ -552,12 +549,12 @@ class SegmentationDataset(Dataset):
         With `resolution_augmentation` the normalised image crop is blurred and / or passed through the low-resolution
         simulation (out of place, one launch each for all modalities) before the intensity transforms; mask and frame
         are untouched.
-        For M > 1 the image crop is a view of channels-last [z, y, x, M] memory (what the stem reads, without a copy)."""
+        The image crop is a view of channels-last [z, y, x, M] memory (what the stem reads, without a copy)."""
         return self.sample(index)
 
     def sample(self, index, out=None):
-        """__getitem__; for M > 1 `out` may be a contiguous [z, y, x, M] destination (a slot of an NDHWC batch) into which
-        the crop is resampled (one launch for all modalities) and normalised in place (one launch)"""
+        """__getitem__; `out` may be a contiguous [z, y, x, M] destination (a slot of an NDHWC batch) into which the crop
+        is resampled (one launch for all modalities) and normalised in place (one launch)"""
         case = self.case(index)
         case_name = self.case_name(index)
         center, crop_spacing = self.sample_crop_geometry(index)
@@ -570,36 +567,25 @@ class SegmentationDataset(Dataset):
             deform = None if aug['control'] is None else (
                 torch.from_numpy(aug['control']).to(self.device, non_blocking=True), self.augmentation['elastic_grid_mm'])
             spatial = {'rotation': aug['rotation'], 'deform': deform}
-        if self._num_modality == 1:
-            im = image_tools.crop_image_device(case.image, case.frame, center, self.crop_size, crop_spacing,
-                                               self.interpolation, mirror=mirror, **spatial)
-            if self.crop_normalizers[0] is not None:
-                im = image_tools.normalize_crop_device(im, self.crop_normalizers[0])
-            for f in filters:                      # blur, then low resolution: each into a fresh tensor
-                im = f(im.contiguous(), None)
-            if aug is not None and aug['intensity'] is not None:
-                im = image_tools.augment_intensity_device(im.contiguous(), aug['intensity'], aug['seed'])
-            im = im.unsqueeze(0)
+        # the k filters of this sample run out of place and the last one must write the destination, so the
+        # resampling launch writes the destination for even k and a scratch buffer for odd k: no copy pass
+        if filters:
+            cz, cy, cx = (int(v) for v in self.crop_size[::-1])
+            shape = (cz, cy, cx, self._num_modality)
+            if out is None:
+                out = torch.empty(shape, dtype=torch.float32, device=self.device)
+            scratch = torch.empty(shape, dtype=torch.float32, device=self.device)
+            first, other = (out, scratch) if len(filters) % 2 == 0 else (scratch, out)
         else:
-            # the k filters of this sample run out of place and the last one must write the destination, so the
-            # resampling launch writes the destination for even k and a scratch buffer for odd k: no copy pass
-            if filters:
-                cz, cy, cx = (int(v) for v in self.crop_size[::-1])
-                shape = (cz, cy, cx, self._num_modality)
-                if out is None:
-                    out = torch.empty(shape, dtype=torch.float32, device=self.device)
-                scratch = torch.empty(shape, dtype=torch.float32, device=self.device)
-                first, other = (out, scratch) if len(filters) % 2 == 0 else (scratch, out)
-            else:
-                first = out
-            im = image_tools.crop_image_device_mc(case.image, case.frame, center, self.crop_size, crop_spacing,
-                                                  self.interpolation, out=first, mirror=mirror, **spatial)
-            im = image_tools.normalize_crop_device_mc(im, self._norm_params, out=im)
-            for f in filters:
-                im, other = f(im, other), im
-            if aug is not None and aug['intensity'] is not None:
-                image_tools.augment_intensity_device(im, aug['intensity'], aug['seed'])
-            im = im.permute(3, 0, 1, 2)
+            first = out
+        im = image_tools.crop_image_device_mc(case.volume, case.frame, center, self.crop_size, crop_spacing,
+                                              self.interpolation, out=first, mirror=mirror, **spatial)
+        im = image_tools.normalize_crop_device_mc(im, self._norm_params, out=im)
+        for f in filters:
+            im, other = f(im, other), im
+        if aug is not None and aug['intensity'] is not None:
+            image_tools.augment_intensity_device(im, aug['intensity'], aug['seed'])
+        im = im.permute(3, 0, 1, 2)
         seg = image_tools.crop_image_device(case.seg, case.seg_frame, center, self.crop_size, crop_spacing, 'NN',
                                             mirror=mirror, **spatial)
         origin = image_tools.crop_origin(center, self.crop_size, crop_spacing)
@@ -611,7 +597,7 @@ class SegmentationDataset(Dataset):
 
 
 class DeviceCropLoader(object):
-    """batches of device-resident samples in sampler order: iterable of (crops [B,1,z,y,x], masks [B,1,z,y,x], frames,
+    """batches of device-resident samples in sampler order: iterable of (crops [B,M,z,y,x], masks [B,1,z,y,x], frames,
     case names).  Replaces torch's DataLoader + worker processes (core/seg_train.py:69-70) for the GPU data path."""
 
     def __init__(self, dataset, sampler, batch_size, drop_last=False):
@@ -622,25 +608,8 @@ class DeviceCropLoader(object):
         return n // self.batch_size if self.drop_last else (n + self.batch_size - 1) // self.batch_size
 
     def __iter__(self):
-        if self.dataset.num_modality() > 1:
-            yield from self._iter_channels_last()
-            return
-        ims, segs, frames, names = [], [], [], []
-        for index in self.sampler:
-            im, seg, frame, name = self.dataset[index]
-            ims.append(im)
-            segs.append(seg)
-            frames.append(frame)
-            names.append(name)
-            if len(ims) == self.batch_size:
-                yield torch.stack(ims), torch.stack(segs), np.stack(frames), names
-                ims, segs, frames, names = [], [], [], []
-        if ims and not self.drop_last:
-            yield torch.stack(ims), torch.stack(segs), np.stack(frames), names
-
-    def _iter_channels_last(self):
-        """M > 1: every sample is resampled straight into slot b of a fresh [B, z, y, x, M] batch (no stack, no layout
-        kernel); the batch is handed out as its [B, M, z, y, x] view"""
+        """every sample is resampled straight into slot b of a fresh [B, z, y, x, M] batch (no stack, no layout kernel);
+        the batch is handed out as its [B, M, z, y, x] view"""
         M = self.dataset.num_modality()
         cz, cy, cx = (int(v) for v in self.dataset.crop_size[::-1])
         batch, segs, frames, names = None, [], [], []

@@ -201,36 +201,24 @@ def _crop_index_map(src_frame, dst_frame, out_size, rotation, mirror):
 
 def resample_device(src, src_frame, out_size, dst_frame, interp_method, padding_value=0.0, mirror=None, rotation=None,
                     deform=None):
-    """src: float32 device tensor [Z, Y, X]; returns the float32 device tensor [Zo, Yo, Xo] of the destination grid.
-    mirror = (x, y, z) flags: the destination grid is sampled mirrored along those axes (mirror_index_affine).
-    rotation = (gx, gy, gz) radians: the grid is rotated about its centre (rotate_index_affine).  deform = (ctrl, grid_mm):
-    the sampled points are displaced by a cubic B-spline field (seg3d_resample_deform; ctrl float32 device
-    [gz, gy, gx, 3] mm, bspline_control_dims points).  Without the last two this is the plain affine launch."""
-    if interp_method not in ('LINEAR', 'NN'):
-        raise ValueError('Unsupported interpolation type.')
+    """src: float32 device tensor [Z, Y, X]; returns the float32 device tensor [Zo, Yo, Xo] of the destination grid: the
+    M = 1 case of resample_device_mc (a [Z, Y, X] volume is the same memory as [Z, Y, X, 1])."""
     E.require_device(src)
-    src = src.contiguous()
-    Zi, Yi, Xi = src.shape
-    Xo, Yo, Zo = (int(v) for v in out_size)
-    dst = torch.empty((Zo, Yo, Xo), dtype=torch.float32, device=src.device)
-    M = _crop_index_map(src_frame, dst_frame, (Xo, Yo, Zo), rotation, mirror)
-    if deform is None:
-        E.call('seg3d_resample_affine', E.ptr(src), E.ptr(dst), Xi, Yi, Zi, Xo, Yo, Zo,
-               M.ctypes.data_as(ctypes.c_void_p), int(interp_method == 'LINEAR'), float(padding_value), E.stream_ptr())
-        return dst
-    L, ctrl, g, t, mask = _deform_call_args(src_frame, dst_frame, (Xo, Yo, Zo), deform, mirror)
-    E.call('seg3d_resample_deform', E.ptr(src), E.ptr(dst), Xi, Yi, Zi, Xo, Yo, Zo, M.ctypes.data_as(ctypes.c_void_p),
-           int(interp_method == 'LINEAR'), float(padding_value), L.ctypes.data_as(ctypes.c_void_p), E.ptr(ctrl), g[0], g[1],
-           g[2], t.ctypes.data_as(ctypes.c_void_p), mask, E.stream_ptr())
-    return dst
+    if src.dim() != 3:
+        raise ValueError('src must be a [Z, Y, X] tensor')
+    return resample_device_mc(src.unsqueeze(3), src_frame, out_size, dst_frame, interp_method, padding_value,
+                              mirror=mirror, rotation=rotation, deform=deform)[..., 0]
 
 
 def resample_device_mc(src, src_frame, out_size, dst_frame, interp_method, padding_value=0.0, out=None, mirror=None,
                        rotation=None, deform=None):
     """M co-registered channels in one launch: src float32 device tensor [Z, Y, X, M] (channels-last) -> [Zo, Yo, Xo, M].
     `out`: a contiguous [Zo, Yo, Xo, M] destination, e.g. slot b of an NDHWC batch.  Channel m equals resample_device
-    on src[..., m] bit for bit (seg3d_resample_affine_mc; with `deform` seg3d_resample_deform_mc).  rotation / deform as
-    in resample_device."""
+    on src[..., m] bit for bit (seg3d_resample_affine_mc; with `deform` seg3d_resample_deform_mc).
+    mirror = (x, y, z) flags: the destination grid is sampled mirrored along those axes (mirror_index_affine).
+    rotation = (gx, gy, gz) radians: the grid is rotated about its centre (rotate_index_affine).  deform = (ctrl, grid_mm):
+    the sampled points are displaced by a cubic B-spline field (ctrl float32 device [gz, gy, gx, 3] mm,
+    bspline_control_dims points).  Without the last two this is the plain affine launch."""
     if interp_method not in ('LINEAR', 'NN'):
         raise ValueError('Unsupported interpolation type.')
     E.require_device(src)
@@ -268,8 +256,10 @@ def planar_to_channels_last(planes):
 
 def images_to_device(images, device):
     """list of M co-registered Image3d -> resident float32 [Z, Y, X, M] device tensor"""
-    planes = np.stack([np.asarray(im.array, dtype=np.float32) for im in images], 0)
-    return planar_to_channels_last(torch.from_numpy(planes).to(device))
+    planes = torch.from_numpy(np.stack([np.asarray(im.array, dtype=np.float32) for im in images], 0)).to(device)
+    if len(images) == 1:                    # [1, Z, Y, X] is the same memory as [Z, Y, X, 1]
+        return planes[0].unsqueeze(3)
+    return planar_to_channels_last(planes)
 
 
 def normalizer_params(normalizers, num_modality):
@@ -402,15 +392,10 @@ def crop_origin(cropping_center, cropping_size, cropping_spacing):
 
 def crop_image_device(volume, frame, cropping_center, cropping_size, cropping_spacing, interp_method, mirror=None,
                       rotation=None, deform=None):
-    """volume: float32 device tensor [Z, Y, X] with frame (spacing, origin, direction) -> crop [z, y, x] of
-    `cropping_size` voxels at `cropping_spacing`, centred at the world point `cropping_center`, zero outside;
-    mirror = (x, y, z) flags: the crop comes out mirrored along those axes (same launch, mirrored index map);
-    rotation / deform: training augmentation inside the same launch, see resample_device"""
-    size = [int(cropping_size[idx]) for idx in range(3)]
-    spacing = [float(cropping_spacing[idx]) for idx in range(3)]
-    dst_frame = (spacing, crop_origin(cropping_center, size, spacing), frame[2])
-    return resample_device(volume, frame, size, dst_frame, interp_method, 0.0, mirror=mirror, rotation=rotation,
-                           deform=deform)
+    """volume: float32 device tensor [Z, Y, X] with frame (spacing, origin, direction) -> crop [z, y, x]: the M = 1 case
+    of crop_image_device_mc"""
+    return crop_image_device_mc(volume.unsqueeze(3), frame, cropping_center, cropping_size, cropping_spacing, interp_method,
+                                mirror=mirror, rotation=rotation, deform=deform)[..., 0]
 
 
 def crop_image(image, cropping_center, cropping_size, cropping_spacing, interp_method):
@@ -424,29 +409,17 @@ def crop_image(image, cropping_center, cropping_size, cropping_spacing, interp_m
 
 def normalize_crop_device(crop, normalizer):
     """apply a FixedNormalizer / AdaptiveNormalizer (utils/normalizer.py) to a float32 device crop [z, y, x] with the
-    patch kernel of the inference path (csrc/patch.hip: fp64 statistics, population std floored at 1e-6)"""
-    d = normalizer.to_dict() if hasattr(normalizer, 'to_dict') else dict(normalizer)
-    crop = crop.contiguous()
-    bz, by, bx = crop.shape
-    if d['type'] == 0:
-        ntype, mean, std, clip, sigma = 0, float(d['mean']), float(d['stddev']), int(bool(d['clip'])), 1.0
-    elif d['type'] == 1:
-        ntype, mean, std, clip, sigma = 1, 0.0, 1.0, 1, float(d['clip_sigma'])
-    else:
-        raise ValueError('Unsupported normalization type.')
-    dev = crop.device
-    out = torch.empty((1, 1, bz, by, bx), dtype=torch.float32, device=dev)
-    starts = torch.zeros((1, 3), dtype=torch.int32, device=dev)
-    ws = torch.empty((E.query('seg3d_patch_stats_blocks', bx, by, bz) * 2,), dtype=torch.float64, device=dev)
-    mean_std = torch.empty((1, 2), dtype=torch.float32, device=dev)
-    E.call('seg3d_patch_gather_normalize', E.ptr(crop), E.ptr(starts), E.ptr(out), E.ptr(ws), E.ptr(mean_std), bz, by, bx,
-           bx, by, bz, 1, ntype, mean, std, clip, sigma, E.stream_ptr())
-    return out[0, 0]
+    patch kernel of the inference path (csrc/patch.hip: fp64 statistics, population std floored at 1e-6): the M = 1 case
+    of normalize_crop_device_mc"""
+    return normalize_crop_device_mc(crop.contiguous().unsqueeze(3), normalizer_params([normalizer], 1))[..., 0]
 
 
 def crop_image_device_mc(volume, frame, cropping_center, cropping_size, cropping_spacing, interp_method, out=None,
                          mirror=None, rotation=None, deform=None):
-    """crop_image_device for a channels-last [Z, Y, X, M] volume: one launch for all modalities -> [z, y, x, M]"""
+    """volume: float32 device tensor [Z, Y, X, M] (channels-last) with frame (spacing, origin, direction) -> crop
+    [z, y, x, M] of `cropping_size` voxels at `cropping_spacing`, centred at the world point `cropping_center`, zero
+    outside, one launch for all modalities; mirror = (x, y, z) flags: the crop comes out mirrored along those axes (same
+    launch, mirrored index map); rotation / deform: training augmentation inside the same launch, see resample_device_mc"""
     size = [int(cropping_size[idx]) for idx in range(3)]
     spacing = [float(cropping_spacing[idx]) for idx in range(3)]
     dst_frame = (spacing, crop_origin(cropping_center, size, spacing), frame[2])

@@ -1,6 +1,8 @@
 """GPU parity tests of the individual HIP operators against stock torch CPU ops (the operators the reference composes)
 and the oracle's loss closed forms.  Every call goes through the C ABI of libseg3d_hip.so.
 Tolerances: fp32 kernels, 1e-4 absolute on O(1) values (north_star), relative 1e-3..1e-4 on gradients."""
+import ctypes
+
 import numpy as np
 import pytest
 import torch
@@ -1237,6 +1239,181 @@ def test_patch_batcher_against_numpy_oracle(hip_device):
         assert np.array_equal(batcher.count.cpu().numpy(), cnt)
         assert max_err(probs_d, rp) == 0.0          # same summation order as the sequential reference loop
         assert np.array_equal(mask_d.cpu().numpy(), rm)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the single-modality C entries, called directly: each is the M = 1 case of its _mc / _blend entry (no Python path reaches
+# them any more), pinned against the numpy oracle and, bit for bit, against that entry at M = 1
+# ---------------------------------------------------------------------------------------------------------------------
+_SINGLE_NORMS = [{'type': 0, 'mean': -150.0, 'stddev': 280.0, 'clip': True}, {'type': 0, 'mean': -150.0, 'stddev': 280.0, 'clip': False},
+                 {'type': 1, 'clip_sigma': 2.5}, None]
+
+
+def _single_norm_args(d):
+    """(normalizer_type, mean, stddev, clip, clip_sigma) of the single-modality gather entries"""
+    if d is None:
+        return -1, 0.0, 1.0, 0, 1.0
+    if d['type'] == 0:
+        return 0, float(d['mean']), float(d['stddev']), int(bool(d['clip'])), 1.0
+    return 1, 0.0, 1.0, 1, float(d['clip_sigma'])
+
+
+def _gather_single(E, vol, starts, out, dims, d, flip=None):
+    Z, Y, X, bx, by, bz, P = dims
+    ws = torch.empty((P * E.query('seg3d_patch_stats_blocks', bx, by, bz) * 2,), dtype=torch.float64, device=vol.device)
+    ms = torch.empty((P, 2), dtype=torch.float32, device=vol.device)
+    args = (E.ptr(vol), E.ptr(starts), E.ptr(out), E.ptr(ws), E.ptr(ms), Z, Y, X, bx, by, bz, P) + _single_norm_args(d)
+    if flip is None:
+        E.call('seg3d_patch_gather_normalize', *args, E.stream_ptr())
+    else:
+        E.call('seg3d_patch_gather_normalize_flip', *args, flip, E.stream_ptr())
+    return out
+
+
+def _gather_mc1(E, vol, starts, out, dims, d, flip):
+    from segmentation3d.utils.image_tools import normalizer_params
+    Z, Y, X, bx, by, bz, P = dims
+    ws = torch.empty((E.query('seg3d_patch_stats_mc_doubles', bx, by, bz, P, 1),), dtype=torch.float64, device=vol.device)
+    ms = torch.empty((P, 1, 2), dtype=torch.float32, device=vol.device)
+    E.call('seg3d_patch_gather_normalize_mc_flip', E.ptr(vol), E.ptr(starts), E.ptr(out), E.ptr(ws), E.ptr(ms), Z, Y, X, bx,
+           by, bz, P, 1, normalizer_params([d], 1), flip, E.stream_ptr())
+    return out
+
+
+@pytest.mark.parametrize('norm', _SINGLE_NORMS, ids=['fixed_clip', 'fixed', 'adaptive', 'none'])
+def test_single_modality_gather_entries(hip_device, norm):
+    """seg3d_patch_gather_normalize / _flip: 8640 voxels per patch (two statistics chunks, the second partial, no edge a
+    multiple of 4), two distinct starts plus one padding patch, flip masks 0, 1 and 7"""
+    from segmentation3d import _engine as E
+    Z, Y, X, bx, by, bz, P = dims = (20, 23, 29, 24, 20, 18, 3)
+    assert E.query('seg3d_patch_stats_blocks', bx, by, bz) == 2
+    vol_h = (detgen.normal(431, 'single/gather', (Z, Y, X)) * 300 - 200).astype(np.float32)
+    vol = torch.from_numpy(vol_h).to(hip_device)
+    starts_h = [[5, 3, 2], [0, 1, 0], [5, 3, 2]]
+    starts = torch.tensor(starts_h, dtype=torch.int32, device=hip_device)
+    for flip in (None, 0, 1, 7):
+        got = _gather_single(E, vol, starts, torch.empty((P, 1, bz, by, bx), device=hip_device), dims, norm, flip)
+        same = _gather_mc1(E, vol, starts, torch.empty((P, bz, by, bx, 1), device=hip_device), dims, norm, flip or 0)
+        assert torch.equal(got.reshape(-1), same.reshape(-1)), (norm, flip)
+        axes = [ax for bit, ax in ((1, 2), (2, 1), (4, 0)) if (flip or 0) & bit]
+        for p, (sx, sy, sz) in enumerate(starts_h):
+            want = numpy_ref.apply_normalizer(vol_h[sz:sz + bz, sy:sy + by, sx:sx + bx].copy(), norm)
+            e = max_err(got[p, 0], np.flip(want, axes).copy() if axes else want)
+            assert e < 2e-5, (norm, flip, p, e)
+
+
+def test_single_modality_gather_in_place_and_messages(hip_device):
+    """batch == volume for P = 1 and box = volume (a crop normalised in place); a bad clip_sigma and a bad flip mask are
+    refused with a message that starts with the name of the entry that was called"""
+    from segmentation3d import _engine as E
+    Z, Y, X = 20, 23, 29
+    dims = (Z, Y, X, X, Y, Z, 1)
+    norm = {'type': 1, 'clip_sigma': 2.5}
+    vol_h = (detgen.normal(432, 'single/inplace', (Z, Y, X)) * 300 - 200).astype(np.float32)
+    vol = torch.from_numpy(vol_h).to(hip_device)
+    starts = torch.zeros((1, 3), dtype=torch.int32, device=hip_device)
+    out = _gather_single(E, vol, starts, torch.empty((1, 1, Z, Y, X), device=hip_device), dims, norm)
+    _gather_single(E, vol, starts, vol, dims, norm)
+    assert torch.equal(vol, out[0, 0])
+    assert max_err(vol, numpy_ref.apply_normalizer(vol_h.copy(), norm)) < 2e-5
+    with pytest.raises(ValueError, match='^seg3d_patch_gather_normalize: .*clip_sigma'):
+        _gather_single(E, vol, starts, out, dims, {'type': 1, 'clip_sigma': 0.0})
+    with pytest.raises(ValueError, match='^seg3d_patch_gather_normalize_flip: .*flip mask'):
+        _gather_single(E, vol, starts, out, dims, None, flip=8)
+
+
+def test_single_modality_scatter_accumulate_entry(hip_device):
+    """seg3d_patch_scatter_accumulate: three overlapping valid patches and one padding patch against a float32 host loop in
+    list order, bit for bit, and against seg3d_patch_scatter_blend without table and mirror"""
+    from segmentation3d import _engine as E
+    Z, Y, X, bx, by, bz, C, P = 9, 10, 12, 6, 5, 4, 2, 4
+    starts_h = [[1, 1, 1], [3, 3, 2], [4, 2, 3]]
+    probs_h = detgen.uniform(433, 'single/probs', (P, C, bz, by, bx)).astype(np.float32)
+    probs_h[3] = 1e6                                                   # the padding patch: gathered, never scattered
+    acc_h = detgen.normal(434, 'single/acc', (C, Z, Y, X)).astype(np.float32)
+    cnt_h = np.zeros((Z, Y, X), np.float32)
+    lo = np.min(starts_h, 0)
+    ext = np.max(starts_h, 0) + np.array([bx, by, bz]) - lo
+    ctl = torch.tensor(sum(starts_h + [starts_h[0]], []) + list(lo) + list(ext) + [3], dtype=torch.int32, device=hip_device)
+    probs = torch.from_numpy(probs_h).to(hip_device)
+    got = []
+    for entry in ('seg3d_patch_scatter_accumulate', 'seg3d_patch_scatter_blend'):
+        acc, cnt = torch.from_numpy(acc_h).to(hip_device), torch.from_numpy(cnt_h).to(hip_device)
+        extra = (None,) if entry.endswith('blend') else ()
+        flip = (0,) if entry.endswith('blend') else ()
+        E.call(entry, E.ptr(probs), E.ptr(ctl), ctypes.c_void_p(ctl.data_ptr() + 4 * 3 * P), *extra, E.ptr(acc), E.ptr(cnt),
+               Z, Y, X, bx, by, bz, C, *flip, int(np.prod(ext)), E.stream_ptr())
+        got.append((acc.cpu().numpy(), cnt.cpu().numpy()))
+    for k, s in enumerate(starts_h):
+        numpy_ref.accumulate_patch(acc_h, cnt_h, s, [s[0] + bx, s[1] + by, s[2] + bz], probs_h[k])
+    assert acc_h.dtype == np.float32 and set(np.unique(cnt_h)) == {0.0, 1.0, 2.0, 3.0}
+    for acc, cnt in got:
+        assert np.array_equal(acc, acc_h) and np.array_equal(cnt, cnt_h)
+
+
+def _single_rs():
+    """source (x, y, z) = (11, 9, 7) and destination (10, 8, 6) grids with other spacings and oblique directions; the
+    destination is shifted so that part of it lies outside the source"""
+    from test_augment import oracle_rotation
+
+    def frame(spacing, origin, angles):
+        return (tuple(spacing), tuple(origin), tuple(np.asarray(oracle_rotation(angles), dtype=np.float64).ravel()))
+    return dict(src_size=(11, 9, 7), src=frame((0.7, 1.1, 2.3), (-5.0, 3.0, 1.0), (0.0, 0.0, 0.35)),
+                dst_size=(10, 8, 6), dst=frame((0.9, 0.8, 1.7), (-7.5, 5.0, 1.0), (0.1, -0.05, -0.6)))
+
+
+def _resample_single(E, entry, src, M, linear, deform=None):
+    """one of the four resample entries on the _single_rs grids, pad -2.5; deform = (L, ctrl, t)"""
+    c = _single_rs()
+    (Xi, Yi, Zi), (Xo, Yo, Zo) = c['src_size'], c['dst_size']
+    A = np.ascontiguousarray(numpy_ref.index_affine(c['src'], c['dst']), dtype=np.float64)
+    dst = torch.empty((Zo, Yo, Xo), dtype=torch.float32, device=src.device)
+    args = (E.ptr(src), E.ptr(dst)) + ((1, 1) if entry.endswith('_mc') else ()) + (
+        Xi, Yi, Zi, Xo, Yo, Zo, A.ctypes.data_as(ctypes.c_void_p), int(linear), -2.5)
+    if deform is not None:
+        L, ctrl, t = deform
+        gz, gy, gx = ctrl.shape[:3]
+        args += (L.ctypes.data_as(ctypes.c_void_p), E.ptr(ctrl), gx, gy, gz, t.ctypes.data_as(ctypes.c_void_p), 0)
+    E.call(entry, *args, E.stream_ptr())
+    return dst
+
+
+@pytest.mark.parametrize('interp', ['LINEAR', 'NN'])
+def test_single_modality_resample_entries(hip_device, interp):
+    """seg3d_resample_affine / seg3d_resample_deform between two oblique grids, part of the destination outside the source:
+    the affine entry against oracle/numpy_ref, both against their _mc entry at M = 1 bit for bit, and the deform entry with
+    the smallest accepted control grid -- a zero field is the affine entry exactly, a non-zero one against the oracle of
+    test_augment (LINEAR; nearest neighbour is pinned by the exact comparisons)"""
+    from segmentation3d import _engine as E
+    from test_augment import oracle_coords, oracle_sample
+    c = _single_rs()
+    linear = interp == 'LINEAR'
+    src_h = detgen.normal(435, 'single/rs', c['src_size'][::-1]).astype(np.float32)
+    src = torch.from_numpy(src_h).to(hip_device)
+    ref = numpy_ref.resample_affine(src_h, numpy_ref.index_affine(c['src'], c['dst']), c['dst_size'], linear, pad=-2.5)
+    assert 0.1 < float((ref == -2.5).mean()) < 0.9                       # inside and padded voxels both occur
+    plain = _resample_single(E, 'seg3d_resample_affine', src, 1, linear)
+    e = max_err(plain, ref)
+    assert e < (1e-5 if linear else 1e-7), e
+    assert torch.equal(plain, _resample_single(E, 'seg3d_resample_affine_mc', src, 1, linear))
+    # control grid: h = 4 mm over the destination grid, floor((n - 1) sp / h) + 4 points per axis
+    h = 4.0
+    t = np.array([sp / h for sp in c['dst'][0]], dtype=np.float64)
+    g = [int(np.floor((n - 1) * tt)) + 4 for n, tt in zip(c['dst_size'], t)]
+    s_sp, _, s_dir = (np.asarray(v, dtype=np.float64) for v in c['src'])
+    L = np.ascontiguousarray(np.diag(1.0 / s_sp) @ np.linalg.inv(s_dir.reshape(3, 3)), dtype=np.float64)
+    zero = torch.zeros((g[2], g[1], g[0], 3), dtype=torch.float32, device=hip_device)
+    assert torch.equal(_resample_single(E, 'seg3d_resample_deform', src, 1, linear, (L, zero, t)), plain)
+    with pytest.raises(ValueError, match='^seg3d_resample_deform: '):      # one control point short on x
+        _resample_single(E, 'seg3d_resample_deform', src, 1, linear, (L, zero[:, :, :-1].contiguous(), t))
+    ctrl_h = ((detgen.uniform(436, 'single/ctrl', (g[2], g[1], g[0], 3)) - 0.5) * (2 * 0.9 * h / 6.0)).astype(np.float32)
+    ctrl = torch.from_numpy(ctrl_h).to(hip_device)
+    bent = _resample_single(E, 'seg3d_resample_deform', src, 1, linear, (L, ctrl, t))
+    assert torch.equal(bent, _resample_single(E, 'seg3d_resample_deform_mc', src, 1, linear, (L, ctrl, t)))
+    assert not torch.equal(bent, plain)
+    if linear:
+        want = oracle_sample(src_h, oracle_coords(c['src'], c['dst'], c['dst_size'], None, ctrl_h, h), True, -2.5)
+        assert max_err(bent, want) < 2e-5
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -1,5 +1,6 @@
-"""Multi-modality input on the MI355X: the two channels-last kernels against the single-channel kernels the suite already
-pins (bit for bit), the file-backed dataset against the numpy oracle, train() -> segmentation() end to end against a CPU
+"""Multi-modality input on the MI355X: the MC = 2 / 3 / 4 / 0 instantiations of the two channels-last kernel templates
+against their MC = 1 instantiation, which single-modality volumes run (bit for bit; the numpy oracle pins MC = 1 in
+test_gpu_kernels.py), the file-backed dataset against the numpy oracle, train() -> segmentation() end to end against a CPU
 oracle, and sharded inference."""
 import ctypes
 import os
