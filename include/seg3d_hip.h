@@ -545,6 +545,26 @@ int seg3d_patch_scatter_blend(const float* probs, const int* starts_xyz, const i
                               const float* wtab, float* acc, float* count, int Z, int Y, int X, int bx, int by, int bz,
                               int C, int flip_mask, long long max_box_voxels, void* stream);
 
+/* ---- model ensembling on the image grid (not in the reference) ---------------------------
+ * One launch per ensemble member: its finalized probabilities src [C][Zi][Yi][Xi] (planar, on the member's own grid) are
+ * interpolated onto the image grid and added with the member's weight into acc [C][Zo][Yo][Xo].  For an output voxel v
+ * and plane c:
+ *   s_c = what seg3d_resample_affine(src_c, .., affine_host, linear = 1, pad) writes at v, bit for bit, with pad = pad0
+ *         for c = 0 and 0 otherwise (the coordinate, the inside test and the weights are computed once per voxel and
+ *         shared by the C planes);
+ *   a_c = first ? weight * s_c : acc_c + weight * s_c in fp32, a rounded multiply and a rounded add (no FMA);
+ *         acc_c = a_c.  With `first` acc is not read, so the caller need not clear it.
+ * mask (int8 [Zo][Yo][Xo]; NULL on every member but the last) is written from the a_c of the same pass:
+ *   order_host == NULL: mask = argmax_c a_c, first maximum wins (the rule of seg3d_finalize_argmax);
+ *   order_host != NULL (C host ints in 1..127): mask = 0, then for r = 0 .. C-1 in order a_r > 0.5 (strictly) writes
+ *   order_host[r] (the rule of seg3d_finalize_regions).
+ * The caller normalises the weights to sum 1, so acc after the last member is the mean: there is no scale pass.
+ * 1 <= C <= 16.  affine_host: 12 doubles on the HOST, as seg3d_resample_affine.  16-byte accesses when Xo % 4 == 0 and acc
+ * is 16-byte (mask 4-byte) aligned, a scalar path otherwise; no workspace, no host sync. */
+int seg3d_ensemble_accumulate(const float* src, float* acc, signed char* mask, int C, int Xi, int Yi, int Zi, int Xo,
+                              int Yo, int Zo, const double* affine_host, float weight, int first, float pad0,
+                              const int* order_host, void* stream);
+
 /* ---- evaluation metric: utils/metrics.py:5-37 cal_dsc, core/seg_eval.py:8-57 ---------------
  * counts[3k..3k+2] += (area_gt, area_seg, intersection) of labels_host[k] over two label volumes of n elements;
  * the caller zeroes counts first.  dtype: 0 int8, 1 uint8, 2 int16, 3 int32, 4 float32.  1..16 labels per call. */

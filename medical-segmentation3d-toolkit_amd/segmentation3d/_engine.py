@@ -217,6 +217,7 @@ _SIGNATURES = {
     'seg3d_patch_gather_normalize_flip': (_c_int, [_c_p] * 5 + [_c_int] * 8 + [_c_f, _c_f, _c_int, _c_f, _c_int, _c_p]),
     'seg3d_patch_gather_normalize_mc_flip': (_c_int, [_c_p] * 5 + [_c_int] * 8 + [Normalizers, _c_int, _c_p]),
     'seg3d_patch_scatter_blend': (_c_int, [_c_p] * 6 + [_c_int] * 8 + [_c_ll, _c_p]),
+    'seg3d_ensemble_accumulate': (_c_int, [_c_p] * 3 + [_c_int] * 7 + [_c_p, _c_f, _c_int, _c_f, _c_p, _c_p]),
 }
 
 _lib = None

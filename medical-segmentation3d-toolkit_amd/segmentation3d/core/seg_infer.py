@@ -100,6 +100,100 @@ def blend_options(cfg):
     return blend, sigma, axes
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# model ensembling (not in the reference)
+# ---------------------------------------------------------------------------------------------------------------------
+ENSEMBLE_MEMBER_KEYS = ('in_channels', 'out_channels', 'output_activation', 'region_class_order')
+
+
+def ensemble_weights(weights, K):
+    """-> K Python floats that sum to 1: the members' weights, normalised in double.  None = equal weights; K = 1 gives
+    exactly 1.0.  ValueError for a wrong length or an entry that is not a positive finite number."""
+    K = int(K)
+    if K < 1:
+        raise ValueError('an ensemble needs at least one member, got {}'.format(K))
+    if weights is None:
+        weights = [1.0] * K
+    if isinstance(weights, (str, bytes)) or not hasattr(weights, '__len__'):
+        raise ValueError('ensemble weights must be a list of {} numbers, got {!r}'.format(K, weights))
+    if len(weights) != K:
+        raise ValueError('{} ensemble weights for {} members'.format(len(weights), K))
+    w = []
+    for v in weights:
+        if isinstance(v, (bool, str, bytes)) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise ValueError('ensemble weight {!r} is not a number'.format(v))
+        v = float(v)
+        if not (np.isfinite(v) and v > 0.0):
+            raise ValueError('ensemble weight {!r} is not positive and finite'.format(v))
+        w.append(v)
+    if K == 1:
+        return [1.0]
+    total = float(np.sum(np.asarray(w, dtype=np.float64)))
+    if not np.isfinite(total):
+        raise ValueError('ensemble weights {} do not have a finite sum'.format(w))
+    return [v / total for v in w]
+
+
+def check_ensemble_members(members):
+    """the members of an ensemble are averaged plane by plane, so they must agree in in_channels, out_channels,
+    output_activation and region_class_order (ValueError naming the key and the member); network type, spacing,
+    max_stride, interpolation and normalisers may differ.  -> the list of members"""
+    members = list(members)
+    if not members:
+        raise ValueError('an ensemble needs at least one member')
+
+    def value(m, key):
+        v = m.get(key)
+        if key == 'output_activation':
+            return v or 'softmax'
+        if key == 'region_class_order':
+            return None if v is None else [int(l) for l in v]
+        return None if v is None else int(v)
+    for key in ENSEMBLE_MEMBER_KEYS:
+        want = value(members[0], key)
+        for k, m in enumerate(members[1:], 1):
+            if value(m, key) != want:
+                raise ValueError('ensemble member {} has {} = {!r}, member 0 has {!r}'.format(k, key, value(m, key), want))
+    return members
+
+
+def ensemble_options(stage_cfg):
+    """(names, weights, checkpoints) of a stage section of infer_config.py, from its optional keys
+      ensemble = ['fold_0', 'fold_1', ...]   model folders under the model folder
+      ensemble_weights = None                K positive numbers; None = equal
+      checkpoint = 'latest'                  as for a single model, or a list of K
+    names: the K folder names, weights: ensemble_weights(.., K), checkpoints: K selections.  Without the `ensemble` key (or
+    with None) the stage is the single model `model_name`, as before: (None, None, None).  ValueError for an empty list, a
+    non-list, duplicate or non-string names and for a `checkpoint` list whose length is not K (or one without `ensemble`)."""
+    names = getattr(stage_cfg, 'ensemble', None)
+    checkpoint = getattr(stage_cfg, 'checkpoint', 'latest')
+    if names is None:
+        if isinstance(checkpoint, (list, tuple)):
+            raise ValueError('checkpoint = {!r} is a list but the stage has no ensemble'.format(checkpoint))
+        if getattr(stage_cfg, 'ensemble_weights', None) is not None:
+            raise ValueError('ensemble_weights without ensemble')
+        return None, None, None
+    if not isinstance(names, (list, tuple)):
+        raise ValueError('ensemble must be a list of model folder names, got {!r}'.format(names))
+    names = list(names)
+    if not names:
+        raise ValueError('ensemble is empty: list at least one model folder')
+    for n in names:
+        if not isinstance(n, str) or not n:
+            raise ValueError('ensemble entry {!r} is not a model folder name'.format(n))
+    if len(set(names)) != len(names):
+        raise ValueError('ensemble lists a model twice: {}'.format(names))
+    K = len(names)
+    weights = ensemble_weights(getattr(stage_cfg, 'ensemble_weights', None), K)
+    if isinstance(checkpoint, (list, tuple)):
+        if len(checkpoint) != K:
+            raise ValueError('{} checkpoint selections for {} ensemble members'.format(len(checkpoint), K))
+        checkpoints = list(checkpoint)
+    else:
+        checkpoints = [checkpoint] * K
+    return names, weights, checkpoints
+
+
 class SlidingWindowBatcher(object):
     """device-side crop/normalise + accumulate for one resident volume.
 
@@ -653,13 +747,33 @@ def load_models(model_folder, gpu_id=0):
     if scale not in ('coarse', 'fine', 'DISABLE'):
         raise ValueError('Unsupported single scale type!')
     models.coarse_model = models.fine_model = None
-    if scale in ('coarse', 'DISABLE'):
-        models.coarse_model = load_single_model(os.path.join(model_folder, infer_cfg.coarse.model_name), gpu_id,
-                                                getattr(infer_cfg.coarse, 'checkpoint', 'latest'))
-    if scale in ('fine', 'DISABLE'):
-        models.fine_model = load_single_model(os.path.join(model_folder, infer_cfg.fine.model_name), gpu_id,
-                                              getattr(infer_cfg.fine, 'checkpoint', 'latest'))
+    for stage in ('coarse', 'fine'):
+        if scale not in (stage, 'DISABLE'):
+            continue
+        stage_cfg = getattr(infer_cfg, stage)
+        names, weights, checkpoints = ensemble_options(stage_cfg)
+        if names is None:
+            models[stage + '_model'] = load_single_model(os.path.join(model_folder, stage_cfg.model_name), gpu_id,
+                                                         getattr(stage_cfg, 'checkpoint', 'latest'))
+            continue
+        # an ensemble stage: every member is a model folder of its own; <stage>_model stays member 0 for callers that
+        # read it
+        members = check_ensemble_members([load_single_model(os.path.join(model_folder, n), gpu_id, c)
+                                          for n, c in zip(names, checkpoints)])
+        models[stage + '_model'] = members[0]
+        models[stage + '_members'] = members
+        models[stage + '_weights'] = weights
     return models
+
+
+def _segment_stage(models, stage, image, bbox_start_voxel, bbox_end_voxel, tta):
+    """one stage of segmentation(): its ensemble when the stage section has an `ensemble` key, else its single model"""
+    cfg = getattr(models['infer_cfg'], stage)
+    members = models.get(stage + '_members')
+    if members is not None:
+        return segmentation_volume_ensemble(members, cfg, image, bbox_start_voxel, bbox_end_voxel,
+                                            weights=models[stage + '_weights'], **tta)
+    return segmentation_volume(models[stage + '_model'], cfg, image, bbox_start_voxel, bbox_end_voxel, True, **tta)
 
 
 def _case_images(model, image, case=None):
@@ -745,8 +859,13 @@ def segmentation_volume(model, cfg, image, bbox_start_voxel, bbox_end_voxel, use
                                     mirror_axes)
 
 
-def _segmentation_volume(model, cfg, images, bbox_start_voxel, bbox_end_voxel, batch_size, blend='constant',
-                         sigma_scale=0.125, mirror_axes=()):
+def _member_probabilities(model, cfg, images, bbox_start_voxel, bbox_end_voxel, batch_size, blend, sigma_scale, mirror_axes,
+                          src=None):
+    """the front half of a volume job, shared by the single-model path and by every member of an ensemble: resample the
+    image to the model's grid, partition (the bounding box mapped into that grid), run the sliding window.
+    src: the resident [Z, Y, X, M] image when the caller already uploaded it.
+    Returns (probs [C, Zp, Yp, Xp], net_mask int8 [Zp, Yp, Xp], iso_frame, (Xp, Yp, Zp)) on the model's grid; the batcher
+    and the volume graph are gone when this returns (graphs that share the device pool must not be alive together)."""
     image = images[0]
     dev = model['device']
     ms = int(model['max_stride'])
@@ -758,7 +877,8 @@ def _segmentation_volume(model, cfg, images, bbox_start_voxel, bbox_end_voxel, b
     Xp, Yp, Zp = image_tools.resampled_size((X, Y, Z), image.GetSpacing(), spacing, ms)
     interp = model.get('interpolation', 'LINEAR') or 'LINEAR'
     # all modalities to the model grid in one launch: [Zp, Yp, Xp, M]
-    src = image_tools.images_to_device(images, dev)
+    if src is None:
+        src = image_tools.images_to_device(images, dev)
     vol = image_tools.resample_device_mc(src, img_frame, (Xp, Yp, Zp), iso_frame, interp, 0.0)
     del src
     if cfg.partition_type == 'DISABLE':
@@ -779,10 +899,22 @@ def _segmentation_volume(model, cfg, images, bbox_start_voxel, bbox_end_voxel, b
         raise ValueError('Unsupported partition type!')
     norm = _model_normalizers(model, len(images))
     order = model.get('region_class_order')     # region-based model: one sigmoid plane per region, composed label map
-    probs, net_mask, batcher = sliding_window_inference(model['net'], vol, starts, box, num_classes, norm,
-                                                        batch_size=min(batch_size, max(1, len(starts))), blend=blend,
-                                                        sigma_scale=sigma_scale, mirror_axes=mirror_axes,
-                                                        regions_order=order)
+    probs, net_mask, _ = sliding_window_inference(model['net'], vol, starts, box, num_classes, norm,
+                                                  batch_size=min(batch_size, max(1, len(starts))), blend=blend,
+                                                  sigma_scale=sigma_scale, mirror_axes=mirror_axes, regions_order=order)
+    return probs, net_mask, iso_frame, (Xp, Yp, Zp)
+
+
+def _segmentation_volume(model, cfg, images, bbox_start_voxel, bbox_end_voxel, batch_size, blend='constant',
+                         sigma_scale=0.125, mirror_axes=()):
+    image = images[0]
+    num_classes = int(model['out_channels'])
+    spacing = [float(s) for s in model['spacing']]
+    img_frame = (image.GetSpacing(), image.GetOrigin(), image.GetDirection())
+    X, Y, Z = image.GetSize()
+    order = model.get('region_class_order')
+    probs, net_mask, iso_frame, (Xp, Yp, Zp) = _member_probabilities(model, cfg, images, bbox_start_voxel, bbox_end_voxel,
+                                                                     batch_size, blend, sigma_scale, mirror_axes)
     # (voxels no patch covered -- bounding-box runs -- have count 0: their probabilities are 0 and the arg-max there is
     # class 0, as with ITK's division in the reference, see finalize_argmax_kernel)
     # back to the image grid (identity when the image already is at the model spacing and a stride multiple)
@@ -816,6 +948,58 @@ def compose_region_mask(probs, regions_order):
     for r, label in enumerate(regions_order):
         mask[probs[r] > 0.5] = int(label)
     return mask
+
+
+def segmentation_volume_ensemble(members, cfg, image, bbox_start_voxel, bbox_end_voxel, weights=None, batch_size=8, blend=None,
+                                 mirror_axes=None):
+    """segment a whole volume with an ensemble: the weighted mean of the members' probabilities on the image grid, then the
+    label map.  members: loaded models (load_single_model) that agree in
+    check_ensemble_members' keys -- one per cross-validation fold, or several configurations; their network, spacing,
+    max_stride and normalisers may differ.  weights: K positive numbers (ensemble_weights; None = equal).
+    The members run one after another, each exactly as in segmentation_volume up to its finalized probabilities on its own
+    grid (resample, partition with the bounding box mapped into that grid, sliding window with the stage's blending and
+    mirror TTA); one seg3d_ensemble_accumulate launch then interpolates all its planes onto the image grid and adds them
+    with the member's weight, and the launch of the last member writes the label map in the same pass (arg-max, or the
+    region overwrite rule for sigmoid members).  Also when a member's grid is the image grid.  Only one member's
+    probabilities and volume graph exist at a time.
+    Returns (mean_probs: list of Image3d, mask: Image3d int8), like segmentation_volume."""
+    members = check_ensemble_members(members)
+    K = len(members)
+    weights = ensemble_weights(weights, K)
+    images, _ = _case_images(members[0], image)
+    dev = members[0]['device']
+    for k, m in enumerate(members):
+        if m['device'] != dev:
+            raise ValueError('ensemble member {} is on {}, member 0 on {}'.format(k, m['device'], dev))
+    cfg_blend, sigma_scale, cfg_axes = blend_options(cfg)
+    blend = cfg_blend if blend is None else check_blend_mode(blend)
+    mirror_axes = cfg_axes if mirror_axes is None else check_mirror_axes(mirror_axes)
+    with torch.cuda.device(dev):
+        image = images[0]
+        num_classes = int(members[0]['out_channels'])
+        order = members[0].get('region_class_order')
+        img_frame = (image.GetSpacing(), image.GetOrigin(), image.GetDirection())
+        X, Y, Z = image.GetSize()
+        src = image_tools.images_to_device(images, dev)
+        acc = torch.empty((num_classes, Z, Y, X), dtype=torch.float32, device=dev)      # the first member overwrites it
+        mask = torch.empty((Z, Y, X), dtype=torch.int8, device=dev)
+        for k, model in enumerate(members):
+            probs, _, iso_frame, _ = _member_probabilities(model, cfg, images, bbox_start_voxel, bbox_end_voxel, batch_size,
+                                                           blend, sigma_scale, mirror_axes, src=src)
+            # (outside a member's grid: class 0 with probability 1, as in segmentation_volume; region planes are all
+            # foreground and 0 there)
+            image_tools.ensemble_accumulate_device(probs, iso_frame, acc, img_frame, weights[k], k == 0,
+                                                   pad0=1.0 if order is None else 0.0,
+                                                   mask=mask if k == K - 1 else None, regions_order=order)
+            del probs       # stream-ordered: the next member may reuse the block after the launch above
+        del src
+        labels = list(range(1, num_classes)) if order is None else sorted(set(order))
+        if getattr(cfg, 'pick_largest_cc', False) and labels:
+            mask = image_tools.connected_component_filter_device(mask, labels, 'largest')
+        if getattr(cfg, 'remove_small_cc', 0) and cfg.remove_small_cc > 0 and labels:
+            mask = image_tools.connected_component_filter_device(mask, labels, 'min_size', int(cfg.remove_small_cc))
+        mean_probs = [Image3d(acc[c].cpu().numpy(), *img_frame) for c in range(num_classes)]
+        return mean_probs, Image3d(mask.cpu().numpy(), *img_frame)
 
 
 _IMAGE_SUFFIXES = ('.mhd', '.nii', '.hdr', '.nii.gz', '.mha', '.image3d')     # core/seg_infer.py:80, 375-376
@@ -929,14 +1113,14 @@ def segmentation(input_path, model_folder, output_folder, seg_name, gpu_id, retu
         read_image_time = time.time() - begin
         begin = time.time()
         if scale == 'coarse':
-            mean_probs, mask = segmentation_volume(models['coarse_model'], models['infer_cfg'].coarse, image, None, None, True, **tta)
+            mean_probs, mask = _segment_stage(models, 'coarse', image, None, None, tta)
         elif scale == 'fine':
-            mean_probs, mask = segmentation_volume(models['fine_model'], models['infer_cfg'].fine, image, None, None, True, **tta)
+            mean_probs, mask = _segment_stage(models, 'fine', image, None, None, tta)
         else:
             # coarse -> fine cascade (seg_infer.py:428-444): the coarse mask's bounding box restricts the fine pass
             from segmentation3d.utils.image_tools import get_bounding_box
             print('Coarse segmentation: ')
-            _, mask = segmentation_volume(models['coarse_model'], models['infer_cfg'].coarse, image, None, None, True, **tta)
+            _, mask = _segment_stage(models, 'coarse', image, None, None, tta)
             start_voxel, end_voxel = get_bounding_box(mask, None)
             if start_voxel is None:
                 start_voxel, end_voxel = [0, 0, 0], list(mask.GetSize())
@@ -944,8 +1128,7 @@ def segmentation(input_path, model_folder, output_folder, seg_name, gpu_id, retu
             for idx in range(3):
                 bbox_ratio *= (end_voxel[idx] - start_voxel[idx]) / mask.GetSize()[idx]
             print('Fine segmentation (bbox ratio: {:.2f}%): '.format(bbox_ratio))
-            mean_probs, mask = segmentation_volume(models['fine_model'], models['infer_cfg'].fine, image, start_voxel,
-                                                   end_voxel, True, **tta)
+            mean_probs, mask = _segment_stage(models, 'fine', image, start_voxel, end_voxel, tta)
         torch.cuda.synchronize()
         inference_time = time.time() - begin
         total += inference_time

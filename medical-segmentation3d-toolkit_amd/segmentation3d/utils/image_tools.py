@@ -244,6 +244,46 @@ def resample_device_mc(src, src_frame, out_size, dst_frame, interp_method, paddi
     return out
 
 
+def ensemble_accumulate_device(probs, src_frame, acc, dst_frame, weight, first, pad0=1.0, mask=None, regions_order=None):
+    """one ensemble member onto the image grid (seg3d_ensemble_accumulate):
+    probs float32 contiguous device [C, Zi, Yi, Xi] on the grid `src_frame`, acc float32 contiguous device [C, Zo, Yo, Xo]
+    on the grid `dst_frame`.  Plane c of probs is resampled exactly as resample_device(probs[c], src_frame, (Xo, Yo, Zo),
+    dst_frame, 'LINEAR', pad0 if c == 0 else 0.0) and acc[c] = weight * that when `first` (acc is not read), else
+    acc[c] + weight * that (float32, rounded multiply then rounded add).  mask: None, or an int8 device [Zo, Yo, Xo] tensor
+    that receives the label map of the updated acc in the same pass -- the first-maximum arg-max, or with regions_order
+    (C labels in 1..127) the sequential overwrite rule p_r > 0.5.  Returns acc."""
+    for name, t, dtype, dim in (('probs', probs, torch.float32, 4), ('acc', acc, torch.float32, 4),
+                                ('mask', mask, torch.int8, 3)):
+        if t is None and name == 'mask':
+            continue
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype or t.dim() != dim or not t.is_contiguous():
+            raise ValueError('{} must be a contiguous {} device tensor with {} dimensions'.format(name, dtype, dim))
+        if t.device != probs.device:
+            raise ValueError('{} is on {} but probs on {}'.format(name, t.device, probs.device))
+    E.require_device(probs, acc, mask)
+    C, Zi, Yi, Xi = (int(v) for v in probs.shape)
+    Zo, Yo, Xo = (int(v) for v in acc.shape[1:])
+    if not 1 <= C <= 16:
+        raise ValueError('{} planes: 1..16 are supported'.format(C))
+    if int(acc.shape[0]) != C:
+        raise ValueError('acc has {} planes, probs {}'.format(int(acc.shape[0]), C))
+    if min(Zi, Yi, Xi, Zo, Yo, Xo) < 1:
+        raise ValueError('empty grid: probs {}, acc {}'.format(tuple(probs.shape), tuple(acc.shape)))
+    if mask is not None and tuple(mask.shape) != (Zo, Yo, Xo):
+        raise ValueError('mask must be [{}, {}, {}], got {}'.format(Zo, Yo, Xo, tuple(mask.shape)))
+    order = None
+    if regions_order is not None:
+        from segmentation3d.loss.region_loss import check_region_class_order
+        order = (ctypes.c_int * C)(*check_region_class_order(regions_order, C))
+    weight = float(weight)
+    if not np.isfinite(weight):
+        raise ValueError('weight must be finite, got {!r}'.format(weight))
+    M_ = _crop_index_map(src_frame, dst_frame, (Xo, Yo, Zo), None, None)
+    E.call('seg3d_ensemble_accumulate', E.ptr(probs), E.ptr(acc), E.ptr(mask), C, Xi, Yi, Zi, Xo, Yo, Zo,
+           M_.ctypes.data_as(ctypes.c_void_p), weight, int(bool(first)), float(pad0), order, E.stream_ptr())
+    return acc
+
+
 def planar_to_channels_last(planes):
     """[M, Z, Y, X] float32 device tensor -> [Z, Y, X, M] (seg3d_ncdhw_to_ndhwc with N = 1, C = M)"""
     E.require_device(planes)
