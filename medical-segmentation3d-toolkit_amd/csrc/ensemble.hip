@@ -1,70 +1,21 @@
-// ensemble.hip -- model ensembling on the image grid (not in the reference).
-// The members of an ensemble may run at different spacings and strides, so their finalized probabilities can only be
-// averaged on the image grid.  One launch per member: for every image voxel the source coordinate, the inside test and the
-// trilinear weights are computed once and shared by the C planes; every plane is interpolated exactly as
-// seg3d_resample_affine(linear = 1) does it (postproc.hip: same double-precision coordinate, same inside test
-// -0.5 <= c < size - 0.5, same clamped 8-neighbourhood, same lerp order -- the library is built with -ffp-contract=off, so
-// the same expressions give the same bits), multiplied by the member's weight and added into the image-grid accumulator;
-// the launch of the last member writes the label map in the same pass (first-maximum arg-max, or the sequential region
-// overwrite rule of finalize_regions_kernel).
+// ensemble.hip -- the image-grid tail of inference (not in the reference).
+// A model's finalized probabilities live on the model's grid (its own spacing, sized to its stride); one launch per member
+// brings all C planes to the image grid, multiplies them by the member's weight and adds them into the image-grid
+// accumulator, and the launch of the last member writes the label map in the same pass.  A single model is the K = 1 case:
+// weight 1.0f (w * s == s exactly) and `first`, so the accumulator is never read and leaves as the resampled planes.
+// Per image voxel the tap is computed once and shared by the C planes; tap, lerp and label rules are the resampler's and
+// the finalize kernels' own (seg3d_imagegrid.h): every plane equals seg3d_resample_affine(linear = 1) bit for bit.
 // HBM-bound: the bytes are the accumulator planes (C * V * 4 read and written per member), moved 16 bytes per lane; the
 // source taps are gathers from the (usually smaller) planar source and come from cache.  No LDS, no atomics, no scratch.
-#include "seg3d_common.h"
+#include "seg3d_imagegrid.h"
 #include "seg3d_hip.h"
 
 #define ENSEMBLE_MAXC 16
 
-struct EnsAffine {
-  double m[12];  // c = M[:, :3] * (x, y, z) + M[:, 3], rows = (cx, cy, cz)
-};
-
-// the region labels by value, one byte each: label r = (r < 8 ? lo >> 8 r : hi >> 8 (r - 8)) & 0xff.  Bytes in two words
-// instead of an array: the generic kernel indexes them with a runtime r, and a by-value array indexed at run time would be
-// copied to scratch.
-struct EnsOrder {
-  unsigned long long lo, hi;
-};
-__device__ __forceinline__ int ens_label(const EnsOrder& o, int r) {
-  return (int)(((r < 8 ? o.lo >> (8 * r) : o.hi >> (8 * (r - 8)))) & 0xffull);
-}
-
-// what one output voxel needs from the geometry: computed once, used by every plane
-struct EnsTap {
-  i64 r00, r01, r10, r11;  // row offsets (z0, y0), (z0, y1), (z1, y0), (z1, y1) inside a source plane
-  int x0, x1;
-  double dx, dy, dz;
-  bool inside;
-};
-
-__device__ __forceinline__ void ens_tap(const EnsAffine& A, int x, int y, int z, int Xi, int Yi, int Zi, EnsTap& t) {
-  const double cx = A.m[0] * x + A.m[1] * y + A.m[2] * z + A.m[3];
-  const double cy = A.m[4] * x + A.m[5] * y + A.m[6] * z + A.m[7];
-  const double cz = A.m[8] * x + A.m[9] * y + A.m[10] * z + A.m[11];
-  t.inside = cx >= -0.5 && cx < Xi - 0.5 && cy >= -0.5 && cy < Yi - 0.5 && cz >= -0.5 && cz < Zi - 0.5;
-  // (outside -- or a NaN coordinate -- the clamps below still give indices inside the source; they are not read then)
-  const double fx = fmin(fmax(cx, 0.0), (double)(Xi - 1)), fy = fmin(fmax(cy, 0.0), (double)(Yi - 1)),
-               fz = fmin(fmax(cz, 0.0), (double)(Zi - 1));
-  const int x0 = (int)floor(fx), y0 = (int)floor(fy), z0 = (int)floor(fz);
-  const int y1 = y0 + 1 < Yi ? y0 + 1 : y0, z1 = z0 + 1 < Zi ? z0 + 1 : z0;
-  t.x0 = x0;
-  t.x1 = x0 + 1 < Xi ? x0 + 1 : x0;
-  t.dx = fx - x0;
-  t.dy = fy - y0;
-  t.dz = fz - z0;
-  t.r00 = ((i64)z0 * Yi + y0) * Xi;
-  t.r01 = ((i64)z0 * Yi + y1) * Xi;
-  t.r10 = ((i64)z1 * Yi + y0) * Xi;
-  t.r11 = ((i64)z1 * Yi + y1) * Xi;
-}
-
-// resample_mc_lerp of postproc.hip on one planar source
-__device__ __forceinline__ float ens_lerp(const float* __restrict__ p, const EnsTap& t) {
-  const double v000 = p[t.r00 + t.x0], v100 = p[t.r00 + t.x1], v010 = p[t.r01 + t.x0], v110 = p[t.r01 + t.x1];
-  const double v001 = p[t.r10 + t.x0], v101 = p[t.r10 + t.x1], v011 = p[t.r11 + t.x0], v111 = p[t.r11 + t.x1];
-  const double a00 = v000 + (v100 - v000) * t.dx, a01 = v010 + (v110 - v010) * t.dx;
-  const double a10 = v001 + (v101 - v001) * t.dx, a11 = v011 + (v111 - v011) * t.dx;
-  const double b0 = a00 + (a01 - a00) * t.dy, b1 = a10 + (a11 - a10) * t.dy;
-  return (float)(b0 + (b1 - b0) * t.dz);
+// trilinear_lerp on one planar source
+__device__ __forceinline__ float ens_plane(const float* __restrict__ p, const TrilinearTap& t) {
+  return trilinear_lerp(p[t.r00 + t.x0], p[t.r00 + t.x1], p[t.r01 + t.x0], p[t.r01 + t.x1], p[t.r10 + t.x0], p[t.r10 + t.x1],
+                        p[t.r11 + t.x0], p[t.r11 + t.x1], t.dx, t.dy, t.dz);
 }
 
 // CT = 1 .. 5: the class loop is compiled for exactly CT planes; CT = 0: runtime C <= 16.
@@ -74,8 +25,8 @@ __device__ __forceinline__ float ens_lerp(const float* __restrict__ p, const Ens
 template <int CT, bool VEC, bool FIRST>
 __global__ __launch_bounds__(256) void ensemble_accumulate_kernel(const float* __restrict__ src, float* __restrict__ acc,
                                                                     signed char* __restrict__ mask, int Crt, int Xi, int Yi,
-                                                                    int Zi, int Xo, int Yo, int Zo, EnsAffine A, float weight,
-                                                                    float pad0, int mode, EnsOrder order) {
+                                                                    int Zi, int Xo, int Yo, int Zo, Affine12 A, float weight,
+                                                                    float pad0, int mode, RegionOrder order) {
   constexpr int W = VEC ? 4 : 1;
   constexpr int UNROLL = CT > 0 ? CT : 1;   // the generic form keeps a runtime loop over its planes
   const int C = CT > 0 ? CT : Crt;
@@ -87,9 +38,15 @@ __global__ __launch_bounds__(256) void ensemble_accumulate_kernel(const float* _
     const i64 row = it / Xq;
     const int y = (int)(row % Yo), z = (int)(row / Yo);
     const i64 v0 = it * W;  // = (z * Yo + y) * Xo + xq * W
-    EnsTap tap[W];
+    TrilinearTap tap[W];
+    bool inside[W];
 #pragma unroll
-    for (int j = 0; j < W; ++j) ens_tap(A, xq * W + j, y, z, Xi, Yi, Zi, tap[j]);
+    for (int j = 0; j < W; ++j) {
+      double cx, cy, cz;
+      affine12_apply(A, xq * W + j, y, z, cx, cy, cz);
+      inside[j] = SEG3D_INSIDE_BUFFER(cx, cy, cz, Xi, Yi, Zi);
+      trilinear_tap(cx, cy, cz, Xi, Yi, Zi, tap[j]);
+    }
     int lab[W];
     float bv[W];
 #pragma unroll
@@ -114,7 +71,7 @@ __global__ __launch_bounds__(256) void ensemble_accumulate_kernel(const float* _
 #pragma unroll
       for (int j = 0; j < W; ++j) {
         float s = pad;
-        if (tap[j].inside) s = ens_lerp(sp, tap[j]);
+        if (inside[j]) s = ens_plane(sp, tap[j]);
         const float p = __fmul_rn(weight, s);   // one rounding for the product, one for the sum: never an FMA
         a[j] = FIRST ? p : __fadd_rn(a[j], p);
       }
@@ -125,15 +82,11 @@ __global__ __launch_bounds__(256) void ensemble_accumulate_kernel(const float* _
       }
       if (mode == 1) {
 #pragma unroll
-        for (int j = 0; j < W; ++j)
-          if (c == 0 || a[j] > bv[j]) {
-            lab[j] = c;
-            bv[j] = a[j];
-          }
+        for (int j = 0; j < W; ++j) label_first_max(c, a[j], lab[j], bv[j]);
       } else if (mode == 2) {
-        const int label = ens_label(order, c);
+        const int label = region_label(order, c);
 #pragma unroll
-        for (int j = 0; j < W; ++j) lab[j] = a[j] > 0.5f ? label : lab[j];
+        for (int j = 0; j < W; ++j) lab[j] = label_region_overwrite(a[j], label, lab[j]);
       }
     }
     if (mode != 0) {
@@ -169,18 +122,10 @@ extern "C" int seg3d_ensemble_accumulate(const float* src, float* acc, signed ch
   SEG3D_REQUIRE(src && acc && affine_host, "seg3d_ensemble_accumulate: null pointer");
   SEG3D_REQUIRE(C >= 1 && C <= ENSEMBLE_MAXC, "seg3d_ensemble_accumulate: %d planes not in [1, %d]", C, ENSEMBLE_MAXC);
   SEG3D_REQUIRE(Xi > 0 && Yi > 0 && Zi > 0 && Xo > 0 && Yo > 0 && Zo > 0, "seg3d_ensemble_accumulate: bad dims");
-  EnsOrder order = {0ull, 0ull};
-  if (order_host) {
-    for (int r = 0; r < C; ++r) {
-      const int o = order_host[r];
-      SEG3D_REQUIRE(o >= 1 && o <= 127, "seg3d_ensemble_accumulate: region_class_order[%d] = %d not in [1, 127]", r, o);
-      if (r < 8)
-        order.lo |= (unsigned long long)o << (8 * r);
-      else
-        order.hi |= (unsigned long long)o << (8 * (r - 8));
-    }
-  }
-  EnsAffine A;
+  RegionOrder order = {0ull, 0ull};
+  if (order_host && region_order_from_host("seg3d_ensemble_accumulate", order_host, C, &order) != SEG3D_OK)
+    return SEG3D_ERR_INVALID;
+  Affine12 A;
   for (int k = 0; k < 12; ++k) A.m[k] = affine_host[k];
   const int mode = mask ? (order_host ? 2 : 1) : 0;
   // 16-byte rows: every plane of acc starts 16-byte aligned when the base is and Xo % 4 == 0 (the plane is a multiple of 4)

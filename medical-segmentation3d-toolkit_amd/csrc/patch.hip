@@ -10,7 +10,7 @@
 //   * probs *= 1 / count ; mask = argmax_c -> int8                    core/seg_infer.py:325-327, 336-339
 // Voxel (x, y, z) of a volume with size (X, Y, Z) lives at [z][y][x] (utils/image_tools.py:448,465).
 // All kernels are HBM-bound byte movers over fp32 / int8 data.
-#include "seg3d_common.h"
+#include "seg3d_imagegrid.h"
 #include "seg3d_hip.h"
 
 #define PATCH_STAT_CHUNK 8192
@@ -408,7 +408,7 @@ extern "C" int seg3d_patch_scatter_blend(const float* probs, const int* starts, 
                        max_box_voxels, stream);
 }
 
-// acc[c][v] *= 1/count[v] (in place);  mask[v] = argmax_c (first maximum), int8.
+// acc[c][v] *= 1/count[v] (in place);  mask[v] = argmax_c (first maximum: label_first_max, seg3d_imagegrid.h), int8.
 // A voxel no patch covered (count 0: bounding-box runs of the coarse -> fine cascade) gets probabilities 0 and class 0: the
 // reference divides SimpleITK images (core/seg_infer.py:325-327), and ITK's Div functor yields NumericTraits::max() -- not
 // inf -- for a zero denominator, so its product with the zero accumulator is 0, never NaN.
@@ -423,10 +423,7 @@ __global__ __launch_bounds__(256) void finalize_argmax_kernel(float* __restrict_
     for (int c = 0; c < C; ++c) {
       const float p = acc[(i64)c * cstride + v] * r;
       acc[(i64)c * cstride + v] = p;
-      if (c == 0 || p > bv) {
-        best = c;
-        bv = p;
-      }
+      label_first_max(c, p, best, bv);
     }
     if (mask) mask[v] = (signed char)best;
   }
@@ -445,27 +442,29 @@ extern "C" int seg3d_finalize_argmax(float* acc, const float* count, signed char
 }
 
 // Region-based inference: acc[r][v] *= 1/count[v] (in place), then the sequential overwrite
-// rule -- mask = 0; for r = 0 .. R-1 in order: p_r > 0.5 (strictly) sets mask = order[r] -- so regions are listed from the
+// rule (label_region_overwrite, seg3d_imagegrid.h) -- mask = 0; for r = 0 .. R-1 in order: p_r > 0.5 (strictly) sets mask =
+// order[r] -- so regions are listed from the
 // largest to the smallest.  count 0: probabilities 0 and mask 0, as in finalize_argmax_kernel.
-struct RegionOrder {
+// (a byte array, not RegionOrder's two words: unrolled, those put all 16 labels in SGPRs -- 104, 7 waves, 11 % slower at R = 16)
+struct RegionOrderBytes {
   signed char v[16];
 };
 
 __global__ __launch_bounds__(256) void finalize_regions_kernel(float* __restrict__ acc, const float* __restrict__ count,
-                                                                 signed char* __restrict__ mask, int R, RegionOrder order,
+                                                                 signed char* __restrict__ mask, int R, RegionOrderBytes order,
                                                                  i64 vol, i64 cstride) {
   for (i64 v = (i64)blockIdx.x * 256 + threadIdx.x; v < vol; v += (i64)gridDim.x * 256) {
     const float cnt = count[v];
     const float rc = cnt > 0.f ? 1.0f / cnt : 0.f;
-    signed char m = 0;
+    int m = 0;
 #pragma unroll
     for (int r = 0; r < 16; ++r)
       if (r < R) {
         const float p = acc[(i64)r * cstride + v] * rc;
         acc[(i64)r * cstride + v] = p;
-        m = p > 0.5f ? order.v[r] : m;
+        m = label_region_overwrite(p, order.v[r], m);
       }
-    if (mask) mask[v] = m;
+    if (mask) mask[v] = (signed char)m;
   }
 }
 
@@ -476,13 +475,11 @@ extern "C" int seg3d_finalize_regions(float* acc, const float* count, signed cha
                 "seg3d_finalize_regions: bad arguments");
   SEG3D_REQUIRE(R >= 1 && R <= 16, "seg3d_finalize_regions: %d regions not in [1, 16]", R);
   RegionOrder order;
-  for (int r = 0; r < 16; ++r) {
-    const int o = r < R ? order_host[r] : 0;
-    SEG3D_REQUIRE(r >= R || (o >= 1 && o <= 127), "seg3d_finalize_regions: region_class_order[%d] = %d not in [1, 127]", r, o);
-    order.v[r] = (signed char)o;
-  }
+  if (region_order_from_host("seg3d_finalize_regions", order_host, R, &order) != SEG3D_OK) return SEG3D_ERR_INVALID;
+  RegionOrderBytes bytes;
+  for (int r = 0; r < 16; ++r) bytes.v[r] = (signed char)(r < R ? order_host[r] : 0);
   hipLaunchKernelGGL(finalize_regions_kernel, dim3(seg3d_ew_grid(voxels, 256)), dim3(256), 0, (hipStream_t)stream, acc, count,
-                     mask, R, order, (i64)voxels, (i64)(class_stride ? class_stride : voxels));
+                     mask, R, bytes, (i64)voxels, (i64)(class_stride ? class_stride : voxels));
   SEG3D_LAUNCH_CHECK("seg3d_finalize_regions");
   return SEG3D_OK;
 }

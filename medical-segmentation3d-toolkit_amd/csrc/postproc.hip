@@ -12,12 +12,8 @@
 //   ConnectedComponentImageFilter(FullyConnected) + RelabelComponent: components ordered by size, ties by first
 //   voxel in raster order -- the labels here are the component's smallest linear index, which gives the same order.
 // All kernels are HBM-bound byte movers / integer work.
-#include "seg3d_common.h"
+#include "seg3d_imagegrid.h"
 #include "seg3d_hip.h"
-
-struct Affine12 {
-  double m[12];  // c = M[:, :3] * (x, y, z) + M[:, 3], rows = (cx, cy, cz)
-};
 
 // ---- elastic deformation of the sampled point (training augmentation) ----------------------
 // c_src = M (i, 1) + L u(i'): u is a tensor-product cubic B-spline (millimetres, world axes) over a coarse control grid
@@ -141,23 +137,11 @@ static int deform_args(const char* name, int Xo, int Yo, int Zo, const double* l
 // ---- resampling: M co-registered channels in one pass (multi-modality training crops and inference resampling) --------
 // src [Zi][Yi][Xi][M] (channels-last), dst: voxel (x, y, z) of the output grid at dst + ((z * Yo + y) * Xo + x) * dst_stride,
 // M floats.  The affine coordinate, the inside test and the trilinear weights (or the NN index) are computed once per
-// output voxel; each of the 8 taps is one contiguous M-float row.  Per channel the arithmetic is in double with one fixed
-// operation order, clamping and padding whatever M is, so channel m of an M-channel launch equals the M = 1 launch on
-// plane m bit for bit.  A single volume [Zi][Yi][Xi] is the M = 1, dst_stride = 1 case of the same memory:
+// output voxel (trilinear_tap / trilinear_lerp of seg3d_imagegrid.h, shared with the ensemble accumulate); each of the 8
+// taps is one contiguous M-float row.  Per channel the arithmetic is in double with one fixed operation order, clamping and
+// padding whatever M is, so channel m of an M-channel launch equals the M = 1 launch on plane m bit for bit.  A single volume [Zi][Yi][Xi] is the M = 1, dst_stride = 1 case of the same memory:
 // seg3d_resample_affine / seg3d_resample_deform are those entries.
 // MC = 1, 2, 3, 4: compile-time width (VEC: the rows are 8- / 16-byte aligned); MC = 0: runtime M <= 8.
-template <int MC>
-__device__ __forceinline__ void resample_mc_lerp(const float* t000, const float* t100, const float* t010, const float* t110,
-                                                 const float* t001, const float* t101, const float* t011, const float* t111,
-                                                 double dx, double dy, double dz, int m, float* out) {
-  const double v000 = t000[m], v100 = t100[m], v010 = t010[m], v110 = t110[m];
-  const double v001 = t001[m], v101 = t101[m], v011 = t011[m], v111 = t111[m];
-  const double a00 = v000 + (v100 - v000) * dx, a01 = v010 + (v110 - v010) * dx;
-  const double a10 = v001 + (v101 - v001) * dx, a11 = v011 + (v111 - v011) * dx;
-  const double b0 = a00 + (a01 - a00) * dy, b1 = a10 + (a11 - a10) * dy;
-  out[m] = (float)(b0 + (b1 - b0) * dz);
-}
-
 template <int MC, bool VEC, bool DEFORM>
 __global__ __launch_bounds__(256) void resample_affine_mc_kernel(const float* __restrict__ src, float* __restrict__ dst,
                                                                    int Mrt, i64 dst_stride, int Xi, int Yi, int Zi, int Xo,
@@ -173,25 +157,21 @@ __global__ __launch_bounds__(256) void resample_affine_mc_kernel(const float* __
     const int x = (int)(idx % Xo);
     const i64 t = idx / Xo;
     const int y = (int)(t % Yo), z = (int)(t / Yo);
-    double cx = A.m[0] * x + A.m[1] * y + A.m[2] * z + A.m[3];
-    double cy = A.m[4] * x + A.m[5] * y + A.m[6] * z + A.m[7];
-    double cz = A.m[8] * x + A.m[9] * y + A.m[10] * z + A.m[11];
+    double cx, cy, cz;
+    affine12_apply(A, x, y, z, cx, cy, cz);
     if constexpr (DEFORM) deform_apply(lds, dfm, x, y, z, Xo, Yo, Zo, cx, cy, cz);
     float out[MR];
 #pragma unroll
     for (int m = 0; m < MR; ++m) out[m] = pad;
-    if (cx >= -0.5 && cx < Xi - 0.5 && cy >= -0.5 && cy < Yi - 0.5 && cz >= -0.5 && cz < Zi - 0.5) {
+    if (SEG3D_INSIDE_BUFFER(cx, cy, cz, Xi, Yi, Zi)) {
       if (linear) {
-        const double fx = fmin(fmax(cx, 0.0), (double)(Xi - 1)), fy = fmin(fmax(cy, 0.0), (double)(Yi - 1)),
-                     fz = fmin(fmax(cz, 0.0), (double)(Zi - 1));
-        const int x0 = (int)floor(fx), y0 = (int)floor(fy), z0 = (int)floor(fz);
-        const int x1 = x0 + 1 < Xi ? x0 + 1 : x0, y1 = y0 + 1 < Yi ? y0 + 1 : y0, z1 = z0 + 1 < Zi ? z0 + 1 : z0;
-        const double dx = fx - x0, dy = fy - y0, dz = fz - z0;
-        const i64 r00 = ((i64)z0 * Yi + y0) * Xi, r01 = ((i64)z0 * Yi + y1) * Xi, r10 = ((i64)z1 * Yi + y0) * Xi,
-                  r11 = ((i64)z1 * Yi + y1) * Xi;
-        const float *p000 = src + (r00 + x0) * M, *p100 = src + (r00 + x1) * M, *p010 = src + (r01 + x0) * M,
-                    *p110 = src + (r01 + x1) * M, *p001 = src + (r10 + x0) * M, *p101 = src + (r10 + x1) * M,
-                    *p011 = src + (r11 + x0) * M, *p111 = src + (r11 + x1) * M;
+        TrilinearTap tap;
+        trilinear_tap(cx, cy, cz, Xi, Yi, Zi, tap);
+        const double dx = tap.dx, dy = tap.dy, dz = tap.dz;
+        const float *p000 = src + (tap.r00 + tap.x0) * M, *p100 = src + (tap.r00 + tap.x1) * M,
+                    *p010 = src + (tap.r01 + tap.x0) * M, *p110 = src + (tap.r01 + tap.x1) * M,
+                    *p001 = src + (tap.r10 + tap.x0) * M, *p101 = src + (tap.r10 + tap.x1) * M,
+                    *p011 = src + (tap.r11 + tap.x0) * M, *p111 = src + (tap.r11 + tap.x1) * M;
         if constexpr (MC > 0) {
           float t000[MC], t100[MC], t010[MC], t110[MC], t001[MC], t101[MC], t011[MC], t111[MC];
           mc_load_row<MC, VEC>(p000, t000);
@@ -204,11 +184,12 @@ __global__ __launch_bounds__(256) void resample_affine_mc_kernel(const float* __
           mc_load_row<MC, VEC>(p111, t111);
 #pragma unroll
           for (int m = 0; m < MC; ++m)
-            resample_mc_lerp<MC>(t000, t100, t010, t110, t001, t101, t011, t111, dx, dy, dz, m, out);
+            out[m] = trilinear_lerp(t000[m], t100[m], t010[m], t110[m], t001[m], t101[m], t011[m], t111[m], dx, dy, dz);
         } else {
 #pragma unroll
           for (int m = 0; m < MR; ++m)
-            if (m < M) resample_mc_lerp<MC>(p000, p100, p010, p110, p001, p101, p011, p111, dx, dy, dz, m, out);
+            if (m < M)
+              out[m] = trilinear_lerp(p000[m], p100[m], p010[m], p110[m], p001[m], p101[m], p011[m], p111[m], dx, dy, dz);
         }
       } else {
         int xn = (int)floor(cx + 0.5), yn = (int)floor(cy + 0.5), zn = (int)floor(cz + 0.5);

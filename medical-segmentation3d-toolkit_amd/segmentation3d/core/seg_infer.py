@@ -752,12 +752,9 @@ def load_models(model_folder, gpu_id=0):
             continue
         stage_cfg = getattr(infer_cfg, stage)
         names, weights, checkpoints = ensemble_options(stage_cfg)
-        if names is None:
-            models[stage + '_model'] = load_single_model(os.path.join(model_folder, stage_cfg.model_name), gpu_id,
-                                                         getattr(stage_cfg, 'checkpoint', 'latest'))
-            continue
-        # an ensemble stage: every member is a model folder of its own; <stage>_model stays member 0 for callers that
-        # read it
+        if names is None:       # a single model is the ensemble of one member with weight 1.0
+            names, weights, checkpoints = [stage_cfg.model_name], [1.0], [getattr(stage_cfg, 'checkpoint', 'latest')]
+        # every member is a model folder of its own; <stage>_model stays member 0 for callers that read it
         members = check_ensemble_members([load_single_model(os.path.join(model_folder, n), gpu_id, c)
                                           for n, c in zip(names, checkpoints)])
         models[stage + '_model'] = members[0]
@@ -767,13 +764,9 @@ def load_models(model_folder, gpu_id=0):
 
 
 def _segment_stage(models, stage, image, bbox_start_voxel, bbox_end_voxel, tta):
-    """one stage of segmentation(): its ensemble when the stage section has an `ensemble` key, else its single model"""
-    cfg = getattr(models['infer_cfg'], stage)
-    members = models.get(stage + '_members')
-    if members is not None:
-        return segmentation_volume_ensemble(members, cfg, image, bbox_start_voxel, bbox_end_voxel,
-                                            weights=models[stage + '_weights'], **tta)
-    return segmentation_volume(models[stage + '_model'], cfg, image, bbox_start_voxel, bbox_end_voxel, True, **tta)
+    """one stage of segmentation(): its members (one for a stage without an `ensemble` key) with their weights"""
+    return segmentation_volume_ensemble(models[stage + '_members'], getattr(models['infer_cfg'], stage), image,
+                                        bbox_start_voxel, bbox_end_voxel, weights=models[stage + '_weights'], **tta)
 
 
 def _case_images(model, image, case=None):
@@ -839,8 +832,10 @@ def segmentation_volume(model, cfg, image, bbox_start_voxel, bbox_end_voxel, use
     download of the probability maps / mask on the device:
       resample to the model spacing, size up to a multiple of max_stride (image_tools.py:348-377)  -> seg3d_resample_affine_mc
       partition (host index arithmetic), one batched gather -> net -> scatter per hipGraph replay, divide by overlap
-      resample the class probabilities back onto the image grid, padding 1.0 for class 0 and 0.0 otherwise (:330-333)
-      arg-max -> int8 mask (:336-339); largest component / small-component removal (:342-348)
+      the class probabilities back onto the image grid, padding 1.0 for class 0 and 0.0 otherwise (:330-333), and the
+      arg-max -> int8 mask (:336-339) in one launch -> seg3d_ensemble_accumulate (a single model is the K = 1, weight 1.0
+      case of segmentation_volume_ensemble; that launch takes 1..16 planes, so a model with more out_channels whose grid is
+      not the image grid raises ValueError); largest component / small-component removal (:342-348)
     `use_gpu` is kept for signature compatibility (the reference shrinks spacing / partitions on the CPU path only).
     image: an Image3d, or a list of M co-registered Image3d (one per modality; the model must take in_channels = M):
     the M modalities are resampled to the model grid in one launch (seg3d_resample_affine_mc) and every patch is
@@ -850,18 +845,13 @@ def segmentation_volume(model, cfg, image, bbox_start_voxel, bbox_end_voxel, use
     when not None, override the config.
     Returns (mean_probs: list of Image3d, mask: Image3d int8).
     """
-    images, M = _case_images(model, image)
-    cfg_blend, sigma_scale, cfg_axes = blend_options(cfg)
-    blend = cfg_blend if blend is None else check_blend_mode(blend)
-    mirror_axes = cfg_axes if mirror_axes is None else check_mirror_axes(mirror_axes)
-    with torch.cuda.device(model['device']):
-        return _segmentation_volume(model, cfg, images, bbox_start_voxel, bbox_end_voxel, batch_size, blend, sigma_scale,
-                                    mirror_axes)
+    images, _ = _case_images(model, image)
+    return _image_grid_result([model], [1.0], cfg, images, bbox_start_voxel, bbox_end_voxel, batch_size, blend, mirror_axes)
 
 
 def _member_probabilities(model, cfg, images, bbox_start_voxel, bbox_end_voxel, batch_size, blend, sigma_scale, mirror_axes,
                           src=None):
-    """the front half of a volume job, shared by the single-model path and by every member of an ensemble: resample the
+    """the front half of a volume job, once per member (a single model is the ensemble of one): resample the
     image to the model's grid, partition (the bounding box mapped into that grid), run the sliding window.
     src: the resident [Z, Y, X, M] image when the caller already uploaded it.
     Returns (probs [C, Zp, Yp, Xp], net_mask int8 [Zp, Yp, Xp], iso_frame, (Xp, Yp, Zp)) on the model's grid; the batcher
@@ -905,49 +895,59 @@ def _member_probabilities(model, cfg, images, bbox_start_voxel, bbox_end_voxel, 
     return probs, net_mask, iso_frame, (Xp, Yp, Zp)
 
 
-def _segmentation_volume(model, cfg, images, bbox_start_voxel, bbox_end_voxel, batch_size, blend='constant',
-                         sigma_scale=0.125, mirror_axes=()):
-    image = images[0]
-    num_classes = int(model['out_channels'])
+def _on_image_grid(model, image):
+    """the model's grid IS the image grid: the size a stride multiple already, the spacings equal within 1e-9 relative"""
     spacing = [float(s) for s in model['spacing']]
-    img_frame = (image.GetSpacing(), image.GetOrigin(), image.GetDirection())
-    X, Y, Z = image.GetSize()
-    order = model.get('region_class_order')
-    probs, net_mask, iso_frame, (Xp, Yp, Zp) = _member_probabilities(model, cfg, images, bbox_start_voxel, bbox_end_voxel,
-                                                                     batch_size, blend, sigma_scale, mirror_axes)
-    # (voxels no patch covered -- bounding-box runs -- have count 0: their probabilities are 0 and the arg-max there is
-    # class 0, as with ITK's division in the reference, see finalize_argmax_kernel)
-    # back to the image grid (identity when the image already is at the model spacing and a stride multiple)
-    same_grid = (Xp, Yp, Zp) == (X, Y, Z) and all(abs(a - b) <= 1e-9 * max(abs(a), abs(b), 1.0)
-                                                 for a, b in zip(image.GetSpacing(), spacing))
-    if same_grid:
-        out_probs = probs
-    else:       # (region planes are all foreground: outside the model grid every one of them is 0)
-        out_probs = torch.stack([image_tools.resample_device(probs[c], iso_frame, (X, Y, Z), img_frame, 'LINEAR',
-                                                              1.0 if c == 0 and order is None else 0.0)
-                                 for c in range(num_classes)])
-    if order is None:
-        mask = out_probs.argmax(0).to(torch.int8)       # first maximum wins, like tensor.max(0) in the reference
-        labels = list(range(1, num_classes))
-    else:
-        mask = net_mask if same_grid else compose_region_mask(out_probs, order)
-        labels = sorted(set(order))
-    if getattr(cfg, 'pick_largest_cc', False) and labels:
-        mask = image_tools.connected_component_filter_device(mask, labels, 'largest')
-    if getattr(cfg, 'remove_small_cc', 0) and cfg.remove_small_cc > 0 and labels:
-        mask = image_tools.connected_component_filter_device(mask, labels, 'min_size', int(cfg.remove_small_cc))
-    mean_probs = [Image3d(out_probs[c].cpu().numpy(), *img_frame) for c in range(num_classes)]
-    return mean_probs, Image3d(mask.cpu().numpy(), *img_frame)
+    size = image_tools.resampled_size(image.GetSize(), image.GetSpacing(), spacing, int(model['max_stride']))
+    return tuple(size) == tuple(image.GetSize()) and all(abs(a - b) <= 1e-9 * max(abs(a), abs(b), 1.0)
+                                                         for a, b in zip(image.GetSpacing(), spacing))
 
 
-def compose_region_mask(probs, regions_order):
-    """the label map of region probabilities [R, Z, Y, X] that are already means (the image-grid resampling of the
-    finalized planes): 0, then for r = 0 .. R-1 in order p_r > 0.5 writes regions_order[r] -- the rule of
-    seg3d_finalize_regions, as plain device plumbing off the patch path"""
-    mask = torch.zeros(probs.shape[1:], dtype=torch.int8, device=probs.device)
-    for r, label in enumerate(regions_order):
-        mask[probs[r] > 0.5] = int(label)
-    return mask
+def _image_grid_result(members, weights, cfg, images, bbox_start_voxel, bbox_end_voxel, batch_size, blend, mirror_axes):
+    """the back half of a volume job, for one model (members = [model], weights = [1.0]) and for an ensemble alike: every
+    member's finalized probabilities to the image grid and into the weighted sum, the label map, the connected-component
+    options, the download.  blend / mirror_axes: None = what cfg says.
+    One case stays off the kernel: a single member whose grid IS the image grid.  Its finalized probabilities are the
+    result as they stand: index_affine is an exact identity only for an identity direction matrix and bitwise equal
+    spacings, and a tap weight of 1e-16 changes a probability of 1e-30."""
+    cfg_blend, sigma_scale, cfg_axes = blend_options(cfg)
+    blend = cfg_blend if blend is None else check_blend_mode(blend)
+    mirror_axes = cfg_axes if mirror_axes is None else check_mirror_axes(mirror_axes)
+    front = (cfg, images, bbox_start_voxel, bbox_end_voxel, batch_size, blend, sigma_scale, mirror_axes)
+    dev = members[0]['device']
+    K = len(members)
+    with torch.cuda.device(dev):
+        image = images[0]
+        num_classes = int(members[0]['out_channels'])
+        order = members[0].get('region_class_order')
+        img_frame = (image.GetSpacing(), image.GetOrigin(), image.GetDirection())
+        X, Y, Z = image.GetSize()
+        if K == 1 and _on_image_grid(members[0], image):
+            out_probs, mask, _, _ = _member_probabilities(members[0], *front)
+            if order is None:       # first maximum wins, like tensor.max(0) in the reference
+                mask = out_probs.argmax(0).to(torch.int8)
+        else:
+            if not 1 <= num_classes <= 16:
+                raise ValueError('out_channels = {}: bringing probabilities to an image grid that is not the model\'s grid '
+                                 'takes 1..16 planes (seg3d_ensemble_accumulate)'.format(num_classes))
+            src = image_tools.images_to_device(images, dev) if K > 1 else None     # (one member uploads, and frees, its own)
+            out_probs = torch.empty((num_classes, Z, Y, X), dtype=torch.float32, device=dev)    # the first member overwrites it
+            mask = torch.empty((Z, Y, X), dtype=torch.int8, device=dev)
+            for k, model in enumerate(members):
+                probs, _, iso_frame, _ = _member_probabilities(model, *front, src=src)
+                # (outside a member's grid: class 0 with probability 1; region planes are all foreground and 0 there)
+                image_tools.ensemble_accumulate_device(probs, iso_frame, out_probs, img_frame, weights[k], k == 0,
+                                                       pad0=1.0 if order is None else 0.0,
+                                                       mask=mask if k == K - 1 else None, regions_order=order)
+                del probs       # stream-ordered: the next member may reuse the block after the launch above
+            del src
+        labels = list(range(1, num_classes)) if order is None else sorted(set(order))
+        if getattr(cfg, 'pick_largest_cc', False) and labels:
+            mask = image_tools.connected_component_filter_device(mask, labels, 'largest')
+        if getattr(cfg, 'remove_small_cc', 0) and cfg.remove_small_cc > 0 and labels:
+            mask = image_tools.connected_component_filter_device(mask, labels, 'min_size', int(cfg.remove_small_cc))
+        mean_probs = [Image3d(out_probs[c].cpu().numpy(), *img_frame) for c in range(num_classes)]
+        return mean_probs, Image3d(mask.cpu().numpy(), *img_frame)
 
 
 def segmentation_volume_ensemble(members, cfg, image, bbox_start_voxel, bbox_end_voxel, weights=None, batch_size=8, blend=None,
@@ -956,50 +956,21 @@ def segmentation_volume_ensemble(members, cfg, image, bbox_start_voxel, bbox_end
     label map.  members: loaded models (load_single_model) that agree in
     check_ensemble_members' keys -- one per cross-validation fold, or several configurations; their network, spacing,
     max_stride and normalisers may differ.  weights: K positive numbers (ensemble_weights; None = equal).
-    The members run one after another, each exactly as in segmentation_volume up to its finalized probabilities on its own
-    grid (resample, partition with the bounding box mapped into that grid, sliding window with the stage's blending and
-    mirror TTA); one seg3d_ensemble_accumulate launch then interpolates all its planes onto the image grid and adds them
-    with the member's weight, and the launch of the last member writes the label map in the same pass (arg-max, or the
-    region overwrite rule for sigmoid members).  Also when a member's grid is the image grid.  Only one member's
+    The members run one after another, each up to its finalized probabilities on its own grid (_member_probabilities:
+    resample, partition with the bounding box mapped into that grid, sliding window with the stage's blending and mirror
+    TTA); one seg3d_ensemble_accumulate launch then interpolates all its planes onto the image grid and adds them with the
+    member's weight, and the launch of the last member writes the label map in the same pass (arg-max, or the region
+    overwrite rule for sigmoid members).  With K > 1 also when a member's grid is the image grid.  Only one member's
     probabilities and volume graph exist at a time.
     Returns (mean_probs: list of Image3d, mask: Image3d int8), like segmentation_volume."""
     members = check_ensemble_members(members)
-    K = len(members)
-    weights = ensemble_weights(weights, K)
+    weights = ensemble_weights(weights, len(members))
     images, _ = _case_images(members[0], image)
     dev = members[0]['device']
     for k, m in enumerate(members):
         if m['device'] != dev:
             raise ValueError('ensemble member {} is on {}, member 0 on {}'.format(k, m['device'], dev))
-    cfg_blend, sigma_scale, cfg_axes = blend_options(cfg)
-    blend = cfg_blend if blend is None else check_blend_mode(blend)
-    mirror_axes = cfg_axes if mirror_axes is None else check_mirror_axes(mirror_axes)
-    with torch.cuda.device(dev):
-        image = images[0]
-        num_classes = int(members[0]['out_channels'])
-        order = members[0].get('region_class_order')
-        img_frame = (image.GetSpacing(), image.GetOrigin(), image.GetDirection())
-        X, Y, Z = image.GetSize()
-        src = image_tools.images_to_device(images, dev)
-        acc = torch.empty((num_classes, Z, Y, X), dtype=torch.float32, device=dev)      # the first member overwrites it
-        mask = torch.empty((Z, Y, X), dtype=torch.int8, device=dev)
-        for k, model in enumerate(members):
-            probs, _, iso_frame, _ = _member_probabilities(model, cfg, images, bbox_start_voxel, bbox_end_voxel, batch_size,
-                                                           blend, sigma_scale, mirror_axes, src=src)
-            # (outside a member's grid: class 0 with probability 1, as in segmentation_volume; region planes are all
-            # foreground and 0 there)
-            image_tools.ensemble_accumulate_device(probs, iso_frame, acc, img_frame, weights[k], k == 0,
-                                                   pad0=1.0 if order is None else 0.0,
-                                                   mask=mask if k == K - 1 else None, regions_order=order)
-            del probs       # stream-ordered: the next member may reuse the block after the launch above
-        del src
-        labels = list(range(1, num_classes)) if order is None else sorted(set(order))
-        if getattr(cfg, 'pick_largest_cc', False) and labels:
-            mask = image_tools.connected_component_filter_device(mask, labels, 'largest')
-        if getattr(cfg, 'remove_small_cc', 0) and cfg.remove_small_cc > 0 and labels:
-            mask = image_tools.connected_component_filter_device(mask, labels, 'min_size', int(cfg.remove_small_cc))
-        mean_probs = [Image3d(acc[c].cpu().numpy(), *img_frame) for c in range(num_classes)]
-        return mean_probs, Image3d(mask.cpu().numpy(), *img_frame)
+    return _image_grid_result(members, weights, cfg, images, bbox_start_voxel, bbox_end_voxel, batch_size, blend, mirror_axes)
 
 
 _IMAGE_SUFFIXES = ('.mhd', '.nii', '.hdr', '.nii.gz', '.mha', '.image3d')     # core/seg_infer.py:80, 375-376

@@ -1,6 +1,8 @@
 """Model ensembling on the GPU: seg3d_ensemble_accumulate against the existing resampler
 (bit for bit), against float64 restatements that do not use the resampler, the region rule, the identity grid, bad
-arguments, and the file-level engine with ensemble stages against the single-model path run member by member.
+arguments, and the file-level engine -- ensemble stages and the single-model path, which is the K = 1 case of the same
+code -- against every member's probabilities brought to the image grid plane by plane with the resampler and labelled in
+numpy, plus the single model's same-grid exit.
 
 Bars: bit equality wherever the contract promises it.  General floats against float64: the accumulator holds values <= 1
 and takes two float32 roundings per member (product and sum, each at most 2^-24) plus the float cast of the interpolated
@@ -50,10 +52,10 @@ def _bits(a):
     return np.ascontiguousarray(a).view(np.uint32 if a.dtype == np.float32 else np.uint8)
 
 
-def _resampler_planes(probs_dev, frame, out_size, pad0):
+def _resampler_planes(probs_dev, frame, out_size, pad0, dst_frame=IMG_FRAME):
     """the s_c of one member from the existing single-plane resampler"""
     from segmentation3d.utils import image_tools
-    return np.stack([image_tools.resample_device(probs_dev[c], frame, out_size, IMG_FRAME, 'LINEAR',
+    return np.stack([image_tools.resample_device(probs_dev[c], frame, out_size, dst_frame, 'LINEAR',
                                                  pad0 if c == 0 else 0.0).cpu().numpy() for c in range(probs_dev.shape[0])])
 
 
@@ -296,11 +298,34 @@ def _write_member(root, name, seed, spacing, sigmoid_order=None):
     torch.save(state, str(chk / 'params.pth'))
 
 
+def _frame(image):
+    return image.GetSpacing(), image.GetOrigin(), image.GetDirection()
+
+
+def _model_grid(model, stage_cfg, image, start=None, end=None):
+    """one model up to its finalized probabilities on its own grid -> (planes [C, Zp, Yp, Xp] on the device, iso_frame)"""
+    from segmentation3d.core.seg_infer import _member_probabilities, blend_options
+    blend, sigma_scale, axes = blend_options(stage_cfg)
+    with torch.cuda.device(model['device']):
+        probs, _, iso_frame, _ = _member_probabilities(model, stage_cfg, [image], start, end, 8, blend, sigma_scale, axes)
+    return probs, iso_frame
+
+
+def _alone(model, stage_cfg, image, start=None, end=None):
+    """the image-grid result of one model WITHOUT the accumulate kernel: _member_probabilities, one resampler launch per
+    plane (pad 1.0 for class 0 of a soft-max model, 0.0 for region planes), the label rule in numpy -> (planes, mask)"""
+    probs, iso_frame = _model_grid(model, stage_cfg, image, start, end)
+    order = model.get('region_class_order')
+    planes = _resampler_planes(probs, iso_frame, image.GetSize(), 1.0 if order is None else 0.0, _frame(image))
+    return planes, (argmax_first(planes) if order is None else compose_regions(planes, order))
+
+
 @pytest.fixture(scope='module')
 def e2e(tmp_path_factory, hip_device):
     """two soft-max members (spacings 1.0 and 1.5) and a coarse model as model folders, one 40 x 36 x 33 image at spacing
-    0.8 as a file, and every member run alone through the single-model path on the whole image (the shared reference)"""
-    from segmentation3d.core.seg_infer import load_single_model, segmentation_volume
+    0.8 as a file, and every member alone on the whole image, composed without the accumulate kernel (_alone: the shared
+    reference)"""
+    from segmentation3d.core.seg_infer import load_single_model
     from segmentation3d.utils.file_io import load_config
     from segmentation3d.utils.image3d import Image3d
     from segmentation3d.utils.mha_io import write_mha
@@ -315,15 +340,27 @@ def e2e(tmp_path_factory, hip_device):
     (root / 'infer_config.py').write_text(_infer_cfg('fine'))
     cfg = load_config(str(root / 'infer_config.py'))
     members = [load_single_model(str(root / n), 0) for n in ('fold_0', 'fold_1')]
-    alone = [segmentation_volume(m, cfg.fine, image, None, None) for m in members]
+    alone = [_alone(m, cfg.fine, image) for m in members]
     return dict(tmp=tmp, root=root, image=image, members=members, cfg=cfg, alone=alone)
 
 
+REGION_ORDER = [2, 1, 3]
+
+
+@pytest.fixture(scope='module')
+def region_members(e2e):
+    """two sigmoid members (spacings 1.0 and 1.5) with region order [2, 1, 3]"""
+    from segmentation3d.core.seg_infer import load_single_model
+    _write_member(e2e['root'], 'region_0', 51, 1.0, sigmoid_order=REGION_ORDER)
+    _write_member(e2e['root'], 'region_1', 52, 1.5, sigmoid_order=REGION_ORDER)
+    return [load_single_model(str(e2e['root'] / n), 0) for n in ('region_0', 'region_1')]
+
+
 def _combine(alone, weights):
-    """the members' image-grid probabilities (each from the single-model path) combined in the kernel's order"""
+    """the members' image-grid probabilities (each from _alone) combined in the kernel's order"""
     acc = None
-    for k, (probs, _) in enumerate(alone):
-        acc = accumulate_f32(acc, np.stack([p.array for p in probs]), weights[k], k == 0)
+    for k, (planes, _) in enumerate(alone):
+        acc = accumulate_f32(acc, planes, weights[k], k == 0)
     return acc
 
 
@@ -349,13 +386,16 @@ def test_segmentation_with_a_fine_ensemble(e2e):
     assert np.array_equal(written, argmax_first(want)) and np.array_equal(masks[0].array, written)
     assert len(np.unique(written)) == 2
     # and the two members do differ: the mean is neither of them
-    assert not np.array_equal(want, np.stack([p.array for p in e2e['alone'][0][0]]))
+    assert not np.array_equal(want, e2e['alone'][0][0])
 
 
 def test_single_member_ensemble_writes_the_plain_files(e2e):
-    from segmentation3d.core.seg_infer import segmentation
+    from segmentation3d.core.seg_infer import load_models, segmentation
     root, tmp = e2e['root'], e2e['tmp']
     (root / 'infer_config.py').write_text(_infer_cfg('fine'))
+    plain = load_models(str(root), 0)       # a stage without `ensemble`: one member, weight 1.0
+    assert len(plain.fine_members) == 1 and plain.fine_model is plain.fine_members[0]
+    assert plain.fine_weights == [1.0] and plain.coarse_model is None
     segmentation(str(tmp / 'case.mha'), str(root), str(tmp / 'out_plain'), 'seg.mha', 0, False, True, False, True)
     (root / 'infer_config.py').write_text(_infer_cfg('fine', "__C.fine.ensemble = ['fold_0']\n"))
     segmentation(str(tmp / 'case.mha'), str(root), str(tmp / 'out_one'), 'seg.mha', 0, False, True, False, True)
@@ -378,24 +418,99 @@ def test_cascade_with_a_fine_ensemble(e2e):
     start, end = get_bounding_box(coarse_mask, None)
     if start is None:
         start, end = [0, 0, 0], list(coarse_mask.GetSize())
-    alone = [segmentation_volume(m, cfg.fine, image, list(start), list(end)) for m in e2e['members']]
+    alone = [_alone(m, cfg.fine, image, list(start), list(end)) for m in e2e['members']]
     want = _combine(alone, ensemble_weights(None, 2))
     assert np.array_equal(_bits(probs), _bits(want))
     assert np.array_equal(written, argmax_first(want))
 
 
-def test_sigmoid_members_compose_the_mask(e2e):
-    from segmentation3d.core.seg_infer import load_single_model, segmentation_volume, segmentation_volume_ensemble
-    root, image, cfg = e2e['root'], e2e['image'], e2e['cfg']
-    order = [2, 1, 3]
-    _write_member(root, 'region_0', 51, 1.0, sigmoid_order=order)
-    _write_member(root, 'region_1', 52, 1.5, sigmoid_order=order)
-    members = [load_single_model(str(root / n), 0) for n in ('region_0', 'region_1')]
+def test_sigmoid_members_compose_the_mask(e2e, region_members):
+    from segmentation3d.core.seg_infer import segmentation_volume_ensemble
+    image, cfg = e2e['image'], e2e['cfg']
+    order, members = REGION_ORDER, region_members
     weights = [0.75, 0.25]
     probs, mask = segmentation_volume_ensemble(members, cfg.fine, image, None, None, weights=[3, 1])
-    alone = [segmentation_volume(m, cfg.fine, image, None, None) for m in members]
+    alone = [_alone(m, cfg.fine, image) for m in members]
     want = _combine(alone, weights)
     assert np.array_equal(_bits(np.stack([p.array for p in probs])), _bits(want))
     assert np.array_equal(mask.array, compose_regions(want, order)) and mask.array.dtype == np.int8
     with pytest.raises(ValueError):     # a soft-max and a sigmoid member do not mix
         segmentation_volume_ensemble([members[0], e2e['members'][0]], cfg.fine, image, None, None)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 8. a single model is the K = 1 case
+# ---------------------------------------------------------------------------------------------------------------------
+def _record_calls(monkeypatch):
+    from segmentation3d import _engine as E
+    calls = []
+    real_call = E.call
+    monkeypatch.setattr(E, 'call', lambda name, *a: (calls.append(name), real_call(name, *a))[1])
+    return calls
+
+
+# (start, end) in image voxels (x, y, z); the fixture's image array is [Z, Y, X] = 40 x 36 x 33, so this is the whole x (33)
+# and y (36) extent and 12 of the 40 z planes -- one 32 x 32 x 16 patch on either member's grid
+BBOX = ([0, 0, 10], [33, 36, 22])
+
+
+@pytest.mark.parametrize('bbox', [None, BBOX], ids=['whole', 'bbox'])
+@pytest.mark.parametrize('kind', ['softmax', 'sigmoid'])
+def test_single_model_equals_the_resampler_composition(e2e, region_members, monkeypatch, kind, bbox):
+    """segmentation_volume on an image that is not on the model's grid: probabilities and mask bit-equal to the planes
+    resampled one by one and labelled in numpy, from exactly one accumulate launch and no resampler launch behind the
+    sliding window"""
+    from segmentation3d.core.seg_infer import segmentation_volume
+    image, cfg = e2e['image'], e2e['cfg']
+    start, end = (None, None) if bbox is None else bbox
+    for k, model in enumerate(e2e['members'] if kind == 'softmax' else region_members):
+        if kind == 'softmax' and bbox is None:
+            want, want_m = e2e['alone'][k]
+        else:
+            want, want_m = _alone(model, cfg.fine, image, None if start is None else list(start),
+                                  None if end is None else list(end))
+        calls = _record_calls(monkeypatch)
+        probs, mask = segmentation_volume(model, cfg.fine, image, None if start is None else list(start),
+                                          None if end is None else list(end))
+        monkeypatch.undo()
+        got = np.stack([p.array for p in probs])
+        uncovered = (want == 0).all(0)
+        print('single {} member {} {}: labels {}, uncovered voxels {}'.format(
+            kind, k, 'whole' if bbox is None else 'bbox', np.unique(want_m).tolist(), int(uncovered.sum())))
+        assert np.array_equal(_bits(got), _bits(want))
+        assert np.array_equal(mask.array, want_m) and mask.array.dtype == np.int8
+        assert len(np.unique(want_m)) >= 2
+        if bbox is not None:        # no patch covered them: count 0, every probability 0, label 0
+            assert uncovered.any() and (got[:, uncovered] == 0).all() and (mask.array[uncovered] == 0).all()
+        assert calls.count('seg3d_ensemble_accumulate') == 1
+        tail = max(i for i, n in enumerate(calls) if n.startswith('seg3d_finalize_'))
+        assert not [n for n in calls[tail:] if n.startswith('seg3d_resample_affine')]
+
+
+@pytest.mark.parametrize('kind', ['softmax', 'sigmoid'])
+def test_single_model_same_grid_exit(e2e, region_members, monkeypatch, kind):
+    """a 32^3 image at the model's spacing (stride 16 divides it): segmentation_volume returns the sliding window's
+    finalized planes as they stand and their label map, and launches no accumulate"""
+    from segmentation3d.core.seg_infer import segmentation_volume
+    from segmentation3d.utils.image3d import Image3d
+    model = e2e['members'][0] if kind == 'softmax' else region_members[0]
+    rng = np.random.RandomState(77)
+    image = Image3d((rng.randn(32, 32, 32) * 100).astype(np.float32), (1.0, 1.0, 1.0), (1.0, -2.0, 3.0), EYE)
+    planes, _ = _model_grid(model, e2e['cfg'].fine, image)
+    want = planes.cpu().numpy()
+    assert want.shape[1:] == (32, 32, 32)
+    calls = _record_calls(monkeypatch)
+    probs, mask = segmentation_volume(model, e2e['cfg'].fine, image, None, None)
+    monkeypatch.undo()
+    assert np.array_equal(_bits(np.stack([p.array for p in probs])), _bits(want))
+    want_m = argmax_first(want) if kind == 'softmax' else compose_regions(want, REGION_ORDER)
+    assert np.array_equal(mask.array, want_m) and mask.array.dtype == np.int8
+    assert calls.count('seg3d_ensemble_accumulate') == 0 and any(n.startswith('seg3d_finalize_') for n in calls)
+
+
+def test_single_model_plane_limit_names_out_channels(e2e):
+    """the image-grid launch takes 1..16 planes: a wider model on another grid is refused in Python, before any launch"""
+    from segmentation3d.core.seg_infer import segmentation_volume
+    model = dict(e2e['members'][0], out_channels=17)
+    with pytest.raises(ValueError, match='out_channels = 17'):
+        segmentation_volume(model, e2e['cfg'].fine, e2e['image'], None, None)
