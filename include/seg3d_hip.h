@@ -77,7 +77,9 @@ int seg3d_wgrad_reduce(const float* part, float* dw, int chunks, int T, int A, i
 /* fp32 MFMA implicit-GEMM path for k3 s1 p1 with Cin % 4 == 0 (the FLOP-dominant C->C layers) */
 long long seg3d_conv3d_k3_mfma_stats_count(int N, int D, int H, int W, int Cin, int Cout);
 long long seg3d_conv3d_k3_mfma_fwd_workspace_floats(int N, int D, int H, int W, int Cin, int Cout);
-/* kernel instantiation a shape runs: MA (1..4) = conv3d_k3_mfma_kernel<MA>; 100 + 10*MA + NB = conv3d_k3_mfma2_kernel<MA, NB> */
+/* kernel instantiation a shape runs: MA (1..4) = conv3d_k3_mfma_kernel<MA>; 100 + 10*MA + NB = conv3d_k3_mfma2_kernel<MA, NB>
+ * (conv3d_k3_mfma2_splitk_kernel<MA, NB> + conv3d_splitk_finish_kernel when the workspace query is not 0);
+ * 300 + 10*MA + NB = conv3d_k3_mfma2w8_kernel<MA, NB> (8 waves, whole K only) */
 int seg3d_conv3d_k3_mfma_variant(int N, int D, int H, int W, int Cin, int Cout);
 int seg3d_conv3d_k3_mfma_fwd(const float* x, const float* wp_mfma, const float* bias,
                              const float* addend /* optional, shape of y: y = conv + bias + addend */, float* y,
@@ -86,6 +88,19 @@ int seg3d_conv3d_k3_mfma_fwd(const float* x, const float* wp_mfma, const float* 
 long long seg3d_conv3d_k3_mfma_wgrad_workspace_floats(int N, int D, int H, int W, int Cin, int Cout);
 int seg3d_conv3d_k3_mfma_wgrad(const float* x, const float* dy, float* dw, float* workspace, int N, int D, int H, int W,
                                int Cin, int Cout, int accumulate, void* stream);
+/* Which kernels of csrc/conv_mfma.hip a weight-gradient call runs (pure host arithmetic: the launchers decide through the
+ * same plan functions).  Negative where the launcher would refuse the arguments (a dimension <= 0, Cin % 4 or Cout % 4 != 0,
+ * 2^31 elements, fp32: 2^22 tiles).  seg3d_conv3d_k3_mfma_wgrad: bf16 = 0, seg3d_conv3d_k3_bf16_wgrad: bf16 = 1.  10 k + r
+ *   k = 0  conv3d_k3_wgrad2_kernel<1, 4, 4, 8>             fp32, the default tile (also every shape no tile divides)
+ *   k = 1  conv3d_k3_wgrad2_kernel<1, 4, 4, 4>             fp32, D % 4 == H % 4 == W % 4 == 0 and W % 8 != 0
+ *   k = 2  conv3d_k3_wgrad2_kernel<1, 2, 6, 6>             fp32, D % 2 == H % 6 == W % 6 == 0, not whole 4 x 4 x 4 tiles
+ *   k = 3  conv3d_k3_wgrad3_bf16_kernel<4, 4, 8, false>    bf16, Cin % 8 == Cout % 8 == 0, whole 4 x 4 x 8 tiles
+ *   k = 4  conv3d_k3_wgrad3_bf16_kernel<4, 4, 8, true>     the same tile with ragged extents (IRR)
+ *   k = 5  conv3d_k3_wgrad3_bf16_kernel<4, 4, 4, false>    bf16, the 4 x 4 x 4 tile (it covers fewer voxels than 4 x 4 x 8), whole tiles
+ *   k = 6  conv3d_k3_wgrad3_bf16_kernel<4, 4, 4, true>     the same tile with ragged extents
+ *   k = 7  conv3d_k3_wgrad_mfma_bf16_kernel                bf16, other channel counts: operands widened while staging
+ *   r = 1  conv3d_k3_wgrad_reduce_kernel<16> follows (32 or more partial slabs), r = 0  conv3d_k3_wgrad_reduce_kernel<4> */
+int seg3d_conv3d_k3_wgrad_variant(int N, int D, int H, int W, int Cin, int Cout, int bf16);
 
 /* bf16 mode (BASELINE config 5: bf16 activations and weights, fp32 accumulation, fp32 GroupNorm statistics, fp32 master
  * weights).  Conv INPUTS (x) and packed weights are bf16 (raw 16-bit patterns, `void*` at this boundary); bias, addend,
@@ -153,7 +168,8 @@ int seg3d_conv3d_k3_wino2d_wgrad(const float* x, const float* dy, float* dw, flo
                                  int Cin, int Cout, int accumulate, void* stream);
 long long seg3d_conv3d_k3_bf16_stats_count(int N, int D, int H, int W, int Cin, int Cout);
 long long seg3d_conv3d_k3_bf16_fwd_workspace_floats(int N, int D, int H, int W, int Cin, int Cout);
-/* 200 + 10*MA + NB = conv3d_k3_mfma2_bf16_kernel<MA, NB>; 0 = shape not supported */
+/* 200 + 10*MA + NB = conv3d_k3_mfma2_bf16_kernel<MA, NB> (split-K: conv3d_k3_mfma2_bf16_splitk_kernel<MA, NB> + the finish
+ * kernel); 400 + 10*MA + NB = conv3d_k3_mfma2w8_bf16_kernel<MA, NB> (8 waves, whole K only); 0 = shape not supported */
 int seg3d_conv3d_k3_bf16_variant(int N, int D, int H, int W, int Cin, int Cout);
 /* out_bf16 = 1: y is bf16 storage (used for data-gradients, whose consumer is the GroupNorm backward of a bf16 unit);
  * addend stays fp32 and is added before the rounding */

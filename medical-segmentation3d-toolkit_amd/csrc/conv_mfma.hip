@@ -2146,6 +2146,7 @@ extern "C" int seg3d_conv3d_k3_mfma_wgrad(const float* x, const float* dy, float
 struct Seg3dWgrad16Plan {
   int version;  // 3: bf16 MFMA, transposing LDS reads; 1: register-staged, fp32 MFMA
   int tx;       // 8 or 4 (version 3)
+  bool irr;     // version 3: an extent is not a multiple of the 4 x 4 x tx tile (the kernel's masked form)
   int slabs;
 };
 
@@ -2155,6 +2156,7 @@ static Seg3dWgrad16Plan seg3d_wgrad16_plan(int N, int D, int H, int W, int Cin, 
   Seg3dWgrad16Plan p;
   p.version = 1;
   p.tx = 8;
+  p.irr = false;
   p.slabs = seg3d_wgrad_slabs(N, D, H, W, npairs);
   if ((Cin & 7) || (Cout & 7)) return p;
   // tile 4x4x8 unless 4x4x4 wastes fewer voxels (levels that are multiples of 4 but not of 8, e.g. 12^3)
@@ -2165,6 +2167,7 @@ static Seg3dWgrad16Plan seg3d_wgrad16_plan(int N, int D, int H, int W, int Cin, 
   if (ntiles >= SEG3D_FDIV_MAX) return p;
   p.version = 3;
   p.tx = tx;
+  p.irr = D % 4 || H % 4 || W % tx;
   int slabs = 256 / npairs;   // one resident workgroup per CU over the whole grid
   if (slabs > (ntiles + 1) / 2) slabs = (int)((ntiles + 1) / 2);
   if (slabs < 1) slabs = 1;
@@ -2208,9 +2211,8 @@ extern "C" int seg3d_conv3d_k3_bf16_wgrad(const void* x, const void* dy, float* 
   const int slabs = plan.slabs;
   hipStream_t s = (hipStream_t)stream;
   if (plan.version == 3) {
-    const bool irr = D % 4 || H % 4 || W % plan.tx;
     int rc;
-    if (irr)
+    if (plan.irr)
       rc = plan.tx == 8 ? launch_wgrad3<8, true>(x, dy, workspace, N, D, H, W, Cin, Cout, slabs, s)
                         : launch_wgrad3<4, true>(x, dy, workspace, N, D, H, W, Cin, Cout, slabs, s);
     else
@@ -2227,4 +2229,29 @@ extern "C" int seg3d_conv3d_k3_bf16_wgrad(const void* x, const void* dy, float* 
   seg3d_launch_wgrad_reduce(workspace, dw, slabs, Cin, Cout, COB32, npairs, (i64)27, (i64)Cin * 27, accumulate, s);
   SEG3D_LAUNCH_CHECK("seg3d_conv3d_k3_bf16_wgrad(reduce)");
   return SEG3D_OK;
+}
+
+// which kernels a weight-gradient call runs (seg3d_conv3d_k3_mfma_wgrad: bf16 = 0, seg3d_conv3d_k3_bf16_wgrad: bf16 = 1), from
+// the plans the launchers call: 10 k + r.  k = 0 / 1 / 2: conv3d_k3_wgrad2_kernel<1, 4,4,8 | 4,4,4 | 2,6,6>;
+// k = 3 / 4 / 5 / 6: conv3d_k3_wgrad3_bf16_kernel<4,4, 8,false | 8,true | 4,false | 4,true>; k = 7: conv3d_k3_wgrad_mfma_bf16_kernel;
+// r = 1: conv3d_k3_wgrad_reduce_kernel<16> follows (32 or more slabs), r = 0: <4>.  Negative where the launcher refuses.
+extern "C" int seg3d_conv3d_k3_wgrad_variant(int N, int D, int H, int W, int Cin, int Cout, int bf16) {
+  SEG3D_REQUIRE(N > 0 && D > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, "seg3d_conv3d_k3_wgrad_variant: bad dims");
+  SEG3D_REQUIRE((Cin % 4) == 0 && (Cout % 4) == 0,
+                "seg3d_conv3d_k3_wgrad_variant: Cin and Cout must be multiples of 4 (got %d, %d)", Cin, Cout);
+  SEG3D_REQUIRE((i64)N * D * H * W * (Cin > Cout ? Cin : Cout) < (1ll << 31),
+                "seg3d_conv3d_k3_wgrad_variant: tensor exceeds 2^31 elements");
+  int k, slabs;
+  if (bf16) {
+    const Seg3dWgrad16Plan p = seg3d_wgrad16_plan(N, D, H, W, Cin, Cout);
+    k = p.version == 3 ? 3 + (p.tx == 4 ? 2 : 0) + (p.irr ? 1 : 0) : 7;
+    slabs = p.slabs;
+  } else {
+    const Seg3dWgradPlan p = seg3d_wgrad_plan(N, D, H, W, Cin, Cout);
+    SEG3D_REQUIRE((i64)N * seg3d_cdiv(D, p.tz) * seg3d_cdiv(H, p.ty) * seg3d_cdiv(W, p.tx) < SEG3D_FDIV_MAX,
+                  "seg3d_conv3d_k3_wgrad_variant: more than 2^22 tiles");
+    k = p.tx == 4 ? 1 : p.tx == 6 ? 2 : 0;
+    slabs = p.slabs;
+  }
+  return 10 * k + (slabs >= 32 ? 1 : 0);
 }
