@@ -402,6 +402,38 @@ int seg3d_compound_loss_bwd(const float* probs, const float* target, const float
                             const float* gout, float* dprobs, int N, int C, long long S, float gamma, int batch_dice,
                             float ignore_label, void* stream);
 
+/* Dice + top-k cross-entropy (no counterpart in the reference; nnU-Net's DC_and_topk_loss):
+ * L = dice_weight * L_region + ce_weight * L_topk on probabilities [N][C][S] (fp32, 0 <= p <= 1, 1 <= C <= 16) and a float
+ * class-id target [N][S].  A voxel counts iff 0 <= t < C and t != ignore_label (the compound loss's rule, above).
+ *   L_region = exactly the compound loss's soft-Dice term (wdice, batch_dice, eps = 1e-5), from the same device code.
+ *   ell_v    = alpha_t * (-log(max(p_t, 1e-12))) in fp32 on counted voxels; alpha positive, NOT normalised; -0.0 is +0.0.
+ *   n = number of counted voxels of the whole batch; k = max(1, (long long)((double)n * k_percent / 100.0)) for n > 0,
+ *       k_percent a double in (0, 100]; n == 0: L_topk = 0, zero gradient, k = 0.
+ *   tau = the k-th largest ell (as fp32 values), m = #{ell > tau}, n_eq = #{ell == tau}, r = k - m (1 <= r <= n_eq).
+ *   L_topk = (sum_{ell > tau} ell + r * tau) / k.  A term whose weight is 0 does not enter L and sends no gradient.
+ *   dL/dp of the top-k term sits on the plane c == t of counted voxels: ce_weight * w_v / k * (p_t >= 1e-12 ? -alpha_t / p_t
+ *       : 0), w_v = 1 for ell_v > tau, r / n_eq for ell_v == tau (ties share the remaining r places equally), 0 below.
+ * n, k and tau are the calling rank's own: there is no collective.  NaN and p > 1 are outside the contract for values; the
+ * kernels stay inside their buffers and terminate on them (their ell is stored as +0.0).
+ * tau comes from a three-level radix select (11 / 11 / 10 bits) over the bits of ell, driven by a device control block:
+ * integer atomics only (bit-reproducible), nothing is read back, nothing data-dependent is baked into a launch.  The entry
+ * zeroes its own counters on the stream at every call, allocates nothing and synchronises nothing, so it can be captured
+ * into a hipGraph and replayed on other contents.  N * S must be below 2^32 (the histogram counters).
+ * workspace: seg3d_topk_loss_workspace_bytes(N, C, S) bytes, 8-byte aligned, free after the call;
+ * ell: N * S floats kept for the backward (a negative sentinel on voxels that do not count);
+ * coef: 2 * R * C + 3 floats kept for the backward, R = batch_dice ? 1 : N -- the compound loss's (A, B) pairs, then tau,
+ *       ce_weight / k and ce_weight * (r / n_eq) / k (0 when the term is off or nothing counts);
+ * loss: 3 floats (L, L_region, L_topk); selection: 5 int64 (n, k, m, n_eq, r); threshold: 1 float, tau. */
+long long seg3d_topk_loss_workspace_bytes(int N, int C, long long S);
+int seg3d_topk_loss_fwd(const float* probs, const float* target, const float* wdice, const float* alpha, void* workspace,
+                        float* ell, float* coef, float* loss, long long* selection, float* threshold, int N, int C,
+                        long long S, double k_percent, float dice_weight, float ce_weight, int batch_dice,
+                        float ignore_label, void* stream);
+/* dprobs[n][c][s] = gout[0] * dL/dp: all C planes in one pass, zeros on voxels that do not count. */
+int seg3d_topk_loss_bwd(const float* probs, const float* target, const float* ell, const float* coef, const float* alpha,
+                        const float* gout, float* dprobs, int N, int C, long long S, int batch_dice, float ignore_label,
+                        void* stream);
+
 /* ---- region-based models (no counterpart in the reference) -----------------------------
  * Head sigmoid: the counterparts of the soft-max pair above, same layouts (NDHWC in, contiguous NCDHW out), 1 <= C <= 16.
  * p = 1 / (1 + exp(-x)) evaluated through exp(-|x|): finite and inside [0, 1] for every x.  Backward: din = dp p (1 - p). */

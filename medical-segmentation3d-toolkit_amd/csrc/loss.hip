@@ -14,8 +14,7 @@
 // fp64 finalize in fixed order.
 #include "seg3d_common.h"
 #include "seg3d_hip.h"
-
-#define SEG3D_MAXC 16
+#include "compound_device.h"   // SEG3D_MAXC, DICE_VPB, focal_pow and the compound loss's device functions
 
 // ---- softmax over channels: in NDHWC [V][C] -> out NCDHW [N][C][S] ----------------------------------------------
 __global__ __launch_bounds__(256) void softmax_fwd_kernel(const float* __restrict__ in, float* __restrict__ out, int C,
@@ -86,8 +85,6 @@ extern "C" int seg3d_softmax_bwd(const float* probs_ncdhw, const float* dprobs_n
 }
 
 // ---- Dice ---------------------------------------------------------------------------------------------------------
-#define DICE_VPB 4096  // voxels per workgroup
-
 // part[n][blk][c][3] = (sum phat*t, sum phat^2, sum t) over the block's voxels
 __global__ __launch_bounds__(256) void dice_partial_kernel(const float* __restrict__ probs,
                                                              const float* __restrict__ target, float* __restrict__ part,
@@ -302,12 +299,6 @@ extern "C" int seg3d_binary_dice_bwd(const float* probs, const float* target, co
 // ---- Focal ----------------------------------------------------------------------------------------------------------
 // probs element (n, c, s) lives at n*sn + c*sc + s*ss (planar NCDHW: sn = C*S, sc = S, ss = 1;
 // [sample, class] matrices: sn = 0, sc = 1, ss = C)
-__device__ __forceinline__ float focal_pow(float q, float gamma) {
-  if (gamma == 2.0f) return q * q;
-  if (gamma == 1.0f) return q;
-  return powf(q, gamma);
-}
-
 __global__ __launch_bounds__(256) void focal_partial_kernel(const float* __restrict__ probs,
                                                               const float* __restrict__ target,
                                                               const float* __restrict__ alpha, float* __restrict__ part,
@@ -413,54 +404,8 @@ extern "C" int seg3d_focal_bwd(const float* probs, const float* target, const fl
 //   coef_dist = ce_weight / sum a_t  (0 when nothing is valid or ce_weight is 0)
 // CT is the compile-time class count (1..5: exact, accumulators in registers; 16: generic, planes c >= C predicated
 // off); VEC: S % 4 == 0 and 16-byte aligned bases -> one 16-byte access per lane and plane, else a scalar path.
-#define COMPOUND_EPS 1e-5
-#define COMPOUND_PMIN 1e-12f
-
-template <int CT>
-struct CompoundAcc {
-  float r[3 * CT];   // (I, P, T) per class
-  float num, den;    // distribution numerator / denominator
-};
-
-// (1 - pt)^gamma (-log pt) for pt already clamped; q = max(1 - pt, 0)
-__device__ __forceinline__ float compound_dist(float pt, float gamma) {
-  const float nl = -logf(pt);
-  if (gamma == 0.0f) return nl;
-  return focal_pow(fmaxf(1.0f - pt, 0.0f), gamma) * nl;
-}
-
-// d/dpt of the above:  gamma q^(gamma-1) log pt - q^gamma / pt   (q = 0: the first product's limit is 0 for every gamma > 0)
-__device__ __forceinline__ float compound_dist_grad(float pt, float gamma) {
-  if (gamma == 0.0f) return -1.0f / pt;
-  const float q = fmaxf(1.0f - pt, 0.0f), lp = logf(pt);
-  float qg1;
-  if (gamma == 2.0f) qg1 = q;
-  else if (gamma == 1.0f) qg1 = 1.0f;
-  else qg1 = q > 0.0f ? powf(q, gamma - 1.0f) : 0.0f;
-  return gamma * qg1 * lp - focal_pow(q, gamma) / pt;
-}
-
-template <int CT>
-__device__ __forceinline__ void compound_voxel(CompoundAcc<CT>& a, float t, const float (&p)[CT], const float (&alpha)[CT],
-                                               int C, float ignore, float gamma) {
-  const bool valid = t >= 0.0f && t < (float)C && t != ignore;
-  if (!valid) return;
-  const int ti = (int)t;
-  float pt = 0.f, at = 0.f;
-#pragma unroll
-  for (int c = 0; c < CT; ++c)
-    if (CT <= 5 || c < C) {
-      const bool is = ti == c;
-      a.r[3 * c + 0] += is ? p[c] : 0.f;
-      a.r[3 * c + 1] += p[c];
-      a.r[3 * c + 2] += is ? 1.f : 0.f;
-      pt = is ? p[c] : pt;
-      at = is ? alpha[c] : at;
-    }
-  a.num += at * compound_dist(fmaxf(pt, COMPOUND_PMIN), gamma);
-  a.den += at;
-}
-
+// The per-voxel sums, the region term's finalize rule and the per-voxel gradient live in compound_device.h (shared with
+// topk_loss.hip).
 // part[n][blk][3C + 2] = (I, P, T) x C, dist numerator, dist denominator over the block's voxels
 template <int CT, bool VEC>
 __global__ __launch_bounds__(256) void compound_partial_kernel(const float* __restrict__ probs,
@@ -552,44 +497,9 @@ __global__ __launch_bounds__(256) void compound_finalize_kernel(const float* __r
   den = redd[0] + redd[1] + redd[2] + redd[3];
   __syncthreads();
 
-  const int grp = threadIdx.x >> 5, l32 = threadIdx.x & 31;
   const int R = batch_dice ? 1 : N;
-  const i64 cnt = batch_dice ? nent : (i64)nblk;
-  const double k = batch_dice ? 1.0 : 1.0 / (double)N;
-  double acc = 0.0;
-  for (int idx0 = 0; idx0 < R * C; idx0 += 8) {   // uniform trip count: the shuffles below need whole waves
-    const int idx = idx0 + grp;
-    const bool ok = idx < R * C;
-    const int r = ok ? idx / C : 0, c = ok ? idx % C : 0;
-    double I = 0.0, P = 0.0, T = 0.0;
-    if (ok) {
-      const float* p = part + (i64)r * nblk * NV + 3 * c;
-      for (i64 m = l32; m < cnt; m += 32) {
-        I += (double)p[m * NV + 0];
-        P += (double)p[m * NV + 1];
-        T += (double)p[m * NV + 2];
-      }
-    }
-#pragma unroll
-    for (int off = 16; off > 0; off >>= 1) {   // within the 32-lane group
-      I += __shfl_down(I, off, 32);
-      P += __shfl_down(P, off, 32);
-      T += __shfl_down(T, off, 32);
-    }
-    if (ok && l32 == 0) {
-      const double w = (double)wdice[c];
-      const double U = P + T + COMPOUND_EPS, nu = 2.0 * I + COMPOUND_EPS;
-      acc += w * k * (1.0 - nu / U);
-      const bool on = dice_weight > 0.f && w > 0.0;
-      coef[2 * idx + 0] = on ? (float)(-(double)dice_weight * w * k * 2.0 / U) : 0.f;
-      coef[2 * idx + 1] = on ? (float)((double)dice_weight * w * k * nu / (U * U)) : 0.f;
-    }
-  }
-  if (l32 == 0) red[grp] = acc;
-  __syncthreads();
+  const double lr = compound_region_finalize(part, wdice, coef, N, C, nblk, batch_dice, dice_weight, red);
   if (threadIdx.x == 0) {
-    double lr = 0.0;
-    for (int g = 0; g < 8; ++g) lr += red[g];
     const double ld = den > 0.0 ? num / den : 0.0;
     double l = 0.0;
     if (dice_weight > 0.f) l += (double)dice_weight * lr;
@@ -599,24 +509,6 @@ __global__ __launch_bounds__(256) void compound_finalize_kernel(const float* __r
     loss[2] = (float)ld;
     coef[2 * R * C] = (ce_weight > 0.f && den > 0.0) ? (float)((double)ce_weight / den) : 0.f;
   }
-}
-
-// one voxel's C gradients; g[c] is written for every c < C
-template <int CT>
-__device__ __forceinline__ void compound_voxel_grad(float (&g)[CT], float t, float pt_in, const float (&A)[CT],
-                                                    const float (&B)[CT], const float (&alpha)[CT], int C, float ignore,
-                                                    float gamma, float cd, float go) {
-  const bool valid = t >= 0.0f && t < (float)C && t != ignore;
-  const int ti = valid ? (int)t : -1;
-  float dt = 0.f;
-  if (valid && cd != 0.f && pt_in >= COMPOUND_PMIN) dt = cd * compound_dist_grad(pt_in, gamma);
-#pragma unroll
-  for (int c = 0; c < CT; ++c)
-    if (CT <= 5 || c < C) {
-      const bool is = ti == c;
-      const float d = (is ? A[c] + B[c] : B[c]) + (is ? alpha[c] * dt : 0.f);
-      g[c] = valid ? go * d : 0.f;
-    }
 }
 
 // grid (blocks, N): the sample -- and with it the coefficient row -- is uniform per workgroup
@@ -680,22 +572,6 @@ __global__ __launch_bounds__(256) void compound_bwd_kernel(const float* __restri
     }
   }
 }
-
-static inline bool compound_vec_ok(long long S, const void* a, const void* b, const void* c) {
-  return S % 4 == 0 && (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) == 0;
-}
-
-#define COMPOUND_DISPATCH(KERNEL, C, vec, ...)                                         \
-  do {                                                                                 \
-    switch (C) {                                                                       \
-      case 1: if (vec) KERNEL<1, true> __VA_ARGS__; else KERNEL<1, false> __VA_ARGS__; break;    \
-      case 2: if (vec) KERNEL<2, true> __VA_ARGS__; else KERNEL<2, false> __VA_ARGS__; break;    \
-      case 3: if (vec) KERNEL<3, true> __VA_ARGS__; else KERNEL<3, false> __VA_ARGS__; break;    \
-      case 4: if (vec) KERNEL<4, true> __VA_ARGS__; else KERNEL<4, false> __VA_ARGS__; break;    \
-      case 5: if (vec) KERNEL<5, true> __VA_ARGS__; else KERNEL<5, false> __VA_ARGS__; break;    \
-      default: if (vec) KERNEL<SEG3D_MAXC, true> __VA_ARGS__; else KERNEL<SEG3D_MAXC, false> __VA_ARGS__; break; \
-    }                                                                                  \
-  } while (0)
 
 extern "C" long long seg3d_compound_loss_part_floats(int N, int C, long long S) {
   return (long long)N * seg3d_dice_blocks(S) * (3 * C + 2);

@@ -190,6 +190,9 @@ _SIGNATURES = {
     'seg3d_compound_loss_part_floats': (_c_ll, [_c_int, _c_int, _c_ll]),
     'seg3d_compound_loss_fwd': (_c_int, [_c_p] * 7 + [_c_int, _c_int, _c_ll, _c_f, _c_f, _c_f, _c_int, _c_f, _c_p]),
     'seg3d_compound_loss_bwd': (_c_int, [_c_p] * 6 + [_c_int, _c_int, _c_ll, _c_f, _c_int, _c_f, _c_p]),
+    'seg3d_topk_loss_workspace_bytes': (_c_ll, [_c_int, _c_int, _c_ll]),
+    'seg3d_topk_loss_fwd': (_c_int, [_c_p] * 10 + [_c_int, _c_int, _c_ll, ctypes.c_double, _c_f, _c_f, _c_int, _c_f, _c_p]),
+    'seg3d_topk_loss_bwd': (_c_int, [_c_p] * 7 + [_c_int, _c_int, _c_ll, _c_int, _c_f, _c_p]),
     'seg3d_sigmoid_fwd': (_c_int, [_c_p, _c_p, _c_int, _c_int, _c_ll, _c_p]),
     'seg3d_sigmoid_bwd': (_c_int, [_c_p, _c_p, _c_p, _c_int, _c_int, _c_ll, _c_p]),
     'seg3d_ds_head_supported': (_c_int, [_c_int] * 2),

@@ -1439,6 +1439,53 @@ class CompoundLossFunction(torch.autograd.Function):
         return (dp,) + (None,) * 8
 
 
+class TopKLossFunction(torch.autograd.Function):
+    """DiceTopKLoss.forward (loss/topk_loss.py): soft Dice + cross-entropy over the hardest k_percent of the batch's counted
+    voxels.  The k-th largest per-voxel loss comes from an on-device radix select (seg3d_topk_loss_fwd): no read-back, so
+    the call can be captured into a hipGraph.  `wdice`, `alpha`, `ignore` as for CompoundLossFunction.  Every buffer is
+    allocated per call (a DeepSupervisionLoss calls one loss object several times before any backward runs).
+    Returns (loss, terms, selection, threshold): the 0-dim loss, the device tensors (L, L_region, L_topk), int64
+    (n, k, m, n_eq, r) and the fp32 threshold tau; only the loss carries a gradient."""
+
+    @staticmethod
+    def forward(ctx, probs, target, wdice, alpha, k_percent, dice_weight, ce_weight, batch_dice, ignore):
+        E.require_device(probs, target, wdice, alpha)
+        if probs.dtype != torch.float32:
+            raise ValueError('probabilities must be float32, got {}'.format(probs.dtype))
+        p = probs.contiguous()
+        t = target.contiguous().float()
+        N, C = p.shape[0], p.shape[1]
+        S = p[0, 0].numel()
+        if t.numel() != N * S:
+            raise ValueError('target shape {} does not match input {}'.format(tuple(target.shape), tuple(probs.shape)))
+        cfg = (int(bool(batch_dice)), float(ignore))
+        work = _empty(((E.query('seg3d_topk_loss_workspace_bytes', N, C, S) + 7) // 8,), p, dtype=torch.int64)
+        ell = _empty((N * S,), p)
+        coef = _empty((2 * (1 if cfg[0] else N) * C + 3,), p)
+        terms = _empty((3,), p)
+        selection = _empty((5,), p, dtype=torch.int64)
+        threshold = _empty((1,), p)
+        E.call('seg3d_topk_loss_fwd', E.ptr(p), E.ptr(t), E.ptr(wdice), E.ptr(alpha), E.ptr(work), E.ptr(ell), E.ptr(coef),
+               E.ptr(terms), E.ptr(selection), E.ptr(threshold), N, C, S, float(k_percent), float(dice_weight),
+               float(ce_weight), cfg[0], cfg[1], E.stream_ptr())
+        ctx.save_for_backward(p, t, ell, coef, alpha)
+        ctx.cfg = cfg
+        ctx.mark_non_differentiable(terms, selection, threshold)
+        return terms[0], terms, selection, threshold
+
+    @staticmethod
+    def backward(ctx, gout, _gterms, _gselection, _gthreshold):
+        p, t, ell, coef, alpha = ctx.saved_tensors
+        batch_dice, ignore = ctx.cfg
+        N, C = p.shape[0], p.shape[1]
+        S = p[0, 0].numel()
+        g = gout.contiguous().reshape(1).float()
+        dp = torch.empty_like(p)
+        E.call('seg3d_topk_loss_bwd', E.ptr(p), E.ptr(t), E.ptr(ell), E.ptr(coef), E.ptr(alpha), E.ptr(g), E.ptr(dp), N, C, S,
+               batch_dice, ignore, E.stream_ptr())
+        return (dp,) + (None,) * 8
+
+
 class BinaryDiceLossFunction(torch.autograd.Function):
     """BinaryDiceLoss.forward called on its own (loss/binary_dice_loss.py:9-36): one fused reduction + one elementwise
     backward; probs [N, 2, ...], float target with N * S elements"""

@@ -24,14 +24,21 @@ from segmentation3d.loss.cross_entropy_loss import CrossEntropyLoss
 from segmentation3d.loss.deep_supervision_loss import DeepSupervisionLoss, normalise_level_weights
 from segmentation3d.loss.focal_loss import FocalLoss
 from segmentation3d.loss.multi_dice_loss import MultiDiceLoss
+from segmentation3d.loss.topk_loss import DiceTopKLoss
 from segmentation3d.optim.fused_adam import FusedAdam
 from segmentation3d.optim.fused_sgd import FusedSGD
 
 
 def build_loss(name, num_classes, obj_weight=None, focal_gamma=2, use_gpu=True, dice_weight=1.0, ce_weight=1.0,
-               include_background=True, batch_dice=False, ignore_label=None):
-    """loss selection of core/seg_train.py:91-102, plus the compound losses 'DiceCE' (soft Dice + cross-entropy) and
-    'DiceFocal' (soft Dice + focal with focal_gamma); the keyword options after use_gpu apply to those two only"""
+               include_background=True, batch_dice=False, ignore_label=None, topk_percent=10.0):
+    """loss selection of core/seg_train.py:91-102, plus the compound losses 'DiceCE' (soft Dice + cross-entropy),
+    'DiceFocal' (soft Dice + focal with focal_gamma) and 'DiceTopK' (soft Dice + cross-entropy over the hardest
+    topk_percent of the batch's voxels); the keyword options after use_gpu apply to those three only, topk_percent to
+    'DiceTopK' only"""
+    if name == 'DiceTopK':
+        return DiceTopKLoss(num_classes, weights=obj_weight, dice_weight=dice_weight, ce_weight=ce_weight,
+                            k_percent=topk_percent, include_background=include_background, batch_dice=batch_dice,
+                            ignore_label=ignore_label, use_gpu=use_gpu)
     if name in ('DiceCE', 'DiceFocal'):
         return DiceCELoss(num_classes, weights=obj_weight, dice_weight=dice_weight, ce_weight=ce_weight,
                           gamma=focal_gamma if name == 'DiceFocal' else 0.0, include_background=include_background,
@@ -48,10 +55,14 @@ def build_loss(name, num_classes, obj_weight=None, focal_gamma=2, use_gpu=True, 
 
 def loss_options_from_config(loss_cfg):
     """the optional keys of the config's `loss` section that the compound losses read, with their defaults (a config
-    without them -- every reference config -- loads unchanged)"""
-    return {'dice_weight': getattr(loss_cfg, 'dice_weight', 1.0), 'ce_weight': getattr(loss_cfg, 'ce_weight', 1.0),
+    without them -- every reference config -- loads unchanged); `topk_percent` ('DiceTopK') is passed on only when the
+    section has it"""
+    opts = {'dice_weight': getattr(loss_cfg, 'dice_weight', 1.0), 'ce_weight': getattr(loss_cfg, 'ce_weight', 1.0),
             'include_background': getattr(loss_cfg, 'include_background', True),
             'batch_dice': getattr(loss_cfg, 'batch_dice', False), 'ignore_label': getattr(loss_cfg, 'ignore_label', None)}
+    if hasattr(loss_cfg, 'topk_percent'):
+        opts['topk_percent'] = loss_cfg.topk_percent
+    return opts
 
 
 def optim_options_from_config(train_cfg, num_samples=None, world_size=1):
@@ -138,7 +149,8 @@ def build_optimizer(name, params, lr, betas=(0.9, 0.999), optim_options=None):
 class TrainStep(object):
     """network + loss + FusedAdam or FusedSGD (+ gradient reducer when distributed) on one device; `loss_options` is a
     dict of build_loss's keyword options for the compound losses (dice_weight, ce_weight, include_background, batch_dice,
-    ignore_label); `optimizer` / `optim_options` are build_optimizer's (gradient-norm clipping, lr schedule, SGD);
+    ignore_label, and topk_percent for loss_name='DiceTopK'); `optimizer` / `optim_options` are build_optimizer's
+    (gradient-norm clipping, lr schedule, SGD);
     `deep_supervision` = L in 1..3 builds the network with L auxiliary heads and trains on the weighted per-level losses
     (loss/deep_supervision_loss.py; `deep_supervision_weights`: L + 1 weights, None = halving per level)"""
 
