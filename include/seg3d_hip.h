@@ -285,6 +285,10 @@ long long seg3d_conv3d_k3_thin_in_persistent_stats_count(int D, int H, int W, in
 int seg3d_conv3d_k3_thin_in_persistent_fwd(const float* x, const float* wp_thin, const float* bias, void* y,
                                            float* stats_partial, int N, int D, int H, int W, int CT, int Cout, int out_bf16,
                                            void* stream);
+/* read-only: the row form the launcher picks from Cout (16 or 32), and grid.x of its tile walk (min(1024 / Cout blocks,
+ * tiles)); both call the functions the launcher calls */
+int seg3d_conv3d_k3_thin_in_persistent_variant(int Cout);
+long long seg3d_conv3d_k3_thin_in_persistent_workgroups(int N, int D, int H, int W, int Cout);
 /* fp32 head conv on the fp32 matrix cores (csrc/conv_thin_f32.hip; Cin in {16, 32}, Cout <= 5): x taps in the reduction
  * dimension of v_mfma_f32_16x16x4_f32, (kz, ky) taps in its output rows, the ninth tap on the VALU when 8 taps fill the
  * rows exactly (2 and 4 classes); every voxel row is read once, no LDS staging of activations.  Exact fp32 arithmetic.
@@ -293,6 +297,8 @@ int seg3d_conv3d_k3_thin_out_f32mfma_supported(int Cin, int Cout);
 long long seg3d_thin_out_f32mfma_packed_floats(int Cin, int Cout);
 int seg3d_pack_weights_thin_out_f32mfma(const float* w, float* wpk, int A, int B, long long sa, long long sb, int flip,
                                         void* stream);
+/* read-only: the z extent of a wave's tile (8, 12, 16, 24, 32 or 48) the launcher's cost model picks */
+int seg3d_conv3d_k3_thin_out_f32mfma_tz(int N, int D, int H, int W);
 long long seg3d_conv3d_k3_thin_out_f32mfma_stats_count(int N, int D, int H, int W);
 int seg3d_conv3d_k3_thin_out_f32mfma_fwd(const float* x, const float* wpk, const float* bias, float* y,
                                          float* stats_partial, int N, int D, int H, int W, int Cin, int Cout, void* stream);

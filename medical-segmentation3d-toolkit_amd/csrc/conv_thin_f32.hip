@@ -426,6 +426,12 @@ static int thin_out_f32_tz(int N, int D, int H, int W) {
   return best;
 }
 
+// read-only view of thin_out_f32_tz (tests/thin_cases.py)
+extern "C" int seg3d_conv3d_k3_thin_out_f32mfma_tz(int N, int D, int H, int W) {
+  if (N <= 0 || D <= 0 || H <= 0 || W <= 0) return 0;
+  return thin_out_f32_tz(N, D, H, W);
+}
+
 extern "C" long long seg3d_conv3d_k3_thin_out_f32mfma_stats_count(int N, int D, int H, int W) {
   const int tz = thin_out_f32_tz(N, D, H, W);
   return (long long)seg3d_cdiv(D, tz) * seg3d_cdiv(H, TF_TY) * seg3d_cdiv(W, TF_TX);
@@ -879,17 +885,38 @@ __global__ __launch_bounds__(256, 2) void conv3d_k3_thin_in_persistent16_kernel(
   }
 }
 
+// 16-row MFMA (no empty rows, whole 64-byte voxel rows per store) or the 32-row body
+static int thin_in_persistent_rows(int Cout) { return (Cout <= 16 && (Cout & 3) == 0) ? 16 : 32; }
+
+// tiles of the walk, Cout blocks, and grid.x = min(1024 / cobs, tiles)
+struct ThinInPersistentPlan { int ntz, nty, ntx, ntiles, cobs, wgs; };
+
+static ThinInPersistentPlan thin_in_persistent_plan(int N, int D, int H, int W, int Cout) {
+  ThinInPersistentPlan p;
+  p.ntz = seg3d_cdiv(D, TP_TZ); p.nty = seg3d_cdiv(H, TP_TY); p.ntx = seg3d_cdiv(W, TP_TX);
+  p.ntiles = N * p.ntz * p.nty * p.ntx;
+  p.cobs = (Cout + 31) / 32;
+  p.wgs = 1024 / p.cobs;               // ~4 workgroups per CU over the whole grid (LDS 2.4 KB x CT, <= 128 registers)
+  if (p.wgs > p.ntiles) p.wgs = p.ntiles;
+  if (p.wgs < 1) p.wgs = 1;
+  return p;
+}
+
+// read-only views of the two rules above (tests/thin_cases.py): the row form, and grid.x of the tile walk
+extern "C" int seg3d_conv3d_k3_thin_in_persistent_variant(int Cout) { return Cout > 0 ? thin_in_persistent_rows(Cout) : 0; }
+
+extern "C" long long seg3d_conv3d_k3_thin_in_persistent_workgroups(int N, int D, int H, int W, int Cout) {
+  if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || Cout <= 0 || (i64)N * D * H * W >= (1ll << 31)) return 0;   // as the launcher
+  return thin_in_persistent_plan(N, D, H, W, Cout).wgs;
+}
+
 template <int CT>
 static void launch_thin_in_persistent(const float* x, const float* wp, const float* bias, float* y, float* stats, int N, int D,
                                       int H, int W, int Cout, hipStream_t s, int out_bf16) {
-  const int ntz = seg3d_cdiv(D, TP_TZ), nty = seg3d_cdiv(H, TP_TY), ntx = seg3d_cdiv(W, TP_TX);
-  const int ntiles = N * ntz * nty * ntx;
-  const int cobs = (Cout + 31) / 32;
-  int wgs = 1024 / cobs;               // ~4 workgroups per CU over the whole grid (LDS 2.4 KB x CT, <= 128 registers)
-  if (wgs > ntiles) wgs = ntiles;
-  if (wgs < 1) wgs = 1;
-  dim3 grid((unsigned)wgs, (unsigned)cobs);
-  if (Cout <= 16 && (Cout & 3) == 0) {   // 16-row MFMA: no empty rows, whole 64-byte voxel rows per store
+  const ThinInPersistentPlan p = thin_in_persistent_plan(N, D, H, W, Cout);
+  const int ntz = p.ntz, nty = p.nty, ntx = p.ntx, ntiles = p.ntiles;
+  dim3 grid((unsigned)p.wgs, (unsigned)p.cobs);
+  if (thin_in_persistent_rows(Cout) == 16) {
     if (out_bf16)
       hipLaunchKernelGGL((conv3d_k3_thin_in_persistent16_kernel<CT, true>), grid, dim3(256), 0, s, x, wp, bias, y, stats, N, D, H,
                          W, Cout, ntz, nty, ntx, ntiles);

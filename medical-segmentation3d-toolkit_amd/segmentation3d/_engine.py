@@ -136,6 +136,8 @@ _SIGNATURES = {
     'seg3d_conv3d_k3_thin_in_bf16out_fwd': (_c_int, [_c_p] * 5 + [_c_int] * 6 + [_c_p]),
     'seg3d_conv3d_k3_thin_in_persistent_stats_count': (_c_ll, [_c_int] * 4),
     'seg3d_conv3d_k3_thin_in_persistent_fwd': (_c_int, [_c_p] * 5 + [_c_int] * 7 + [_c_p]),
+    'seg3d_conv3d_k3_thin_in_persistent_variant': (_c_int, [_c_int]),
+    'seg3d_conv3d_k3_thin_in_persistent_workgroups': (_c_ll, [_c_int] * 5),
     'seg3d_conv3d_k3_wino_supported': (_c_int, [_c_int] * 6),
     'seg3d_conv3d_k3_wino_preferred': (_c_int, [_c_int] * 6),
     'seg3d_conv3d_k3_wino_stats_count': (_c_ll, [_c_int] * 6),
@@ -156,6 +158,7 @@ _SIGNATURES = {
     'seg3d_conv3d_k3_thin_out_f32mfma_supported': (_c_int, [_c_int] * 2),
     'seg3d_thin_out_f32mfma_packed_floats': (_c_ll, [_c_int] * 2),
     'seg3d_pack_weights_thin_out_f32mfma': (_c_int, [_c_p, _c_p, _c_int, _c_int, _c_ll, _c_ll, _c_int, _c_p]),
+    'seg3d_conv3d_k3_thin_out_f32mfma_tz': (_c_int, [_c_int] * 4),
     'seg3d_conv3d_k3_thin_out_f32mfma_stats_count': (_c_ll, [_c_int] * 4),
     'seg3d_conv3d_k3_thin_out_f32mfma_fwd': (_c_int, [_c_p] * 5 + [_c_int] * 6 + [_c_p]),
     'seg3d_pack_weights_thin_out': (_c_int, [_c_p, _c_p, _c_int, _c_int, _c_int, _c_ll, _c_ll, _c_int, _c_p]),

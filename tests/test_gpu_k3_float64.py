@@ -38,36 +38,12 @@ import torch
 import torch.nn.functional as F
 
 import k3_cases as K
-from float64_util import (FLOOR_EW, FLOOR_RED, Figures, Guarded, _activation, _check_stats, _engine, _noise, _weight,
-                          bf16_round)
+from float64_util import (FLOOR_EW, FLOOR_RED, Figures, Guarded, _activation, _check_stats, _conv_def, _engine, _noise, _weight,
+                          _wgrad_def, bf16_round)
 
 pytestmark = pytest.mark.gpu
 
 CAP_Y_ABS, CAP_Y_BF16_REL, CAP_WGRAD_REL, CAP_WGRAD_BF16_REL = 1e-4, 2e-5, 2e-4, 2e-5
-TAPS = [(kz, ky, kx) for kz in range(3) for ky in range(3) for kx in range(3)]
-
-
-# ---- float64 references (device) -------------------------------------------------------------------------------------------
-def _pad(x):
-    return F.pad(x, (0, 0, 1, 1, 1, 1, 1, 1))            # [N, D + 2, H + 2, W + 2, C], zeros
-
-
-def _conv_def(x, w):
-    """x [N, D, H, W, Ci], w [Co, Ci, 3, 3, 3], both float64"""
-    N, D, H, W, Ci = x.shape
-    xp = _pad(x)
-    out = torch.zeros((N * D * H * W, w.shape[0]), dtype=torch.float64, device=x.device)
-    for (kz, ky, kx) in TAPS:
-        out += xp[:, kz:kz + D, ky:ky + H, kx:kx + W, :].reshape(-1, Ci) @ w[:, :, kz, ky, kx].t()
-    return out.reshape(N, D, H, W, w.shape[0])
-
-
-def _wgrad_def(x, dy):
-    """x [N, D, H, W, Ci], dy [N, D, H, W, Co] -> dw [Co, Ci, 27]"""
-    N, D, H, W, Ci = x.shape
-    xp = _pad(x)
-    dyt = dy.reshape(-1, dy.shape[-1]).t().contiguous()
-    return torch.stack([dyt @ xp[:, kz:kz + D, ky:ky + H, kx:kx + W, :].reshape(-1, Ci) for (kz, ky, kx) in TAPS], 2)
 
 
 def _bits(t):

@@ -476,8 +476,9 @@ def test_conv3d_k3_thin_out_mfma(hip_device, shape, flip):
 def test_conv3d_k3_thin_out_f32mfma(hip_device, shape, flip):
     """fp32 head conv on the fp32 matrix cores (x taps in K of v_mfma_f32_16x16x4_f32, (kz, ky) taps in the output rows,
     ninth tap on the VALU for 2 / 4 classes) against the float64 convolution: 1..5 classes, Cin 16 / 32, ragged tiles in
-    every dimension, z marches longer than one tile, flipped taps (the adjoint form), no-bias / no-stats calls, and
-    per-tile statistics equal to those of its own output"""
+    every dimension, several z tiles (every shape here has at most 1024 tiles, so the launcher picks tz = 8; the longer z
+    marches tz = 12 .. 48 run in tests/test_gpu_thin_float64.py), flipped taps (the adjoint form), no-bias / no-stats calls,
+    and per-tile statistics equal to those of its own output"""
     from segmentation3d import _ops, _engine as E
     N, Cin, Cout, D, H, W = shape
     assert E.query('seg3d_conv3d_k3_thin_out_f32mfma_supported', Cin, Cout) == 1
@@ -581,9 +582,10 @@ def test_conv3d_k3_thin_in_mfma16(hip_device, shape, flip):
 @pytest.mark.parametrize('out_bf16', [0, 1])
 def test_conv3d_k3_thin_in_persistent(hip_device, shape, flip, out_bf16):
     """persistent thin-input conv (stem forward / head data-gradient, fp32 arithmetic) against the float64 convolution:
-    1..8 thin channels (even: immediate LDS offsets, odd: per-lane table), whole and ragged tiles, several tiles per
-    workgroup, partial channel blocks, flipped taps, fp32 and bf16-storage outputs, no-bias / no-stats calls, per-wave
-    statistics equal to those of the unrounded output"""
+    1..8 thin channels (even: immediate LDS offsets, odd: per-lane table), whole and ragged tiles, one tile per workgroup
+    (at most 225 tiles on up to 1024 workgroups; the walk over several tiles runs in tests/test_gpu_thin_float64.py),
+    partial channel blocks, flipped taps, fp32 and bf16-storage outputs, no-bias / no-stats calls, per-wave statistics
+    equal to those of the unrounded output"""
     from segmentation3d import _ops, _engine as E
     N, CT, Cout, D, H, W = shape
     x = _t(74, 'px', (N, CT, D, H, W))
