@@ -166,6 +166,22 @@ int seg3d_conv3d_k3_wino2d_wgrad_preferred(int N, int D, int H, int W, int Cin, 
 long long seg3d_conv3d_k3_wino2d_wgrad_workspace_floats(int N, int D, int H, int W, int Cin, int Cout);
 int seg3d_conv3d_k3_wino2d_wgrad(const float* x, const float* dy, float* dw, float* workspace, int N, int D, int H, int W,
                                  int Cin, int Cout, int accumulate, void* stream);
+/* Read-only: which kernels a Winograd launch of this shape runs (tests/wino_cases.py names every one).  Each query calls the
+ * function its launcher calls.
+ *   seg3d_conv3d_k3_wino2d_fwd_variant     8: conv3d_k3_wino2d_kernel (whole 8^3 tiles), 4 / 2: conv3d_k3_wino2d_c4_kernel with that
+ *                                          many 4^3 cells per item (four where that makes 192 items), 0: unsupported
+ *   seg3d_conv3d_k3_wino2d_fwd_sk_chunks   K chunks (of four input channels) per workgroup range of the stream-K form that
+ *                                          seg3d_conv3d_k3_wino2d_fwd_ws runs when given its workspace; 0: whole items
+ *   seg3d_conv3d_k3_wino_wgrad_variant     10 k + r.  k = 0: conv3d_k3_wgrad_wino_kernel<4, 4, 8> (W % 8 == 0), 1: <4, 4, 4>;
+ *                                          r = 1: conv3d_k3_wgrad_wino_reduce_kernel<8> (32 slabs or more), 0: <4>
+ *   seg3d_conv3d_k3_wino2d_wgrad_variant   10 k + r.  k = 0: conv3d_k3_wgrad_wino2d_kernel;
+ *                                          r = 1: conv3d_k3_wgrad_wino2d_reduce16_kernel<16> (64 slabs or more), 0: <4>
+ * The weight-gradient queries return -1 for a shape their launcher refuses.  Slabs = workspace floats / (npairs * 36 * 1024)
+ * and / (npairs * 48 * 1024), npairs = ceil(Cin / 32) * ceil(Cout / 32) */
+int seg3d_conv3d_k3_wino2d_fwd_variant(int N, int D, int H, int W, int Cin, int Cout);
+int seg3d_conv3d_k3_wino2d_fwd_sk_chunks(int N, int D, int H, int W, int Cin, int Cout);
+int seg3d_conv3d_k3_wino_wgrad_variant(int N, int D, int H, int W, int Cin, int Cout);
+int seg3d_conv3d_k3_wino2d_wgrad_variant(int N, int D, int H, int W, int Cin, int Cout);
 long long seg3d_conv3d_k3_bf16_stats_count(int N, int D, int H, int W, int Cin, int Cout);
 long long seg3d_conv3d_k3_bf16_fwd_workspace_floats(int N, int D, int H, int W, int Cin, int Cout);
 /* 200 + 10*MA + NB = conv3d_k3_mfma2_bf16_kernel<MA, NB> (split-K: conv3d_k3_mfma2_bf16_splitk_kernel<MA, NB> + the finish

@@ -10,7 +10,7 @@
 //     M_p = sum_{kz, ky, ci} U_p D_p            y[x0] = M0 + M1 + M2,  y[x0 + 1] = M1 - M2 - M3
 // i.e. four implicit GEMMs with K = 9 Cin instead of one with K = 27 Cin per output PAIR: 2/3 of the MFMAs.  The
 // transforms are exact in fp32 up to one rounding each (coefficients 1, 1/2), the accumulation is the same fp32 MFMA
-// chain; measured against float64 the error stays at the direct kernel's level (tests/test_gpu_kernels.py).
+// chain; measured against float64 the error stays at the fp32 yardsticks' level (tests/test_gpu_wino_float64.py).
 //
 // Structure = the persistent kernel of conv_mfma.hip (one workgroup per CU walks (tile, column block) items, K chunks of 8
 // input channels arrive by LDS-DMA, packed weight images are straight 1-KiB copies), with
@@ -645,6 +645,9 @@ static WnWgradPlan wn_wgrad_plan(int N, int D, int H, int W, int Cin, int Cout) 
   return p;
 }
 
+// waves of the reduce kernel over the slabs
+static int wn_reduce_waves(int slabs) { return slabs >= 32 ? 8 : 4; }
+
 // shapes the Winograd weight gradient takes: whole 4 x 4 x 4 tiles, channels in fours
 extern "C" int seg3d_conv3d_k3_wino_wgrad_supported(int N, int D, int H, int W, int Cin, int Cout) {
   if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return 0;
@@ -657,6 +660,14 @@ extern "C" int seg3d_conv3d_k3_wino_wgrad_supported(int N, int D, int H, int W, 
 extern "C" long long seg3d_conv3d_k3_wino_wgrad_workspace_floats(int N, int D, int H, int W, int Cin, int Cout) {
   const int npairs = ((Cin + 31) / 32) * ((Cout + 31) / 32);
   return (long long)wn_wgrad_plan(N, D, H, W, Cin, Cout).slabs * npairs * 36 * 1024;
+}
+
+// read-only: the kernels a launch of this shape runs, 10 k + r as seg3d_conv3d_k3_wgrad_variant -- k = 0: the 4 x 4 x 8 tile,
+// 1: 4 x 4 x 4; r = 1: conv3d_k3_wgrad_wino_reduce_kernel<8>, 0: <4>; -1 for an unsupported shape
+extern "C" int seg3d_conv3d_k3_wino_wgrad_variant(int N, int D, int H, int W, int Cin, int Cout) {
+  if (!seg3d_conv3d_k3_wino_wgrad_supported(N, D, H, W, Cin, Cout)) return -1;
+  const WnWgradPlan plan = wn_wgrad_plan(N, D, H, W, Cin, Cout);
+  return 10 * (plan.tx == 8 ? 0 : 1) + (wn_reduce_waves(plan.slabs) == 8 ? 1 : 0);
 }
 
 template <int TZ, int TY, int TX>
@@ -690,7 +701,7 @@ extern "C" int seg3d_conv3d_k3_wino_wgrad(const float* x, const float* dy, float
   SEG3D_LAUNCH_CHECK("seg3d_conv3d_k3_wino_wgrad");
   const i64 totalq = (i64)npairs * 9 * 256;
   const unsigned grid = (unsigned)((totalq + 63) / 64);
-  if (plan.slabs >= 32)
+  if (wn_reduce_waves(plan.slabs) == 8)
     hipLaunchKernelGGL(conv3d_k3_wgrad_wino_reduce_kernel<8>, dim3(grid), dim3(512), 0, s, workspace, dw, plan.slabs, Cin, Cout,
                        COB32, npairs, (i64)27, (i64)Cin * 27, accumulate);
   else

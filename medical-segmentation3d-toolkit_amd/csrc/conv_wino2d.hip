@@ -9,7 +9,7 @@
 //     M = sum_{kz, ci} U (.) V   (16 points)                          Y = A^T M A,  A^T = [1 1 1 0; 0 1 -1 -1]
 // i.e. sixteen implicit GEMMs with K = 3 Cin per output quad: 4/9 of the direct kernel's MFMAs (2/3 of conv_wino.hip's).
 // All coefficients are 1, 1/2, 1/4: the transforms are exact in fp32 up to one rounding per add, the accumulation is the
-// same fp32 MFMA chain (error against float64: tests/test_gpu_kernels.py::test_conv3d_k3_winograd2d).
+// same fp32 MFMA chain (error against float64: tests/test_gpu_wino_float64.py::test_wino_forward).
 //
 // Structure: the persistent skeleton of conv_wino.hip (one workgroup per CU walks (tile, column block) items; K chunks
 // arrive by LDS-DMA; packed weight images are straight copies), with
@@ -1075,6 +1075,17 @@ extern "C" long long seg3d_conv3d_k3_wino2d_fwd_workspace_floats(int N, int D, i
   return w2_sk_per(N, D, H, W, Cin, Cout) > 0 ? 2ll * seg3d_device_cus() * (W2_TS * W2_TS * W2_TS * 32) : 0;
 }
 
+// read-only: the kernel a launch of this shape runs -- 8: the tile kernel, 4 / 2: the cell kernel with that many cells per item,
+// 0: unsupported -- and the chunks per workgroup range of its stream-K form (0: whole items, as with a null workspace)
+extern "C" int seg3d_conv3d_k3_wino2d_fwd_variant(int N, int D, int H, int W, int Cin, int Cout) {
+  if (!seg3d_conv3d_k3_wino2d_supported(N, D, H, W, Cin, Cout)) return 0;
+  return w2_tiles(D, H, W) ? W2_TS : w2_cells_per_item(N, D, H, W, Cout);
+}
+extern "C" int seg3d_conv3d_k3_wino2d_fwd_sk_chunks(int N, int D, int H, int W, int Cin, int Cout) {
+  if (!seg3d_conv3d_k3_wino2d_supported(N, D, H, W, Cin, Cout)) return 0;
+  return w2_sk_per(N, D, H, W, Cin, Cout);
+}
+
 // x [N][D][H][W][Cin], wp = seg3d_pack_weights_mfma(A = Cin, B = Cout, T = 48) (the F(2x2, 3x3) image), y [N][D][H][W][Cout];
 // bias, addend, stats as seg3d_conv3d_k3_mfma_fwd; workspace: seg3d_conv3d_k3_wino2d_fwd_workspace_floats floats, or null (no stream-K)
 extern "C" int seg3d_conv3d_k3_wino2d_fwd_ws(const float* x, const float* wp, const float* bias, const float* addend, float* y,
@@ -1831,6 +1842,9 @@ static int g2_slabs(int N, int D, int H, int W, int Cin, int Cout) {
   return (int)slabs;
 }
 
+// waves of the reduce kernel over the slabs: 16 where there are many of them, 4 otherwise
+static int g2_reduce_waves(int slabs) { return slabs >= 64 ? 16 : 4; }
+
 // shapes the F(3x3, 2x2) weight gradient takes: whole 4 x 4 x 4 tiles, channels in fours
 extern "C" int seg3d_conv3d_k3_wino2d_wgrad_supported(int N, int D, int H, int W, int Cin, int Cout) {
   if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return 0;
@@ -1853,6 +1867,13 @@ extern "C" int seg3d_conv3d_k3_wino2d_wgrad_preferred(int N, int D, int H, int W
 extern "C" long long seg3d_conv3d_k3_wino2d_wgrad_workspace_floats(int N, int D, int H, int W, int Cin, int Cout) {
   const int npairs = ((Cin + 31) / 32) * ((Cout + 31) / 32);
   return (long long)g2_slabs(N, D, H, W, Cin, Cout) * npairs * 48 * 1024;
+}
+
+// read-only: the kernels a launch of this shape runs, 10 k + r as seg3d_conv3d_k3_wgrad_variant -- k = 0 (one tile shape),
+// r = 1: conv3d_k3_wgrad_wino2d_reduce16_kernel<16>, r = 0: <4>; -1 for an unsupported shape
+extern "C" int seg3d_conv3d_k3_wino2d_wgrad_variant(int N, int D, int H, int W, int Cin, int Cout) {
+  if (!seg3d_conv3d_k3_wino2d_wgrad_supported(N, D, H, W, Cin, Cout)) return -1;
+  return g2_reduce_waves(g2_slabs(N, D, H, W, Cin, Cout)) == 16 ? 1 : 0;
 }
 
 // x [N][D][H][W][Cin], dy [N][D][H][W][Cout]; dw in the reference Conv3d layout [Cout][Cin][3][3][3] (written, or added to
@@ -1883,8 +1904,8 @@ extern "C" int seg3d_conv3d_k3_wino2d_wgrad(const float* x, const float* dy, flo
                        dy, workspace, N, D, H, W, Cin, Cout, ntz, nty, ntx, ntiles, slabs, COB32);
   SEG3D_LAUNCH_CHECK("seg3d_conv3d_k3_wino2d_wgrad");
   const i64 totalq = (i64)npairs * 3 * 256;
-  // one point row per lane; 16 waves over the slabs where there are many of them, 4 otherwise
-  if (slabs >= 64)
+  // one point row per lane
+  if (g2_reduce_waves(slabs) == 16)
     hipLaunchKernelGGL(conv3d_k3_wgrad_wino2d_reduce16_kernel<16>, dim3((unsigned)(totalq / 16)), dim3(1024), 0, s, workspace, dw,
                        slabs, Cin, Cout, COB32, npairs, (i64)27, (i64)Cin * 27, accumulate);
   else

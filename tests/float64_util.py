@@ -1,5 +1,5 @@
 """helpers shared by the "every kernel instantiation against float64" device tests (tests/test_gpu_k2_float64.py,
-tests/test_gpu_k3_float64.py, tests/test_gpu_thin_float64.py): deterministic inputs, the float64 3x3x3 references, NaN guard
+tests/test_gpu_k3_float64.py, tests/test_gpu_thin_float64.py, tests/test_gpu_wino_float64.py): deterministic inputs, the float64 3x3x3 references, NaN guard
 bands, and the bookkeeping of (error, yardstick, scale, bar)"""
 import torch
 import torch.nn.functional as F
@@ -105,6 +105,95 @@ def _wgrad_def(x, dy):
     return torch.stack([dyt @ xp[:, kz:kz + D, ky:ky + H, kx:kx + W, :].reshape(-1, Ci) for (kz, ky, kx) in TAPS], 2)
 
 
+# ---- the Winograd forms of the same operations, restated from the header comments of csrc/conv_wino.hip and csrc/conv_wino2d.hip,
+# in the dtype of their operands (fp32 on the CPU: the second yardstick of tests/test_gpu_wino_float64.py; float64: the same sums
+# in another order, which tests/test_wino_variants.py holds against _conv_def / _wgrad_def) ------------------------------------------
+def _bt(d0, d1, d2, d3):
+    """B^T d of F(2, 3) and of F(3, 2): (d0 - d2, d1 + d2, d2 - d1, d1 - d3)"""
+    return d0 - d2, d1 + d2, d2 - d1, d1 - d3
+
+
+def _x_points(xp, W):
+    """the four x points of every output pair: [N, D + 2, H + 2, W / 2, C] each"""
+    return _bt(*[xp[:, :, :, k:k + W - 1:2] for k in range(4)])
+
+
+def _yx_points(xp, H, W):
+    """V = B^T d B of every 4 x 4 patch: V[py][px] of [N, D + 2, H / 2, W / 2, C]"""
+    return [_x_points(r, W) for r in _bt(*[xp[:, :, k:k + H - 1:2] for k in range(4)])]
+
+
+def _g3(g0, g1, g2):
+    """G g of a 3-tap filter: (g0, (g0 + g1 + g2) / 2, (g0 - g1 + g2) / 2, g2)"""
+    return g0, (g0 + g1 + g2) * 0.5, (g0 - g1 + g2) * 0.5, g2
+
+
+def _wino_f23_conv(x, w):
+    """F(2, 3) along x.  x [N, D, H, W, Ci], w [Co, Ci, 3, 3, 3] -> [N, D, H, W, Co]; W even"""
+    N, D, H, W, Ci = x.shape
+    Dp = _x_points(_pad(x), W)
+    U = _g3(w[..., 0], w[..., 1], w[..., 2])                               # [Co, Ci, kz, ky] per point
+    M = []
+    for p in range(4):
+        m = torch.zeros((N * D * H * (W // 2), w.shape[0]), dtype=x.dtype, device=x.device)
+        for kz in range(3):
+            for ky in range(3):
+                m += Dp[p][:, kz:kz + D, ky:ky + H].reshape(-1, Ci) @ U[p][:, :, kz, ky].t()
+        M.append(m.reshape(N, D, H, W // 2, -1))
+    return torch.stack([M[0] + M[1] + M[2], M[1] - M[2] - M[3]], 4).reshape(N, D, H, W, -1)
+
+
+def _wino_f2x2_conv(x, w):
+    """F(2x2, 3x3) over (y, x): V = B^T d B, U = G g G^T, M = sum_{kz, ci} U (.) V, Y = A^T M A; H and W even"""
+    N, D, H, W, Ci = x.shape
+    V = _yx_points(_pad(x), H, W)
+    Ur = _g3(w[:, :, :, 0], w[:, :, :, 1], w[:, :, :, 2])                   # rows: [Co, Ci, kz, kx]
+    M = [[None] * 4 for _ in range(4)]
+    for py in range(4):
+        U = _g3(Ur[py][..., 0], Ur[py][..., 1], Ur[py][..., 2])            # [Co, Ci, kz] per px
+        for px in range(4):
+            m = torch.zeros((N * D * (H // 2) * (W // 2), w.shape[0]), dtype=x.dtype, device=x.device)
+            for kz in range(3):
+                m += V[py][px][:, kz:kz + D].reshape(-1, Ci) @ U[px][:, :, kz].t()
+            M[py][px] = m.reshape(N, D, H // 2, W // 2, -1)
+    at = lambda m: (m[0] + m[1] + m[2], m[1] - m[2] - m[3])               # A^T = [1 1 1 0; 0 1 -1 -1]
+    rows = at([torch.stack(at(M[py]), 4) for py in range(4)])             # each [N, D, H / 2, W / 2, 2, Co]
+    return torch.stack(rows, 3).reshape(N, D, H, W, -1)
+
+
+def _wino_f32_wgrad(x, dy):
+    """F(3, 2) along x: E = (g0, g0 + g1, g0 - g1, g1) of a dy pair, M_p = sum_pairs D_p (x) E_p,
+    dW[kx = 0] = M0 + (M1 + M2) / 2, [1] = (M1 - M2) / 2, [2] = (M1 + M2) / 2 - M3 -> [Co, Ci, 27]"""
+    N, D, H, W, Ci = x.shape
+    Dp = _x_points(_pad(x), W)
+    g0, g1 = dy[:, :, :, 0::2], dy[:, :, :, 1::2]
+    E = [e.reshape(-1, dy.shape[-1]).t().contiguous() for e in (g0, g0 + g1, g0 - g1, g1)]
+    taps = []
+    for kz in range(3):
+        for ky in range(3):
+            M = [E[p] @ Dp[p][:, kz:kz + D, ky:ky + H].reshape(-1, Ci) for p in range(4)]
+            hs, hd = (M[1] + M[2]) * 0.5, (M[1] - M[2]) * 0.5
+            taps += [M[0] + hs, hd, hs - M[3]]
+    return torch.stack(taps, 2)
+
+
+def _wino_f3x3_wgrad(x, dy):
+    """F(3x3, 2x2) over (y, x): V = B^T d B, E = G' g G'^T with G' = [1 0; 1 1; 1 -1; 0 1], M_p = sum_quads V_p (x) E_p,
+    dW[kz] = A'^T M A' with A'^T = [1 1/2 1/2 0; 0 1/2 -1/2 0; 0 1/2 1/2 -1] -> [Co, Ci, 27]"""
+    N, D, H, W, Ci = x.shape
+    V = _yx_points(_pad(x), H, W)
+    gp = lambda a, b: (a, a + b, a - b, b)
+    rows = gp(dy[:, :, 0::2], dy[:, :, 1::2])
+    E = [[e.reshape(-1, dy.shape[-1]).t().contiguous() for e in gp(r[:, :, :, 0::2], r[:, :, :, 1::2])] for r in rows]
+    at = lambda m: (m[0] + (m[1] + m[2]) * 0.5, (m[1] - m[2]) * 0.5, (m[1] + m[2]) * 0.5 - m[3])
+    taps = []
+    for kz in range(3):
+        M = [[E[py][px] @ V[py][px][:, kz:kz + D].reshape(-1, Ci) for px in range(4)] for py in range(4)]
+        for r in at([torch.stack(at(M[py]), 2) for py in range(4)]):       # ky rows of [Co, Ci, kx]
+            taps += [r[:, :, 0], r[:, :, 1], r[:, :, 2]]
+    return torch.stack(taps, 2)
+
+
 # ---- bookkeeping ---------------------------------------------------------------------------------------------------------
 class Figures:
     """collects (device error, yardstick, scale, bar) per quantity of one case, reports them, then asserts"""
@@ -119,13 +208,14 @@ class Figures:
     def check(self, key, dev, ref, yard, floor, cap=None, bf16_out=False, yardstick=True):
         """bar = min(4 * yardstick + floor * scale, cap).  yardstick = False drops the first term -- for a kernel whose error is
         not the yardstick's (an operand carried as a bf16 hi + lo pair) the bar is `cap` alone.  bf16_out: per element,
-        2^-8 |ref| is allowed beside the bar"""
+        2^-8 |ref| is allowed beside the bar.  `yard` may be a tuple of fp32 results: the yardstick is the largest of their errors"""
         dev = dev.detach().double().reshape(ref.shape)
         if not bool(torch.isfinite(dev).all()):
             self.fails.append('{}: {} elements were not written (or are not finite)'.format(key, int((~torch.isfinite(dev)).sum())))
             return
         scale = float(ref.abs().max())
-        ye = float((yard.double().to(ref.device).reshape(ref.shape) - ref).abs().max())
+        yards = yard if isinstance(yard, (tuple, list)) else (yard,)
+        ye = max(float((y.double().to(ref.device).reshape(ref.shape) - ref).abs().max()) for y in yards)
         lim = 4.0 * ye + floor * scale if yardstick else cap
         if not ye <= 1e-4 * scale:       # (a test of the test: the fp32 restatement and the float64 formula are the same operation)
             self.fails.append('{}: the fp32 yardstick is {:.3e} away from the float64 reference (scale {:.3e})'.format(key, ye, scale))
@@ -149,14 +239,17 @@ def _check_stats(fig, stats, ref_y, yard_y, N, cap=CAP_STAT, yardstick=True):
     bars are `cap` of sum |y| and of sum y^2 alone"""
     got = stats.t.reshape(N, -1, 2).double().sum(1)
     r = ref_y.reshape(N, -1)
-    yd = yard_y.reshape(N, -1)
     ref = torch.stack([r.sum(1), (r * r).sum(1)], 1)
-    yard = torch.stack([yd.sum(1), (yd * yd).sum(1)], 1)
+    yards = []                                         # (yard_y may be a tuple of fp32 results, as in Figures.check)
+    for yd in (yard_y if isinstance(yard_y, (tuple, list)) else (yard_y,)):
+        yd = yd.reshape(N, -1)
+        yards.append(torch.stack([yd.sum(1), (yd * yd).sum(1)], 1))
     fig.require(not bool(torch.isnan(stats.t).any()), 'stats: a slot was not written')
     fig.require(stats.guards_untouched(), 'stats: the guard bands were written')
     norm = (float(r.abs().sum(1).max()), float(ref[:, 1].abs().max()))
     for j, key in enumerate(('stat_sum', 'stat_sq')):
-        fig.check(key, got[:, j], ref[:, j], yard[:, j], FLOOR_RED, cap=None if yardstick else cap * norm[j], yardstick=yardstick)
+        fig.check(key, got[:, j], ref[:, j], tuple(y[:, j] for y in yards), FLOOR_RED, cap=None if yardstick else cap * norm[j],
+                  yardstick=yardstick)
     cap_sum = float(((got[:, 0] - ref[:, 0]).abs() / r.abs().sum(1)).max())
     cap_sq = float((got[:, 1] - ref[:, 1]).abs().max() / ref[:, 1].abs().max())
     fig.figs.update(stat_sum_vs_abs=cap_sum, stat_sq_rel=cap_sq)
