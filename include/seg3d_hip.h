@@ -456,6 +456,51 @@ int seg3d_topk_loss_bwd(const float* probs, const float* target, const float* el
                         const float* gout, float* dprobs, int N, int C, long long S, int batch_dice, float ignore_label,
                         void* stream);
 
+/* Dense, batched signed Euclidean distance map of a class-id target (no counterpart in the reference; DESIGN.md section 7,
+ * row f16).  target [N][Z][Y][X] float class ids, phi [N][K][Z][Y][X] fp32, class_ids.id[0 .. K-1] the K <= 16 classes.
+ * A voxel counts iff 0 <= t < num_class and t != ignore_label (the compound loss's rule; its class is (int)t).  For
+ * sample n and class c = class_ids.id[k]:  G = counted voxels of class c,  H = counted voxels of any other class;
+ *   phi[n][k](v) = +d(v, G) for v in H,  -d(v, H) for v in G,  0 for a voxel that does not count,
+ *   d = sqrt(sx^2 dx^2 + sy^2 dy^2 + sz^2 dz^2) between voxel centres -- the plain signed map edt(~m) - edt(m), WITHOUT the
+ *   "- 1" offset of Kervadec's reference code.  G or H empty in a sample: phi[n][k] is 0 everywhere.  Nothing exists outside
+ *   the volume, and voxels that do not count are features of no transform (an ignored wall between G and H is no boundary).
+ * Exact: three separable passes of out(u) = min_i f(i) + w^2 (u - i)^2 by brute force over the staged line (x, then y, then
+ * z), both transforms from one read of each target row; with unit spacing the squared distances are exact integers and
+ * |phi| is their correctly rounded fp32 root; otherwise |phi| carries a few fp32 roundings (relative error below 1e-6).
+ * Every axis in [1, 256], spacing in [1e-6, 1e6], N * K <= 65535, N * X * Y * Z < 2^31; anything else is an error.
+ * workspace: seg3d_signed_distance_workspace_bytes(N, K, X, Y, Z) bytes (two fp32 fields per (n, k)), 4-byte aligned, free
+ * after the call.  Allocates nothing, synchronises nothing, reads nothing back: it can be captured into a hipGraph. */
+typedef struct Seg3dClassList {
+  int id[16];
+} Seg3dClassList;
+long long seg3d_signed_distance_workspace_bytes(int N, int K, int X, int Y, int Z);
+int seg3d_signed_distance(const float* target, float* phi, void* workspace, int N, int X, int Y, int Z,
+                          Seg3dClassList class_ids, int K, int num_class, double sx, double sy, double sz,
+                          float ignore_label, void* stream);
+/* Soft Dice + boundary loss (Kervadec et al., MIDL 2019) on probabilities [N][C][S] (fp32,
+ * 1 <= C <= 16, N * S < 2^31), a float class-id target [N][S] and phi [N][C - c0][S] from seg3d_signed_distance for the
+ * classes c0 .. C-1 with num_class = C and the same ignore_label (c0 = include_background ? 0 : 1; 16-byte aligned):
+ *   L_boundary = sum_c wdice[c] * (sum_{n, counted v} phi[n][c](v) p[n][c](v)) / max(1, n_counted)   (may be negative),
+ *   L = dice_weight * L_region + boundary_weight[0] * L_boundary,
+ *   L_region = exactly the compound loss's soft-Dice term (wdice, batch_dice, eps = 1e-5), from the same device code and
+ *   the same order of additions: bit-equal to seg3d_compound_loss_fwd's loss[1] on the same inputs.
+ * wdice: the region weights normalised over the included classes (0 for an excluded background); n_counted: the counted
+ * voxels of the whole batch (the calling rank's own: no collective).  boundary_weight is a DEVICE float read by the
+ * finalize kernel, so a captured graph follows a schedule that the host writes between replays; dice_weight >= 0.
+ * One streaming pass (fp32 partial sums per thread, one slot per workgroup, no atomics) and a one-workgroup fp64 finalize in
+ * fixed order: bit-reproducible.  workspace: seg3d_boundary_loss_workspace_bytes(N, C, S) bytes, free after the call;
+ * coef: 2 * R * C + C floats kept for the backward, R = batch_dice ? 1 : N -- the compound loss's (A, B) pairs, then per
+ * class boundary_weight * wdice[c] / max(1, n_counted);  loss: 3 floats (L, L_region, L_boundary). */
+long long seg3d_boundary_loss_workspace_bytes(int N, int C, long long S);
+int seg3d_boundary_loss_fwd(const float* probs, const float* target, const float* phi, const float* wdice,
+                            const float* boundary_weight, void* workspace, float* coef, float* loss, int N, int C,
+                            long long S, float dice_weight, int include_background, int batch_dice, float ignore_label,
+                            void* stream);
+/* dprobs[n][c][s] = gout[0] * ((A t_c + B) + coef_c * phi[n][c](s)) on counted voxels (no phi part on an excluded background
+ * plane), zeros on voxels that do not count: all C planes in one pass.  Neither term's derivative depends on p. */
+int seg3d_boundary_loss_bwd(const float* target, const float* phi, const float* coef, const float* gout, float* dprobs, int N,
+                            int C, long long S, int include_background, int batch_dice, float ignore_label, void* stream);
+
 /* ---- region-based models (no counterpart in the reference) -----------------------------
  * Head sigmoid: the counterparts of the soft-max pair above, same layouts (NDHWC in, contiguous NCDHW out), 1 <= C <= 16.
  * p = 1 / (1 + exp(-x)) evaluated through exp(-|x|): finite and inside [0, 1] for every x.  Backward: din = dp p (1 - p). */

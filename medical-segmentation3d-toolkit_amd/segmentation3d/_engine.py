@@ -47,6 +47,11 @@ class LowresParams(ctypes.Structure):
     """Seg3dLowresParams: per-modality low-grid sizes (n' = n on all axes = copy), BY VALUE to seg3d_augment_lowres"""
     _fields_ = [('nx', _c_int * 8), ('ny', _c_int * 8), ('nz', _c_int * 8)]
 
+
+class ClassList(ctypes.Structure):
+    """Seg3dClassList: up to 16 class ids, BY VALUE to seg3d_signed_distance"""
+    _fields_ = [('id', _c_int * 16)]
+
 # name -> (restype, argtypes); keep in sync with include/seg3d_hip.h (tests/test_abi.py checks every symbol)
 _SIGNATURES = {
     'seg3d_last_error': (ctypes.c_char_p, []),
@@ -200,6 +205,12 @@ _SIGNATURES = {
     'seg3d_topk_loss_workspace_bytes': (_c_ll, [_c_int, _c_int, _c_ll]),
     'seg3d_topk_loss_fwd': (_c_int, [_c_p] * 10 + [_c_int, _c_int, _c_ll, ctypes.c_double, _c_f, _c_f, _c_int, _c_f, _c_p]),
     'seg3d_topk_loss_bwd': (_c_int, [_c_p] * 7 + [_c_int, _c_int, _c_ll, _c_int, _c_f, _c_p]),
+    'seg3d_signed_distance_workspace_bytes': (_c_ll, [_c_int] * 5),
+    'seg3d_signed_distance': (_c_int, [_c_p] * 3 + [_c_int] * 4 + [ClassList, _c_int, _c_int] + [ctypes.c_double] * 3
+                              + [_c_f, _c_p]),
+    'seg3d_boundary_loss_workspace_bytes': (_c_ll, [_c_int, _c_int, _c_ll]),
+    'seg3d_boundary_loss_fwd': (_c_int, [_c_p] * 8 + [_c_int, _c_int, _c_ll, _c_f, _c_int, _c_int, _c_f, _c_p]),
+    'seg3d_boundary_loss_bwd': (_c_int, [_c_p] * 5 + [_c_int, _c_int, _c_ll, _c_int, _c_int, _c_f, _c_p]),
     'seg3d_sigmoid_fwd': (_c_int, [_c_p, _c_p, _c_int, _c_int, _c_ll, _c_p]),
     'seg3d_sigmoid_bwd': (_c_int, [_c_p, _c_p, _c_p, _c_int, _c_int, _c_ll, _c_p]),
     'seg3d_ds_head_supported': (_c_int, [_c_int] * 2),

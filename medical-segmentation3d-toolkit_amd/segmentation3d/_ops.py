@@ -10,6 +10,7 @@ InputBlock/DownBlock/UpBlock/OutputBlock):   out = act( GN_1(conv(x) + b) [+ res
 """
 import contextlib
 import ctypes
+import math
 
 import torch
 
@@ -1483,6 +1484,98 @@ class TopKLossFunction(torch.autograd.Function):
         dp = torch.empty_like(p)
         E.call('seg3d_topk_loss_bwd', E.ptr(p), E.ptr(t), E.ptr(ell), E.ptr(coef), E.ptr(alpha), E.ptr(g), E.ptr(dp), N, C, S,
                batch_dice, ignore, E.stream_ptr())
+        return (dp,) + (None,) * 8
+
+
+def _spacing3(spacing):
+    """three positive finite voxel spacings (sx, sy, sz) in [1e-6, 1e6] as floats; ValueError otherwise"""
+    try:
+        sp = tuple(float(v) for v in spacing)
+    except TypeError:
+        raise ValueError('spacing must be three positive finite numbers, got {!r}'.format(spacing))
+    if len(sp) != 3 or not all(math.isfinite(v) and v > 0.0 for v in sp):
+        raise ValueError('spacing must be three positive finite numbers, got {!r}'.format(spacing))
+    if not all(1e-6 <= v <= 1e6 for v in sp):   # the range in which the kernels' "no feature" sentinel is safe
+        raise ValueError('spacing must lie in [1e-6, 1e6] mm, got {!r}'.format(spacing))
+    return sp
+
+
+def signed_distance(target, class_ids, spacing, ignore, num_class=None):
+    """phi [N, K, Z, Y, X] float32: the signed Euclidean distance map of every sample of the float class-id `target`
+    ([N, Z, Y, X] or [N, 1, Z, Y, X]) and every class of `class_ids` (1..16 ids), in the units of `spacing` = (sx, sy, sz):
+    +distance to the class outside it, -distance to the rest inside it, 0 on voxels that do not count and where the class
+    or the rest is empty (seg3d_signed_distance).  A voxel counts iff 0 <= t < num_class and
+    t != ignore (`ignore` None: no ignore label; `num_class` None: every non-negative id counts).  One call, nothing read
+    back: it can be captured into a hipGraph."""
+    E.require_device(target)
+    if target.dim() == 5 and target.shape[1] == 1:
+        target = target[:, 0]
+    if target.dim() != 4:
+        raise ValueError('target must be [N, Z, Y, X] or [N, 1, Z, Y, X], got {}'.format(tuple(target.shape)))
+    ids = [int(c) for c in class_ids]
+    if not 1 <= len(ids) <= 16:
+        raise ValueError('class_ids must hold 1..16 ids, got {}'.format(len(ids)))
+    sx, sy, sz = _spacing3(spacing)
+    N, Z, Y, X = (int(v) for v in target.shape)
+    if max(X, Y, Z) > 256 or min(N, X, Y, Z) < 1:
+        raise ValueError('every axis of the volume must be in 1..256, got {}'.format((Z, Y, X)))
+    t = target.contiguous().float()
+    K = len(ids)
+    phi = _empty((N, K, Z, Y, X), t)
+    work = _empty(((E.query('seg3d_signed_distance_workspace_bytes', N, K, X, Y, Z) + 3) // 4,), t)
+    cls = E.ClassList()
+    for i, c in enumerate(ids):
+        cls.id[i] = c
+    E.call('seg3d_signed_distance', E.ptr(t), E.ptr(phi), E.ptr(work), N, X, Y, Z, cls, K,
+           (1 << 24) if num_class is None else int(num_class), sx, sy, sz, -1.0 if ignore is None else float(ignore),
+           E.stream_ptr())
+    return phi
+
+
+class BoundaryLossFunction(torch.autograd.Function):
+    """DiceBoundaryLoss.forward (loss/boundary_loss.py): soft Dice + boundary loss.  The signed distance maps of the
+    included classes come from `signed_distance` on the device in the same call; `bweight` is the 1-element device tensor
+    holding boundary_weight (read by the kernels, so a captured graph follows a schedule).  `wdice`, `ignore` as for
+    CompoundLossFunction.  Every buffer is allocated per call.  Neither term's derivative depends on p, so the backward
+    keeps the target, phi and the coefficient block only.
+    Returns (loss, terms): the 0-dim loss and the device tensor (L, L_region, L_boundary); only the loss carries a gradient."""
+
+    @staticmethod
+    def forward(ctx, probs, target, wdice, bweight, spacing, dice_weight, include_background, batch_dice, ignore):
+        E.require_device(probs, target, wdice, bweight)
+        if probs.dtype != torch.float32:
+            raise ValueError('probabilities must be float32, got {}'.format(probs.dtype))
+        if probs.dim() != 5:
+            raise ValueError('probabilities must be [N, C, Z, Y, X], got {}'.format(tuple(probs.shape)))
+        p = probs.contiguous()
+        t = target.contiguous().float()
+        N, C = p.shape[0], p.shape[1]
+        S = p[0, 0].numel()
+        if t.numel() != N * S:
+            raise ValueError('target shape {} does not match input {}'.format(tuple(target.shape), tuple(probs.shape)))
+        cfg = (int(bool(include_background)), int(bool(batch_dice)), float(ignore))
+        phi = signed_distance(t.reshape((N,) + tuple(p.shape[2:])), range(0 if cfg[0] else 1, C), spacing, cfg[2], num_class=C)
+        work = _empty(((E.query('seg3d_boundary_loss_workspace_bytes', N, C, S) + 3) // 4,), p)
+        coef = _empty((2 * (1 if cfg[1] else N) * C + C,), p)
+        terms = _empty((3,), p)
+        E.call('seg3d_boundary_loss_fwd', E.ptr(p), E.ptr(t), E.ptr(phi), E.ptr(wdice), E.ptr(bweight), E.ptr(work),
+               E.ptr(coef), E.ptr(terms), N, C, S, float(dice_weight), cfg[0], cfg[1], cfg[2], E.stream_ptr())
+        ctx.save_for_backward(t, phi, coef)
+        ctx.cfg = cfg
+        ctx.pshape = tuple(p.shape)
+        ctx.mark_non_differentiable(terms)
+        return terms[0], terms
+
+    @staticmethod
+    def backward(ctx, gout, _gterms):
+        t, phi, coef = ctx.saved_tensors
+        include_background, batch_dice, ignore = ctx.cfg
+        N, C = ctx.pshape[0], ctx.pshape[1]
+        S = t.numel() // N
+        g = gout.contiguous().reshape(1).float()
+        dp = _empty(ctx.pshape, t)
+        E.call('seg3d_boundary_loss_bwd', E.ptr(t), E.ptr(phi), E.ptr(coef), E.ptr(g), E.ptr(dp), N, C, S,
+               include_background, batch_dice, ignore, E.stream_ptr())
         return (dp,) + (None,) * 8
 
 

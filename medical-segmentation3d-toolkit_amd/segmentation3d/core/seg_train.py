@@ -19,6 +19,7 @@ import torch.distributed as dist
 
 from segmentation3d import _ops
 from segmentation3d.core.ddp import GradientReducer
+from segmentation3d.loss.boundary_loss import DiceBoundaryLoss
 from segmentation3d.loss.compound_loss import DiceCELoss
 from segmentation3d.loss.cross_entropy_loss import CrossEntropyLoss
 from segmentation3d.loss.deep_supervision_loss import DeepSupervisionLoss, normalise_level_weights
@@ -30,11 +31,17 @@ from segmentation3d.optim.fused_sgd import FusedSGD
 
 
 def build_loss(name, num_classes, obj_weight=None, focal_gamma=2, use_gpu=True, dice_weight=1.0, ce_weight=1.0,
-               include_background=True, batch_dice=False, ignore_label=None, topk_percent=10.0):
+               include_background=True, batch_dice=False, ignore_label=None, topk_percent=10.0, boundary_weight=0.01,
+               spacing=(1, 1, 1)):
     """loss selection of core/seg_train.py:91-102, plus the compound losses 'DiceCE' (soft Dice + cross-entropy),
-    'DiceFocal' (soft Dice + focal with focal_gamma) and 'DiceTopK' (soft Dice + cross-entropy over the hardest
-    topk_percent of the batch's voxels); the keyword options after use_gpu apply to those three only, topk_percent to
-    'DiceTopK' only"""
+    'DiceFocal' (soft Dice + focal with focal_gamma), 'DiceTopK' (soft Dice + cross-entropy over the hardest
+    topk_percent of the batch's voxels) and 'DiceBoundary' (soft Dice + boundary loss on signed distance maps in units of
+    `spacing`, weighted by boundary_weight; ce_weight is not read); the keyword options after use_gpu apply to those four
+    only, topk_percent to 'DiceTopK' only, boundary_weight and spacing to 'DiceBoundary' only"""
+    if name == 'DiceBoundary':
+        return DiceBoundaryLoss(num_classes, weights=obj_weight, dice_weight=dice_weight, boundary_weight=boundary_weight,
+                                spacing=spacing, include_background=include_background, batch_dice=batch_dice,
+                                ignore_label=ignore_label, use_gpu=use_gpu)
     if name == 'DiceTopK':
         return DiceTopKLoss(num_classes, weights=obj_weight, dice_weight=dice_weight, ce_weight=ce_weight,
                             k_percent=topk_percent, include_background=include_background, batch_dice=batch_dice,
@@ -55,14 +62,35 @@ def build_loss(name, num_classes, obj_weight=None, focal_gamma=2, use_gpu=True, 
 
 def loss_options_from_config(loss_cfg):
     """the optional keys of the config's `loss` section that the compound losses read, with their defaults (a config
-    without them -- every reference config -- loads unchanged); `topk_percent` ('DiceTopK') is passed on only when the
-    section has it"""
+    without them -- every reference config -- loads unchanged); `topk_percent` ('DiceTopK') and `boundary_weight`
+    ('DiceBoundary') are passed on only when the section has them"""
     opts = {'dice_weight': getattr(loss_cfg, 'dice_weight', 1.0), 'ce_weight': getattr(loss_cfg, 'ce_weight', 1.0),
             'include_background': getattr(loss_cfg, 'include_background', True),
             'batch_dice': getattr(loss_cfg, 'batch_dice', False), 'ignore_label': getattr(loss_cfg, 'ignore_label', None)}
     if hasattr(loss_cfg, 'topk_percent'):
         opts['topk_percent'] = loss_cfg.topk_percent
+    if hasattr(loss_cfg, 'boundary_weight'):
+        opts['boundary_weight'] = loss_cfg.boundary_weight
     return opts
+
+
+def boundary_schedule_from_config(loss_cfg):
+    """the weight of the boundary term of 'DiceBoundary' as a function of the epoch index, from three optional keys of the
+    config's `loss` section: boundary_weight (w0, default 0.01), boundary_weight_step (default 0.0) and
+    boundary_weight_max (default 1.0):  w(epoch) = min(max, w0 + step * epoch) -- Kervadec's "increase" strategy.  It keeps
+    no state, so a resumed run continues it.  Bad values raise ValueError."""
+    w0 = float(getattr(loss_cfg, 'boundary_weight', 0.01))
+    step = float(getattr(loss_cfg, 'boundary_weight_step', 0.0))
+    top = float(getattr(loss_cfg, 'boundary_weight_max', 1.0))
+    for key, v in (('boundary_weight', w0), ('boundary_weight_step', step), ('boundary_weight_max', top)):
+        if not (math.isfinite(v) and v >= 0.0):
+            raise ValueError('loss.{} must be finite and >= 0, got {}'.format(key, v))
+    if w0 > top:
+        raise ValueError('loss.boundary_weight = {} is above loss.boundary_weight_max = {}'.format(w0, top))
+
+    def weight(epoch):
+        return min(top, w0 + step * max(0, int(epoch)))
+    return weight
 
 
 def optim_options_from_config(train_cfg, num_samples=None, world_size=1):
@@ -115,6 +143,8 @@ def build_validator(cfg, val_cfg, step, num_modality):
             val_cfg['imseg_list'], held_out.num_modality(), num_modality))
     crops, masks = collect_fixed_crops(held_out, val_cfg['crops_per_case'], val_cfg['seed'])
     loss_options = loss_options_from_config(cfg.loss)
+    if cfg.loss.name == 'DiceBoundary':
+        loss_options['spacing'] = tuple(cfg.dataset.spacing)
     loss_func = build_loss(cfg.loss.name, cfg.dataset.num_classes, cfg.loss.obj_weight, cfg.loss.focal_gamma, use_gpu=True,
                            **loss_options)   # a second object: the training loss's .last_terms stays the train step's
     batchsize = val_cfg['batchsize'] if val_cfg['batchsize'] is not None else cfg.train.batchsize
@@ -149,14 +179,18 @@ def build_optimizer(name, params, lr, betas=(0.9, 0.999), optim_options=None):
 class TrainStep(object):
     """network + loss + FusedAdam or FusedSGD (+ gradient reducer when distributed) on one device; `loss_options` is a
     dict of build_loss's keyword options for the compound losses (dice_weight, ce_weight, include_background, batch_dice,
-    ignore_label, and topk_percent for loss_name='DiceTopK'); `optimizer` / `optim_options` are build_optimizer's
-    (gradient-norm clipping, lr schedule, SGD);
+    ignore_label, topk_percent for loss_name='DiceTopK', boundary_weight and spacing for loss_name='DiceBoundary', which
+    serves one resolution and is refused together with deep supervision); `optimizer` / `optim_options` are
+    build_optimizer's (gradient-norm clipping, lr schedule, SGD);
     `deep_supervision` = L in 1..3 builds the network with L auxiliary heads and trains on the weighted per-level losses
     (loss/deep_supervision_loss.py; `deep_supervision_weights`: L + 1 weights, None = halving per level)"""
 
     def __init__(self, net_name, in_channels, num_classes, loss_name='Dice', obj_weight=None, focal_gamma=2, lr=1e-4,
                  betas=(0.9, 0.999), device=None, seed=0, distributed=None, num_buckets=4, use_graph=False,
                  loss_options=None, optimizer='Adam', optim_options=None, deep_supervision=0, deep_supervision_weights=None):
+        if loss_name == 'DiceBoundary' and int(deep_supervision) > 0:
+            # one loss object would be called at levels whose spacing is 2^k times the nominal one
+            raise ValueError("loss_name='DiceBoundary' is not combined with deep supervision")
         self.device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
         if self.device.type == 'cuda' and self.device.index is not None:
             torch.cuda.set_device(self.device)   # the engine launches on the current device's stream (_engine.stream_ptr)
@@ -284,6 +318,7 @@ def train(train_config_file, data_iter_factory=None):
     # optional `validation` section (None: off, and then nothing below differs from a run without it); bad keys / values
     # raise before anything is built
     val_cfg = validate_validation(getattr(cfg, 'validation', None), cfg.dataset.num_classes)
+    boundary_schedule = boundary_schedule_from_config(cfg.loss) if cfg.loss.name == 'DiceBoundary' else None   # likewise
     model_folder = os.path.join(cfg.general.save_dir, cfg.general.model_scale)
     distributed = dist.is_available() and dist.is_initialized()
     rank = dist.get_rank() if distributed else 0
@@ -325,13 +360,16 @@ def train(train_config_file, data_iter_factory=None):
     optim_options = optim_options_from_config(cfg.train, num_samples, world_size)
     show_lr = optim_options['lr_schedule'] is not None and optim_options['lr_schedule']['name'] != 'constant'
     deep = deep_supervision_from_config(cfg.train)
+    loss_options = loss_options_from_config(cfg.loss)
+    if boundary_schedule is not None:
+        loss_options['spacing'] = tuple(cfg.dataset.spacing)
     if cfg.general.resume_epoch >= 0 and not hasattr(cfg.train, 'deep_supervision'):
         from segmentation3d.utils.model_io import checkpoint_deep_supervision
         deep['deep_supervision'] = checkpoint_deep_supervision(cfg.general.resume_epoch, model_folder)   # rebuild the same net
     step = TrainStep(cfg.net.name, num_modality, cfg.dataset.num_classes, cfg.loss.name, cfg.loss.obj_weight,
                      cfg.loss.focal_gamma, cfg.train.lr, tuple(cfg.train.betas), seed=cfg.general.seed,
                      use_graph=bool(getattr(cfg.train, 'use_graph', False)),
-                     loss_options=loss_options_from_config(cfg.loss), optimizer=optim_options.pop('optimizer'),
+                     loss_options=loss_options, optimizer=optim_options.pop('optimizer'),
                      optim_options=optim_options, **deep)
     assert np.all(np.array(cfg.dataset.crop_size) % step.max_stride == 0), 'crop size not divisible by max stride'
     last_save_epoch, batch_idx = 0, 0
@@ -357,10 +395,18 @@ def train(train_config_file, data_iter_factory=None):
                 validator.load_state_dict(stored)   # the moving average and the best value continue
         step.validator = validator
     steps_this_run = 0
+    boundary_epoch = None
     for batch in batches:
         crops, masks = batch[0], batch[1]
         begin_t = time.time()
         crops, masks = crops.to(step.device, non_blocking=True), masks.to(step.device, non_blocking=True)
+        if boundary_schedule is not None:
+            epoch_now = epoch_of_batch(batch_idx, cfg.train.batchsize, num_samples, world_size)
+            if epoch_now != boundary_epoch:   # a plain fill of the device scalar, outside the captured step
+                boundary_epoch = epoch_now
+                step.loss_func.set_boundary_weight(boundary_schedule(epoch_now))
+                if validator is not None:
+                    validator.loss_func.set_boundary_weight(boundary_schedule(epoch_now))
         loss = step(crops, masks)
         epoch_idx = epoch_of_batch(batch_idx, cfg.train.batchsize, num_samples, world_size)
         batch_idx += 1
@@ -378,6 +424,8 @@ def train(train_config_file, data_iter_factory=None):
                                                                                         sample_duration)
             if show_lr:   # the reference's log format unless a schedule moves the rate
                 line += ', lr: {:.6e}'.format(step.opt.param_groups[0]['lr'])
+            if boundary_schedule is not None:
+                line += ', boundary_weight: {:.6g}'.format(step.loss_func.boundary_weight)
             logger.info(line)
         if validator is not None and epoch_idx != 0 and epoch_idx % val_cfg['epochs'] == 0 and last_val_epoch != epoch_idx:
             result = validator.run(epoch_idx)     # every rank: the counts are all-reduced

@@ -651,6 +651,20 @@ def lowres_device(crop, zooms, out=None):
     return out
 
 
+def signed_distance_device(labels, class_ids, spacing, ignore_label=None):
+    """signed Euclidean distance maps of a device label volume: `labels` [Z, Y, X] or a batch [N, Z, Y, X] of class ids
+    (any dtype), `class_ids` 1..16 ids, `spacing` = (sx, sy, sz).  Returns float32 [K, Z, Y, X] or [N, K, Z, Y, X]: for
+    each class the distance between voxel centres to the class (positive outside it) or to the rest (negative inside it),
+    0 where the class or the rest is empty.  Negative labels and `ignore_label` are neither object nor background.  Every
+    axis is at most 256 voxels (seg3d_signed_distance)."""
+    from segmentation3d import _ops
+    batched = labels.dim() == 4
+    if labels.dim() not in (3, 4):
+        raise ValueError('labels must be [Z, Y, X] or [N, Z, Y, X], got {}'.format(tuple(labels.shape)))
+    phi = _ops.signed_distance(labels if batched else labels[None], class_ids, spacing, ignore_label)
+    return phi if batched else phi[0]
+
+
 def get_image_frame(image):
     """spacing, origin, direction packed into 15 float32 (image_tools.py:26-41)"""
     return np.array(list(image.GetSpacing()) + list(image.GetOrigin()) + list(image.GetDirection()), dtype=np.float32)
