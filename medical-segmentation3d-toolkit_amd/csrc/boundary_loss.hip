@@ -1,7 +1,7 @@
 // boundary_loss.hip -- boundary (signed-distance) loss of Kervadec et al. (MIDL 2019) next to the compound loss's soft-Dice
 // term, with the dense batched signed Euclidean distance map computed on the device (no counterpart in the reference;
 // definitions in DESIGN.md section 7, row f16, and include/seg3d_hip.h).
-//   counted voxel:  0 <= t < C && t != ignore (the compound loss's rule)
+//   counted voxel:  the compound loss family's rule (compound_device.h)
 //   for sample n and class c:  G = counted voxels with (int)t == c,  H = counted voxels with (int)t != c
 //   phi[n,c](v) = +d(v, G) on H,  -d(v, H) on G,  0 on voxels that do not count and wherever G or H is empty
 //   d = Euclidean distance of voxel centres in physical units; plain edt(~m) - edt(m), no "- 1" offset
@@ -30,12 +30,6 @@
 #define SDF_MAX_SPACING 1e6
 #define SDF_MIN_SPACING 1e-6
 
-// class code of a target value: its class id if the voxel counts, -1 otherwise
-__device__ __forceinline__ int sdf_code(float t, int C, float ignore) {
-  const bool valid = t >= 0.0f && t < (float)C && t != ignore;
-  return valid ? (int)t : -1;
-}
-
 // pass x: field[n][k][0 / 1][z][y][x] = squared distance along the row to the nearest G / H voxel (SDF_NONE: none).
 // grid (rows / 4, K); one wave per row, lane handles u = lane + 64 j, j < J.
 template <int J>
@@ -53,7 +47,7 @@ __global__ __launch_bounds__(256) void sdf_x_kernel(const float* __restrict__ ta
 #pragma unroll
     for (int j = 0; j < J; ++j) {
       const int u = lane + 64 * j;
-      if (u < X) code[wave][u] = sdf_code(tr[u], C, ignore);
+      if (u < X) code[wave][u] = compound_class(tr[u], C, ignore);
     }
   }
   __syncthreads();
@@ -138,7 +132,7 @@ __global__ __launch_bounds__(256) void sdf_line_kernel(float* __restrict__ field
       const float gv = fminf(g[j], SDF_NONE), hv = fminf(h[j], SDF_NONE);
       if constexpr (FINAL) {
         const int n = nk / K, c = cls.id[nk % K];
-        const int ct = sdf_code(target[(i64)n * S + base + (i64)u * inner], C, ignore);
+        const int ct = compound_class(target[(i64)n * S + base + (i64)u * inner], C, ignore);
         float v = 0.f;
         if (ct >= 0) {
           const float q = ct == c ? hv : gv;          // a G voxel asks for H, an H voxel for G
@@ -201,10 +195,9 @@ extern "C" int seg3d_signed_distance(const float* target, float* phi, void* work
 }
 
 // ---- the loss ----------------------------------------------------------------------------------------------------------
-// Forward pass A: part[n][blk][3C + 2] exactly as compound_partial_kernel leaves the (I, P, T) triples (same workgroup and
-// thread to voxel map, same additions: the region term is bit-equal to the compound loss's), the two distribution slots 0;
-// bpart[n][blk][C + 1] = per class sum phi p over the block's counted voxels (0 for an excluded background), then the
-// number of counted voxels.  phi: [N][C - c0][S], c0 = 0 with the background, 1 without.
+// Forward pass A: the (I, P, T) triples of part (its two trailing slots are 0) and, by the same walk, bpart[n][blk][C + 1] =
+// per class sum phi p over the block's counted voxels (0 for an excluded background), then the number of counted voxels.
+// phi: [N][C - c0][S], c0 = 0 with the background, 1 without.
 template <int CT>
 __device__ __forceinline__ void boundary_voxel(CompoundAcc<CT>& a, float (&b)[CT], float& cnt, float t, const float (&p)[CT],
                                                const float (&ph)[CT], const float (&zero)[CT], int C, float ignore) {
@@ -221,71 +214,30 @@ __global__ __launch_bounds__(256) void boundary_partial_kernel(const float* __re
                                                                  const float* __restrict__ phi, float* __restrict__ part,
                                                                  float* __restrict__ bpart, int C, int c0, i64 S, int nblk,
                                                                  float ignore) {
+  constexpr int W = VEC ? 4 : 1;
   __shared__ float red[4 * 3];
-  const int n = blockIdx.y;
-  const i64 s0 = (i64)blockIdx.x * DICE_VPB;
-  i64 s1 = s0 + DICE_VPB;
-  if (s1 > S) s1 = S;
-  const float* tg = target + (i64)n * S;
-  const float* pb = probs + (i64)n * C * S;
-  const float* hb = phi + (i64)n * (C - c0) * S;   // plane of class c >= c0 at hb + (c - c0) * S
-  float zero[CT], b[CT];
-#pragma unroll
-  for (int c = 0; c < CT; ++c) {
-    zero[c] = 0.f;
-    b[c] = 0.f;
-  }
+  const float* hb = phi + (i64)blockIdx.y * (C - c0) * S;   // plane of class c >= c0 at hb + (c - c0) * S
+  float zero[CT] = {}, b[CT] = {};
   float cnt = 0.f;
   CompoundAcc<CT> a;
+  compound_block_walk<CT, W>(probs, target, C, S, [&](i64 s, const float (&t)[W], const float (&p)[W][CT]) {
+    float plane[CT][W] = {};
 #pragma unroll
-  for (int k = 0; k < 3 * CT; ++k) a.r[k] = 0.f;
-  a.num = 0.f;
-  a.den = 0.f;
-  if constexpr (VEC) {
-    for (i64 s = s0 + (i64)threadIdx.x * 4; s < s1; s += 256 * 4) {   // s1 is a multiple of 4 here (S % 4 == 0)
-      const float4 t4 = *reinterpret_cast<const float4*>(tg + s);
-      float4 p4[CT], h4[CT];
+    for (int c = 0; c < CT; ++c)
+      if ((CT <= 5 || c < C) && c >= c0) compound_load<W>(plane[c], hb + (i64)(c - c0) * S + s);
 #pragma unroll
-      for (int c = 0; c < CT; ++c)
-        if (CT <= 5 || c < C) {
-          p4[c] = *reinterpret_cast<const float4*>(pb + (i64)c * S + s);
-          h4[c] = c >= c0 ? *reinterpret_cast<const float4*>(hb + (i64)(c - c0) * S + s) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-      float p[CT], ph[CT];
+    for (int j = 0; j < W; ++j) {
+      float ph[CT];
 #pragma unroll
-      for (int c = 0; c < CT; ++c) { const bool on = CT <= 5 || c < C; p[c] = on ? p4[c].x : 0.f; ph[c] = on ? h4[c].x : 0.f; }
-      boundary_voxel<CT>(a, b, cnt, t4.x, p, ph, zero, C, ignore);
-#pragma unroll
-      for (int c = 0; c < CT; ++c) { const bool on = CT <= 5 || c < C; p[c] = on ? p4[c].y : 0.f; ph[c] = on ? h4[c].y : 0.f; }
-      boundary_voxel<CT>(a, b, cnt, t4.y, p, ph, zero, C, ignore);
-#pragma unroll
-      for (int c = 0; c < CT; ++c) { const bool on = CT <= 5 || c < C; p[c] = on ? p4[c].z : 0.f; ph[c] = on ? h4[c].z : 0.f; }
-      boundary_voxel<CT>(a, b, cnt, t4.z, p, ph, zero, C, ignore);
-#pragma unroll
-      for (int c = 0; c < CT; ++c) { const bool on = CT <= 5 || c < C; p[c] = on ? p4[c].w : 0.f; ph[c] = on ? h4[c].w : 0.f; }
-      boundary_voxel<CT>(a, b, cnt, t4.w, p, ph, zero, C, ignore);
+      for (int c = 0; c < CT; ++c) ph[c] = plane[c][j];
+      boundary_voxel<CT>(a, b, cnt, t[j], p[j], ph, zero, C, ignore);
     }
-  } else {
-    for (i64 s = s0 + threadIdx.x; s < s1; s += 256) {
-      const float t = tg[s];
-      float p[CT], ph[CT];
-#pragma unroll
-      for (int c = 0; c < CT; ++c) {
-        const bool on = CT <= 5 || c < C;
-        p[c] = on ? pb[(i64)c * S + s] : 0.f;
-        ph[c] = (on && c >= c0) ? hb[(i64)(c - c0) * S + s] : 0.f;
-      }
-      boundary_voxel<CT>(a, b, cnt, t, p, ph, zero, C, ignore);
-    }
-  }
-  float* dst = part + ((i64)n * nblk + blockIdx.x) * (3 * C + 2);
-  float* bdst = bpart + ((i64)n * nblk + blockIdx.x) * (C + 1);
+  });
+  float* dst = compound_region_store<CT>(a, part, C, nblk, red);
+  float* bdst = bpart + ((i64)blockIdx.y * nblk + blockIdx.x) * (C + 1);
 #pragma unroll
   for (int c = 0; c < CT; ++c)
     if (CT <= 5 || c < C) {
-      float v[3] = {a.r[3 * c + 0], a.r[3 * c + 1], a.r[3 * c + 2]};
-      block_sum_256<3>(v, red);
-      if (threadIdx.x == 0) { dst[3 * c + 0] = v[0]; dst[3 * c + 1] = v[1]; dst[3 * c + 2] = v[2]; }
       float q[1] = {b[c]};
       block_sum_256<1>(q, red);
       if (threadIdx.x == 0) bdst[c] = q[0];
@@ -311,13 +263,9 @@ __global__ __launch_bounds__(256) void boundary_finalize_kernel(const float* __r
   __shared__ double tot[SEG3D_MAXC + 1];
   const i64 nent = (i64)N * nblk;
   for (int c = 0; c <= C; ++c) {
-    double v = 0.0;
-    for (i64 m = threadIdx.x; m < nent; m += 256) v += (double)bpart[m * (C + 1) + c];
-    v = wave_sum_d(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) tot[c] = red[0] + red[1] + red[2] + red[3];
-    __syncthreads();
+    double v[1];
+    compound_column_sum(v, bpart + c, nent, C + 1, red);
+    if (threadIdx.x == 0) tot[c] = v[0];
   }
   const double lr = compound_region_finalize(part, wdice, coef, N, C, nblk, batch_dice, dice_weight, red);
   if (threadIdx.x == 0) {
@@ -345,50 +293,30 @@ __global__ __launch_bounds__(256) void boundary_bwd_kernel(const float* __restri
                                                              const float* __restrict__ coef, const float* __restrict__ gout,
                                                              float* __restrict__ dprobs, int C, int c0, i64 S, int R,
                                                              float ignore) {
+  constexpr int W = VEC ? 4 : 1;
   const int n = blockIdx.y;
-  const int r = R == 1 ? 0 : n;
   const float go = gout[0];
-  float A[CT], B[CT], W[CT];
-#pragma unroll
-  for (int c = 0; c < CT; ++c) {
-    const bool on = CT <= 5 || c < C;
-    A[c] = on ? coef[2 * (r * C + c) + 0] : 0.f;
-    B[c] = on ? coef[2 * (r * C + c) + 1] : 0.f;
-    W[c] = (on && c >= c0) ? coef[2 * R * C + c] : 0.f;
-  }
+  float A[CT], B[CT], bw[CT];
+  compound_load_coef<CT>(A, B, bw, coef, R == 1 ? 0 : n, coef + 2 * R * C, C);
+  if (c0 > 0) bw[0] = 0.f;
   const float* tg = target + (i64)n * S;
   const float* hb = phi + (i64)n * (C - c0) * S;
   float* db = dprobs + (i64)n * C * S;
-  if constexpr (VEC) {
-    for (i64 s = ((i64)blockIdx.x * 256 + threadIdx.x) * 4; s < S; s += (i64)gridDim.x * 256 * 4) {
-      const float4 t4 = *reinterpret_cast<const float4*>(tg + s);
-      const float tt[4] = {t4.x, t4.y, t4.z, t4.w};
-      int ti[4];
+  for (i64 s = ((i64)blockIdx.x * 256 + threadIdx.x) * W; s < S; s += (i64)gridDim.x * 256 * W) {
+    float t[W];
+    compound_load<W>(t, tg + s);
+    int ti[W];
 #pragma unroll
-      for (int j = 0; j < 4; ++j) ti[j] = sdf_code(tt[j], C, ignore);
+    for (int j = 0; j < W; ++j) ti[j] = compound_class(t[j], C, ignore);
 #pragma unroll
-      for (int c = 0; c < CT; ++c)
-        if (CT <= 5 || c < C) {
-          float4 h4 = make_float4(0.f, 0.f, 0.f, 0.f);
-          if (c >= c0) h4 = *reinterpret_cast<const float4*>(hb + (i64)(c - c0) * S + s);
-          const float hh[4] = {h4.x, h4.y, h4.z, h4.w};
-          float g[4];
+    for (int c = 0; c < CT; ++c)
+      if (CT <= 5 || c < C) {
+        float h[W] = {}, g[W];
+        if (c >= c0) compound_load<W>(h, hb + (i64)(c - c0) * S + s);
 #pragma unroll
-          for (int j = 0; j < 4; ++j)
-            g[j] = ti[j] >= 0 ? go * fmaf(W[c], hh[j], ti[j] == c ? A[c] + B[c] : B[c]) : 0.f;
-          *reinterpret_cast<float4*>(db + (i64)c * S + s) = make_float4(g[0], g[1], g[2], g[3]);
-        }
-    }
-  } else {
-    for (i64 s = (i64)blockIdx.x * 256 + threadIdx.x; s < S; s += (i64)gridDim.x * 256) {
-      const int ti = sdf_code(tg[s], C, ignore);
-#pragma unroll
-      for (int c = 0; c < CT; ++c)
-        if (CT <= 5 || c < C) {
-          const float h = c >= c0 ? hb[(i64)(c - c0) * S + s] : 0.f;
-          db[(i64)c * S + s] = ti >= 0 ? go * fmaf(W[c], h, ti == c ? A[c] + B[c] : B[c]) : 0.f;
-        }
-    }
+        for (int j = 0; j < W; ++j) g[j] = ti[j] >= 0 ? go * fmaf(bw[c], h[j], ti[j] == c ? A[c] + B[c] : B[c]) : 0.f;
+        compound_store<W>(db + (i64)c * S + s, g);
+      }
   }
 }
 
@@ -434,15 +362,11 @@ extern "C" int seg3d_boundary_loss_bwd(const float* target, const float* phi, co
   SEG3D_REQUIRE(include_background || C >= 2, "seg3d_boundary_loss_bwd: no class is left without the background");
   SEG3D_REQUIRE((i64)N * S < (1ll << 31), "seg3d_boundary_loss_bwd: N * S = %lld not below 2^31", (i64)N * S);
   const bool vec = compound_vec_ok(S, target, phi, dprobs);
-  const i64 items = vec ? S / 4 : S;
-  i64 gx = (items + 255) / 256, cap = 8192 / N;
-  if (cap < 1) cap = 1;
-  if (gx > cap) gx = cap;
   const int R = batch_dice ? 1 : N;
   const int c0 = include_background ? 0 : 1;
   COMPOUND_DISPATCH(boundary_bwd_kernel, C, vec,
-                    <<<dim3((unsigned)gx, N), dim3(256), 0, (hipStream_t)stream>>>(target, phi, coef, gout, dprobs, C, c0,
-                                                                                  (i64)S, R, ignore_label));
+                    <<<compound_bwd_grid(S, N, vec), dim3(256), 0, (hipStream_t)stream>>>(target, phi, coef, gout, dprobs, C,
+                                                                                         c0, (i64)S, R, ignore_label));
   SEG3D_LAUNCH_CHECK("seg3d_boundary_loss_bwd");
   return SEG3D_OK;
 }

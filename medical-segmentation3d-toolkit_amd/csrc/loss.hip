@@ -323,12 +323,9 @@ __global__ __launch_bounds__(256) void focal_partial_kernel(const float* __restr
 __global__ __launch_bounds__(256) void focal_finalize_kernel(const float* __restrict__ part, float* __restrict__ loss,
                                                                int nblk, double scale) {
   __shared__ double red[4];
-  double acc = 0.0;
-  for (int k = threadIdx.x; k < nblk; k += 256) acc += (double)part[k];
-  acc = wave_sum_d(acc);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) loss[0] = (float)((red[0] + red[1] + red[2] + red[3]) * scale);
+  double total[1];
+  compound_column_sum(total, part, nblk, 1, red);
+  if (threadIdx.x == 0) loss[0] = (float)(total[0] * scale);
 }
 
 // d/dp_t [-alpha q^gamma log p] = alpha (gamma q^(gamma-1) log p - q^gamma / p),  q = 1 - p
@@ -402,69 +399,24 @@ extern "C" int seg3d_focal_bwd(const float* probs, const float* target, const fl
 //   dL/dp[n,c,s] = v (A[r,c] t_c + B[r,c]) + [c == t] v coef_dist a_t d/dpt[(1 - pt)^gamma (-log pt)] [p_t >= 1e-12]
 //   A = -dice_weight w'_c k 2 / (U + eps),  B = dice_weight w'_c k (2 I + eps) / (U + eps)^2,  k = 1/N (r = n) or 1 (batch_dice, r = 0)
 //   coef_dist = ce_weight / sum a_t  (0 when nothing is valid or ce_weight is 0)
-// CT is the compile-time class count (1..5: exact, accumulators in registers; 16: generic, planes c >= C predicated
-// off); VEC: S % 4 == 0 and 16-byte aligned bases -> one 16-byte access per lane and plane, else a scalar path.
-// The per-voxel sums, the region term's finalize rule and the per-voxel gradient live in compound_device.h (shared with
-// topk_loss.hip).
-// part[n][blk][3C + 2] = (I, P, T) x C, dist numerator, dist denominator over the block's voxels
+// The walk over the voxels, the partial-sum layout, the region term's finalize rule and the per-voxel gradient live in
+// compound_device.h, shared with topk_loss.hip and boundary_loss.hip.
 template <int CT, bool VEC>
 __global__ __launch_bounds__(256) void compound_partial_kernel(const float* __restrict__ probs,
                                                                  const float* __restrict__ target,
                                                                  const float* __restrict__ alpha_g, float* __restrict__ part,
                                                                  int C, i64 S, int nblk, float ignore, float gamma) {
+  constexpr int W = VEC ? 4 : 1;
   __shared__ float red[4 * 3];
-  const int n = blockIdx.y;
-  const i64 s0 = (i64)blockIdx.x * DICE_VPB;
-  i64 s1 = s0 + DICE_VPB;
-  if (s1 > S) s1 = S;
-  const float* tg = target + (i64)n * S;
-  const float* pb = probs + (i64)n * C * S;
   float alpha[CT];
 #pragma unroll
   for (int c = 0; c < CT; ++c) alpha[c] = (CT <= 5 || c < C) ? alpha_g[c] : 0.f;
   CompoundAcc<CT> a;
+  compound_block_walk<CT, W>(probs, target, C, S, [&](i64, const float (&t)[W], const float (&p)[W][CT]) {
 #pragma unroll
-  for (int k = 0; k < 3 * CT; ++k) a.r[k] = 0.f;
-  a.num = 0.f;
-  a.den = 0.f;
-  if constexpr (VEC) {
-    for (i64 s = s0 + (i64)threadIdx.x * 4; s < s1; s += 256 * 4) {   // s1 is a multiple of 4 here (S % 4 == 0)
-      const float4 t4 = *reinterpret_cast<const float4*>(tg + s);
-      float4 p4[CT];
-#pragma unroll
-      for (int c = 0; c < CT; ++c)
-        if (CT <= 5 || c < C) p4[c] = *reinterpret_cast<const float4*>(pb + (i64)c * S + s);
-      float p[CT];
-#pragma unroll
-      for (int c = 0; c < CT; ++c) p[c] = (CT <= 5 || c < C) ? p4[c].x : 0.f;
-      compound_voxel<CT>(a, t4.x, p, alpha, C, ignore, gamma);
-#pragma unroll
-      for (int c = 0; c < CT; ++c) p[c] = (CT <= 5 || c < C) ? p4[c].y : 0.f;
-      compound_voxel<CT>(a, t4.y, p, alpha, C, ignore, gamma);
-#pragma unroll
-      for (int c = 0; c < CT; ++c) p[c] = (CT <= 5 || c < C) ? p4[c].z : 0.f;
-      compound_voxel<CT>(a, t4.z, p, alpha, C, ignore, gamma);
-#pragma unroll
-      for (int c = 0; c < CT; ++c) p[c] = (CT <= 5 || c < C) ? p4[c].w : 0.f;
-      compound_voxel<CT>(a, t4.w, p, alpha, C, ignore, gamma);
-    }
-  } else {
-    for (i64 s = s0 + threadIdx.x; s < s1; s += 256) {
-      const float t = tg[s];
-      float p[CT];
-#pragma unroll
-      for (int c = 0; c < CT; ++c) p[c] = (CT <= 5 || c < C) ? pb[(i64)c * S + s] : 0.f;
-      compound_voxel<CT>(a, t, p, alpha, C, ignore, gamma);
-    }
-  }
-  float* dst = part + ((i64)n * nblk + blockIdx.x) * (3 * C + 2);
-#pragma unroll
-  for (int c = 0; c < CT; ++c)
-    if (CT <= 5 || c < C) {
-      float v[3] = {a.r[3 * c + 0], a.r[3 * c + 1], a.r[3 * c + 2]};
-      block_sum_256<3>(v, red);
-      if (threadIdx.x == 0) { dst[3 * c + 0] = v[0]; dst[3 * c + 1] = v[1]; dst[3 * c + 2] = v[2]; }
-    }
+    for (int j = 0; j < W; ++j) compound_voxel<CT>(a, t[j], p[j], alpha, C, ignore, gamma);
+  });
+  float* dst = compound_region_store<CT>(a, part, C, nblk, red);
   float v[2] = {a.num, a.den};
   block_sum_256<2>(v, red);
   if (threadIdx.x == 0) { dst[3 * C + 0] = v[0]; dst[3 * C + 1] = v[1]; }
@@ -478,25 +430,10 @@ __global__ __launch_bounds__(256) void compound_finalize_kernel(const float* __r
                                                                   const float* __restrict__ wdice, float* __restrict__ coef,
                                                                   float* __restrict__ loss, int N, int C, int nblk,
                                                                   int batch_dice, float dice_weight, float ce_weight) {
-  __shared__ double red[8], redd[8];
-  const int NV = 3 * C + 2;
-  const i64 nent = (i64)N * nblk;
-  double num = 0.0, den = 0.0;
-  for (i64 m = threadIdx.x; m < nent; m += 256) {
-    num += (double)part[m * NV + 3 * C + 0];
-    den += (double)part[m * NV + 3 * C + 1];
-  }
-  num = wave_sum_d(num);
-  den = wave_sum_d(den);
-  if ((threadIdx.x & 63) == 0) {
-    red[threadIdx.x >> 6] = num;
-    redd[threadIdx.x >> 6] = den;
-  }
-  __syncthreads();
-  num = red[0] + red[1] + red[2] + red[3];   // every thread holds the same totals
-  den = redd[0] + redd[1] + redd[2] + redd[3];
-  __syncthreads();
-
+  __shared__ double red[8];
+  double dist[2];   // the distribution numerator and denominator
+  compound_column_sum(dist, part + 3 * C, (i64)N * nblk, 3 * C + 2, red);
+  const double num = dist[0], den = dist[1];
   const int R = batch_dice ? 1 : N;
   const double lr = compound_region_finalize(part, wdice, coef, N, C, nblk, batch_dice, dice_weight, red);
   if (threadIdx.x == 0) {
@@ -511,66 +448,17 @@ __global__ __launch_bounds__(256) void compound_finalize_kernel(const float* __r
   }
 }
 
-// grid (blocks, N): the sample -- and with it the coefficient row -- is uniform per workgroup
 template <int CT, bool VEC>
 __global__ __launch_bounds__(256) void compound_bwd_kernel(const float* __restrict__ probs, const float* __restrict__ target,
                                                              const float* __restrict__ coef, const float* __restrict__ alpha_g,
                                                              const float* __restrict__ gout, float* __restrict__ dprobs,
                                                              int C, i64 S, int R, float ignore, float gamma) {
-  const int n = blockIdx.y;
-  const int r = R == 1 ? 0 : n;
-  const float go = gout[0];
-  const float cd = coef[2 * R * C];
-  float A[CT], B[CT], alpha[CT];
+  constexpr int W = VEC ? 4 : 1;
+  const float coef_dist = coef[2 * R * C];
+  compound_bwd_body<CT, W>(probs, target, coef, alpha_g, gout, dprobs, C, S, R, ignore, gamma, [&](i64, float (&cd)[W]) {
 #pragma unroll
-  for (int c = 0; c < CT; ++c) {
-    const bool on = CT <= 5 || c < C;
-    A[c] = on ? coef[2 * (r * C + c) + 0] : 0.f;
-    B[c] = on ? coef[2 * (r * C + c) + 1] : 0.f;
-    alpha[c] = on ? alpha_g[c] : 0.f;
-  }
-  const float* tg = target + (i64)n * S;
-  const float* pb = probs + (i64)n * C * S;
-  float* db = dprobs + (i64)n * C * S;
-  if constexpr (VEC) {
-    for (i64 s = ((i64)blockIdx.x * 256 + threadIdx.x) * 4; s < S; s += (i64)gridDim.x * 256 * 4) {
-      const float4 t4 = *reinterpret_cast<const float4*>(tg + s);
-      const float tt[4] = {t4.x, t4.y, t4.z, t4.w};
-      float pt[4] = {0.f, 0.f, 0.f, 0.f};
-      if constexpr (CT <= 5) {   // all planes with 16-byte loads, p_t picked in registers
-#pragma unroll
-        for (int c = 0; c < CT; ++c) {
-          const float4 p4 = *reinterpret_cast<const float4*>(pb + (i64)c * S + s);
-          pt[0] = tt[0] == (float)c ? p4.x : pt[0];
-          pt[1] = tt[1] == (float)c ? p4.y : pt[1];
-          pt[2] = tt[2] == (float)c ? p4.z : pt[2];
-          pt[3] = tt[3] == (float)c ? p4.w : pt[3];
-        }
-      } else {                   // many planes: gather the one probability each voxel needs
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          if (tt[j] >= 0.0f && tt[j] < (float)C) pt[j] = pb[(i64)(int)tt[j] * S + s + j];
-      }
-      float g[4][CT];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) compound_voxel_grad<CT>(g[j], tt[j], pt[j], A, B, alpha, C, ignore, gamma, cd, go);
-#pragma unroll
-      for (int c = 0; c < CT; ++c)
-        if (CT <= 5 || c < C)
-          *reinterpret_cast<float4*>(db + (i64)c * S + s) = make_float4(g[0][c], g[1][c], g[2][c], g[3][c]);
-    }
-  } else {
-    for (i64 s = (i64)blockIdx.x * 256 + threadIdx.x; s < S; s += (i64)gridDim.x * 256) {
-      const float t = tg[s];
-      float pt = 0.f;
-      if (t >= 0.0f && t < (float)C) pt = pb[(i64)(int)t * S + s];
-      float g[CT];
-      compound_voxel_grad<CT>(g, t, pt, A, B, alpha, C, ignore, gamma, cd, go);
-#pragma unroll
-      for (int c = 0; c < CT; ++c)
-        if (CT <= 5 || c < C) db[(i64)c * S + s] = g[c];
-    }
-  }
+    for (int j = 0; j < W; ++j) cd[j] = coef_dist;
+  });
 }
 
 extern "C" long long seg3d_compound_loss_part_floats(int N, int C, long long S) {
@@ -605,14 +493,11 @@ extern "C" int seg3d_compound_loss_bwd(const float* probs, const float* target, 
   SEG3D_REQUIRE(C >= 1 && C <= SEG3D_MAXC, "seg3d_compound_loss_bwd: num_class %d not in [1, %d]", C, SEG3D_MAXC);
   SEG3D_REQUIRE(gamma >= 0.f, "seg3d_compound_loss_bwd: gamma must be >= 0");
   const bool vec = compound_vec_ok(S, probs, target, dprobs);
-  const i64 items = vec ? S / 4 : S;
-  i64 gx = (items + 255) / 256, cap = 8192 / N;
-  if (cap < 1) cap = 1;
-  if (gx > cap) gx = cap;
   const int R = batch_dice ? 1 : N;
   COMPOUND_DISPATCH(compound_bwd_kernel, C, vec,
-                    <<<dim3((unsigned)gx, N), dim3(256), 0, (hipStream_t)stream>>>(probs, target, coef, alpha, gout, dprobs, C,
-                                                                                  (i64)S, R, ignore_label, gamma));
+                    <<<compound_bwd_grid(S, N, vec), dim3(256), 0, (hipStream_t)stream>>>(probs, target, coef, alpha, gout,
+                                                                                         dprobs, C, (i64)S, R, ignore_label,
+                                                                                         gamma));
   SEG3D_LAUNCH_CHECK("seg3d_compound_loss_bwd");
   return SEG3D_OK;
 }

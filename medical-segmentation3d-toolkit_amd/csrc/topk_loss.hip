@@ -1,7 +1,6 @@
 // topk_loss.hip -- soft Dice + top-k cross-entropy on probabilities, forward + backward (no counterpart in the reference;
 // nnU-Net's DC_and_topk_loss; definitions in DESIGN.md section 7, row f15, and include/seg3d_hip.h).
-//   counted voxel:  0 <= t < C && t != ignore (the compound loss's rule)
-//   L_region:       the compound loss's soft-Dice term, from its own device code (compound_device.h)
+//   counted voxel and L_region:  the compound loss family's (compound_device.h)
 //   ell_v = a_t (-log max(p_t, 1e-12)) in fp32 on counted voxels, stored as +0.0 when it is not > 0
 //   n = #counted,  k = max(1, (long long)((double)n * k_percent / 100.0))  (n = 0: k = 0, L_topk = 0)
 //   tau = k-th largest ell,  m = #{ell > tau},  n_eq = #{ell == tau},  r = k - m
@@ -56,67 +55,25 @@ __device__ __forceinline__ float topk_voxel(CompoundAcc<CT>& a, float t, const f
   return l > 0.0f ? l : 0.0f;   // -0.0 (p_t == 1) -> +0.0; out of contract (p_t > 1, NaN) -> +0.0 as well
 }
 
-// pass A: part[n][blk][3C + 2] as compound_partial_kernel leaves it (the two distribution slots are 0), ell[n][s]
+// pass A: the (I, P, T) triples of part (its two trailing slots are 0) and ell[n][s]
 template <int CT, bool VEC>
 __global__ __launch_bounds__(256) void topk_partial_kernel(const float* __restrict__ probs, const float* __restrict__ target,
                                                              const float* __restrict__ alpha_g, float* __restrict__ part,
                                                              float* __restrict__ ell, int C, i64 S, int nblk, float ignore) {
+  constexpr int W = VEC ? 4 : 1;
   __shared__ float red[4 * 3];
-  const int n = blockIdx.y;
-  const i64 s0 = (i64)blockIdx.x * DICE_VPB;
-  i64 s1 = s0 + DICE_VPB;
-  if (s1 > S) s1 = S;
-  const float* tg = target + (i64)n * S;
-  const float* pb = probs + (i64)n * C * S;
-  float* eb = ell + (i64)n * S;
+  float* eb = ell + (i64)blockIdx.y * S;
   float alpha[CT];
 #pragma unroll
   for (int c = 0; c < CT; ++c) alpha[c] = (CT <= 5 || c < C) ? alpha_g[c] : 0.f;
   CompoundAcc<CT> a;
+  compound_block_walk<CT, W>(probs, target, C, S, [&](i64 s, const float (&t)[W], const float (&p)[W][CT]) {
+    float e[W];
 #pragma unroll
-  for (int k = 0; k < 3 * CT; ++k) a.r[k] = 0.f;
-  a.num = 0.f;
-  a.den = 0.f;
-  if constexpr (VEC) {
-    for (i64 s = s0 + (i64)threadIdx.x * 4; s < s1; s += 256 * 4) {   // s1 is a multiple of 4 here (S % 4 == 0)
-      const float4 t4 = *reinterpret_cast<const float4*>(tg + s);
-      float4 p4[CT];
-#pragma unroll
-      for (int c = 0; c < CT; ++c)
-        if (CT <= 5 || c < C) p4[c] = *reinterpret_cast<const float4*>(pb + (i64)c * S + s);
-      float p[CT];
-      float4 e4;
-#pragma unroll
-      for (int c = 0; c < CT; ++c) p[c] = (CT <= 5 || c < C) ? p4[c].x : 0.f;
-      e4.x = topk_voxel<CT>(a, t4.x, p, alpha, C, ignore);
-#pragma unroll
-      for (int c = 0; c < CT; ++c) p[c] = (CT <= 5 || c < C) ? p4[c].y : 0.f;
-      e4.y = topk_voxel<CT>(a, t4.y, p, alpha, C, ignore);
-#pragma unroll
-      for (int c = 0; c < CT; ++c) p[c] = (CT <= 5 || c < C) ? p4[c].z : 0.f;
-      e4.z = topk_voxel<CT>(a, t4.z, p, alpha, C, ignore);
-#pragma unroll
-      for (int c = 0; c < CT; ++c) p[c] = (CT <= 5 || c < C) ? p4[c].w : 0.f;
-      e4.w = topk_voxel<CT>(a, t4.w, p, alpha, C, ignore);
-      *reinterpret_cast<float4*>(eb + s) = e4;
-    }
-  } else {
-    for (i64 s = s0 + threadIdx.x; s < s1; s += 256) {
-      const float t = tg[s];
-      float p[CT];
-#pragma unroll
-      for (int c = 0; c < CT; ++c) p[c] = (CT <= 5 || c < C) ? pb[(i64)c * S + s] : 0.f;
-      eb[s] = topk_voxel<CT>(a, t, p, alpha, C, ignore);
-    }
-  }
-  float* dst = part + ((i64)n * nblk + blockIdx.x) * (3 * C + 2);
-#pragma unroll
-  for (int c = 0; c < CT; ++c)
-    if (CT <= 5 || c < C) {
-      float v[3] = {a.r[3 * c + 0], a.r[3 * c + 1], a.r[3 * c + 2]};
-      block_sum_256<3>(v, red);
-      if (threadIdx.x == 0) { dst[3 * c + 0] = v[0]; dst[3 * c + 1] = v[1]; dst[3 * c + 2] = v[2]; }
-    }
+    for (int j = 0; j < W; ++j) e[j] = topk_voxel<CT>(a, t[j], p[j], alpha, C, ignore);
+    compound_store<W>(eb + s, e);
+  });
+  float* dst = compound_region_store<CT>(a, part, C, nblk, red);
   if (threadIdx.x == 0) { dst[3 * C + 0] = 0.f; dst[3 * C + 1] = 0.f; }
 }
 
@@ -250,18 +207,13 @@ __global__ __launch_bounds__(256) void topk_finalize_kernel(const float* __restr
                                                               float* __restrict__ threshold, int N, int C, int nblk,
                                                               int batch_dice, float dice_weight, float ce_weight) {
   __shared__ double red[8];
-  double above = 0.0;
-  for (int i = threadIdx.x; i < nslots; i += 256) above += slots[i];
-  above = wave_sum_d(above);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = above;
-  __syncthreads();
-  above = red[0] + red[1] + red[2] + red[3];   // every thread holds the same total
-  __syncthreads();
+  double above[1];
+  compound_column_sum(above, slots, nslots, 1, red);
   const double lr = compound_region_finalize(part, wdice, coef, N, C, nblk, batch_dice, dice_weight, red);
   if (threadIdx.x == 0) {
     const i64 n = ctrl[TOPK_N], k = ctrl[TOPK_K], m = ctrl[TOPK_M], neq = ctrl[TOPK_NEQ], r = ctrl[TOPK_LEFT];
     const float tau = __uint_as_float((unsigned)ctrl[TOPK_PREFIX]);
-    const double lt = k > 0 ? (above + (double)r * (double)tau) / (double)k : 0.0;
+    const double lt = k > 0 ? (above[0] + (double)r * (double)tau) / (double)k : 0.0;
     double l = 0.0;
     if (dice_weight > 0.f) l += (double)dice_weight * lr;
     if (ce_weight > 0.f) l += (double)ce_weight * lt;
@@ -284,72 +236,22 @@ __device__ __forceinline__ float topk_coef(float e, int tau, float c_above, floa
   return key > tau ? c_above : (key == tau ? c_at : 0.f);
 }
 
-// grid (blocks, N), the layout of compound_bwd_kernel; the distribution part of compound_voxel_grad (gamma = 0: -1 / p_t)
-// takes this voxel's own coefficient
+// the distribution part of compound_voxel_grad (gamma = 0: -1 / p_t) takes each voxel's own coefficient
 template <int CT, bool VEC>
 __global__ __launch_bounds__(256) void topk_bwd_kernel(const float* __restrict__ probs, const float* __restrict__ target,
                                                          const float* __restrict__ ell, const float* __restrict__ coef,
                                                          const float* __restrict__ alpha_g, const float* __restrict__ gout,
                                                          float* __restrict__ dprobs, int C, i64 S, int R, float ignore) {
-  const int n = blockIdx.y;
-  const int r = R == 1 ? 0 : n;
-  const float go = gout[0];
+  constexpr int W = VEC ? 4 : 1;
   const int tau = (int)__float_as_uint(coef[2 * R * C + 0]);
   const float c_above = coef[2 * R * C + 1], c_at = coef[2 * R * C + 2];
-  float A[CT], B[CT], alpha[CT];
+  const float* eb = ell + (i64)blockIdx.y * S;
+  compound_bwd_body<CT, W>(probs, target, coef, alpha_g, gout, dprobs, C, S, R, ignore, 0.0f, [&](i64 s, float (&cd)[W]) {
+    float e[W];
+    compound_load<W>(e, eb + s);
 #pragma unroll
-  for (int c = 0; c < CT; ++c) {
-    const bool on = CT <= 5 || c < C;
-    A[c] = on ? coef[2 * (r * C + c) + 0] : 0.f;
-    B[c] = on ? coef[2 * (r * C + c) + 1] : 0.f;
-    alpha[c] = on ? alpha_g[c] : 0.f;
-  }
-  const float* tg = target + (i64)n * S;
-  const float* eb = ell + (i64)n * S;
-  const float* pb = probs + (i64)n * C * S;
-  float* db = dprobs + (i64)n * C * S;
-  if constexpr (VEC) {
-    for (i64 s = ((i64)blockIdx.x * 256 + threadIdx.x) * 4; s < S; s += (i64)gridDim.x * 256 * 4) {
-      const float4 t4 = *reinterpret_cast<const float4*>(tg + s);
-      const float4 e4 = *reinterpret_cast<const float4*>(eb + s);
-      const float tt[4] = {t4.x, t4.y, t4.z, t4.w};
-      const float ee[4] = {e4.x, e4.y, e4.z, e4.w};
-      float pt[4] = {0.f, 0.f, 0.f, 0.f};
-      if constexpr (CT <= 5) {   // all planes with 16-byte loads, p_t picked in registers
-#pragma unroll
-        for (int c = 0; c < CT; ++c) {
-          const float4 p4 = *reinterpret_cast<const float4*>(pb + (i64)c * S + s);
-          pt[0] = tt[0] == (float)c ? p4.x : pt[0];
-          pt[1] = tt[1] == (float)c ? p4.y : pt[1];
-          pt[2] = tt[2] == (float)c ? p4.z : pt[2];
-          pt[3] = tt[3] == (float)c ? p4.w : pt[3];
-        }
-      } else {                   // many planes: gather the one probability each voxel needs
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          if (tt[j] >= 0.0f && tt[j] < (float)C) pt[j] = pb[(i64)(int)tt[j] * S + s + j];
-      }
-      float g[4][CT];
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        compound_voxel_grad<CT>(g[j], tt[j], pt[j], A, B, alpha, C, ignore, 0.0f, topk_coef(ee[j], tau, c_above, c_at), go);
-#pragma unroll
-      for (int c = 0; c < CT; ++c)
-        if (CT <= 5 || c < C)
-          *reinterpret_cast<float4*>(db + (i64)c * S + s) = make_float4(g[0][c], g[1][c], g[2][c], g[3][c]);
-    }
-  } else {
-    for (i64 s = (i64)blockIdx.x * 256 + threadIdx.x; s < S; s += (i64)gridDim.x * 256) {
-      const float t = tg[s];
-      float pt = 0.f;
-      if (t >= 0.0f && t < (float)C) pt = pb[(i64)(int)t * S + s];
-      float g[CT];
-      compound_voxel_grad<CT>(g, t, pt, A, B, alpha, C, ignore, 0.0f, topk_coef(eb[s], tau, c_above, c_at), go);
-#pragma unroll
-      for (int c = 0; c < CT; ++c)
-        if (CT <= 5 || c < C) db[(i64)c * S + s] = g[c];
-    }
-  }
+    for (int j = 0; j < W; ++j) cd[j] = topk_coef(e[j], tau, c_above, c_at);
+  });
 }
 
 // control block | three histograms | fp64 sum slots | Dice partial sums
@@ -416,14 +318,10 @@ extern "C" int seg3d_topk_loss_bwd(const float* probs, const float* target, cons
                 "seg3d_topk_loss_bwd: bad arguments");
   SEG3D_REQUIRE(C >= 1 && C <= SEG3D_MAXC, "seg3d_topk_loss_bwd: num_class %d not in [1, %d]", C, SEG3D_MAXC);
   const bool vec = compound_vec_ok(S, probs, target, dprobs) && ((uintptr_t)ell & 15) == 0;
-  const i64 items = vec ? S / 4 : S;
-  i64 gx = (items + 255) / 256, cap = 8192 / N;
-  if (cap < 1) cap = 1;
-  if (gx > cap) gx = cap;
   const int R = batch_dice ? 1 : N;
   COMPOUND_DISPATCH(topk_bwd_kernel, C, vec,
-                    <<<dim3((unsigned)gx, N), dim3(256), 0, (hipStream_t)stream>>>(probs, target, ell, coef, alpha, gout, dprobs,
-                                                                                  C, (i64)S, R, ignore_label));
+                    <<<compound_bwd_grid(S, N, vec), dim3(256), 0, (hipStream_t)stream>>>(probs, target, ell, coef, alpha, gout,
+                                                                                         dprobs, C, (i64)S, R, ignore_label));
   SEG3D_LAUNCH_CHECK("seg3d_topk_loss_bwd");
   return SEG3D_OK;
 }

@@ -6,8 +6,8 @@
 // Here ONE streaming pass over probs [N][C][S] (planar fp32, what the soft-max head writes) and target [N][S] (float class
 // ids, what the losses take) adds, for every valid voxel,
 //     tp[c] += [pred == c && t == c]      fp[c] += [pred == c && t != c]      fn[c] += [pred != c && t == c]
-// into counts[c] = (tp, fp, fn).  valid is the compound loss's rule (loss.hip compound_voxel): t >= 0 && t < C && t != ignore,
-// class (int)t.  pred is the FIRST maximum: class 0, replaced only by a strictly greater value (finalize_argmax_kernel,
+// into counts[c] = (tp, fp, fn).  valid is the compound loss's rule (compound_device.h compound_class): t >= 0 && t < C &&
+// t != ignore, class (int)t.  pred is the FIRST maximum: class 0, replaced only by a strictly greater value (finalize_argmax_kernel,
 // tensor.max(0)).  NaN probabilities are outside the contract: every comparison with a NaN is false, so a NaN in a class
 // above 0 never becomes the maximum and a NaN in class 0 is never replaced (np.argmax would return the NaN's index in both
 // cases).  Integer counting only: per-thread 32-bit counters, a wave64
@@ -15,8 +15,8 @@
 // HBM-bound: algorithmic bytes = (C + 1) * 4 per voxel.
 #include "seg3d_common.h"
 #include "seg3d_hip.h"
+#include "compound_device.h"   // SEG3D_MAXC, compound_class, compound_load
 
-#define CONF_MAXC 16      // SEG3D_MAXC of loss.hip
 #define CONF_THREADS 1024
 #define CONF_WAVES (CONF_THREADS / 64)
 
@@ -28,9 +28,8 @@ struct ConfAcc {
 
 template <int CT>
 __device__ __forceinline__ void conf_voxel(ConfAcc<CT>& a, float t, int pred, int C, float ignore) {
-  const bool valid = t >= 0.0f && t < (float)C && t != ignore;
-  if (!valid) return;
-  const int ti = (int)t;
+  const int ti = compound_class(t, C, ignore);
+  if (ti < 0) return;
 #pragma unroll
   for (int c = 0; c < CT; ++c)
     if (CT <= 5 || c < C) {
@@ -54,37 +53,26 @@ __global__ __launch_bounds__(CONF_THREADS) void confusion_counts_kernel(const fl
   ConfAcc<CT> a;
 #pragma unroll
   for (int c = 0; c < CT; ++c) a.tp[c] = a.fp[c] = a.fn[c] = 0u;
-  if constexpr (VEC) {   // S % 4 == 0 and 16-byte aligned bases: every plane row starts aligned
-    for (i64 s = ((i64)blockIdx.x * CONF_THREADS + threadIdx.x) * 4; s < S; s += (i64)gridDim.x * CONF_THREADS * 4) {
-      const float4 t4 = *reinterpret_cast<const float4*>(tg + s);
-      float4 best = *reinterpret_cast<const float4*>(pb + s);
-      int ix = 0, iy = 0, iz = 0, iw = 0;
+  constexpr int W = VEC ? 4 : 1;   // VEC: S % 4 == 0 and 16-byte aligned bases, so every plane row starts aligned
+  for (i64 s = ((i64)blockIdx.x * CONF_THREADS + threadIdx.x) * W; s < S; s += (i64)gridDim.x * CONF_THREADS * W) {
+    float t[W], best[W];
+    int idx[W] = {};
+    compound_load<W>(t, tg + s);
+    compound_load<W>(best, pb + s);
 #pragma unroll
-      for (int c = 1; c < CT; ++c)
-        if (CT <= 5 || c < C) {
-          const float4 p = *reinterpret_cast<const float4*>(pb + (i64)c * S + s);
-          if (p.x > best.x) { best.x = p.x; ix = c; }
-          if (p.y > best.y) { best.y = p.y; iy = c; }
-          if (p.z > best.z) { best.z = p.z; iz = c; }
-          if (p.w > best.w) { best.w = p.w; iw = c; }
-        }
-      conf_voxel<CT>(a, t4.x, ix, C, ignore);
-      conf_voxel<CT>(a, t4.y, iy, C, ignore);
-      conf_voxel<CT>(a, t4.z, iz, C, ignore);
-      conf_voxel<CT>(a, t4.w, iw, C, ignore);
-    }
-  } else {
-    for (i64 s = (i64)blockIdx.x * CONF_THREADS + threadIdx.x; s < S; s += (i64)gridDim.x * CONF_THREADS) {
-      const float t = tg[s];
-      float best = pb[s];
-      int idx = 0;
+    for (int c = 1; c < CT; ++c)
+      if (CT <= 5 || c < C) {
+        float p[W];
+        compound_load<W>(p, pb + (i64)c * S + s);
 #pragma unroll
-      for (int c = 1; c < CT; ++c)
-        if (CT <= 5 || c < C) {
-          const float p = pb[(i64)c * S + s];
-          if (p > best) { best = p; idx = c; }
-        }
-      conf_voxel<CT>(a, t, idx, C, ignore);
+        for (int j = 0; j < W; ++j)
+          if (p[j] > best[j]) { best[j] = p[j]; idx[j] = c; }
+      }
+    conf_voxel<CT>(a, t[0], idx[0], C, ignore);
+    if constexpr (W == 4) {   // written out: as a loop over j, CT = 16 keeps 32 more registers live
+      conf_voxel<CT>(a, t[1], idx[1], C, ignore);
+      conf_voxel<CT>(a, t[2], idx[2], C, ignore);
+      conf_voxel<CT>(a, t[3], idx[3], C, ignore);
     }
   }
   // a thread counts at most S / 1024 + 4 voxels and a wave 64 times that: 32 bits hold both for S < 2^33 (checked by the entry)
@@ -123,8 +111,8 @@ extern "C" int seg3d_confusion_counts(const float* probs, const float* target, l
                                       float ignore_label, void* stream) {
   SEG3D_REQUIRE(probs && target && counts, "seg3d_confusion_counts: null pointer");
   SEG3D_REQUIRE(N > 0 && N <= 65535 && S > 0 && S < (1ll << 33), "seg3d_confusion_counts: bad sizes (N = %d, S = %lld)", N, S);
-  SEG3D_REQUIRE(C >= 1 && C <= CONF_MAXC, "seg3d_confusion_counts: num_class %d not in [1, %d]", C, CONF_MAXC);
-  const bool vec = S % 4 == 0 && (((uintptr_t)probs | (uintptr_t)target) & 15) == 0;
+  SEG3D_REQUIRE(C >= 1 && C <= SEG3D_MAXC, "seg3d_confusion_counts: num_class %d not in [1, %d]", C, SEG3D_MAXC);
+  const bool vec = compound_vec_ok(S, probs, target, probs);
   const i64 items = vec ? S / 4 : S;
   // two workgroups of 16 waves per compute unit over the whole batch; the grid-stride loop takes the rest
   i64 gx = (items + CONF_THREADS - 1) / CONF_THREADS;
@@ -140,7 +128,7 @@ extern "C" int seg3d_confusion_counts(const float* probs, const float* target, l
     case 3: if (vec) CONF_LAUNCH(3, true); else CONF_LAUNCH(3, false); break;
     case 4: if (vec) CONF_LAUNCH(4, true); else CONF_LAUNCH(4, false); break;
     case 5: if (vec) CONF_LAUNCH(5, true); else CONF_LAUNCH(5, false); break;
-    default: if (vec) CONF_LAUNCH(CONF_MAXC, true); else CONF_LAUNCH(CONF_MAXC, false); break;
+    default: if (vec) CONF_LAUNCH(SEG3D_MAXC, true); else CONF_LAUNCH(SEG3D_MAXC, false); break;
   }
   SEG3D_LAUNCH_CHECK("seg3d_confusion_counts");
   return SEG3D_OK;

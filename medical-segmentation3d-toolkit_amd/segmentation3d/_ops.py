@@ -1366,6 +1366,26 @@ def sigmoid_channels(x):
     return SigmoidFunction.apply(x)
 
 
+def _loss_inputs(probs, target, *others):
+    """the shared prologue of the compound loss Functions: device and float32 checks, contiguous probabilities p
+    [N, C, *spatial] and float target t with N * S elements; returns (p, t, N, C, S)"""
+    E.require_device(probs, target, *others)
+    if probs.dtype != torch.float32:
+        raise ValueError('probabilities must be float32, got {}'.format(probs.dtype))
+    p = probs.contiguous()
+    t = target.contiguous().float()
+    N, C = p.shape[0], p.shape[1]
+    S = p[0, 0].numel()
+    if t.numel() != N * S:
+        raise ValueError('target shape {} does not match input {}'.format(tuple(target.shape), tuple(probs.shape)))
+    return p, t, N, C, S
+
+
+def _gout1(gout):
+    """the incoming gradient of a scalar loss as a 1-element float32 tensor the kernels read"""
+    return gout.contiguous().reshape(1).float()
+
+
 class DiceLossFunction(torch.autograd.Function):
     """MultiDiceLoss.forward (loss/multi_dice_loss.py:24-43) as one fused reduction + one elementwise backward"""
 
@@ -1392,7 +1412,7 @@ class DiceLossFunction(torch.autograd.Function):
         p, t, sums, weights = ctx.saved_tensors
         N, C = p.shape[0], p.shape[1]
         S = p[0, 0].numel()
-        g = gout.contiguous().reshape(1).float()
+        g = _gout1(gout)
         dp = torch.empty_like(p)
         E.call('seg3d_dice_bwd', E.ptr(p), E.ptr(t), E.ptr(sums), E.ptr(weights), E.ptr(g), E.ptr(dp), N, C, S,
                E.stream_ptr())
@@ -1407,15 +1427,7 @@ class CompoundLossFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, probs, target, wdice, alpha, gamma, dice_weight, ce_weight, batch_dice, ignore):
-        E.require_device(probs, target, wdice, alpha)
-        if probs.dtype != torch.float32:
-            raise ValueError('probabilities must be float32, got {}'.format(probs.dtype))
-        p = probs.contiguous()
-        t = target.contiguous().float()
-        N, C = p.shape[0], p.shape[1]
-        S = p[0, 0].numel()
-        if t.numel() != N * S:
-            raise ValueError('target shape {} does not match input {}'.format(tuple(target.shape), tuple(probs.shape)))
+        p, t, N, C, S = _loss_inputs(probs, target, wdice, alpha)
         cfg = (float(gamma), int(bool(batch_dice)), float(ignore))
         part = _empty((E.query('seg3d_compound_loss_part_floats', N, C, S),), p)
         coef = _empty((2 * (1 if cfg[1] else N) * C + 1,), p)
@@ -1433,7 +1445,7 @@ class CompoundLossFunction(torch.autograd.Function):
         gamma, batch_dice, ignore = ctx.cfg
         N, C = p.shape[0], p.shape[1]
         S = p[0, 0].numel()
-        g = gout.contiguous().reshape(1).float()
+        g = _gout1(gout)
         dp = torch.empty_like(p)
         E.call('seg3d_compound_loss_bwd', E.ptr(p), E.ptr(t), E.ptr(coef), E.ptr(alpha), E.ptr(g), E.ptr(dp), N, C, S,
                gamma, batch_dice, ignore, E.stream_ptr())
@@ -1450,15 +1462,7 @@ class TopKLossFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, probs, target, wdice, alpha, k_percent, dice_weight, ce_weight, batch_dice, ignore):
-        E.require_device(probs, target, wdice, alpha)
-        if probs.dtype != torch.float32:
-            raise ValueError('probabilities must be float32, got {}'.format(probs.dtype))
-        p = probs.contiguous()
-        t = target.contiguous().float()
-        N, C = p.shape[0], p.shape[1]
-        S = p[0, 0].numel()
-        if t.numel() != N * S:
-            raise ValueError('target shape {} does not match input {}'.format(tuple(target.shape), tuple(probs.shape)))
+        p, t, N, C, S = _loss_inputs(probs, target, wdice, alpha)
         cfg = (int(bool(batch_dice)), float(ignore))
         work = _empty(((E.query('seg3d_topk_loss_workspace_bytes', N, C, S) + 7) // 8,), p, dtype=torch.int64)
         ell = _empty((N * S,), p)
@@ -1480,7 +1484,7 @@ class TopKLossFunction(torch.autograd.Function):
         batch_dice, ignore = ctx.cfg
         N, C = p.shape[0], p.shape[1]
         S = p[0, 0].numel()
-        g = gout.contiguous().reshape(1).float()
+        g = _gout1(gout)
         dp = torch.empty_like(p)
         E.call('seg3d_topk_loss_bwd', E.ptr(p), E.ptr(t), E.ptr(ell), E.ptr(coef), E.ptr(alpha), E.ptr(g), E.ptr(dp), N, C, S,
                batch_dice, ignore, E.stream_ptr())
@@ -1542,17 +1546,9 @@ class BoundaryLossFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, probs, target, wdice, bweight, spacing, dice_weight, include_background, batch_dice, ignore):
-        E.require_device(probs, target, wdice, bweight)
-        if probs.dtype != torch.float32:
-            raise ValueError('probabilities must be float32, got {}'.format(probs.dtype))
+        p, t, N, C, S = _loss_inputs(probs, target, wdice, bweight)
         if probs.dim() != 5:
             raise ValueError('probabilities must be [N, C, Z, Y, X], got {}'.format(tuple(probs.shape)))
-        p = probs.contiguous()
-        t = target.contiguous().float()
-        N, C = p.shape[0], p.shape[1]
-        S = p[0, 0].numel()
-        if t.numel() != N * S:
-            raise ValueError('target shape {} does not match input {}'.format(tuple(target.shape), tuple(probs.shape)))
         cfg = (int(bool(include_background)), int(bool(batch_dice)), float(ignore))
         phi = signed_distance(t.reshape((N,) + tuple(p.shape[2:])), range(0 if cfg[0] else 1, C), spacing, cfg[2], num_class=C)
         work = _empty(((E.query('seg3d_boundary_loss_workspace_bytes', N, C, S) + 3) // 4,), p)
@@ -1572,7 +1568,7 @@ class BoundaryLossFunction(torch.autograd.Function):
         include_background, batch_dice, ignore = ctx.cfg
         N, C = ctx.pshape[0], ctx.pshape[1]
         S = t.numel() // N
-        g = gout.contiguous().reshape(1).float()
+        g = _gout1(gout)
         dp = _empty(ctx.pshape, t)
         E.call('seg3d_boundary_loss_bwd', E.ptr(t), E.ptr(phi), E.ptr(coef), E.ptr(g), E.ptr(dp), N, C, S,
                include_background, batch_dice, ignore, E.stream_ptr())
@@ -1608,7 +1604,7 @@ class BinaryDiceLossFunction(torch.autograd.Function):
         p, t, sums = ctx.saved_tensors
         N = p.shape[0]
         S = p[0, 0].numel()
-        g = gout.contiguous().reshape(1).float()
+        g = _gout1(gout)
         dp = torch.empty_like(p)
         E.call('seg3d_binary_dice_bwd', E.ptr(p), E.ptr(t), E.ptr(sums), E.ptr(g), E.ptr(dp), N, S, E.stream_ptr())
         return dp, None
@@ -1638,7 +1634,7 @@ class FocalLossFunction(torch.autograd.Function):
     def backward(ctx, gout):
         p, t, alpha = ctx.saved_tensors
         gamma, size_average, N, C, S, sn, sc, ss = ctx.cfg
-        g = gout.contiguous().reshape(1).float()
+        g = _gout1(gout)
         dp = torch.empty_like(p)
         E.call('seg3d_focal_bwd', E.ptr(p), E.ptr(t), E.ptr(alpha), E.ptr(g), E.ptr(dp), N, C, S, sn, sc, ss, gamma,
                size_average, E.stream_ptr())

@@ -29,6 +29,7 @@ import torch
 import torch.nn as nn
 
 from segmentation3d import _ops
+from segmentation3d.loss.compound_loss import class_weight_tensors
 
 MAX_AXIS = 256
 
@@ -60,28 +61,16 @@ class DiceBoundaryLoss(nn.Module):
         num_class = int(num_class)
         if not 1 <= num_class <= 16:
             raise ValueError('num_class must be in 1..16, got {}'.format(num_class))
-        if weights is None:
-            weights = [1.0] * num_class
-        weights = [float(w) for w in weights]
-        if len(weights) != num_class:
-            raise ValueError('weights has {} entries but num_class is {}'.format(len(weights), num_class))
-        if not all(math.isfinite(w) and w > 0.0 for w in weights):
-            raise ValueError('class weights must be positive, got {}'.format(weights))
+        self.region_weights, _ = class_weight_tensors(num_class, weights, include_background, require_finite=True)
         dice_weight = float(dice_weight)
         if not (math.isfinite(dice_weight) and dice_weight >= 0.0):
             raise ValueError('dice_weight must be finite and >= 0, got {}'.format(dice_weight))
-        if not include_background and num_class == 1:
-            raise ValueError('include_background=False leaves no class with num_class = 1')
         self.num_class = num_class
         self.dice_weight = dice_weight
         self.spacing = _ops._spacing3(spacing)
         self.include_background = bool(include_background)
         self.batch_dice = bool(batch_dice)
         self.ignore_label = None if ignore_label is None else float(ignore_label)
-        region = torch.tensor(weights, dtype=torch.float64)
-        if not self.include_background:
-            region[0] = 0.0
-        self.region_weights = (region / region.sum()).float()
         self._boundary_weight = _check_boundary_weight(boundary_weight)
         self._weight_dev = None   # the device scalar, created on the first call's device
         self.use_gpu = use_gpu

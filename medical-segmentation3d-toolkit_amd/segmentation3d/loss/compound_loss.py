@@ -16,10 +16,30 @@ A voxel counts iff 0 <= t < C and t != ignore_label; every other voxel enters no
 
 All sums come from ONE pass over the probabilities (seg3d_compound_loss_fwd) and the backward is one elementwise kernel.
 """
+import math
+
 import torch
 import torch.nn as nn
 
 from segmentation3d import _ops
+
+
+def class_weight_tensors(num_class, weights, include_background, require_finite=False):
+    """validate the per-class weights (None = all ones; positive, and finite if asked) and return (region, classes): the
+    float32 region weights normalised over the included classes (0 for an excluded background) and the weights as given"""
+    if weights is None:
+        weights = [1.0] * num_class
+    weights = [float(w) for w in weights]
+    if len(weights) != num_class:
+        raise ValueError('weights has {} entries but num_class is {}'.format(len(weights), num_class))
+    if not all(w > 0.0 and (math.isfinite(w) or not require_finite) for w in weights):
+        raise ValueError('class weights must be positive, got {}'.format(weights))
+    if not include_background and num_class == 1:
+        raise ValueError('include_background=False leaves no class with num_class = 1')
+    region = torch.tensor(weights, dtype=torch.float64)
+    if not include_background:
+        region[0] = 0.0
+    return (region / region.sum()).float(), torch.tensor(weights, dtype=torch.float32)
 
 
 class DiceCELoss(nn.Module):
@@ -42,33 +62,38 @@ class DiceCELoss(nn.Module):
         num_class = int(num_class)
         if num_class < 1:
             raise ValueError('num_class must be >= 1, got {}'.format(num_class))
-        if weights is None:
-            weights = [1.0] * num_class
-        weights = [float(w) for w in weights]
-        if len(weights) != num_class:
-            raise ValueError('weights has {} entries but num_class is {}'.format(len(weights), num_class))
-        if not all(w > 0.0 for w in weights):
-            raise ValueError('class weights must be positive, got {}'.format(weights))
+        region_weights, class_weights = class_weight_tensors(num_class, weights, include_background)
         dice_weight, ce_weight, gamma = float(dice_weight), float(ce_weight), float(gamma)
         if dice_weight < 0.0 or ce_weight < 0.0 or (dice_weight == 0.0 and ce_weight == 0.0):
             raise ValueError('dice_weight and ce_weight must be >= 0 and not both 0, got {} and {}'.format(dice_weight,
                                                                                                          ce_weight))
         if not gamma >= 0.0:
             raise ValueError('gamma must be >= 0, got {}'.format(gamma))
-        if not include_background and num_class == 1:
-            raise ValueError('include_background=False leaves no class with num_class = 1')
         self.num_class = num_class
         self.dice_weight, self.ce_weight, self.gamma = dice_weight, ce_weight, gamma
         self.include_background = bool(include_background)
         self.batch_dice = bool(batch_dice)
         self.ignore_label = None if ignore_label is None else float(ignore_label)
-        region = torch.tensor(weights, dtype=torch.float64)
-        if not self.include_background:
-            region[0] = 0.0
-        self.region_weights = (region / region.sum()).float()
-        self.class_weights = torch.tensor(weights, dtype=torch.float32)
+        self.region_weights, self.class_weights = region_weights, class_weights
         self.use_gpu = use_gpu
         self.last_terms = None
+
+    def _check_shapes(self, input_tensor, target):
+        if input_tensor.dim() < 3 or input_tensor.shape[1] != self.num_class:
+            raise ValueError('input of shape {} does not have num_class = {} channels'.format(tuple(input_tensor.shape),
+                                                                                              self.num_class))
+        if target.numel() * self.num_class != input_tensor.numel():
+            raise ValueError('target shape {} does not match input {}'.format(tuple(target.shape),
+                                                                              tuple(input_tensor.shape)))
+
+    def _weights_on(self, device):
+        if self.region_weights.device != device:
+            self.region_weights = self.region_weights.to(device)
+            self.class_weights = self.class_weights.to(device)
+
+    def _ignore_value(self):
+        """any value outside [0, C) stands for "no ignore label": such voxels are left out by the range rule anyway"""
+        return -1.0 if self.ignore_label is None else self.ignore_label
 
     def forward(self, input_tensor, target):
         """
@@ -77,18 +102,9 @@ class DiceCELoss(nn.Module):
         :return: the loss (0-dim tensor, differentiable w.r.t. input_tensor); `.last_terms` then holds the device tensor
                  (L, L_region, L_dist) of this call, written without a synchronisation
         """
-        if input_tensor.dim() < 3 or input_tensor.shape[1] != self.num_class:
-            raise ValueError('input of shape {} does not have num_class = {} channels'.format(tuple(input_tensor.shape),
-                                                                                              self.num_class))
-        if target.numel() * self.num_class != input_tensor.numel():
-            raise ValueError('target shape {} does not match input {}'.format(tuple(target.shape),
-                                                                              tuple(input_tensor.shape)))
-        if self.region_weights.device != input_tensor.device:
-            self.region_weights = self.region_weights.to(input_tensor.device)
-            self.class_weights = self.class_weights.to(input_tensor.device)
-        # any value outside [0, C) stands for "no ignore label": such voxels are left out by the range rule anyway
-        ignore = -1.0 if self.ignore_label is None else self.ignore_label
+        self._check_shapes(input_tensor, target)
+        self._weights_on(input_tensor.device)
         loss, self.last_terms = _ops.CompoundLossFunction.apply(
             input_tensor, target, self.region_weights, self.class_weights, self.gamma, self.dice_weight, self.ce_weight,
-            self.batch_dice, ignore)
+            self.batch_dice, self._ignore_value())
         return loss

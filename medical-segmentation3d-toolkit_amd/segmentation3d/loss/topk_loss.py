@@ -59,18 +59,10 @@ class DiceTopKLoss(DiceCELoss):
                  tensor (L, L_region, L_topk), `.last_selection` int64 (n, k, m, n_eq, r) and `.last_threshold` the
                  float32 tau of this call, all written without a synchronisation
         """
-        if input_tensor.dim() < 3 or input_tensor.shape[1] != self.num_class:
-            raise ValueError('input of shape {} does not have num_class = {} channels'.format(tuple(input_tensor.shape),
-                                                                                              self.num_class))
-        if target.numel() * self.num_class != input_tensor.numel():
-            raise ValueError('target shape {} does not match input {}'.format(tuple(target.shape),
-                                                                              tuple(input_tensor.shape)))
-        if self.region_weights.device != input_tensor.device:
-            self.region_weights = self.region_weights.to(input_tensor.device)
-            self.class_weights = self.class_weights.to(input_tensor.device)
-        ignore = -1.0 if self.ignore_label is None else self.ignore_label
+        self._check_shapes(input_tensor, target)
+        self._weights_on(input_tensor.device)
         loss, self.last_terms, self.last_selection, threshold = _ops.TopKLossFunction.apply(
             input_tensor, target, self.region_weights, self.class_weights, self.k_percent, self.dice_weight, self.ce_weight,
-            self.batch_dice, ignore)
+            self.batch_dice, self._ignore_value())
         self.last_threshold = threshold.reshape(())
         return loss

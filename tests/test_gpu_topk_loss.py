@@ -258,10 +258,17 @@ def test_term_weights_and_agreement_with_dicece(hip_device):
 
     ref = dicece(gamma=0.0)
     dice_only = _gpu(dev, p, t, C, ignore_label=255, ce_weight=0.0)
-    assert abs(float(dice_only['terms'][1]) - float(ref[1][1])) < 1e-6
+    assert float(dice_only['terms'][1]) == float(ref[1][1])     # the same forward code: the same number
     assert float(dice_only['loss']) == float(dice_only['terms'][1])
     ref_dice = dicece(ce_weight=0.0)
     assert rel_err(dice_only['grad'], ref_dice[2]) < 1e-6
+    for shape in ((2, 5, 7, 9), (2, 16, 20, 24)):               # the scalar path; the 16-byte path over two workgroups
+        ps, ts = _inputs(SEED, shape, C, **IGNORE)
+        ce = DiceCELoss(C, ignore_label=255)
+        ce(ps.to(dev), ts.to(dev))
+        got = _gpu(dev, ps, ts, C, ignore_label=255, ce_weight=0.0)
+        print('topk_region_vs_dicece', shape, float(got['terms'][1]), float(ce.last_terms[1]))
+        assert np.float32(float(got['terms'][1])).tobytes() == np.float32(float(ce.last_terms[1])).tobytes()
 
     topk_only = _gpu(dev, p, t, C, ignore_label=255, dice_weight=0.0)
     for c in range(C):
