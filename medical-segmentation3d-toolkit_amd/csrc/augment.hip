@@ -13,23 +13,18 @@
 // comes from an fp64 sum reduced in a fixed order (partial pass -> finalize, no atomics): two runs are bit-equal.  fp32
 // arithmetic, no FMA contraction (-ffp-contract=off).  HBM-bound byte movers: one read for the statistics (only with
 // contrast or gamma), one read + one write for the apply pass, 16- / 8-byte rows for M = 4 / 2.
-#include "seg3d_common.h"
+#include "mc_device.h"
 #include "seg3d_hip.h"
-
-#define AUG_STAT_CHUNK 8192
 
 // partial[(m * nblk + blk) * 3 + (0, 1, 2)] = (sum, min, max) of modality m over a chunk of voxels, as doubles
 template <int MC, bool VEC>
 __global__ __launch_bounds__(256) void augment_stats_partial_kernel(const float* __restrict__ crop,
                                                                       double* __restrict__ partial, int Mrt, i64 nv,
                                                                       int nblk) {
-  constexpr int MR = MC > 0 ? MC : 8;
-  const int M = MC > 0 ? MC : Mrt;
+  constexpr int MR = mc_regs<MC>;
+  const int M = mc_width<MC>(Mrt);
   __shared__ double red_s[MR][4];
   __shared__ float red_lo[MR][4], red_hi[MR][4];
-  const i64 e0 = (i64)blockIdx.x * AUG_STAT_CHUNK;
-  i64 e1 = e0 + AUG_STAT_CHUNK;
-  if (e1 > nv) e1 = nv;
   double s[MR];
   float lo[MR], hi[MR];
 #pragma unroll
@@ -38,25 +33,19 @@ __global__ __launch_bounds__(256) void augment_stats_partial_kernel(const float*
     lo[m] = INFINITY;
     hi[m] = -INFINITY;
   }
-  for (i64 e = e0 + threadIdx.x; e < e1; e += 256) {
-    const float* row = crop + e * M;
-    float r[MR];
-    if constexpr (MC > 0) {
-      mc_load_row<MC, VEC>(row, r);
-    } else {
+  mc_chunk_walk<MC, VEC>(
+      nv, M, [&](i64 e) { return crop + e * M; },
+      [&](const float* r) {
 #pragma unroll
-      for (int m = 0; m < MR; ++m) r[m] = m < M ? row[m] : 0.f;
-    }
-#pragma unroll
-    for (int m = 0; m < MR; ++m) {
-      s[m] += (double)r[m];
-      lo[m] = fminf(lo[m], r[m]);
-      hi[m] = fmaxf(hi[m], r[m]);
-    }
-  }
+        for (int m = 0; m < MR; ++m) {
+          s[m] += (double)r[m];
+          lo[m] = fminf(lo[m], r[m]);
+          hi[m] = fmaxf(hi[m], r[m]);
+        }
+      });
+  mc_stat_park(s, red_s, 0);
 #pragma unroll
   for (int m = 0; m < MR; ++m) {
-    s[m] = wave_sum_d(s[m]);
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
       lo[m] = fminf(lo[m], __shfl_down(lo[m], off, 64));
@@ -66,7 +55,6 @@ __global__ __launch_bounds__(256) void augment_stats_partial_kernel(const float*
   if ((threadIdx.x & 63) == 0) {
 #pragma unroll
     for (int m = 0; m < MR; ++m) {
-      red_s[m][threadIdx.x >> 6] = s[m];
       red_lo[m][threadIdx.x >> 6] = lo[m];
       red_hi[m][threadIdx.x >> 6] = hi[m];
     }
@@ -75,7 +63,7 @@ __global__ __launch_bounds__(256) void augment_stats_partial_kernel(const float*
   if (threadIdx.x < M) {
     const int m = threadIdx.x;
     double* out = partial + ((i64)m * nblk + blockIdx.x) * 3;
-    out[0] = red_s[m][0] + red_s[m][1] + red_s[m][2] + red_s[m][3];
+    out[0] = mc_stat_total(red_s[m]);
     out[1] = (double)fminf(fminf(red_lo[m][0], red_lo[m][1]), fminf(red_lo[m][2], red_lo[m][3]));
     out[2] = (double)fmaxf(fmaxf(red_hi[m][0], red_hi[m][1]), fmaxf(red_hi[m][2], red_hi[m][3]));
   }
@@ -164,8 +152,8 @@ __device__ __forceinline__ float augment_value(float x, const Seg3dIntensity& p,
 template <int MC, bool VEC>
 __global__ __launch_bounds__(256) void augment_apply_kernel(float* crop, const float* __restrict__ stats, int Mrt, i64 nv,
                                                               Seg3dIntensityParams prm) {
-  constexpr int MR = MC > 0 ? MC : 8;
-  const int M = MC > 0 ? MC : Mrt;
+  constexpr int MR = mc_regs<MC>;
+  const int M = mc_width<MC>(Mrt);
   float mn[MR], mx[MR], mean[MR];
 #pragma unroll
   for (int m = 0; m < MR; ++m) {
@@ -176,13 +164,13 @@ __global__ __launch_bounds__(256) void augment_apply_kernel(float* crop, const f
   }
   for (i64 v = (i64)blockIdx.x * 256 + threadIdx.x; v < nv; v += (i64)gridDim.x * 256) {
     float* row = crop + v * M;
-    float r[MR];
     if constexpr (MC > 0) {
+      float r[MC];
       mc_load_row<MC, VEC>(row, r);
 #pragma unroll
       for (int m = 0; m < MC; ++m) r[m] = augment_value(r[m], prm.m[m], mn[m], mx[m], mean[m], v, m, prm.seed_lo, prm.seed_hi);
       mc_store_row<MC, VEC>(row, r);
-    } else {
+    } else {   // the runtime width goes channel by channel, in place: held as a row the eight values cost 8 more registers
 #pragma unroll
       for (int m = 0; m < MR; ++m)
         if (m < M) row[m] = augment_value(row[m], prm.m[m], mn[m], mx[m], mean[m], v, m, prm.seed_lo, prm.seed_hi);
@@ -190,7 +178,7 @@ __global__ __launch_bounds__(256) void augment_apply_kernel(float* crop, const f
   }
 }
 
-static long long augment_stat_blocks(long long nv) { return (nv + AUG_STAT_CHUNK - 1) / AUG_STAT_CHUNK; }
+static long long augment_stat_blocks(long long nv) { return (nv + MC_STAT_CHUNK - 1) / MC_STAT_CHUNK; }
 
 // doubles of workspace for seg3d_augment_intensity: M * blocks * 3 partials + the M * 3 float32 statistics behind them
 extern "C" long long seg3d_augment_intensity_workspace_doubles(int X, int Y, int Z, int M) {
@@ -235,22 +223,7 @@ extern "C" int seg3d_augment_intensity(float* crop, double* workspace, int X, in
   float* stats = need_stats ? reinterpret_cast<float*>(workspace + (i64)M * nblk * 3) : nullptr;
   const int grid = grid_blocks > 0 ? grid_blocks : seg3d_ew_grid(nv, 256);
   hipStream_t s = (hipStream_t)stream;
-  const bool vec4 = M == 4 && ((uintptr_t)crop & 15) == 0;
-  const bool vec2 = M == 2 && ((uintptr_t)crop & 7) == 0;
-  if (vec4)
-    augment_launch<4, true>(crop, workspace, stats, M, nv, nblk, need_stats, params, grid, s);
-  else if (M == 4)
-    augment_launch<4, false>(crop, workspace, stats, M, nv, nblk, need_stats, params, grid, s);
-  else if (vec2)
-    augment_launch<2, true>(crop, workspace, stats, M, nv, nblk, need_stats, params, grid, s);
-  else if (M == 2)
-    augment_launch<2, false>(crop, workspace, stats, M, nv, nblk, need_stats, params, grid, s);
-  else if (M == 1)
-    augment_launch<1, false>(crop, workspace, stats, M, nv, nblk, need_stats, params, grid, s);
-  else if (M == 3)
-    augment_launch<3, false>(crop, workspace, stats, M, nv, nblk, need_stats, params, grid, s);
-  else
-    augment_launch<0, false>(crop, workspace, stats, M, nv, nblk, need_stats, params, grid, s);
+  MC_DISPATCH(augment_launch, M, mc_vec_rows(M, crop), (crop, workspace, stats, M, nv, nblk, need_stats, params, grid, s));
   SEG3D_LAUNCH_CHECK("seg3d_augment_intensity");
   return SEG3D_OK;
 }

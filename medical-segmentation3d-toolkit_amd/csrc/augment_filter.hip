@@ -21,7 +21,7 @@
 //   per modality the workgroup gathers the patch of low-grid voxels its tile needs (at most 11 x 11 x 35, each read from its
 //   source voxel) into LDS and up-samples it there along x, y and z; per-axis patch offsets, tap bases and weights are
 //   integer arithmetic done once per tile.  A modality whose three sizes equal the crop's is copied.
-#include "seg3d_common.h"
+#include "mc_device.h"
 #include "seg3d_hip.h"
 
 #define FLT_TX 32
@@ -224,8 +224,8 @@ template <int MC, bool VEC>
 __global__ __launch_bounds__(256) void augment_lowres_kernel(const float* __restrict__ src, float* __restrict__ dst, int X,
                                                                int Y, int Z, int Mrt, int tiles_x, int tiles_y,
                                                                Seg3dLowresParams prm) {
-  constexpr int MR = MC > 0 ? MC : 8;
-  const int M = MC > 0 ? MC : Mrt;
+  constexpr int MR = mc_regs<MC>;
+  const int M = mc_width<MC>(Mrt);
   __shared__ float A[LR_PZ * LR_PY * LR_PX];         // the low-grid patch [nzp][nyp][nxp]; then [nzp][TY][TX] after the y pass
   __shared__ float B[LR_PZ * LR_PY * FLT_TX];        // [nzp][nyp][TX] after the x pass
   __shared__ float WX[FLT_TX][4], WY[FLT_TY][4], WZ[FLT_TZ][4];
@@ -283,17 +283,8 @@ __global__ __launch_bounds__(256) void augment_lowres_kernel(const float* __rest
   }
   if (x0 + x >= X || y0 + y >= Y) return;
 #pragma unroll
-  for (int o = 0; o < FLT_TZ; ++o) {
-    if (z0 + o >= Z) continue;
-    float* row = dst + (v0 + (i64)o * Y * X) * M;
-    if constexpr (MC > 0) {
-      mc_store_row<MC, VEC>(row, out[o]);
-    } else {
-#pragma unroll
-      for (int m = 0; m < MR; ++m)
-        if (m < M) row[m] = out[o][m];
-    }
-  }
+  for (int o = 0; o < FLT_TZ; ++o)
+    if (z0 + o < Z) mc_store_row<MC, VEC>(dst + (v0 + (i64)o * Y * X) * M, out[o], M);
 }
 
 // every modality off: dst = src, 16 bytes per thread where both bases allow it
@@ -355,12 +346,12 @@ extern "C" int seg3d_augment_blur(const float* src, float* dst, int X, int Y, in
   }
   hipStream_t s = (hipStream_t)stream;
   int rc = SEG3D_OK;
-  const uintptr_t both = (uintptr_t)src | (uintptr_t)dst;
+  const bool vec = mc_vec_rows(M, src, dst);
   if (R == 0)
     filter_copy(src, dst, (i64)X * Y * Z * M, s);
-  else if (M == 4 && (both & 15) == 0)
+  else if (vec && M == 4)
     rc = blur_launch<4, true>(src, dst, X, Y, Z, M, R, params, s);
-  else if (M == 2 && (both & 7) == 0)
+  else if (vec)
     rc = blur_launch<2, true>(src, dst, X, Y, Z, M, R, params, s);
   else
     rc = blur_launch<1, false>(src, dst, X, Y, Z, M, R, params, s);
@@ -373,7 +364,8 @@ template <int MC, bool VEC>
 static void lowres_launch(const float* src, float* dst, int X, int Y, int Z, int M, const Seg3dLowresParams& prm,
                           hipStream_t s) {
   const int ntx = seg3d_cdiv(X, FLT_TX), nty = seg3d_cdiv(Y, FLT_TY), ntz = seg3d_cdiv(Z, FLT_TZ);
-  hipLaunchKernelGGL((augment_lowres_kernel<MC, VEC>), dim3((unsigned)(ntx * nty * ntz)), dim3(256), 0, s, src, dst, X, Y, Z, M,
+  constexpr int KC = MC == 3 ? 0 : MC;   // there is no <3> instantiation: M = 3 runs the runtime width
+  hipLaunchKernelGGL((augment_lowres_kernel<KC, VEC>), dim3((unsigned)(ntx * nty * ntz)), dim3(256), 0, s, src, dst, X, Y, Z, M,
                      ntx, nty, prm);
 }
 
@@ -390,17 +382,10 @@ extern "C" int seg3d_augment_lowres(const float* src, float* dst, int X, int Y, 
     any = any || params.nx[m] != X || params.ny[m] != Y || params.nz[m] != Z;
   }
   hipStream_t s = (hipStream_t)stream;
-  const uintptr_t d = (uintptr_t)dst;
   if (!any)
     filter_copy(src, dst, (i64)X * Y * Z * M, s);
-  else if (M == 4)
-    (d & 15) == 0 ? lowres_launch<4, true>(src, dst, X, Y, Z, M, params, s) : lowres_launch<4, false>(src, dst, X, Y, Z, M, params, s);
-  else if (M == 2)
-    (d & 7) == 0 ? lowres_launch<2, true>(src, dst, X, Y, Z, M, params, s) : lowres_launch<2, false>(src, dst, X, Y, Z, M, params, s);
-  else if (M == 1)
-    lowres_launch<1, false>(src, dst, X, Y, Z, M, params, s);
-  else
-    lowres_launch<0, false>(src, dst, X, Y, Z, M, params, s);
+  else   // only the stores are rows: the sources are gathered voxel by voxel
+    MC_DISPATCH(lowres_launch, M, mc_vec_rows(M, dst), (src, dst, X, Y, Z, M, params, s));
   SEG3D_LAUNCH_CHECK("seg3d_augment_lowres");
   return SEG3D_OK;
 }

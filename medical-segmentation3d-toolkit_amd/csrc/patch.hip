@@ -11,9 +11,8 @@
 // Voxel (x, y, z) of a volume with size (X, Y, Z) lives at [z][y][x] (utils/image_tools.py:448,465).
 // All kernels are HBM-bound byte movers over fp32 / int8 data.
 #include "seg3d_imagegrid.h"
+#include "mc_device.h"
 #include "seg3d_hip.h"
-
-#define PATCH_STAT_CHUNK 8192
 
 // SEG3D_LAUNCH_CHECK for a launch chain entered under several names: "<entry><stage>: kernel launch failed: ..."
 #define PATCH_LAUNCH_CHECK(name, stage)                                                           \
@@ -48,7 +47,7 @@ __global__ __launch_bounds__(64) void patch_stats_finalize_kernel(const double* 
 }
 
 extern "C" long long seg3d_patch_stats_blocks(int bx, int by, int bz) {
-  return ((long long)bx * by * bz + PATCH_STAT_CHUNK - 1) / PATCH_STAT_CHUNK;
+  return ((long long)bx * by * bz + MC_STAT_CHUNK - 1) / MC_STAT_CHUNK;
 }
 
 // ---- gather: M co-registered modalities in one launch chain (dataset.py:199-203 crops and normalises a list of images
@@ -58,7 +57,7 @@ extern "C" long long seg3d_patch_stats_blocks(int bx, int by, int bz) {
 // per (patch, modality) and do not depend on M, so channel m of an M-modality gather is bit-identical to the M = 1 gather
 // of plane m with normaliser m.  A single-modality volume [Z][Y][X] is the M = 1 case of the same memory, and so is its
 // batch [P][1][bz][by][bx]: seg3d_patch_gather_normalize(_flip) are the M = 1 entries.
-// MC = 1, 2, 3, 4: compile-time width (VEC: 8- / 16-byte rows); MC = 0: runtime M <= 8.
+// <MC, VEC>: the row width of the instantiation, mc_device.h.
 
 // partial[(p * M + m)][blk][2] = (sum, sum of squares) in fp64 of modality m over a chunk of patch p's voxels
 template <int MC, bool VEC>
@@ -66,55 +65,38 @@ __global__ __launch_bounds__(256) void patch_stats_partial_mc_kernel(const float
                                                                        const int* __restrict__ starts,
                                                                        double* __restrict__ partial, int Mrt, int Y, int X,
                                                                        int bx, int by, int bz, int nblk) {
-  constexpr int MR = MC > 0 ? MC : 8;
-  const int M = MC > 0 ? MC : Mrt;
+  constexpr int MR = mc_regs<MC>;
+  const int M = mc_width<MC>(Mrt);
   __shared__ double red[MR][8];
   const int p = blockIdx.y;
   const int sx = starts[3 * p], sy = starts[3 * p + 1], sz = starts[3 * p + 2];
-  const i64 nv = (i64)bx * by * bz;
-  const i64 e0 = (i64)blockIdx.x * PATCH_STAT_CHUNK;
-  i64 e1 = e0 + PATCH_STAT_CHUNK;
-  if (e1 > nv) e1 = nv;
   double s[MR], ss[MR];
 #pragma unroll
   for (int m = 0; m < MR; ++m) s[m] = ss[m] = 0.0;
-  for (i64 e = e0 + threadIdx.x; e < e1; e += 256) {
-    const int lx = (int)(e % bx);
-    const i64 t = e / bx;
-    const int ly = (int)(t % by), lz = (int)(t / by);
-    const float* row = vol + (((i64)(sz + lz) * Y + (sy + ly)) * X + (sx + lx)) * M;
-    float r[MR];
-    if constexpr (MC > 0) {
-      mc_load_row<MC, VEC>(row, r);
-    } else {
+  mc_chunk_walk<MC, VEC>(
+      (i64)bx * by * bz, M,
+      [&](i64 e) {
+        const int lx = (int)(e % bx);
+        const i64 t = e / bx;
+        const int ly = (int)(t % by), lz = (int)(t / by);
+        return vol + (((i64)(sz + lz) * Y + (sy + ly)) * X + (sx + lx)) * M;
+      },
+      [&](const float* r) {
 #pragma unroll
-      for (int m = 0; m < MR; ++m) r[m] = m < M ? row[m] : 0.f;
-    }
-#pragma unroll
-    for (int m = 0; m < MR; ++m) {
-      const double v = (double)r[m];
-      s[m] += v;
-      ss[m] += v * v;
-    }
-  }
-#pragma unroll
-  for (int m = 0; m < MR; ++m) {
-    s[m] = wave_sum_d(s[m]);
-    ss[m] = wave_sum_d(ss[m]);
-  }
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int m = 0; m < MR; ++m) {
-      red[m][threadIdx.x >> 6] = s[m];
-      red[m][4 + (threadIdx.x >> 6)] = ss[m];
-    }
-  }
+        for (int m = 0; m < MR; ++m) {
+          const double v = (double)r[m];
+          s[m] += v;
+          ss[m] += v * v;
+        }
+      });
+  mc_stat_park(s, red, 0);
+  mc_stat_park(ss, red, 4);
   __syncthreads();
   if (threadIdx.x < M) {
     const int m = threadIdx.x;
     const i64 row = ((i64)p * M + m) * nblk + blockIdx.x;
-    partial[row * 2 + 0] = red[m][0] + red[m][1] + red[m][2] + red[m][3];
-    partial[row * 2 + 1] = red[m][4] + red[m][5] + red[m][6] + red[m][7];
+    partial[row * 2 + 0] = mc_stat_total(red[m]);
+    partial[row * 2 + 1] = mc_stat_total(red[m] + 4);
   }
 }
 
@@ -127,8 +109,8 @@ __global__ __launch_bounds__(256) void patch_gather_normalize_mc_kernel(const fl
                                                                           const float* __restrict__ mean_std, float* batch, int Mrt, int Y, int X,
                                                                           int bx, int by, int bz, int P,
                                                                           Seg3dNormalizers nrm, int flip) {
-  constexpr int MR = MC > 0 ? MC : 8;
-  const int M = MC > 0 ? MC : Mrt;
+  constexpr int MR = mc_regs<MC>;
+  const int M = mc_width<MC>(Mrt);
   const i64 nv = (i64)bx * by * bz;
   const i64 total = nv * P;
   for (i64 idx = (i64)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (i64)gridDim.x * 256) {
@@ -145,12 +127,7 @@ __global__ __launch_bounds__(256) void patch_gather_normalize_mc_kernel(const fl
     const int sx = starts[3 * p], sy = starts[3 * p + 1], sz = starts[3 * p + 2];
     const float* row = vol + (((i64)(sz + lz) * Y + (sy + ly)) * X + (sx + lx)) * M;
     float r[MR];
-    if constexpr (MC > 0) {
-      mc_load_row<MC, VEC>(row, r);
-    } else {
-#pragma unroll
-      for (int m = 0; m < MR; ++m) r[m] = m < M ? row[m] : 0.f;
-    }
+    mc_load_row<MC, VEC>(row, r, M, 0.f);
 #pragma unroll
     for (int m = 0; m < MR; ++m) {
       const Seg3dNormalizer& n = nrm.n[m];
@@ -164,14 +141,7 @@ __global__ __launch_bounds__(256) void patch_gather_normalize_mc_kernel(const fl
       }
       r[m] = v;
     }
-    float* q = batch + idx * M;
-    if constexpr (MC > 0) {
-      mc_store_row<MC, VEC>(q, r);
-    } else {
-#pragma unroll
-      for (int m = 0; m < MR; ++m)
-        if (m < M) q[m] = r[m];
-    }
+    mc_store_row<MC, VEC>(batch + idx * M, r, M);
   }
 }
 
@@ -247,15 +217,8 @@ static int patch_gather_normalize_mc_impl(const char* name, const float* volume,
   }
   SEG3D_REQUIRE(!any_adaptive || (workspace && mean_std), "%s: adaptive normaliser needs workspace and mean_std", name);
   hipStream_t s = (hipStream_t)stream;
-  const bool vec4 = M == 4 && ((uintptr_t)volume & 15) == 0 && ((uintptr_t)batch & 15) == 0;
-  const bool vec2 = M == 2 && ((uintptr_t)volume & 7) == 0 && ((uintptr_t)batch & 7) == 0;
-  if (M == 1) return patch_gather_normalize_mc_launch<1, false>(name, volume, starts, batch, workspace, mean_std, M, Y, X, bx, by, bz, P, nrm, any_adaptive, flip, s);
-  if (vec4) return patch_gather_normalize_mc_launch<4, true>(name, volume, starts, batch, workspace, mean_std, M, Y, X, bx, by, bz, P, nrm, any_adaptive, flip, s);
-  if (M == 4) return patch_gather_normalize_mc_launch<4, false>(name, volume, starts, batch, workspace, mean_std, M, Y, X, bx, by, bz, P, nrm, any_adaptive, flip, s);
-  if (vec2) return patch_gather_normalize_mc_launch<2, true>(name, volume, starts, batch, workspace, mean_std, M, Y, X, bx, by, bz, P, nrm, any_adaptive, flip, s);
-  if (M == 2) return patch_gather_normalize_mc_launch<2, false>(name, volume, starts, batch, workspace, mean_std, M, Y, X, bx, by, bz, P, nrm, any_adaptive, flip, s);
-  if (M == 3) return patch_gather_normalize_mc_launch<3, false>(name, volume, starts, batch, workspace, mean_std, M, Y, X, bx, by, bz, P, nrm, any_adaptive, flip, s);
-  return patch_gather_normalize_mc_launch<0, false>(name, volume, starts, batch, workspace, mean_std, M, Y, X, bx, by, bz, P, nrm, any_adaptive, flip, s);
+  MC_DISPATCH(return patch_gather_normalize_mc_launch, M, mc_vec_rows(M, volume, batch),
+              (name, volume, starts, batch, workspace, mean_std, M, Y, X, bx, by, bz, P, nrm, any_adaptive, flip, s));
 }
 
 extern "C" int seg3d_patch_gather_normalize_mc(const float* volume, const int* starts, float* batch, double* workspace,

@@ -13,6 +13,7 @@
 //   voxel in raster order -- the labels here are the component's smallest linear index, which gives the same order.
 // All kernels are HBM-bound byte movers / integer work.
 #include "seg3d_imagegrid.h"
+#include "mc_device.h"
 #include "seg3d_hip.h"
 
 // ---- elastic deformation of the sampled point (training augmentation) ----------------------
@@ -141,14 +142,14 @@ static int deform_args(const char* name, int Xo, int Yo, int Zo, const double* l
 // taps is one contiguous M-float row.  Per channel the arithmetic is in double with one fixed operation order, clamping and
 // padding whatever M is, so channel m of an M-channel launch equals the M = 1 launch on plane m bit for bit.  A single volume [Zi][Yi][Xi] is the M = 1, dst_stride = 1 case of the same memory:
 // seg3d_resample_affine / seg3d_resample_deform are those entries.
-// MC = 1, 2, 3, 4: compile-time width (VEC: the rows are 8- / 16-byte aligned); MC = 0: runtime M <= 8.
+// <MC, VEC>: the row width of the instantiation, mc_device.h.
 template <int MC, bool VEC, bool DEFORM>
 __global__ __launch_bounds__(256) void resample_affine_mc_kernel(const float* __restrict__ src, float* __restrict__ dst,
                                                                    int Mrt, i64 dst_stride, int Xi, int Yi, int Zi, int Xo,
                                                                    int Yo, int Zo, Affine12 A, int linear, float pad,
                                                                    DeformArgs<DEFORM> dfm) {
-  constexpr int MR = MC > 0 ? MC : 8;          // register rows: MC, or the generic path's bound
-  const int M = MC > 0 ? MC : Mrt;
+  constexpr int MR = mc_regs<MC>;
+  const int M = mc_width<MC>(Mrt);
   extern __shared__ double deform_smem[];
   DeformLds lds;
   if constexpr (DEFORM) lds = deform_stage(deform_smem, dfm, Xo, Yo, Zo);
@@ -185,7 +186,7 @@ __global__ __launch_bounds__(256) void resample_affine_mc_kernel(const float* __
 #pragma unroll
           for (int m = 0; m < MC; ++m)
             out[m] = trilinear_lerp(t000[m], t100[m], t010[m], t110[m], t001[m], t101[m], t011[m], t111[m], dx, dy, dz);
-        } else {
+        } else {   // the runtime width reads the eight rows channel by channel: as rows they would hold 64 registers
 #pragma unroll
           for (int m = 0; m < MR; ++m)
             if (m < M)
@@ -196,57 +197,21 @@ __global__ __launch_bounds__(256) void resample_affine_mc_kernel(const float* __
         xn = xn < 0 ? 0 : (xn >= Xi ? Xi - 1 : xn);
         yn = yn < 0 ? 0 : (yn >= Yi ? Yi - 1 : yn);
         zn = zn < 0 ? 0 : (zn >= Zi ? Zi - 1 : zn);
-        const float* p = src + (((i64)zn * Yi + yn) * Xi + xn) * M;
-        if constexpr (MC > 0) {
-          mc_load_row<MC, VEC>(p, out);
-        } else {
-#pragma unroll
-          for (int m = 0; m < MR; ++m)
-            if (m < M) out[m] = p[m];
-        }
+        mc_load_row<MC, VEC>(src + (((i64)zn * Yi + yn) * Xi + xn) * M, out, M, pad);
       }
     }
-    float* q = dst + idx * dst_stride;
-    if constexpr (MC > 0) {
-      mc_store_row<MC, VEC>(q, out);
-    } else {
-#pragma unroll
-      for (int m = 0; m < MR; ++m)
-        if (m < M) q[m] = out[m];
-    }
+    mc_store_row<MC, VEC>(dst + idx * dst_stride, out, M);
   }
 }
 
-template <bool DEFORM>
+// MC_DISPATCH's callee: DEFORM comes from the argument.  Vector rows need the source base, the destination base and the
+// destination stride aligned to the row width.
+template <int MC, bool VEC, bool DEFORM>
 static void resample_mc_launch(const float* src, float* dst, int M, i64 dst_stride, int Xi, int Yi, int Zi, int Xo, int Yo,
                                int Zo, const Affine12& A, int lin, float pad, const DeformArgs<DEFORM>& D, size_t lds,
                                hipStream_t s) {
-  const i64 total = (i64)Xo * Yo * Zo;
-  const dim3 grid(seg3d_ew_grid(total, 256)), block(256);
-  // vector rows need the source base / destination base and stride aligned to the row width
-  const bool vec4 = M == 4 && ((uintptr_t)src & 15) == 0 && ((uintptr_t)dst & 15) == 0 && dst_stride % 4 == 0;
-  const bool vec2 = M == 2 && ((uintptr_t)src & 7) == 0 && ((uintptr_t)dst & 7) == 0 && dst_stride % 2 == 0;
-  if (M == 1)
-    hipLaunchKernelGGL((resample_affine_mc_kernel<1, false, DEFORM>), grid, block, lds, s, src, dst, M, dst_stride, Xi, Yi,
-                       Zi, Xo, Yo, Zo, A, lin, pad, D);
-  else if (vec4)
-    hipLaunchKernelGGL((resample_affine_mc_kernel<4, true, DEFORM>), grid, block, lds, s, src, dst, M, dst_stride, Xi, Yi, Zi,
-                       Xo, Yo, Zo, A, lin, pad, D);
-  else if (M == 4)
-    hipLaunchKernelGGL((resample_affine_mc_kernel<4, false, DEFORM>), grid, block, lds, s, src, dst, M, dst_stride, Xi, Yi,
-                       Zi, Xo, Yo, Zo, A, lin, pad, D);
-  else if (vec2)
-    hipLaunchKernelGGL((resample_affine_mc_kernel<2, true, DEFORM>), grid, block, lds, s, src, dst, M, dst_stride, Xi, Yi, Zi,
-                       Xo, Yo, Zo, A, lin, pad, D);
-  else if (M == 2)
-    hipLaunchKernelGGL((resample_affine_mc_kernel<2, false, DEFORM>), grid, block, lds, s, src, dst, M, dst_stride, Xi, Yi,
-                       Zi, Xo, Yo, Zo, A, lin, pad, D);
-  else if (M == 3)
-    hipLaunchKernelGGL((resample_affine_mc_kernel<3, false, DEFORM>), grid, block, lds, s, src, dst, M, dst_stride, Xi, Yi,
-                       Zi, Xo, Yo, Zo, A, lin, pad, D);
-  else
-    hipLaunchKernelGGL((resample_affine_mc_kernel<0, false, DEFORM>), grid, block, lds, s, src, dst, M, dst_stride, Xi, Yi,
-                       Zi, Xo, Yo, Zo, A, lin, pad, D);
+  hipLaunchKernelGGL((resample_affine_mc_kernel<MC, VEC, DEFORM>), dim3(seg3d_ew_grid((i64)Xo * Yo * Zo, 256)), dim3(256), lds,
+                     s, src, dst, M, dst_stride, Xi, Yi, Zi, Xo, Yo, Zo, A, lin, pad, D);
 }
 
 // the four entries' common checks and the by-value affine argument
@@ -265,8 +230,9 @@ static int resample_affine(const char* name, const float* src, float* dst, int M
   Affine12 A;
   const int rc = resample_args(name, src, dst, M, dst_stride, Xi, Yi, Zi, Xo, Yo, Zo, affine_host, &A);
   if (rc != SEG3D_OK) return rc;
-  resample_mc_launch<false>(src, dst, M, (i64)dst_stride, Xi, Yi, Zi, Xo, Yo, Zo, A, linear ? 1 : 0, pad, DeformArgs<false>(),
-                            0, (hipStream_t)stream);
+  MC_DISPATCH(resample_mc_launch, M, mc_vec_rows(M, src, dst, dst_stride),
+              (src, dst, M, (i64)dst_stride, Xi, Yi, Zi, Xo, Yo, Zo, A, linear ? 1 : 0, pad, DeformArgs<false>(), 0,
+               (hipStream_t)stream));
   SEG3D_LAUNCH_CHECK(name);
   return SEG3D_OK;
 }
@@ -281,8 +247,9 @@ static int resample_deform(const char* name, const float* src, float* dst, int M
   DeformArgs<true> D;
   rc = deform_args(name, Xo, Yo, Zo, l_host, ctrl, gx, gy, gz, t_host, mirror_mask, &D);
   if (rc != SEG3D_OK) return rc;
-  resample_mc_launch<true>(src, dst, M, (i64)dst_stride, Xi, Yi, Zi, Xo, Yo, Zo, A, linear ? 1 : 0, pad, D,
-                           deform_lds_bytes(Xo, Yo, Zo, D.g), (hipStream_t)stream);
+  MC_DISPATCH(resample_mc_launch, M, mc_vec_rows(M, src, dst, dst_stride),
+              (src, dst, M, (i64)dst_stride, Xi, Yi, Zi, Xo, Yo, Zo, A, linear ? 1 : 0, pad, D,
+               deform_lds_bytes(Xo, Yo, Zo, D.g), (hipStream_t)stream));
   SEG3D_LAUNCH_CHECK(name);
   return SEG3D_OK;
 }

@@ -202,31 +202,4 @@ __device__ __forceinline__ void block_sum_256(float (&v)[NV], float* red) {
     for (int k = 0; k < NV; ++k) v[k] = red[k] + red[NV + k] + red[2 * NV + k] + red[3 * NV + k];
   }
 }
-
-// ---- channels-last voxel rows of MC floats (multi-modality volumes [Z][Y][X][M], patches.hip / postproc.hip) ---------
-// VEC and MC = 4 / 2: one 16- / 8-byte access (the caller guarantees the alignment); otherwise MC scalar accesses.
-template <int MC, bool VEC>
-__device__ __forceinline__ void mc_load_row(const float* p, float* v) {
-  if constexpr (VEC && MC == 4) {
-    const float4 t = *reinterpret_cast<const float4*>(p);
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-  } else if constexpr (VEC && MC == 2) {
-    const float2 t = *reinterpret_cast<const float2*>(p);
-    v[0] = t.x; v[1] = t.y;
-  } else {
-#pragma unroll
-    for (int m = 0; m < MC; ++m) v[m] = p[m];
-  }
-}
-template <int MC, bool VEC>
-__device__ __forceinline__ void mc_store_row(float* p, const float* v) {
-  if constexpr (VEC && MC == 4) {
-    *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-  } else if constexpr (VEC && MC == 2) {
-    *reinterpret_cast<float2*>(p) = make_float2(v[0], v[1]);
-  } else {
-#pragma unroll
-    for (int m = 0; m < MC; ++m) p[m] = v[m];
-  }
-}
 #endif

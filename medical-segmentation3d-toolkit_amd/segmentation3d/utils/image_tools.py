@@ -485,6 +485,17 @@ def normalize_crop_device_mc(crop, params, out=None):
     return out
 
 
+def _crop_modalities(crop):
+    """M of a training crop handed to the intensity, blur and low-resolution passes: contiguous float32 [z, y, x] (M = 1)
+    or channels-last [z, y, x, M], 1 <= M <= 8"""
+    if crop.dtype != torch.float32 or crop.dim() not in (3, 4) or not crop.is_contiguous():
+        raise ValueError('crop must be a contiguous float32 [z, y, x] or [z, y, x, M] tensor')
+    M = 1 if crop.dim() == 3 else int(crop.shape[3])
+    if not 1 <= M <= 8:
+        raise ValueError('{} modalities, 1..8 are supported'.format(M))
+    return M
+
+
 INTENSITY_NEUTRAL = {'brightness': 1.0, 'contrast': 1.0, 'gamma': 1.0, 'invert': False, 'sigma': 0.0}
 
 
@@ -523,11 +534,7 @@ def augment_intensity_device(crop, params, seed=0, grid_blocks=0):
     keys are neutral and a neutral transform is skipped exactly -- or a ready E.IntensityParams.  seed: the noise's 64-bit
     Philox key; the noise of a voxel depends on (seed, voxel index, modality) alone.  Returns `crop`."""
     E.require_device(crop)
-    if crop.dtype != torch.float32 or crop.dim() not in (3, 4) or not crop.is_contiguous():
-        raise ValueError('crop must be a contiguous float32 [z, y, x] or [z, y, x, M] tensor')
-    M = 1 if crop.dim() == 3 else int(crop.shape[3])
-    if not 1 <= M <= 8:
-        raise ValueError('{} modalities, 1..8 are supported'.format(M))
+    M = _crop_modalities(crop)
     Z, Y, X = (int(v) for v in crop.shape[:3])
     prm = params if isinstance(params, E.IntensityParams) else intensity_params(params, M, seed)
     need_stats = any(prm.m[m].contrast != 1.0 or prm.m[m].gamma != 1.0 for m in range(M))
@@ -606,11 +613,7 @@ def lowres_params(sizes, num_modality, crop_size=None):
 
 def _filter_buffers(crop, out):
     E.require_device(crop, out)
-    if crop.dtype != torch.float32 or crop.dim() not in (3, 4) or not crop.is_contiguous():
-        raise ValueError('crop must be a contiguous float32 [z, y, x] or [z, y, x, M] tensor')
-    M = 1 if crop.dim() == 3 else int(crop.shape[3])
-    if not 1 <= M <= 8:
-        raise ValueError('{} modalities, 1..8 are supported'.format(M))
+    M = _crop_modalities(crop)
     if out is None:
         out = torch.empty_like(crop)
     else:
