@@ -501,6 +501,52 @@ int seg3d_boundary_loss_fwd(const float* probs, const float* target, const float
 int seg3d_boundary_loss_bwd(const float* target, const float* phi, const float* coef, const float* gout, float* dprobs, int N,
                             int C, long long S, int include_background, int batch_dice, float ignore_label, void* stream);
 
+/* ---- soft-clDice topology loss (Shit et al., CVPR 2021; no counterpart in the reference) ----
+ * Soft skeleton of `planes` fp32 volumes [planes][Z][Y][X] with `iters` = k iterations.  Nothing exists outside the volume:
+ *   E(x)(v) = min of x over v and its 6 face neighbours inside the volume,
+ *   D(x)(v) = max of x over the 3x3x3 neighbourhood inside the volume,  O(x) = D(E(x)),
+ *   x_0 = x, s_0 = relu(x_0 - O(x_0));  for j = 1..k:  x_j = E(x_{j-1}),  d_j = relu(x_j - O(x_j)),
+ *   s_j = s_{j-1} + relu(d_j - s_{j-1} d_j);  skel = s_k  -- the published soft_skel.
+ * One launch per stage (k + 1 in all): a 32 x 8 x 8 tile with a halo of 2 is staged in LDS, E and D come from there.  Every
+ * stage is a selection or one fp32 operation per voxel, so a 0 / 1 volume gives an exact 0 / 1 skeleton.
+ * 1 <= iters <= 16, every axis in [1, 256], planes <= 65535, planes * X * Y * Z < 2^31, x != skel; anything else is an error.
+ * workspace: seg3d_soft_skeleton_workspace_bytes(planes, X, Y, Z) bytes (two planes' worth of x_j), 4-byte aligned, free
+ * after the call.  Allocates nothing, synchronises nothing, reads nothing back: it can be captured into a hipGraph. */
+long long seg3d_soft_skeleton_workspace_bytes(long long planes, int X, int Y, int Z);
+int seg3d_soft_skeleton(const float* x, float* skel, void* workspace, long long planes, int X, int Y, int Z, int iters,
+                        void* stream);
+/* Soft Dice + soft-clDice on probabilities [N][C][Z][Y][X] (fp32, 1 <= C <= 16) and a float class-id target [N][Z][Y][X].
+ * m(v) = 1 on counted voxels (the compound loss's rule with ignore_label), 0 elsewhere; for sample n and class
+ * c = class_ids.id[k], k < K (distinct ids in [0, C)):  P_c = m p_c,  T_c = m [(int)t == c],
+ *   SP = skel(P_c), ST = skel(T_c),  Tprec = (sum SP T_c + 1) / (sum SP + 1),  Tsens = (sum ST P_c + 1) / (sum ST + 1),
+ *   cl[n][k] = 2 Tprec Tsens / (Tprec + Tsens),  L_cl = sum_k wcl[k] (1 - mean_n cl[n][k])   (batch_dice: the four sums are
+ *   summed over n before the ratios),  L = dice_weight * L_dice + cldice_weight * L_cl,
+ *   L_dice = exactly the compound loss's soft-Dice term (wdice, batch_dice, eps = 1e-5), from the same device code and the
+ *   same order of additions: bit-equal to seg3d_compound_loss_fwd's loss[1] on the same inputs.
+ * wdice: the region weights normalised over the included classes (0 for an excluded background); wcl: K weights normalised
+ * over the class list.  Term weights >= 0, not both 0; a term whose weight is 0 never enters L (L_cl is still reported).
+ * A voxel that does not count is background for both skeletons, enters no sum and gets a zero gradient.
+ * Gradient: relu' is 1 for a positive argument, 0 otherwise; a min or max that several positions attain sends its gradient
+ * to the one with the lowest linear index (z, then y, then x).  The backward is in gather form -- every voxel collects
+ * from the neighbours whose stored selection byte points at it -- in fixed order: no atomics, two runs are bit-equal.
+ * Sums: fp32 partials with one slot per workgroup, then a one-workgroup fp64 finalize in fixed order.
+ * Limits as for seg3d_soft_skeleton, 1 <= K <= 16, N * K <= 65535, N * X * Y * Z < 2^31.
+ * workspace: seg3d_cldice_loss_workspace_bytes(N, C, K, X, Y, Z, iters) bytes, 16-byte aligned; it holds what the backward
+ * needs (ST, and per stage and voxel one selection byte and two floats), so the SAME buffer goes to the backward untouched.
+ * coef: 2 * R * C + 3 * R * K floats kept for the backward, R = batch_dice ? 1 : N -- the compound loss's (A, B) pairs, then
+ * per (r, k) the three factors of the cl term;  loss: 3 floats (L, L_dice, L_cl). */
+long long seg3d_cldice_loss_workspace_bytes(int N, int C, int K, int X, int Y, int Z, int iters);
+int seg3d_cldice_loss_fwd(const float* probs, const float* target, const float* wdice, const float* wcl, void* workspace,
+                          float* coef, float* loss, int N, int C, int X, int Y, int Z, Seg3dClassList class_ids, int K,
+                          int iters, float dice_weight, float cldice_weight, int batch_dice, float ignore_label,
+                          void* stream);
+/* dprobs[n][c][s] = gout[0] * dL/dp[n][c][s] on counted voxels, zeros on voxels that do not count: k + 1 gather passes back
+ * through the prediction's skeleton (none when cldice_weight is 0), then all C planes in one pass.  Same arguments as the
+ * forward call whose workspace and coef it gets. */
+int seg3d_cldice_loss_bwd(const float* target, void* workspace, const float* coef, const float* gout, float* dprobs, int N,
+                          int C, int X, int Y, int Z, Seg3dClassList class_ids, int K, int iters, float cldice_weight,
+                          int batch_dice, float ignore_label, void* stream);
+
 /* ---- region-based models (no counterpart in the reference) -----------------------------
  * Head sigmoid: the counterparts of the soft-max pair above, same layouts (NDHWC in, contiguous NCDHW out), 1 <= C <= 16.
  * p = 1 / (1 + exp(-x)) evaluated through exp(-|x|): finite and inside [0, 1] for every x.  Backward: din = dp p (1 - p). */

@@ -211,6 +211,11 @@ _SIGNATURES = {
     'seg3d_boundary_loss_workspace_bytes': (_c_ll, [_c_int, _c_int, _c_ll]),
     'seg3d_boundary_loss_fwd': (_c_int, [_c_p] * 8 + [_c_int, _c_int, _c_ll, _c_f, _c_int, _c_int, _c_f, _c_p]),
     'seg3d_boundary_loss_bwd': (_c_int, [_c_p] * 5 + [_c_int, _c_int, _c_ll, _c_int, _c_int, _c_f, _c_p]),
+    'seg3d_soft_skeleton_workspace_bytes': (_c_ll, [_c_ll] + [_c_int] * 3),
+    'seg3d_soft_skeleton': (_c_int, [_c_p] * 3 + [_c_ll] + [_c_int] * 4 + [_c_p]),
+    'seg3d_cldice_loss_workspace_bytes': (_c_ll, [_c_int] * 7),
+    'seg3d_cldice_loss_fwd': (_c_int, [_c_p] * 7 + [_c_int] * 5 + [ClassList, _c_int, _c_int, _c_f, _c_f, _c_int, _c_f, _c_p]),
+    'seg3d_cldice_loss_bwd': (_c_int, [_c_p] * 5 + [_c_int] * 5 + [ClassList, _c_int, _c_int, _c_f, _c_int, _c_f, _c_p]),
     'seg3d_sigmoid_fwd': (_c_int, [_c_p, _c_p, _c_int, _c_int, _c_ll, _c_p]),
     'seg3d_sigmoid_bwd': (_c_int, [_c_p, _c_p, _c_p, _c_int, _c_int, _c_ll, _c_p]),
     'seg3d_ds_head_supported': (_c_int, [_c_int] * 2),

@@ -1575,6 +1575,71 @@ class BoundaryLossFunction(torch.autograd.Function):
         return (dp,) + (None,) * 8
 
 
+def soft_skeleton(x, iters):
+    """the soft skeleton of every volume of `x` ([..., Z, Y, X] float32, at least 3 dimensions) with `iters` iterations
+    of iterated min / max pooling (seg3d_soft_skeleton): same shape, forward only.  Every axis
+    is at most 256 voxels, 1 <= iters <= 16.  One call, nothing read back: it can be captured into a hipGraph."""
+    E.require_device(x)
+    iters = int(iters)
+    if not 1 <= iters <= 16:
+        raise ValueError('iters must be in 1..16, got {}'.format(iters))
+    if x.dim() < 3:
+        raise ValueError('x must be [..., Z, Y, X], got {}'.format(tuple(x.shape)))
+    Z, Y, X = (int(v) for v in x.shape[-3:])
+    if max(X, Y, Z) > 256 or min(X, Y, Z) < 1 or x.numel() == 0:
+        raise ValueError('every axis of the volume must be in 1..256, got {}'.format((Z, Y, X)))
+    src = x.contiguous().float()
+    planes = src.numel() // (X * Y * Z)
+    skel = torch.empty_like(src)
+    work = _empty(((E.query('seg3d_soft_skeleton_workspace_bytes', planes, X, Y, Z) + 3) // 4,), src)
+    E.call('seg3d_soft_skeleton', E.ptr(src), E.ptr(skel), E.ptr(work), planes, X, Y, Z, iters, E.stream_ptr())
+    return skel
+
+
+class ClDiceLossFunction(torch.autograd.Function):
+    """DiceClDiceLoss.forward (loss/cldice_loss.py): soft Dice + soft-clDice.  Both soft skeletons are computed on the
+    device in the same call; `wcl` holds the weights of `class_ids` normalised over that list; `wdice`, `ignore` as for
+    CompoundLossFunction.  Every buffer is allocated per call, so one loss object may be called at several resolutions, and
+    several times before any backward runs (deep supervision).  The workspace holds what the backward needs of the
+    prediction's skeleton (one selection byte and two floats per voxel and stage) and goes to it untouched.
+    Returns (loss, terms): the 0-dim loss and the device tensor (L, L_dice, L_cl); only the loss carries a gradient."""
+
+    @staticmethod
+    def forward(ctx, probs, target, wdice, wcl, class_ids, iters, dice_weight, cldice_weight, batch_dice, ignore):
+        p, t, N, C, S = _loss_inputs(probs, target, wdice, wcl)
+        if probs.dim() != 5:
+            raise ValueError('probabilities must be [N, C, Z, Y, X], got {}'.format(tuple(probs.shape)))
+        Z, Y, X = (int(v) for v in p.shape[2:])
+        ids = [int(c) for c in class_ids]
+        K = len(ids)
+        cls = E.ClassList()
+        for i, c in enumerate(ids):
+            cls.id[i] = c
+        cfg = (cls, K, int(iters), float(cldice_weight), int(bool(batch_dice)), float(ignore))
+        work = _empty(((E.query('seg3d_cldice_loss_workspace_bytes', N, C, K, X, Y, Z, cfg[2]) + 3) // 4,), p)
+        R = 1 if cfg[4] else N
+        coef = _empty((2 * R * C + 3 * R * K,), p)
+        terms = _empty((3,), p)
+        E.call('seg3d_cldice_loss_fwd', E.ptr(p), E.ptr(t), E.ptr(wdice), E.ptr(wcl), E.ptr(work), E.ptr(coef), E.ptr(terms),
+               N, C, X, Y, Z, cls, K, cfg[2], float(dice_weight), cfg[3], cfg[4], cfg[5], E.stream_ptr())
+        ctx.save_for_backward(t, work, coef)
+        ctx.cfg = cfg
+        ctx.pshape = tuple(p.shape)
+        ctx.mark_non_differentiable(terms)
+        return terms[0], terms
+
+    @staticmethod
+    def backward(ctx, gout, _gterms):
+        t, work, coef = ctx.saved_tensors
+        cls, K, iters, cldice_weight, batch_dice, ignore = ctx.cfg
+        N, C, Z, Y, X = ctx.pshape
+        g = _gout1(gout)
+        dp = _empty(ctx.pshape, t)
+        E.call('seg3d_cldice_loss_bwd', E.ptr(t), E.ptr(work), E.ptr(coef), E.ptr(g), E.ptr(dp), N, C, X, Y, Z, cls, K, iters,
+               cldice_weight, batch_dice, ignore, E.stream_ptr())
+        return (dp,) + (None,) * 9
+
+
 class BinaryDiceLossFunction(torch.autograd.Function):
     """BinaryDiceLoss.forward called on its own (loss/binary_dice_loss.py:9-36): one fused reduction + one elementwise
     backward; probs [N, 2, ...], float target with N * S elements"""

@@ -20,6 +20,7 @@ import torch.distributed as dist
 from segmentation3d import _ops
 from segmentation3d.core.ddp import GradientReducer
 from segmentation3d.loss.boundary_loss import DiceBoundaryLoss
+from segmentation3d.loss.cldice_loss import DiceClDiceLoss
 from segmentation3d.loss.compound_loss import DiceCELoss
 from segmentation3d.loss.cross_entropy_loss import CrossEntropyLoss
 from segmentation3d.loss.deep_supervision_loss import DeepSupervisionLoss, normalise_level_weights
@@ -32,12 +33,18 @@ from segmentation3d.optim.fused_sgd import FusedSGD
 
 def build_loss(name, num_classes, obj_weight=None, focal_gamma=2, use_gpu=True, dice_weight=1.0, ce_weight=1.0,
                include_background=True, batch_dice=False, ignore_label=None, topk_percent=10.0, boundary_weight=0.01,
-               spacing=(1, 1, 1)):
+               spacing=(1, 1, 1), cldice_weight=1.0, cldice_iters=3, cldice_classes=None):
     """loss selection of core/seg_train.py:91-102, plus the compound losses 'DiceCE' (soft Dice + cross-entropy),
     'DiceFocal' (soft Dice + focal with focal_gamma), 'DiceTopK' (soft Dice + cross-entropy over the hardest
     topk_percent of the batch's voxels) and 'DiceBoundary' (soft Dice + boundary loss on signed distance maps in units of
-    `spacing`, weighted by boundary_weight; ce_weight is not read); the keyword options after use_gpu apply to those four
-    only, topk_percent to 'DiceTopK' only, boundary_weight and spacing to 'DiceBoundary' only"""
+    `spacing`, weighted by boundary_weight; ce_weight is not read) and 'DiceClDice' (soft Dice + soft-clDice topology
+    loss on soft skeletons of cldice_iters iterations for the classes cldice_classes, weighted by cldice_weight; ce_weight
+    is not read); the keyword options after use_gpu apply to those five only, topk_percent to 'DiceTopK' only,
+    boundary_weight and spacing to 'DiceBoundary' only, the cldice_ options to 'DiceClDice' only"""
+    if name == 'DiceClDice':
+        return DiceClDiceLoss(num_classes, weights=obj_weight, dice_weight=dice_weight, cldice_weight=cldice_weight,
+                              iters=cldice_iters, cldice_classes=cldice_classes, include_background=include_background,
+                              batch_dice=batch_dice, ignore_label=ignore_label, use_gpu=use_gpu)
     if name == 'DiceBoundary':
         return DiceBoundaryLoss(num_classes, weights=obj_weight, dice_weight=dice_weight, boundary_weight=boundary_weight,
                                 spacing=spacing, include_background=include_background, batch_dice=batch_dice,
@@ -62,8 +69,9 @@ def build_loss(name, num_classes, obj_weight=None, focal_gamma=2, use_gpu=True, 
 
 def loss_options_from_config(loss_cfg):
     """the optional keys of the config's `loss` section that the compound losses read, with their defaults (a config
-    without them -- every reference config -- loads unchanged); `topk_percent` ('DiceTopK') and `boundary_weight`
-    ('DiceBoundary') are passed on only when the section has them"""
+    without them -- every reference config -- loads unchanged); `topk_percent` ('DiceTopK'), `boundary_weight`
+    ('DiceBoundary') and `cldice_weight`, `cldice_iters`, `cldice_classes` ('DiceClDice'; defaults 1.0, 3, None = every
+    foreground class) are passed on only when the section has them"""
     opts = {'dice_weight': getattr(loss_cfg, 'dice_weight', 1.0), 'ce_weight': getattr(loss_cfg, 'ce_weight', 1.0),
             'include_background': getattr(loss_cfg, 'include_background', True),
             'batch_dice': getattr(loss_cfg, 'batch_dice', False), 'ignore_label': getattr(loss_cfg, 'ignore_label', None)}
@@ -71,6 +79,9 @@ def loss_options_from_config(loss_cfg):
         opts['topk_percent'] = loss_cfg.topk_percent
     if hasattr(loss_cfg, 'boundary_weight'):
         opts['boundary_weight'] = loss_cfg.boundary_weight
+    for key in ('cldice_weight', 'cldice_iters', 'cldice_classes'):
+        if hasattr(loss_cfg, key):
+            opts[key] = getattr(loss_cfg, key)
     return opts
 
 
@@ -180,7 +191,8 @@ class TrainStep(object):
     """network + loss + FusedAdam or FusedSGD (+ gradient reducer when distributed) on one device; `loss_options` is a
     dict of build_loss's keyword options for the compound losses (dice_weight, ce_weight, include_background, batch_dice,
     ignore_label, topk_percent for loss_name='DiceTopK', boundary_weight and spacing for loss_name='DiceBoundary', which
-    serves one resolution and is refused together with deep supervision); `optimizer` / `optim_options` are
+    serves one resolution and is refused together with deep supervision, cldice_weight, cldice_iters and cldice_classes
+    for loss_name='DiceClDice'); `optimizer` / `optim_options` are
     build_optimizer's (gradient-norm clipping, lr schedule, SGD);
     `deep_supervision` = L in 1..3 builds the network with L auxiliary heads and trains on the weighted per-level losses
     (loss/deep_supervision_loss.py; `deep_supervision_weights`: L + 1 weights, None = halving per level)"""

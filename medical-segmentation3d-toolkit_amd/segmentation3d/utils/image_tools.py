@@ -668,6 +668,17 @@ def signed_distance_device(labels, class_ids, spacing, ignore_label=None):
     return phi if batched else phi[0]
 
 
+def soft_skeleton_device(x, iters):
+    """the soft skeleton of a float device volume `x` [Z, Y, X] (or any batch [..., Z, Y, X] of volumes) by `iters` = 1..16
+    iterations of min / max pooling, as the clDice loss computes it: with E = min over a voxel and its 6 face neighbours,
+    D = max over the 3x3x3 neighbourhood (nothing exists outside the volume) and O = D(E(.)):  x_0 = x,
+    s_0 = relu(x_0 - O(x_0)), then x_j = E(x_{j-1}), d_j = relu(x_j - O(x_j)), s_j = s_{j-1} + relu(d_j - s_{j-1} d_j).
+    Returns s_iters, float32, same shape; a 0 / 1 mask gives an exact 0 / 1 skeleton.  Every axis is at most 256 voxels
+    (seg3d_soft_skeleton)."""
+    from segmentation3d import _ops
+    return _ops.soft_skeleton(x, iters)
+
+
 def get_image_frame(image):
     """spacing, origin, direction packed into 15 float32 (image_tools.py:26-41)"""
     return np.array(list(image.GetSpacing()) + list(image.GetOrigin()) + list(image.GetDirection()), dtype=np.float32)
