@@ -73,6 +73,20 @@ int seg3d_wgrad_direct(const float* P, const float* Q, float* part, int N, int D
                        int ksize, int stride, int* n_chunks_out /* host */, void* stream);
 int seg3d_wgrad_reduce(const float* part, float* dw, int chunks, int T, int A, int B, long long sa, long long sb,
                        int accumulate /* dw += instead of = */, void* stream);
+/* What a weight-gradient call of the VALU fallback family (csrc/conv_direct.hip) runs -- pure host arithmetic: the launchers
+ * decide through the same functions.  Arguments as seg3d_wgrad_direct (P's extents) and seg3d_wgrad_reduce.
+ *   seg3d_wgrad_direct_variant   0: wgrad_direct_kernel<3, 1, 1>, 1: wgrad_direct_kernel<2, 2, 0>, 2: wgrad_direct_kernel<1, 1, 0>,
+ *                                3: wgrad_k1_thin_kernel (ksize 1 with CA <= 8 and CB <= 8).  Negative, with seg3d_last_error set,
+ *                                where the launcher refuses: a dimension <= 0, odd extents with stride 2, another (ksize, stride)
+ *   seg3d_wgrad_direct_chunks    the partial slabs the launcher writes and reports in n_chunks_out (<= the slabs
+ *                                seg3d_wgrad_direct_workspace_floats sizes the workspace for); negative as above
+ *   seg3d_wgrad_direct_pairs     PAIRS: the threads of a workgroup that share a voxel, CA * ceil(CB / 4) rounded up to a power of
+ *                                two, 256 at most; 256 / PAIRS voxel lanes, gridDim.y = ceil(CA * ceil(CB / 4) / PAIRS)
+ *   seg3d_wgrad_reduce_variant   0: wgrad_reduce_kernel, 1: wgrad_reduce_wide_kernel (chunks >= 512 and T * A * B <= 2048) */
+int seg3d_wgrad_direct_variant(int N, int Dp, int Hp, int Wp, int CA, int CB, int ksize, int stride);
+int seg3d_wgrad_direct_chunks(int N, int Dp, int Hp, int Wp, int CA, int CB, int ksize, int stride);
+int seg3d_wgrad_direct_pairs(int CA, int CB);
+int seg3d_wgrad_reduce_variant(int chunks, int T, int A, int B);
 
 /* fp32 MFMA implicit-GEMM path for k3 s1 p1 with Cin % 4 == 0 (the FLOP-dominant C->C layers) */
 long long seg3d_conv3d_k3_mfma_stats_count(int N, int D, int H, int W, int Cin, int Cout);

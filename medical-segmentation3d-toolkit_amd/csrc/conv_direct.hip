@@ -351,41 +351,80 @@ extern "C" long long seg3d_wgrad_direct_workspace_floats(int N, int Dq, int Hq, 
   return (long long)wgrad_direct_chunks(nvox, ntaps, CA, CBP) * ntaps * CA * CBP;
 }
 
+// threads of a workgroup that share a voxel: the (a, b-quad) pairs rounded up to a power of two, 256 at most (it divides 256)
+static int wgrad_direct_pairs(int CA, int CBP) {
+  const int total_pairs = CA * (CBP / 4);
+  int PAIRS = 1;
+  while (PAIRS < total_pairs && PAIRS < 256) PAIRS <<= 1;
+  return PAIRS;
+}
+
+// The launch of a weight-gradient problem, decided in one place for seg3d_wgrad_direct and for the read-only queries
+// (seg3d_wgrad_direct_variant / _chunks / _pairs).  kernel: the codes of seg3d_wgrad_direct_variant
+enum { WGD_K3 = 0, WGD_K2S2 = 1, WGD_K1 = 2, WGD_K1_THIN = 3 };
+struct WgradDirectPlan {
+  int Dq, Hq, Wq, CBP, PAIRS, gy, chunks, chunk_vox, kernel;
+  i64 nvox;
+};
 // P dims = (Dp,Hp,Wp), Q dims derived: k3/k1 same, k2s2: half.
+static int wgrad_direct_plan(int N, int Dp, int Hp, int Wp_, int CA, int CB, int ksize, int stride, WgradDirectPlan* p) {
+  SEG3D_REQUIRE(N > 0 && Dp > 0 && Hp > 0 && Wp_ > 0 && CA > 0 && CB > 0, "seg3d_wgrad_direct: bad dims");
+  p->Dq = Dp, p->Hq = Hp, p->Wq = Wp_;
+  if (stride == 2) {
+    SEG3D_REQUIRE((Dp % 2) == 0 && (Hp % 2) == 0 && (Wp_ % 2) == 0, "seg3d_wgrad_direct: k2s2 needs even dims");
+    p->Dq = Dp / 2; p->Hq = Hp / 2; p->Wq = Wp_ / 2;
+  }
+  if (ksize == 3 && stride == 1) p->kernel = WGD_K3;
+  else if (ksize == 2 && stride == 2) p->kernel = WGD_K2S2;
+  else if (ksize == 1 && stride == 1) p->kernel = (CA <= 8 && CB <= 8) ? WGD_K1_THIN : WGD_K1;
+  else SEG3D_UNSUPPORTED("seg3d_wgrad_direct: unsupported ksize=%d stride=%d", ksize, stride);
+  p->CBP = seg3d_round_up(CB, 4);
+  p->PAIRS = wgrad_direct_pairs(CA, p->CBP);
+  p->gy = seg3d_cdiv(CA * (p->CBP / 4), p->PAIRS);
+  p->nvox = (i64)N * p->Dq * p->Hq * p->Wq;
+  const int chunks = wgrad_direct_chunks(p->nvox, ksize * ksize * ksize, CA, p->CBP);
+  p->chunk_vox = (int)((p->nvox + chunks - 1) / chunks);
+  p->chunks = (int)((p->nvox + p->chunk_vox - 1) / p->chunk_vox);
+  return SEG3D_OK;
+}
+
+extern "C" int seg3d_wgrad_direct_variant(int N, int Dp, int Hp, int Wp_, int CA, int CB, int ksize, int stride) {
+  WgradDirectPlan p;
+  const int rc = wgrad_direct_plan(N, Dp, Hp, Wp_, CA, CB, ksize, stride, &p);
+  return rc != SEG3D_OK ? rc : p.kernel;
+}
+
+extern "C" int seg3d_wgrad_direct_chunks(int N, int Dp, int Hp, int Wp_, int CA, int CB, int ksize, int stride) {
+  WgradDirectPlan p;
+  const int rc = wgrad_direct_plan(N, Dp, Hp, Wp_, CA, CB, ksize, stride, &p);
+  return rc != SEG3D_OK ? rc : p.chunks;
+}
+
+extern "C" int seg3d_wgrad_direct_pairs(int CA, int CB) {
+  SEG3D_REQUIRE(CA > 0 && CB > 0, "seg3d_wgrad_direct_pairs: bad dims");
+  return wgrad_direct_pairs(CA, seg3d_round_up(CB, 4));
+}
+
 extern "C" int seg3d_wgrad_direct(const float* P, const float* Q, float* part, int N, int Dp, int Hp, int Wp_, int CA,
                                   int CB, int ksize, int stride, int* n_chunks_out, void* stream) {
   SEG3D_REQUIRE(P && Q && part && n_chunks_out, "seg3d_wgrad_direct: null pointer");
-  SEG3D_REQUIRE(N > 0 && Dp > 0 && Hp > 0 && Wp_ > 0 && CA > 0 && CB > 0, "seg3d_wgrad_direct: bad dims");
-  int Dq = Dp, Hq = Hp, Wq = Wp_;
-  if (stride == 2) {
-    SEG3D_REQUIRE((Dp % 2) == 0 && (Hp % 2) == 0 && (Wp_ % 2) == 0, "seg3d_wgrad_direct: k2s2 needs even dims");
-    Dq = Dp / 2; Hq = Hp / 2; Wq = Wp_ / 2;
-  }
-  const int CBP = seg3d_round_up(CB, 4);
-  const int total_pairs = CA * (CBP / 4);
-  int PAIRS = 1;
-  while (PAIRS < total_pairs && PAIRS < 256) PAIRS <<= 1;  // power of two dividing 256
-  const int gy = seg3d_cdiv(total_pairs, PAIRS);
-  i64 nvox = (i64)N * Dq * Hq * Wq;
-  int chunks = wgrad_direct_chunks(nvox, ksize * ksize * ksize, CA, CBP);
-  const int chunk_vox = (int)((nvox + chunks - 1) / chunks);
-  chunks = (int)((nvox + chunk_vox - 1) / chunk_vox);
-  *n_chunks_out = chunks;
+  WgradDirectPlan p;
+  const int rc = wgrad_direct_plan(N, Dp, Hp, Wp_, CA, CB, ksize, stride, &p);
+  if (rc != SEG3D_OK) return rc;
+  *n_chunks_out = p.chunks;
   hipStream_t s = (hipStream_t)stream;
-  dim3 grid(chunks, gy), block(256);
-  if (ksize == 3 && stride == 1) {
-    hipLaunchKernelGGL((wgrad_direct_kernel<3, 1, 1>), grid, block, 0, s, P, Q, part, N, Dp, Hp, Wp_, Dq, Hq, Wq, CA, CB,
-                       CBP, PAIRS, chunk_vox);
-  } else if (ksize == 2 && stride == 2) {
-    hipLaunchKernelGGL((wgrad_direct_kernel<2, 2, 0>), grid, block, 0, s, P, Q, part, N, Dp, Hp, Wp_, Dq, Hq, Wq, CA, CB,
-                       CBP, PAIRS, chunk_vox);
-  } else if (ksize == 1 && stride == 1 && CA <= 8 && CB <= 8) {
-    hipLaunchKernelGGL(wgrad_k1_thin_kernel, dim3(chunks), block, 0, s, P, Q, part, nvox, CA, CB, CBP, chunk_vox);
-  } else if (ksize == 1 && stride == 1) {
-    hipLaunchKernelGGL((wgrad_direct_kernel<1, 1, 0>), grid, block, 0, s, P, Q, part, N, Dp, Hp, Wp_, Dq, Hq, Wq, CA, CB,
-                       CBP, PAIRS, chunk_vox);
+  dim3 grid(p.chunks, p.gy), block(256);
+  if (p.kernel == WGD_K3) {
+    hipLaunchKernelGGL((wgrad_direct_kernel<3, 1, 1>), grid, block, 0, s, P, Q, part, N, Dp, Hp, Wp_, p.Dq, p.Hq, p.Wq, CA, CB,
+                       p.CBP, p.PAIRS, p.chunk_vox);
+  } else if (p.kernel == WGD_K2S2) {
+    hipLaunchKernelGGL((wgrad_direct_kernel<2, 2, 0>), grid, block, 0, s, P, Q, part, N, Dp, Hp, Wp_, p.Dq, p.Hq, p.Wq, CA, CB,
+                       p.CBP, p.PAIRS, p.chunk_vox);
+  } else if (p.kernel == WGD_K1_THIN) {
+    hipLaunchKernelGGL(wgrad_k1_thin_kernel, dim3(p.chunks), block, 0, s, P, Q, part, p.nvox, CA, CB, p.CBP, p.chunk_vox);
   } else {
-    SEG3D_UNSUPPORTED("seg3d_wgrad_direct: unsupported ksize=%d stride=%d", ksize, stride);
+    hipLaunchKernelGGL((wgrad_direct_kernel<1, 1, 0>), grid, block, 0, s, P, Q, part, N, Dp, Hp, Wp_, p.Dq, p.Hq, p.Wq, CA, CB,
+                       p.CBP, p.PAIRS, p.chunk_vox);
   }
   SEG3D_LAUNCH_CHECK("seg3d_wgrad_direct");
   return SEG3D_OK;
@@ -410,8 +449,9 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restri
   }
 }
 
-// few outputs, many chunks (the head's 1x1x1 conv: 4 outputs x ~14 k chunks took 134 us with one serial thread per
-// output): one workgroup per output, threads stride over the chunks, fixed-shape LDS tree -- still deterministic
+// few outputs, many chunks (the head's 1x1x1 conv: one serial thread per output walks every chunk; wgrad_direct_chunks caps them
+// at 512, and this kernel is reached at exactly that count): one workgroup per output, threads stride over the chunks,
+// fixed-shape LDS tree -- still deterministic
 __global__ __launch_bounds__(256) void wgrad_reduce_wide_kernel(const float* __restrict__ part, float* __restrict__ dw,
                                                                   int chunks, int T, int A, int B, int BP, i64 sa, i64 sb,
                                                                   int accumulate) {
@@ -438,12 +478,20 @@ __global__ __launch_bounds__(256) void wgrad_reduce_wide_kernel(const float* __r
   }
 }
 
+// which reducer a call runs (shared by seg3d_wgrad_reduce and seg3d_wgrad_reduce_variant): 1 = wgrad_reduce_wide_kernel
+static bool wgrad_reduce_is_wide(int chunks, i64 total) { return chunks >= 512 && total <= 2048; }
+
+extern "C" int seg3d_wgrad_reduce_variant(int chunks, int T, int A, int B) {
+  SEG3D_REQUIRE(chunks > 0 && T > 0 && A > 0 && B > 0, "seg3d_wgrad_reduce: bad arguments");
+  return wgrad_reduce_is_wide(chunks, (i64)T * A * B) ? 1 : 0;
+}
+
 extern "C" int seg3d_wgrad_reduce(const float* part, float* dw, int chunks, int T, int A, int B, long long sa,
                                   long long sb, int accumulate, void* stream) {
   SEG3D_REQUIRE(part && dw && chunks > 0 && T > 0 && A > 0 && B > 0, "seg3d_wgrad_reduce: bad arguments");
   const int BP = seg3d_round_up(B, 4);
   i64 total = (i64)T * A * B;
-  if (chunks >= 512 && total <= 2048)
+  if (wgrad_reduce_is_wide(chunks, total))
     hipLaunchKernelGGL(wgrad_reduce_wide_kernel, dim3((unsigned)total), dim3(256), 0, (hipStream_t)stream, part, dw, chunks, T, A,
                        B, BP, (i64)sa, (i64)sb, accumulate);
   else

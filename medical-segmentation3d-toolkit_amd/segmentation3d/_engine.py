@@ -89,6 +89,10 @@ _SIGNATURES = {
     'seg3d_wgrad_direct_workspace_floats': (_c_ll, [_c_int] * 7),
     'seg3d_wgrad_direct': (_c_int, [_c_p, _c_p, _c_p] + [_c_int] * 8 + [ctypes.POINTER(_c_int), _c_p]),
     'seg3d_wgrad_reduce': (_c_int, [_c_p, _c_p, _c_int, _c_int, _c_int, _c_int, _c_ll, _c_ll, _c_int, _c_p]),
+    'seg3d_wgrad_direct_variant': (_c_int, [_c_int] * 8),
+    'seg3d_wgrad_direct_chunks': (_c_int, [_c_int] * 8),
+    'seg3d_wgrad_direct_pairs': (_c_int, [_c_int] * 2),
+    'seg3d_wgrad_reduce_variant': (_c_int, [_c_int] * 4),
     'seg3d_conv3d_k3_mfma_stats_count': (_c_ll, [_c_int] * 6),
     'seg3d_conv3d_k3_mfma_fwd_workspace_floats': (_c_ll, [_c_int] * 6),
     'seg3d_conv3d_k3_mfma_variant': (_c_int, [_c_int] * 6),

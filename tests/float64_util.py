@@ -1,6 +1,6 @@
 """helpers shared by the "every kernel instantiation against float64" device tests (tests/test_gpu_k2_float64.py,
-tests/test_gpu_k3_float64.py, tests/test_gpu_thin_float64.py, tests/test_gpu_wino_float64.py): deterministic inputs, the float64 3x3x3 references, NaN guard
-bands, and the bookkeeping of (error, yardstick, scale, bar)"""
+tests/test_gpu_k3_float64.py, tests/test_gpu_thin_float64.py, tests/test_gpu_wino_float64.py, tests/test_gpu_direct_float64.py): deterministic
+inputs, the float64 references (3x3x3, stride-2 2x2x2, 1x1x1), NaN guard bands, and the bookkeeping of (error, yardstick, scale, bar)"""
 import torch
 import torch.nn.functional as F
 
@@ -97,12 +97,57 @@ def _conv_def(x, w):
     return out.reshape(N, D, H, W, w.shape[0])
 
 
-def _wgrad_def(x, dy):
-    """x [N, D, H, W, Ci], dy [N, D, H, W, Co] -> dw [Co, Ci, 27]"""
+def _blocked(t, blocks):
+    """[V, C] -> [blocks, ceil(V / blocks), C], rows of zeros behind the last one"""
+    rows = (t.shape[0] + blocks - 1) // blocks
+    return F.pad(t, (0, 0, 0, rows * blocks - t.shape[0])).reshape(blocks, rows, t.shape[1])
+
+
+def _wgrad_def(x, dy, blocks=1):
+    """x [N, D, H, W, Ci], dy [N, D, H, W, Co] -> dw [Co, Ci, 27].  blocks > 1: every product over the voxels as that many batched
+    products summed in float64 (for 10^6 voxels and a handful of channels: one skinny product runs in a single workgroup)"""
     N, D, H, W, Ci = x.shape
     xp = _pad(x)
+    if blocks > 1:
+        dyt = _blocked(dy.reshape(-1, dy.shape[-1]), blocks).transpose(1, 2)
+        return torch.stack([(dyt @ _blocked(xp[:, kz:kz + D, ky:ky + H, kx:kx + W, :].reshape(-1, Ci), blocks)).sum(0)
+                            for (kz, ky, kx) in TAPS], 2)
     dyt = dy.reshape(-1, dy.shape[-1]).t().contiguous()
     return torch.stack([dyt @ xp[:, kz:kz + D, ky:ky + H, kx:kx + W, :].reshape(-1, Ci) for (kz, ky, kx) in TAPS], 2)
+
+
+# ---- float64 references of the stride-2 2x2x2 operations (einsums over the 2^3 cells) and of the 1x1x1 convolution ------------------
+def _k2_cells(x):
+    """[N, 2D, 2H, 2W, C] -> [N, D, 2, H, 2, W, 2, C]: the 2^3 cell of every coarse voxel"""
+    N, D2, H2, W2, C = x.shape
+    return x.reshape(N, D2 // 2, 2, H2 // 2, 2, W2 // 2, 2, C)
+
+
+def _k2_gather_def(x, w):
+    """y[v][b] = sum_{t, a} x[2v + t][a] w[b][a][t].  x [N, 2D, 2H, 2W, A], w [B, A, 2, 2, 2] -> [N, D, H, W, B]"""
+    return torch.einsum('nzaybxcq,oqabc->nzyxo', _k2_cells(x), w)
+
+
+def _k2_scatter_def(x, w):
+    """y[2i + t][b] = sum_a x[i][a] w[a][b][t].  x [N, D, H, W, A], w [A, B, 2, 2, 2] -> [N, 2D, 2H, 2W, B]"""
+    N, D, H, W, _ = x.shape
+    return torch.einsum('nzyxq,qoabc->nzaybxco', x, w).reshape(N, 2 * D, 2 * H, 2 * W, w.shape[1])
+
+
+def _k2_wgrad_def(P, Q):
+    """dW(a, b, t) = sum_v P[2v + t][a] Q[v][b].  P [N, 2D, 2H, 2W, CA], Q [N, D, H, W, CB] -> [CA, CB, 8].  The stride-2 conv's
+    weight gradient with P = x, Q = dy; the transposed conv's with P = dy, Q = x"""
+    return torch.einsum('nzaybxcp,nzyxq->pqabc', _k2_cells(P), Q).reshape(P.shape[-1], Q.shape[-1], 8)
+
+
+def _k1_def(x, w):
+    """x [N, D, H, W, Ci], w [Co, Ci] -> [N, D, H, W, Co]"""
+    return (x.reshape(-1, x.shape[-1]) @ w.t()).reshape(x.shape[:-1] + (w.shape[0],))
+
+
+def _k1_wgrad_def(x, dy):
+    """x [N, D, H, W, Ci], dy [N, D, H, W, Co] -> dw [Co, Ci]"""
+    return dy.reshape(-1, dy.shape[-1]).t() @ x.reshape(-1, x.shape[-1])
 
 
 # ---- the Winograd forms of the same operations, restated from the header comments of csrc/conv_wino.hip and csrc/conv_wino2d.hip,

@@ -27,8 +27,8 @@ import torch
 import torch.nn.functional as F
 
 import k2_cases as K
-from float64_util import (FLOOR_EW, FLOOR_RED, Figures, Guarded, _activation, _check_stats, _engine, _noise, _weight, _wide_slice,
-                          bf16_round)
+from float64_util import (FLOOR_EW, FLOOR_RED, Figures, Guarded, _activation, _check_stats, _engine, _k2_gather_def, _k2_scatter_def,
+                          _k2_wgrad_def, _noise, _weight, _wide_slice, bf16_round)
 
 pytestmark = pytest.mark.gpu
 
@@ -65,12 +65,10 @@ def test_gather(hip_device, case):
         x = bf16_round(x)
     wr = bf16_round(w) if c.mode == 2 else w
     # float64 reference (device) and fp32 yardstick (CPU)
-    cells = x.to(dev).double().reshape(c.N, c.D, 2, c.H, 2, c.W, 2, A)
-    ref = torch.einsum('nzaybxcq,oqabc->nzyxo', cells, wr.to(dev).double())
+    ref = _k2_gather_def(x.to(dev).double(), wr.to(dev).double())
     yard = F.conv3d(x.permute(0, 4, 1, 2, 3), wr, bias, stride=2).permute(0, 2, 3, 4, 1)
     if fwd:
         ref = ref + bias.to(dev).double()
-    del cells
     # device operands
     if c.ld_x:
         wide, xd = _wide_slice(x, c.ld_x, dev)
@@ -114,7 +112,7 @@ def test_scatter(hip_device, case):
     if c.mode:
         x = bf16_round(x)
     wr = bf16_round(w) if c.mode == 2 else w
-    ref = torch.einsum('nzyxq,qoabc->nzaybxco', x.to(dev).double(), wr.to(dev).double()).reshape(c.N, 2 * c.D, 2 * c.H, 2 * c.W, B)
+    ref = _k2_scatter_def(x.to(dev).double(), wr.to(dev).double())
     yard = F.conv_transpose3d(x.permute(0, 4, 1, 2, 3), wr, bias, stride=2).permute(0, 2, 3, 4, 1)
     if fwd:
         ref = ref + bias.to(dev).double()
@@ -162,9 +160,7 @@ def test_wgrad(hip_device, case):
     Q = _activation(921, fig.name + '/Q', c.N, (c.D, c.H, c.W), CB, offset=0.0)
     if c.bf16:
         P, Q = bf16_round(P), bf16_round(Q)
-    cells = P.to(dev).double().reshape(c.N, c.D, 2, c.H, 2, c.W, 2, CA)
-    ref = torch.einsum('nzaybxcp,nzyxq->pqabc', cells, Q.to(dev).double()).reshape(CA, CB, 8)     # dW(a, b, t)
-    del cells
+    ref = _k2_wgrad_def(P.to(dev).double(), Q.to(dev).double())                                   # dW(a, b, t)
     w0 = torch.zeros(CB, CA, 2, 2, 2, requires_grad=True)
     yard = torch.autograd.grad(F.conv3d(P.permute(0, 4, 1, 2, 3), w0, stride=2), w0, Q.permute(0, 4, 1, 2, 3))[0]
     yard = yard.reshape(CB, CA, 8).permute(1, 0, 2)
