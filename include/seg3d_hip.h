@@ -877,6 +877,53 @@ long long seg3d_ccl_workspace_ints(long long voxels);
 int seg3d_ccl26_select(const signed char* mask, int label, int X, int Y, int Z, int mode, int threshold, int value,
                        int combine, signed char* out, int* workspace, void* stream);
 
+/* ---- lesion-wise evaluation (not in the reference; csrc/lesion.hip, csrc/postproc.hip) -----
+ * Building blocks of lesion-wise Dice / HD95: the ground truth of a target (a set of label ids) is dilated by the
+ * 18-neighbourhood and split into 26-connected lesions, the prediction into 26-connected components, and every
+ * (lesion, component) pair that shares a voxel is recorded.  Volumes are [Z][Y][X] with fewer than 2^31 voxels.  Integer
+ * work with integer atomics only: every result is exact and identical from run to run.  No entry allocates or
+ * synchronises, no workgroup waits on another, and every loop has a bound known at launch (capturable).
+ *
+ * seg3d_label_set_mask: mask[i] = 1 iff labels[i] is an integer l in [0, 256) with bit (l & 31) of set.bits[l >> 5]
+ * set, else 0.  dtype codes as seg3d_label_overlap_counts.
+ *
+ * seg3d_binary_dilate18: out = mask dilated `iters` times (0..16) by the 18-neighbourhood: a voxel is set if it, or a
+ * neighbour differing by +-1 in at most two axes, was set; nothing exists outside the volume.  One launch per iteration,
+ * ping-ponging between out and workspace (X*Y*Z bytes, needed for iters >= 2) so that the last lands in out; iters = 0
+ * copies.  mask, out and workspace must be distinct.
+ *
+ * seg3d_ccl26_label: ids[v] = 0 where mask[v] == 0, else the id 1..K of v's 26-connected component, ids in the order
+ * of each component's lowest linear voxel index (z*Y + y)*X + x -- independent of the launch order.  count_device[0] = K,
+ * count_device[1] = 1 iff K > capacity (an ordinary return: repeat with a larger sizes array), else 0.  sizes[k - 1] =
+ * voxels of component k for k <= capacity; nothing is written at or beyond sizes[capacity].  workspace:
+ * seg3d_ccl26_label_workspace_ints ints (-1: bad size).
+ *
+ * seg3d_lesion_pairs: one pass over dmap (lesion ids 0..kg), a (0/1 ground-truth mask) and pmap (component ids, 0 =
+ * none).  gsize[i] += |{v : dmap = i, a}|, inter[i] += |{v : dmap = i, a, pmap > 0}| (int64, kg + 1 entries each, zeroed
+ * by the caller), and every distinct key (i << 32 | j) with dmap = i > 0, pmap = j > 0 is inserted into table, an
+ * open-addressing hash set of `capacity` (a power of two) 64-bit words zeroed by the caller (0 = empty; linear probing,
+ * at most capacity probes).  A key that finds no slot sets status[0] (zeroed by the caller) to 1 and nothing else is
+ * lost: the counts are complete, and the caller repeats the launch with a larger table.  collapse != 0: lanes of a wave
+ * with equal keys are merged before the atomics (the default of the Python wrapper); 0: one set of atomics per voxel.
+ * The results do not depend on it.
+ *
+ * seg3d_lesion_select: g[v] = (dmap[v] == lesion && a[v]), u[v] = flag[pmap[v]] != 0 (flag: kp + 1 device bytes, pmap
+ * outside 1..kp gives 0), both as 0/1 bytes: label 1 of a uint8 volume for seg3d_label_surface.  Whole volume. */
+typedef struct Seg3dLabelSet {
+  unsigned int bits[8];
+} Seg3dLabelSet;
+int seg3d_label_set_mask(const void* labels, int dtype, long long n, Seg3dLabelSet set, unsigned char* mask, void* stream);
+int seg3d_binary_dilate18(const unsigned char* mask, unsigned char* out, unsigned char* workspace, int X, int Y, int Z,
+                          int iters, void* stream);
+long long seg3d_ccl26_label_workspace_ints(long long voxels);
+int seg3d_ccl26_label(const unsigned char* mask, int X, int Y, int Z, int* ids, int* count_device, int* sizes, int capacity,
+                      int* workspace, void* stream);
+int seg3d_lesion_pairs(const int* dmap, const unsigned char* a, const int* pmap, long long n, int kg, long long* gsize,
+                       long long* inter, unsigned long long* table, long long capacity, int collapse, int* status,
+                       void* stream);
+int seg3d_lesion_select(const int* dmap, const unsigned char* a, const int* pmap, const unsigned char* flag, int kp,
+                        int lesion, long long n, unsigned char* g, unsigned char* u, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

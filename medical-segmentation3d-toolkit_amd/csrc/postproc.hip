@@ -495,3 +495,151 @@ extern "C" int seg3d_ccl26_select(const signed char* mask, int label, int X, int
   SEG3D_LAUNCH_CHECK("seg3d_ccl26_select");
   return SEG3D_OK;
 }
+
+// ---- 26-connected components of a 0/1 mask as a canonical id map (lesion-wise evaluation) ----
+// ids doubles as the parent array of the union-find above (init / merge / flatten).  ccl_union only ever hangs a root
+// under a SMALLER index (atomicMin, and a lost link is re-united from the displaced parent), so a parent is always below
+// its child and the root that flatten leaves is the lowest linear index of the component, whatever the launch order.
+// Numbering the roots by their rank in linear order therefore gives ids 1..K in the order of each component's lowest
+// voxel.  The rank is an exclusive prefix sum of the root flags in three launches: per-block counts (4096 voxels per
+// block), one block scanning the counts in rounds of 256 with a carry, and the per-block apply; no workgroup waits on
+// another.  A last pass maps every voxel to its root's rank and adds run lengths to the size histogram (integer atomics).
+#define CCL_SCAN_PER_THREAD 16
+#define CCL_SCAN_ITEMS (256 * CCL_SCAN_PER_THREAD)
+
+__global__ __launch_bounds__(256) void ccl_init_mask_kernel(const unsigned char* __restrict__ mask, int* __restrict__ parent,
+                                                              i64 total) {
+  for (i64 idx = (i64)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (i64)gridDim.x * 256)
+    parent[idx] = mask[idx] ? (int)idx : -1;
+}
+
+// exclusive prefix of v over the 256 threads of the block (thread order); total: the block's sum.  wave_tot: 4 shared ints
+__device__ __forceinline__ int ccl_block_scan(int v, int* wave_tot, int& total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int inc = v;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const int u = __shfl_up(inc, off, 64);
+    if (lane >= off) inc += u;
+  }
+  if (lane == 63) wave_tot[wave] = inc;
+  __syncthreads();
+  int base = 0;
+  total = 0;
+#pragma unroll
+  for (int w = 0; w < 4; ++w) {
+    const int t = wave_tot[w];
+    base += w < wave ? t : 0;
+    total += t;
+  }
+  __syncthreads();   // wave_tot is free for the caller's next round
+  return base + inc - v;
+}
+
+// thread t of block b owns the CCL_SCAN_PER_THREAD consecutive voxels from (b * 256 + t) * CCL_SCAN_PER_THREAD on;
+// bit k of the result: voxel k of them is a root
+__device__ __forceinline__ unsigned ccl_thread_roots(const int* __restrict__ parent, i64 first, i64 total) {
+  unsigned bits = 0u;
+#pragma unroll
+  for (int k = 0; k < CCL_SCAN_PER_THREAD; ++k) {
+    const i64 idx = first + k;
+    if (idx < total && parent[idx] == (int)idx) bits |= 1u << k;
+  }
+  return bits;
+}
+
+__global__ __launch_bounds__(256) void ccl_root_sums_kernel(const int* __restrict__ parent, i64 total, int* __restrict__ sums) {
+  __shared__ int wave_tot[4];
+  const i64 first = ((i64)blockIdx.x * 256 + threadIdx.x) * CCL_SCAN_PER_THREAD;
+  int block_total;
+  ccl_block_scan(__popc(ccl_thread_roots(parent, first, total)), wave_tot, block_total);
+  if (threadIdx.x == 0) sums[blockIdx.x] = block_total;
+}
+
+// one block: sums -> their exclusive prefix, count[0] = K, count[1] = (K > capacity); nblocks / 256 rounds
+__global__ __launch_bounds__(256) void ccl_scan_sums_kernel(int* __restrict__ sums, int nblocks, int capacity,
+                                                              int* __restrict__ count) {
+  __shared__ int wave_tot[4];
+  int carry = 0;
+  for (int c0 = 0; c0 < nblocks; c0 += 256) {
+    const int c = c0 + (int)threadIdx.x;
+    const int v = c < nblocks ? sums[c] : 0;
+    int round_total;
+    const int ex = ccl_block_scan(v, wave_tot, round_total);
+    if (c < nblocks) sums[c] = carry + ex;
+    carry += round_total;
+  }
+  if (threadIdx.x == 0) {
+    count[0] = carry;
+    count[1] = carry > capacity ? 1 : 0;
+  }
+}
+
+__global__ __launch_bounds__(256) void ccl_rank_apply_kernel(const int* __restrict__ parent, i64 total,
+                                                               const int* __restrict__ sums, int* __restrict__ rank) {
+  __shared__ int wave_tot[4];
+  const i64 first = ((i64)blockIdx.x * 256 + threadIdx.x) * CCL_SCAN_PER_THREAD;
+  const unsigned bits = ccl_thread_roots(parent, first, total);
+  int block_total;
+  int id = sums[blockIdx.x] + ccl_block_scan(__popc(bits), wave_tot, block_total);
+#pragma unroll
+  for (int k = 0; k < CCL_SCAN_PER_THREAD; ++k)
+    if ((bits >> k) & 1u) rank[first + k] = ++id;   // bit k set implies first + k < total
+}
+
+// ids[v] = rank of v's root (0 on the background), in place over the parent array: a thread reads only its own
+// parent words and the rank array.  sizes[id - 1] += run length for ids within the capacity.
+__global__ __launch_bounds__(256) void ccl_relabel_kernel(int* __restrict__ ids, const int* __restrict__ rank, i64 total,
+                                                            int* __restrict__ sizes, int capacity) {
+  const i64 first = ((i64)blockIdx.x * 256 + threadIdx.x) * CCL_SCAN_PER_THREAD;
+  int cur = 0, run = 0;
+#pragma unroll
+  for (int k = 0; k < CCL_SCAN_PER_THREAD; ++k) {
+    const i64 idx = first + k;
+    if (idx >= total) break;
+    const int r = ids[idx];
+    const int id = r >= 0 ? rank[r] : 0;
+    ids[idx] = id;
+    if (id != cur) {
+      if (cur > 0 && cur <= capacity) atomicAdd(sizes + (cur - 1), run);
+      cur = id;
+      run = 0;
+    }
+    ++run;
+  }
+  if (cur > 0 && cur <= capacity) atomicAdd(sizes + (cur - 1), run);
+}
+
+static inline i64 ccl_scan_blocks(i64 voxels) { return (voxels + CCL_SCAN_ITEMS - 1) / CCL_SCAN_ITEMS; }
+
+extern "C" long long seg3d_ccl26_label_workspace_ints(long long voxels) {
+  if (voxels <= 0 || voxels >= (1ll << 31)) return -1;
+  return voxels + ccl_scan_blocks(voxels);
+}
+
+extern "C" int seg3d_ccl26_label(const unsigned char* mask, int X, int Y, int Z, int* ids, int* count_device, int* sizes,
+                                 int capacity, int* workspace, void* stream) {
+  SEG3D_REQUIRE(mask && ids && count_device && workspace, "seg3d_ccl26_label: null pointer");
+  SEG3D_REQUIRE(X > 0 && Y > 0 && Z > 0 && (i64)X * Y * Z < (1ll << 31),
+                "seg3d_ccl26_label: bad volume size %d x %d x %d (1 .. 2^31 - 1 voxels)", X, Y, Z);
+  SEG3D_REQUIRE(capacity >= 0 && (capacity == 0 || sizes), "seg3d_ccl26_label: capacity %d without a sizes array", capacity);
+  const i64 total = (i64)X * Y * Z;
+  hipStream_t s = (hipStream_t)stream;
+  int* rank = workspace;
+  int* sums = workspace + total;
+  const int nblocks = (int)ccl_scan_blocks(total);
+  if (capacity > 0 && hipMemsetAsync(sizes, 0, (size_t)capacity * sizeof(int), s) != hipSuccess) {
+    seg3d_set_error("seg3d_ccl26_label: hipMemsetAsync failed");
+    return SEG3D_ERR_LAUNCH;
+  }
+  const dim3 grid(seg3d_ew_grid(total, 256));
+  hipLaunchKernelGGL(ccl_init_mask_kernel, grid, dim3(256), 0, s, mask, ids, total);
+  hipLaunchKernelGGL(ccl_merge_kernel, grid, dim3(256), 0, s, ids, X, Y, Z);
+  hipLaunchKernelGGL(ccl_flatten_kernel, grid, dim3(256), 0, s, ids, total);
+  hipLaunchKernelGGL(ccl_root_sums_kernel, dim3(nblocks), dim3(256), 0, s, (const int*)ids, total, sums);
+  hipLaunchKernelGGL(ccl_scan_sums_kernel, dim3(1), dim3(256), 0, s, sums, nblocks, capacity, count_device);
+  hipLaunchKernelGGL(ccl_rank_apply_kernel, dim3(nblocks), dim3(256), 0, s, (const int*)ids, total, (const int*)sums, rank);
+  hipLaunchKernelGGL(ccl_relabel_kernel, dim3(nblocks), dim3(256), 0, s, ids, (const int*)rank, total, sizes, capacity);
+  SEG3D_LAUNCH_CHECK("seg3d_ccl26_label");
+  return SEG3D_OK;
+}

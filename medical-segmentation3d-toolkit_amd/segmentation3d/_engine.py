@@ -52,6 +52,11 @@ class ClassList(ctypes.Structure):
     """Seg3dClassList: up to 16 class ids, BY VALUE to seg3d_signed_distance"""
     _fields_ = [('id', _c_int * 16)]
 
+
+class LabelSet(ctypes.Structure):
+    """Seg3dLabelSet: 256 membership bits (label l: bit l & 31 of bits[l >> 5]), BY VALUE to seg3d_label_set_mask"""
+    _fields_ = [('bits', ctypes.c_uint * 8)]
+
 # name -> (restype, argtypes); keep in sync with include/seg3d_hip.h (tests/test_abi.py checks every symbol)
 _SIGNATURES = {
     'seg3d_last_error': (ctypes.c_char_p, []),
@@ -249,6 +254,12 @@ _SIGNATURES = {
     'seg3d_patch_gather_normalize_mc_flip': (_c_int, [_c_p] * 5 + [_c_int] * 8 + [Normalizers, _c_int, _c_p]),
     'seg3d_patch_scatter_blend': (_c_int, [_c_p] * 6 + [_c_int] * 8 + [_c_ll, _c_p]),
     'seg3d_ensemble_accumulate': (_c_int, [_c_p] * 3 + [_c_int] * 7 + [_c_p, _c_f, _c_int, _c_f, _c_p, _c_p]),
+    'seg3d_label_set_mask': (_c_int, [_c_p, _c_int, _c_ll, LabelSet, _c_p, _c_p]),
+    'seg3d_binary_dilate18': (_c_int, [_c_p] * 3 + [_c_int] * 4 + [_c_p]),
+    'seg3d_ccl26_label_workspace_ints': (_c_ll, [_c_ll]),
+    'seg3d_ccl26_label': (_c_int, [_c_p] + [_c_int] * 3 + [_c_p] * 3 + [_c_int, _c_p, _c_p]),
+    'seg3d_lesion_pairs': (_c_int, [_c_p] * 3 + [_c_ll, _c_int] + [_c_p] * 3 + [_c_ll, _c_int, _c_p, _c_p]),
+    'seg3d_lesion_select': (_c_int, [_c_p] * 4 + [_c_int, _c_int, _c_ll] + [_c_p] * 3),
 }
 
 _lib = None

@@ -1,6 +1,7 @@
 """Dice evaluation metric with the reference's name and return convention (utils/metrics.py:5-37 `cal_dsc`):
 (dsc, seg_type) with seg_type in {'TN', 'FP', 'FN', 'TP'} decided by the voxel-count threshold; and the surface-distance
-metrics HD / HD95 / ASSD (`cal_surface_distances`, which the reference does not have).
+metrics HD / HD95 / ASSD / NSD (`cal_surface_distances`) and the lesion-wise Dice / HD95 with lesion detection counts
+(`cal_lesionwise`), which the reference does not have.
 
 The counting runs on the GPU: ONE pass over the two label volumes (libseg3d_hip.so: seg3d_label_overlap_counts)
 yields area_gt / area_seg / intersection for every requested label; the reference makes three numpy passes per label.
@@ -196,6 +197,14 @@ class _SurfacePlan(object):
             E.call('seg3d_label_surface', E.ptr(vol), self.code, self.X, self.Y, self.Z, int(label), E.ptr(self.surf[k]),
                    E.ptr(self.box), E.ptr(self.box[6 + k:7 + k]), E.stream_ptr())
 
+    def mask_surfaces(self, a, b):
+        """surfaces() for two ready-made 0/1 uint8 device masks of the plan's grid (their label 1) in place of the two
+        label volumes -- the per-lesion masks of cal_lesionwise"""
+        self.box.copy_(self.box_init)
+        for k, vol in enumerate((a, b)):
+            E.call('seg3d_label_surface', E.ptr(vol), _DTYPE_CODES[torch.uint8], self.X, self.Y, self.Z, 1,
+                   E.ptr(self.surf[k]), E.ptr(self.box), E.ptr(self.box[6 + k:7 + k]), E.stream_ptr())
+
     def distances(self, direction, dist2, index=None):
         """launch: squared distances of the query surface to the feature surface into dist2 (+ voxel index), and
         (count, max, sum) into stats[3 * direction ...].  direction 0: D_AB (query dA, feature dB); 1: D_BA"""
@@ -225,7 +234,52 @@ def directed_surface_distances(gt, seg, label, spacing=None):
     return out
 
 
-def cal_surface_distances(gt, seg, labels, spacing=None):
+def check_nsd_tolerance(tau):
+    """None, or the tolerance in millimetres as a float; ValueError unless it is finite and >= 0"""
+    if tau is None:
+        return None
+    try:
+        value = float(tau)
+    except (TypeError, ValueError):
+        raise ValueError('nsd_tolerance must be a number of millimetres, got {!r}'.format(tau))
+    if isinstance(tau, bool) or not math.isfinite(value) or value < 0.0:
+        raise ValueError('nsd_tolerance must be finite and >= 0, got {!r}'.format(tau))
+    return value
+
+
+def _plan_metrics(plan, nsd_tolerance=None):
+    """{'hd', 'hd95', 'assd'} (+ 'nsd' with a tolerance) of the two surfaces that plan.surfaces / plan.mask_surfaces
+    launched last; every value NaN when one of them is empty.  One readback of the counts, one of the statistics."""
+    dev = plan.g.device
+    na, nb = plan.box[6:8].tolist()
+    if na == 0 or nb == 0:
+        out = dict(_NAN_SURFACE)
+        if nsd_tolerance is not None:
+            out['nsd'] = float('nan')
+        return out
+    picks, ranks, within = [plan.stats], [], []
+    for direction, n in enumerate((na, nb)):
+        dist2 = torch.empty(n, dtype=torch.float64, device=dev)
+        plan.distances(direction, dist2)
+        lo, hi, gamma = percentile_ranks(n)
+        ranks.append(gamma)
+        # order statistics of the squared distances are those of the distances (sqrt is monotone)
+        picks.append(torch.stack([torch.kthvalue(dist2, lo + 1).values, torch.kthvalue(dist2, hi + 1).values]))
+        if nsd_tolerance is not None:   # fp64 squared distances against tau * tau in double, counted on the device
+            within.append((dist2 <= nsd_tolerance * nsd_tolerance).sum().to(torch.float64).reshape(1))
+    v = torch.cat(picks + within).tolist()
+    directed = []
+    for direction in (0, 1):
+        count, mx, total = v[3 * direction:3 * direction + 3]
+        a, b = math.sqrt(v[6 + 2 * direction]), math.sqrt(v[7 + 2 * direction])
+        directed.append((int(count), mx, total, percentile_from_order_stats(a, b, ranks[direction])))
+    out = combine_directed(directed[0], directed[1])
+    if nsd_tolerance is not None:
+        out['nsd'] = (int(v[10]) + int(v[11])) / float(na + nb)
+    return out
+
+
+def cal_surface_distances(gt, seg, labels, spacing=None, nsd_tolerance=None):
     """Surface-distance metrics of every label: [{'hd', 'hd95', 'assd'}] as Python floats, in physical units.
 
     For label l: A = (gt == l), B = (seg == l).  The surface dA is the set of voxels of A with at least one of their 6
@@ -235,38 +289,270 @@ def cal_surface_distances(gt, seg, labels, spacing=None):
       HD   = max(max D_AB, max D_BA)
       HD95 = max(P95(D_AB), P95(D_BA)), P95 = numpy.percentile(., 95) with linear interpolation
       ASSD = (sum D_AB + sum D_BA) / (|D_AB| + |D_BA|), summed in fp64
-    If A or B is empty, all three values are NaN.
+      NSD  = (|{d in D_AB : d^2 <= tau^2}| + |{d in D_BA : d^2 <= tau^2}|) / (|D_AB| + |D_BA|)   (normalized surface Dice
+             at tolerance tau = nsd_tolerance; key 'nsd', present only when a tolerance is given)
+    If A or B is empty, all values are NaN.
 
     :param gt, seg: Image3d, numpy arrays or torch tensors, [z, y, x] on one grid
     :param labels: any number of labels
     :param spacing: (sx, sy, sz); default: the Image3d spacing (gt and seg must agree to a relative 1e-6), else 1, 1, 1
+    :param nsd_tolerance: tau in physical units, finite and >= 0; None: no 'nsd' key
     The surfaces, the exact EDT (restricted to the box that encloses both surfaces) and the gather of the distances at
-    the surface voxels run in csrc/surface.hip; HD95 takes two order statistics of the gathered distances on the device.
+    the surface voxels run in csrc/surface.hip; HD95 takes two order statistics of the gathered distances on the device,
+    NSD a count over them.
     """
+    nsd_tolerance = check_nsd_tolerance(nsd_tolerance)
     plan = _SurfacePlan(gt, seg, spacing)
-    dev = plan.g.device
     results = []
     for label in labels:
         plan.surfaces(label)
-        na, nb = plan.box[6:8].tolist()
-        if na == 0 or nb == 0:
-            results.append(dict(_NAN_SURFACE))
+        results.append(_plan_metrics(plan, nsd_tolerance))
+    return results
+
+
+# ---- lesion-wise evaluation (csrc/lesion.hip, csrc/postproc.hip; DESIGN.md section 7 row f18) ---------------------------
+_CCL_CAPACITY = 4096          # components whose sizes one labelling returns without a second launch
+_MIN_PAIR_TABLE = 1024
+
+
+def check_target(target):
+    """a target of the lesion-wise path -> sorted list of distinct label ids in 1..255 (one label l is the set {l})"""
+    if isinstance(target, (int, np.integer)) and not isinstance(target, bool):
+        target = [target]
+    if isinstance(target, (str, bytes)) or not hasattr(target, '__iter__'):
+        raise ValueError('a lesion-wise target is a label id or a set of label ids in 1..255, got {!r}'.format(target))
+    ids = list(target)
+    if not ids:
+        raise ValueError('a lesion-wise target must hold at least one label id')
+    for l in ids:
+        if isinstance(l, bool) or not isinstance(l, (int, float, np.integer, np.floating)) or int(l) != l \
+                or not 1 <= int(l) <= 255:
+            raise ValueError('lesion-wise target {!r}: label id {!r} is not an integer in 1..255'.format(target, l))
+    return sorted(set(int(l) for l in ids))
+
+
+def check_lesion_options(dilation_iters=3, min_lesion_voxels=1, hd95_penalty=374.0):
+    """(dilation_iters, min_lesion_voxels, hd95_penalty) checked: 0..16, >= 1, finite and >= 0 (defaults: BraTS-GLI)"""
+    for name, v in (('dilation_iters', dilation_iters), ('min_lesion_voxels', min_lesion_voxels)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError('{} must be an integer, got {!r}'.format(name, v))
+    if not 0 <= dilation_iters <= 16:
+        raise ValueError('dilation_iters must be in 0..16, got {}'.format(dilation_iters))
+    if min_lesion_voxels < 1:
+        raise ValueError('min_lesion_voxels must be at least 1, got {}'.format(min_lesion_voxels))
+    try:
+        penalty = float(hd95_penalty)
+    except (TypeError, ValueError):
+        raise ValueError('hd95_penalty must be a number, got {!r}'.format(hd95_penalty))
+    if isinstance(hd95_penalty, bool) or not math.isfinite(penalty) or penalty < 0.0:
+        raise ValueError('hd95_penalty must be finite and >= 0, got {!r}'.format(hd95_penalty))
+    return int(dilation_iters), int(min_lesion_voxels), penalty
+
+
+def lesionwise_from_table(gt_sizes, inter, pred_sizes, pairs, hd95_of, min_lesion_voxels=1, hd95_penalty=374.0):
+    """The host half of the lesion-wise score, from exact integers, in doubles.
+
+    :param gt_sizes: |G_i| for the lesions i = 1..Kg (gt_sizes[i - 1])
+    :param inter: |G_i n B| likewise
+    :param pred_sizes: |P_j| for the predicted components j = 1..Kp
+    :param pairs: the (i, j) with P_j touching the dilated lesion D_i
+    :param hd95_of: callable (i, matched ids) -> HD95 between G_i and the union U_i of its matched components
+    A lesion without a match is a false negative (dice 0, hd95 = hd95_penalty); a lesion below min_lesion_voxels is
+    dropped after matching (neither scored nor FN, its matches are no false positives); a component in no M_i is a
+    false positive.  With n = kept + FP: lw_dice = sum dice / n, lw_hd95 = (sum hd95 + penalty * FP) / n (1 and 0 when
+    n = 0), lesion_f1 = 2 TP / (2 TP + FN + FP) (1 when the denominator is 0).
+    :return: {'lw_dice', 'lw_hd95', 'n_gt', 'n_tp', 'n_fn', 'n_fp', 'lesion_f1', 'lesions'}; 'lesions' lists
+             (id, voxels, dice, hd95, matched ids) of every kept lesion"""
+    _, min_lesion_voxels, hd95_penalty = check_lesion_options(0, min_lesion_voxels, hd95_penalty)
+    gt_sizes, inter, pred_sizes = [int(v) for v in gt_sizes], [int(v) for v in inter], [int(v) for v in pred_sizes]
+    if len(inter) != len(gt_sizes):
+        raise ValueError('gt_sizes and inter differ in length: {} vs {}'.format(len(gt_sizes), len(inter)))
+    matched = {}
+    for i, j in pairs:
+        i, j = int(i), int(j)
+        if not (1 <= i <= len(gt_sizes) and 1 <= j <= len(pred_sizes)):
+            raise ValueError('pair ({}, {}) outside 1..{} x 1..{}'.format(i, j, len(gt_sizes), len(pred_sizes)))
+        matched.setdefault(i, set()).add(j)
+    used, lesions = set(), []
+    sum_dice = sum_hd95 = 0.0
+    n_tp = n_fn = 0
+    for i, voxels in enumerate(gt_sizes, 1):
+        ids = tuple(sorted(matched.get(i, ())))
+        used.update(ids)
+        if voxels < min_lesion_voxels:
             continue
-        picks, ranks = [plan.stats], []
-        for direction, n in enumerate((na, nb)):
-            dist2 = torch.empty(n, dtype=torch.float64, device=dev)
-            plan.distances(direction, dist2)
-            lo, hi, gamma = percentile_ranks(n)
-            ranks.append(gamma)
-            # order statistics of the squared distances are those of the distances (sqrt is monotone)
-            picks.append(torch.stack([torch.kthvalue(dist2, lo + 1).values, torch.kthvalue(dist2, hi + 1).values]))
-        v = torch.cat(picks).tolist()
-        directed = []
-        for direction in (0, 1):
-            count, mx, total = v[3 * direction:3 * direction + 3]
-            a, b = math.sqrt(v[6 + 2 * direction]), math.sqrt(v[7 + 2 * direction])
-            directed.append((int(count), mx, total, percentile_from_order_stats(a, b, ranks[direction])))
-        results.append(combine_directed(directed[0], directed[1]))
+        if ids:
+            union = sum(pred_sizes[j - 1] for j in ids)
+            dice = 2.0 * inter[i - 1] / float(voxels + union)
+            hd95 = float(hd95_of(i, ids))
+            n_tp += 1
+        else:
+            dice, hd95 = 0.0, hd95_penalty
+            n_fn += 1
+        sum_dice += dice
+        sum_hd95 += hd95
+        lesions.append((i, voxels, dice, hd95, ids))
+    n_fp = len(pred_sizes) - len(used)
+    n = len(lesions) + n_fp
+    f1_den = 2 * n_tp + n_fn + n_fp
+    return {'lw_dice': sum_dice / n if n else 1.0,
+            'lw_hd95': (sum_hd95 + hd95_penalty * n_fp) / n if n else 0.0,
+            'n_gt': len(lesions), 'n_tp': n_tp, 'n_fn': n_fn, 'n_fp': n_fp,
+            'lesion_f1': 2.0 * n_tp / f1_den if f1_den else 1.0,
+            'lesions': lesions}
+
+
+def _label_set(ids):
+    bits = [0] * 8
+    for l in ids:
+        bits[l >> 5] |= 1 << (l & 31)
+    return E.LabelSet((ctypes.c_uint * 8)(*bits))
+
+
+def _set_mask(vol, ids):
+    """launch: flat uint8 0/1 mask of the voxels of the device label volume whose value is in ids"""
+    mask = torch.empty(vol.numel(), dtype=torch.uint8, device=vol.device)
+    E.call('seg3d_label_set_mask', E.ptr(vol), _DTYPE_CODES[vol.dtype], vol.numel(), _label_set(ids), E.ptr(mask),
+           E.stream_ptr())
+    return mask
+
+
+def _dilate18(mask, shape, iters):
+    """launch: the flat mask dilated iters times by the 18-neighbourhood (iters = 0: the mask itself)"""
+    if iters == 0:
+        return mask
+    Z, Y, X = shape
+    out = torch.empty_like(mask)
+    work = torch.empty_like(mask) if iters >= 2 else None
+    E.call('seg3d_binary_dilate18', E.ptr(mask), E.ptr(out), E.ptr(work), X, Y, Z, iters, E.stream_ptr())
+    return out
+
+
+def _ccl26(mask, shape, capacity):
+    """launch: (flat int32 id map, int32 (K, K > capacity), int32 sizes[capacity]) of the mask's 26-connected components"""
+    Z, Y, X = shape
+    n = mask.numel()
+    words = E.query('seg3d_ccl26_label_workspace_ints', n)
+    if words < 0:
+        raise ValueError('volume of {} voxels is too large (limit 2^31 - 1)'.format(n))
+    ids = torch.empty(n, dtype=torch.int32, device=mask.device)
+    count = torch.empty(2, dtype=torch.int32, device=mask.device)
+    sizes = torch.empty(capacity, dtype=torch.int32, device=mask.device) if capacity else None
+    work = torch.empty(words, dtype=torch.int32, device=mask.device)
+    E.call('seg3d_ccl26_label', E.ptr(mask), X, Y, Z, E.ptr(ids), E.ptr(count), E.ptr(sizes), capacity, E.ptr(work),
+           E.stream_ptr())
+    return ids, count, sizes
+
+
+def _volume3d(vol, device):
+    if device is None:
+        device = vol.device if isinstance(vol, torch.Tensor) and vol.is_cuda else torch.device(
+            'cuda', torch.cuda.current_device())
+    v = _as_device_labels(vol, device)
+    if v.dim() != 3:
+        raise ValueError('expected one 3-D [z, y, x] grid, got shape {}'.format(tuple(v.shape)))
+    E.require_device(v)
+    return v
+
+
+def lesion_components(vol, target, dilation_iters=0, device=None):
+    """26-connected components of the voxels of `vol` whose label is in `target`, after dilation_iters dilations by the
+    18-neighbourhood: (id map as a device int32 tensor [z, y, x], K, sizes).  Ids 1..K follow each component's lowest
+    linear voxel index (z * Y + y) * X + x; sizes[k - 1] is the voxel count of component k (of the dilated mask)."""
+    ids = check_target(target)
+    iters = check_lesion_options(dilation_iters)[0]
+    v = _volume3d(vol, device)
+    shape = tuple(int(d) for d in v.shape)
+    mask = _dilate18(_set_mask(v, ids), shape, iters)
+    capacity = _CCL_CAPACITY
+    while True:
+        idmap, count, sizes = _ccl26(mask, shape, capacity)
+        host = torch.cat([count, sizes]).tolist()
+        if not host[1]:
+            return idmap.view(shape), host[0], host[2:2 + host[0]]
+        capacity = host[0]
+
+
+def lesion_pair_table(dmap, a, pmap, kg, capacity=None, extra=()):
+    """|G_i|, |G_i n B| for i = 1..kg and the sorted distinct (i, j) pairs with dmap = i > 0 and pmap = j > 0, from one
+    pass over the three device arrays (seg3d_lesion_pairs).  The pair set is a device hash table of `capacity` words
+    (a power of two; default 4 * kg, at least 1024); when it overflows the table is doubled and the launch repeated.
+    `extra`: small device integer tensors read back in the same transfer.
+    :return: (gsize list, inter list, pairs list, [extra as lists])"""
+    if capacity is None:
+        capacity = _MIN_PAIR_TABLE
+        while capacity < 4 * kg:
+            capacity *= 2
+    if capacity < 1 or capacity & (capacity - 1):
+        raise ValueError('pair table capacity must be a power of two, got {}'.format(capacity))
+    dmap, pmap, a = dmap.reshape(-1), pmap.reshape(-1), a.reshape(-1)
+    E.require_device(dmap, a, pmap)
+    n = dmap.numel()
+    while True:
+        words = torch.zeros(2 * (kg + 1) + capacity, dtype=torch.int64, device=dmap.device)
+        status = torch.zeros(1, dtype=torch.int32, device=dmap.device)
+        gsize, inter, table = words[:kg + 1], words[kg + 1:2 * (kg + 1)], words[2 * (kg + 1):]
+        E.call('seg3d_lesion_pairs', E.ptr(dmap), E.ptr(a), E.ptr(pmap), n, kg, E.ptr(gsize), E.ptr(inter), E.ptr(table),
+               capacity, 1, E.ptr(status), E.stream_ptr())
+        parts = [status.to(torch.int64), words] + [t.reshape(-1).to(torch.int64) for t in extra]
+        host = torch.cat(parts).cpu().numpy()
+        if not host[0]:
+            break
+        capacity *= 2
+    body = host[1:1 + words.numel()]
+    keys = np.sort(body[2 * (kg + 1):][body[2 * (kg + 1):] != 0])
+    pairs = [(int(k >> 32), int(k & 0xffffffff)) for k in keys]
+    extras, at = [], 1 + words.numel()
+    for t in extra:
+        extras.append(host[at:at + t.numel()].tolist())
+        at += t.numel()
+    return body[1:kg + 1].tolist(), body[kg + 2:2 * (kg + 1)].tolist(), pairs, extras
+
+
+def cal_lesionwise(gt, seg, targets, spacing=None, dilation_iters=3, min_lesion_voxels=1, hd95_penalty=374.0):
+    """Lesion-wise Dice / HD95 and lesion detection counts of every target (BraTS 2023 lesion-wise ranking rule).
+
+    A target is a label id or a set of label ids in 1..255.  A = ground-truth voxels in the target, B = segmentation
+    voxels in the target.  A is dilated dilation_iters times by the 18-neighbourhood; the 26-connected components D_i of
+    the result are the lesions, G_i = A n D_i; P_j are the 26-connected components of B.  Component ids follow the lowest
+    linear voxel index.  M_i = {j : P_j touches D_i}, U_i its union (a component may count in several lesions);
+    dice_i = 2 |G_i n U_i| / (|G_i| + |U_i|) and hd95_i = HD95(G_i, U_i) as cal_surface_distances defines it, or 0 and
+    hd95_penalty for an unmatched lesion.  Aggregation: lesionwise_from_table.
+
+    :param gt, seg, spacing: as cal_surface_distances
+    :return: one dict per target: 'lw_dice', 'lw_hd95', 'n_gt', 'n_tp', 'n_fn', 'n_fp', 'lesion_f1', 'lesions'
+    Masks, dilation, labelling, pair table and the per-lesion masks and distances run on the device; the pair list, the
+    counts and the sizes come back in one transfer per target, distance arrays never leave the device."""
+    iters, min_lesion_voxels, hd95_penalty = check_lesion_options(dilation_iters, min_lesion_voxels, hd95_penalty)
+    targets = [check_target(t) for t in targets]
+    plan = _SurfacePlan(gt, seg, spacing)
+    dev, n, shape = plan.g.device, plan.g.numel(), (plan.Z, plan.Y, plan.X)
+    g_mask = torch.empty(n, dtype=torch.uint8, device=dev)
+    u_mask = torch.empty(n, dtype=torch.uint8, device=dev)
+    results = []
+    for ids in targets:
+        a, b = _set_mask(plan.g, ids), _set_mask(plan.s, ids)
+        grown = _dilate18(a, shape, iters)
+        capacity = _CCL_CAPACITY
+        while True:
+            dmap, dcount, _ = _ccl26(grown, shape, 0)
+            pmap, pcount, psizes = _ccl26(b, shape, capacity)
+            gsize, inter, pairs, (dc, pc, ps) = lesion_pair_table(dmap, a, pmap, capacity, extra=(dcount, pcount, psizes))
+            kg, kp = dc[0], pc[0]
+            if max(kg, kp) <= capacity:
+                break
+            capacity = max(kg, kp)
+
+        def hd95_of(i, matched, dmap=dmap, a=a, pmap=pmap, kp=kp):
+            flag = np.zeros(kp + 1, np.uint8)
+            flag[list(matched)] = 1
+            E.call('seg3d_lesion_select', E.ptr(dmap), E.ptr(a), E.ptr(pmap), E.ptr(torch.from_numpy(flag).to(dev)), kp,
+                   i, n, E.ptr(g_mask), E.ptr(u_mask), E.stream_ptr())
+            plan.mask_surfaces(g_mask, u_mask)
+            return _plan_metrics(plan)['hd95']
+
+        results.append(lesionwise_from_table(gsize[:kg], inter[:kg], ps[:kp], pairs, hd95_of, min_lesion_voxels,
+                                             hd95_penalty))
     return results
 
 
