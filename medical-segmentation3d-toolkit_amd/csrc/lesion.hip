@@ -10,17 +10,14 @@
 //   seg3d_lesion_select     the two masks of lesion i, g = (Dmap == i) & A and u = flag[Pmap], for the surface entries
 // Everything is integer work with integer atomics: exact and identical from run to run.  No workgroup waits on another;
 // every loop has a bound known at launch.  All five are HBM byte movers.
-#include "seg3d_common.h"
+#include "label_device.h"
 #include "seg3d_hip.h"
 
 // ---- set membership ---------------------------------------------------------------------------------------------------
-// a value that is no integer in [0, 256) is outside the set (the rule of metrics.hip's region_bits)
 template <typename T>
 __device__ __forceinline__ bool lesion_in_set(T x, const Seg3dLabelSet& set) {
-  const float f = (float)x;   // exact for every value in [0, 256) of the five types; larger ints may round but stay >= 256
-  if (!(f >= 0.0f && f < 256.0f && f == floorf(f))) return false;
-  const int l = (int)f;
-  return (set.bits[l >> 5] >> (l & 31)) & 1u;
+  const int l = label_byte<T>(x);
+  return l >= 0 && ((set.bits[l >> 5] >> (l & 31)) & 1u);
 }
 
 template <typename T>
@@ -30,24 +27,16 @@ __global__ __launch_bounds__(256) void label_set_mask_kernel(const T* __restrict
     mask[i] = lesion_in_set<T>(vol[i], set) ? 1 : 0;
 }
 
-template <typename T>
-static void launch_set_mask(const void* vol, i64 n, const Seg3dLabelSet& set, unsigned char* mask, hipStream_t s) {
-  hipLaunchKernelGGL((label_set_mask_kernel<T>), dim3(seg3d_ew_grid(n, 256)), dim3(256), 0, s, (const T*)vol, n, set, mask);
-}
-
 extern "C" int seg3d_label_set_mask(const void* labels, int dtype, long long n, Seg3dLabelSet set, unsigned char* mask,
                                     void* stream) {
   SEG3D_REQUIRE(labels && mask, "seg3d_label_set_mask: null pointer");
   SEG3D_REQUIRE(n > 0 && n < (1ll << 31), "seg3d_label_set_mask: bad element count %lld (1 .. 2^31 - 1)", n);
-  hipStream_t s = (hipStream_t)stream;
-  switch (dtype) {
-    case 0: launch_set_mask<signed char>(labels, n, set, mask, s); break;
-    case 1: launch_set_mask<unsigned char>(labels, n, set, mask, s); break;
-    case 2: launch_set_mask<short>(labels, n, set, mask, s); break;
-    case 3: launch_set_mask<int>(labels, n, set, mask, s); break;
-    case 4: launch_set_mask<float>(labels, n, set, mask, s); break;
-    default: SEG3D_UNSUPPORTED("seg3d_label_set_mask: unknown dtype code %d", dtype);
-  }
+  const int rc = label_dispatch(dtype, "seg3d_label_set_mask", [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((label_set_mask_kernel<T>), dim3(seg3d_ew_grid(n, 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const T*)labels, (i64)n, set, mask);
+  });
+  if (rc != SEG3D_OK) return rc;
   SEG3D_LAUNCH_CHECK("seg3d_label_set_mask");
   return SEG3D_OK;
 }

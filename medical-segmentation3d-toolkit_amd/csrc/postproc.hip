@@ -13,6 +13,7 @@
 //   voxel in raster order -- the labels here are the component's smallest linear index, which gives the same order.
 // All kernels are HBM-bound byte movers / integer work.
 #include "seg3d_imagegrid.h"
+#include "label_device.h"
 #include "mc_device.h"
 #include "seg3d_hip.h"
 
@@ -295,7 +296,7 @@ struct LabelSet {
 
 __global__ __launch_bounds__(256) void mask_bbox_kernel(const signed char* __restrict__ mask, int X, int Y, int Z, LabelSet ls,
                                                           int* __restrict__ box /* xmin ymin zmin xmax ymax zmax */) {
-  int lo[3] = {0x7fffffff, 0x7fffffff, 0x7fffffff}, hi[3] = {-1, -1, -1};
+  LabelBox bx;
   const i64 total = (i64)X * Y * Z;
   for (i64 idx = (i64)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (i64)gridDim.x * 256) {
     const int m = mask[idx];
@@ -310,27 +311,10 @@ __global__ __launch_bounds__(256) void mask_bbox_kernel(const signed char* __res
       const int x = (int)(idx % X);
       const i64 t = idx / X;
       const int y = (int)(t % Y), z = (int)(t / Y);
-      lo[0] = min(lo[0], x); lo[1] = min(lo[1], y); lo[2] = min(lo[2], z);
-      hi[0] = max(hi[0], x); hi[1] = max(hi[1], y); hi[2] = max(hi[2], z);
+      bx.add(x, y, z);
     }
   }
-#pragma unroll
-  for (int d = 0; d < 3; ++d) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      lo[d] = min(lo[d], __shfl_down(lo[d], off, 64));
-      hi[d] = max(hi[d], __shfl_down(hi[d], off, 64));
-    }
-  }
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-      if (hi[d] >= 0) {
-        atomicMin(box + d, lo[d]);
-        atomicMax(box + 3 + d, hi[d]);
-      }
-    }
-  }
+  bx.wave_commit(box);
 }
 
 // box_device[6] must be initialised to {INT_MAX x3, -1 x3}; afterwards (xmin, ymin, zmin, xmax, ymax, zmax) inclusive, or
@@ -379,10 +363,20 @@ __device__ __forceinline__ void ccl_union(int* parent, int a, int b) {
   }
 }
 
-__global__ __launch_bounds__(256) void ccl_init_kernel(const signed char* __restrict__ mask, int label, int* __restrict__ parent,
+// foreground predicates of the two entries
+struct CclEqual {
+  int label;
+  __device__ __forceinline__ bool operator()(int m) const { return m == label; }
+};
+struct CclNonZero {
+  __device__ __forceinline__ bool operator()(int m) const { return m != 0; }
+};
+
+template <typename T, typename Pred>
+__global__ __launch_bounds__(256) void ccl_init_kernel(const T* __restrict__ mask, Pred foreground, int* __restrict__ parent,
                                                          i64 total) {
   for (i64 idx = (i64)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (i64)gridDim.x * 256)
-    parent[idx] = mask[idx] == label ? (int)idx : -1;
+    parent[idx] = foreground(mask[idx]) ? (int)idx : -1;
 }
 
 __global__ __launch_bounds__(256) void ccl_merge_kernel(int* __restrict__ parent, int X, int Y, int Z) {
@@ -413,21 +407,44 @@ __global__ __launch_bounds__(256) void ccl_flatten_kernel(int* __restrict__ pare
     if (parent[idx] >= 0) parent[idx] = ccl_find(parent, (int)idx);
 }
 
-// sizes[root] += run length; a thread walks 32 consecutive voxels and flushes one atomic per run of equal roots
-__global__ __launch_bounds__(256) void ccl_count_kernel(const int* __restrict__ parent, int* __restrict__ sizes, i64 total) {
-  const i64 base = ((i64)blockIdx.x * 256 + threadIdx.x) * 32;
-  int cur = -1, run = 0;
-  for (int k = 0; k < 32; ++k) {
-    const i64 idx = base + k;
-    const int r = idx < total ? parent[idx] : -1;
-    if (r != cur) {
-      if (cur >= 0) atomicAdd(sizes + cur, run);
-      cur = r;
+// parent = the flattened forest of the foreground of `mask`: every foreground voxel holds its component's lowest linear index
+template <typename T, typename Pred>
+static void ccl_forest(const T* mask, Pred foreground, int* parent, int X, int Y, int Z, hipStream_t s) {
+  const i64 total = (i64)X * Y * Z;
+  const dim3 grid(seg3d_ew_grid(total, 256));
+  hipLaunchKernelGGL((ccl_init_kernel<T, Pred>), grid, dim3(256), 0, s, mask, foreground, parent, total);
+  hipLaunchKernelGGL(ccl_merge_kernel, grid, dim3(256), 0, s, parent, X, Y, Z);
+  hipLaunchKernelGGL(ccl_flatten_kernel, grid, dim3(256), 0, s, parent, total);
+}
+
+// sizes[id - first] += run length for the ids in first .. last, one atomic per run of equal ids among the consecutive voxels
+// a thread walks: next(id) per voxel, flush() after the last.  Ids outside first .. last are counted nowhere.
+struct CclRunAdd {
+  int* sizes;
+  int first, last;
+  int cur = first - 1, run = 0;
+  __device__ __forceinline__ void flush() {
+    if (cur >= first && cur <= last) atomicAdd(sizes + (cur - first), run);
+  }
+  __device__ __forceinline__ void next(int id) {
+    if (id != cur) {
+      flush();
+      cur = id;
       run = 0;
     }
     ++run;
   }
-  if (cur >= 0) atomicAdd(sizes + cur, run);
+};
+
+// sizes[root] += run length; a thread walks 32 consecutive voxels
+__global__ __launch_bounds__(256) void ccl_count_kernel(const int* __restrict__ parent, int* __restrict__ sizes, i64 total) {
+  const i64 base = ((i64)blockIdx.x * 256 + threadIdx.x) * 32;
+  CclRunAdd runs{sizes, 0, INT_MAX};
+  for (int k = 0; k < 32; ++k) {
+    const i64 idx = base + k;
+    runs.next(idx < total ? parent[idx] : -1);
+  }
+  runs.flush();
 }
 
 // best = max over roots of (size << 32 | ~root): the largest component, ties to the smallest root (first in raster order)
@@ -484,9 +501,7 @@ extern "C" int seg3d_ccl26_select(const signed char* mask, int label, int X, int
     seg3d_set_error("seg3d_ccl26_select: hipMemsetAsync failed");
     return SEG3D_ERR_LAUNCH;
   }
-  hipLaunchKernelGGL(ccl_init_kernel, grid, dim3(256), 0, s, mask, label, parent, total);
-  hipLaunchKernelGGL(ccl_merge_kernel, grid, dim3(256), 0, s, parent, X, Y, Z);
-  hipLaunchKernelGGL(ccl_flatten_kernel, grid, dim3(256), 0, s, parent, total);
+  ccl_forest(mask, CclEqual{label}, parent, X, Y, Z, s);
   hipLaunchKernelGGL(ccl_count_kernel, dim3((unsigned)((total + 256 * 32 - 1) / (256 * 32))), dim3(256), 0, s, parent, sizes,
                      total);
   hipLaunchKernelGGL(ccl_best_kernel, grid, dim3(256), 0, s, parent, sizes, best, total);
@@ -506,12 +521,6 @@ extern "C" int seg3d_ccl26_select(const signed char* mask, int label, int X, int
 // another.  A last pass maps every voxel to its root's rank and adds run lengths to the size histogram (integer atomics).
 #define CCL_SCAN_PER_THREAD 16
 #define CCL_SCAN_ITEMS (256 * CCL_SCAN_PER_THREAD)
-
-__global__ __launch_bounds__(256) void ccl_init_mask_kernel(const unsigned char* __restrict__ mask, int* __restrict__ parent,
-                                                              i64 total) {
-  for (i64 idx = (i64)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (i64)gridDim.x * 256)
-    parent[idx] = mask[idx] ? (int)idx : -1;
-}
 
 // exclusive prefix of v over the 256 threads of the block (thread order); total: the block's sum.  wave_tot: 4 shared ints
 __device__ __forceinline__ int ccl_block_scan(int v, int* wave_tot, int& total) {
@@ -592,7 +601,7 @@ __global__ __launch_bounds__(256) void ccl_rank_apply_kernel(const int* __restri
 __global__ __launch_bounds__(256) void ccl_relabel_kernel(int* __restrict__ ids, const int* __restrict__ rank, i64 total,
                                                             int* __restrict__ sizes, int capacity) {
   const i64 first = ((i64)blockIdx.x * 256 + threadIdx.x) * CCL_SCAN_PER_THREAD;
-  int cur = 0, run = 0;
+  CclRunAdd runs{sizes, 1, capacity};
 #pragma unroll
   for (int k = 0; k < CCL_SCAN_PER_THREAD; ++k) {
     const i64 idx = first + k;
@@ -600,14 +609,9 @@ __global__ __launch_bounds__(256) void ccl_relabel_kernel(int* __restrict__ ids,
     const int r = ids[idx];
     const int id = r >= 0 ? rank[r] : 0;
     ids[idx] = id;
-    if (id != cur) {
-      if (cur > 0 && cur <= capacity) atomicAdd(sizes + (cur - 1), run);
-      cur = id;
-      run = 0;
-    }
-    ++run;
+    runs.next(id);
   }
-  if (cur > 0 && cur <= capacity) atomicAdd(sizes + (cur - 1), run);
+  runs.flush();
 }
 
 static inline i64 ccl_scan_blocks(i64 voxels) { return (voxels + CCL_SCAN_ITEMS - 1) / CCL_SCAN_ITEMS; }
@@ -632,10 +636,7 @@ extern "C" int seg3d_ccl26_label(const unsigned char* mask, int X, int Y, int Z,
     seg3d_set_error("seg3d_ccl26_label: hipMemsetAsync failed");
     return SEG3D_ERR_LAUNCH;
   }
-  const dim3 grid(seg3d_ew_grid(total, 256));
-  hipLaunchKernelGGL(ccl_init_mask_kernel, grid, dim3(256), 0, s, mask, ids, total);
-  hipLaunchKernelGGL(ccl_merge_kernel, grid, dim3(256), 0, s, ids, X, Y, Z);
-  hipLaunchKernelGGL(ccl_flatten_kernel, grid, dim3(256), 0, s, ids, total);
+  ccl_forest(mask, CclNonZero{}, ids, X, Y, Z, s);
   hipLaunchKernelGGL(ccl_root_sums_kernel, dim3(nblocks), dim3(256), 0, s, (const int*)ids, total, sums);
   hipLaunchKernelGGL(ccl_scan_sums_kernel, dim3(1), dim3(256), 0, s, sums, nblocks, capacity, count_device);
   hipLaunchKernelGGL(ccl_rank_apply_kernel, dim3(nblocks), dim3(256), 0, s, (const int*)ids, total, (const int*)sums, rank);

@@ -20,9 +20,7 @@
 // correctly rounded quotient of two such integers is the exact floor, so the squared distances are exact.
 // The box is read on the device: grids are sized from (X, Y, Z) alone, nothing synchronises or allocates, and the
 // launches can be captured.
-#include <limits.h>
-
-#include "seg3d_common.h"
+#include "label_device.h"
 #include "seg3d_hip.h"
 
 #define SURF_BLOCK 256
@@ -53,7 +51,8 @@ __global__ __launch_bounds__(SURF_BLOCK) void label_surface_kernel(const T* __re
                                                                    unsigned char* __restrict__ surf, int* __restrict__ box,
                                                                    int* __restrict__ count) {
   const unsigned XY = (unsigned)X * (unsigned)Y, n = XY * (unsigned)Z;
-  int cnt = 0, x0 = INT_MAX, y0 = INT_MAX, z0 = INT_MAX, x1 = -1, y1 = -1, z1 = -1;
+  int cnt = 0;
+  LabelBox bx;
   for (unsigned i = blockIdx.x * SURF_BLOCK + threadIdx.x; i < n; i += gridDim.x * SURF_BLOCK) {
     const int x = (int)(i % (unsigned)X), y = (int)((i / (unsigned)X) % (unsigned)Y), z = (int)(i / XY);
     bool s = false;
@@ -65,29 +64,13 @@ __global__ __launch_bounds__(SURF_BLOCK) void label_surface_kernel(const T* __re
     surf[i] = s ? 1 : 0;
     if (s) {
       ++cnt;
-      x0 = min(x0, x); y0 = min(y0, y); z0 = min(z0, z);
-      x1 = max(x1, x); y1 = max(y1, y); z1 = max(z1, z);
+      bx.add(x, y, z);
     }
   }
 #pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    cnt += __shfl_down(cnt, off, 64);
-    x0 = min(x0, __shfl_down(x0, off, 64)); y0 = min(y0, __shfl_down(y0, off, 64)); z0 = min(z0, __shfl_down(z0, off, 64));
-    x1 = max(x1, __shfl_down(x1, off, 64)); y1 = max(y1, __shfl_down(y1, off, 64)); z1 = max(z1, __shfl_down(z1, off, 64));
-  }
-  if ((threadIdx.x & 63) == 0 && cnt > 0) {   // one set of atomics per wave that found surface voxels
-    atomicAdd(count, cnt);
-    atomicMin(box + 0, x0); atomicMin(box + 1, y0); atomicMin(box + 2, z0);
-    atomicMax(box + 3, x1); atomicMax(box + 4, y1); atomicMax(box + 5, z1);
-  }
-}
-
-template <typename T>
-static void launch_surface(const void* vol, int X, int Y, int Z, int label, unsigned char* surf, int* box, int* count,
-                           hipStream_t s) {
-  const i64 n = (i64)X * Y * Z;
-  hipLaunchKernelGGL((label_surface_kernel<T>), dim3(seg3d_ew_grid(n, SURF_BLOCK)), dim3(SURF_BLOCK), 0, s, (const T*)vol,
-                     X, Y, Z, (T)label, surf, box, count);
+  for (int off = 32; off > 0; off >>= 1) cnt += __shfl_down(cnt, off, 64);
+  if ((threadIdx.x & 63) == 0 && cnt > 0) atomicAdd(count, cnt);   // like the box: per wave that found surface voxels
+  bx.wave_commit(box);
 }
 
 extern "C" int seg3d_label_surface(const void* labels, int dtype, int X, int Y, int Z, int label, unsigned char* surface,
@@ -95,15 +78,12 @@ extern "C" int seg3d_label_surface(const void* labels, int dtype, int X, int Y, 
   SEG3D_REQUIRE(labels && surface && box_device && count_device, "seg3d_label_surface: null pointer");
   SEG3D_REQUIRE(X > 0 && Y > 0 && Z > 0 && (i64)X * Y * Z < (1ll << 31),
                 "seg3d_label_surface: bad volume size %d x %d x %d (1 .. 2^31 - 1 voxels)", X, Y, Z);
-  hipStream_t s = (hipStream_t)stream;
-  switch (dtype) {
-    case 0: launch_surface<signed char>(labels, X, Y, Z, label, surface, box_device, count_device, s); break;
-    case 1: launch_surface<unsigned char>(labels, X, Y, Z, label, surface, box_device, count_device, s); break;
-    case 2: launch_surface<short>(labels, X, Y, Z, label, surface, box_device, count_device, s); break;
-    case 3: launch_surface<int>(labels, X, Y, Z, label, surface, box_device, count_device, s); break;
-    case 4: launch_surface<float>(labels, X, Y, Z, label, surface, box_device, count_device, s); break;
-    default: SEG3D_UNSUPPORTED("seg3d_label_surface: unknown dtype code %d", dtype);
-  }
+  const int rc = label_dispatch(dtype, "seg3d_label_surface", [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((label_surface_kernel<T>), dim3(seg3d_ew_grid((i64)X * Y * Z, SURF_BLOCK)), dim3(SURF_BLOCK), 0,
+                       (hipStream_t)stream, (const T*)labels, X, Y, Z, (T)label, surface, box_device, count_device);
+  });
+  if (rc != SEG3D_OK) return rc;
   SEG3D_LAUNCH_CHECK("seg3d_label_surface");
   return SEG3D_OK;
 }
@@ -224,6 +204,33 @@ __global__ __launch_bounds__(SURF_BLOCK) void edt_cols_y_kernel(const int* __res
   }
 }
 
+// (count, max, sum) over the workgroup in a fixed order: the wave tree, then waves 0 .. 3 one after the other from zero.
+// The result is valid in thread 0.
+__device__ __forceinline__ void surf_stats_block_reduce(double& count, double& mx, double& sum,
+                                                        double (&red)[SURF_BLOCK / 64][3]) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    count += __shfl_down(count, off, 64);
+    mx = fmax(mx, __shfl_down(mx, off, 64));
+    sum += __shfl_down(sum, off, 64);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    const int wave = threadIdx.x >> 6;
+    red[wave][0] = count;
+    red[wave][1] = mx;
+    red[wave][2] = sum;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    count = mx = sum = 0.0;
+    for (int w = 0; w < SURF_BLOCK / 64; ++w) {
+      count += red[w][0];
+      mx = fmax(mx, red[w][1]);
+      sum += red[w][2];
+    }
+  }
+}
+
 // pass z: columns (y, x) of the box, input f2, emits the squared distance at every query voxel of the column
 __global__ __launch_bounds__(SURF_BLOCK) void edt_cols_z_query_kernel(
     const double* __restrict__ f2, const unsigned char* __restrict__ query, const int* __restrict__ box, int X, int Y, int Z,
@@ -271,31 +278,14 @@ __global__ __launch_bounds__(SURF_BLOCK) void edt_cols_z_query_kernel(
       }
     }
   }
-  // fixed-order workgroup reduction -> partials[blockIdx.x] = (count, max d^2, sum d)
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    cnt += __shfl_down(cnt, off, 64);
-    mx = fmax(mx, __shfl_down(mx, off, 64));
-    sum += __shfl_down(sum, off, 64);
-  }
+  // partials[blockIdx.x] = (count, max d^2, sum d)
   __shared__ double red[SURF_BLOCK / 64][3];
-  const int wave = threadIdx.x >> 6;
-  if (lane == 0) {
-    red[wave][0] = (double)cnt;
-    red[wave][1] = mx;
-    red[wave][2] = sum;
-  }
-  __syncthreads();
+  double c = (double)cnt;
+  surf_stats_block_reduce(c, mx, sum, red);
   if (threadIdx.x == 0) {
-    double c = 0.0, m = 0.0, s = 0.0;
-    for (int w = 0; w < SURF_BLOCK / 64; ++w) {
-      c += red[w][0];
-      m = fmax(m, red[w][1]);
-      s += red[w][2];
-    }
     partials[3 * blockIdx.x] = c;
-    partials[3 * blockIdx.x + 1] = m;
-    partials[3 * blockIdx.x + 2] = s;
+    partials[3 * blockIdx.x + 1] = mx;
+    partials[3 * blockIdx.x + 2] = sum;
   }
 }
 
@@ -308,27 +298,9 @@ __global__ __launch_bounds__(SURF_BLOCK) void surface_stats_finalize_kernel(cons
     m = fmax(m, partials[3 * i + 1]);
     s += partials[3 * i + 2];
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    c += __shfl_down(c, off, 64);
-    m = fmax(m, __shfl_down(m, off, 64));
-    s += __shfl_down(s, off, 64);
-  }
   __shared__ double red[SURF_BLOCK / 64][3];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) {
-    red[wave][0] = c;
-    red[wave][1] = m;
-    red[wave][2] = s;
-  }
-  __syncthreads();
+  surf_stats_block_reduce(c, m, s, red);
   if (threadIdx.x == 0) {
-    c = m = s = 0.0;
-    for (int w = 0; w < SURF_BLOCK / 64; ++w) {
-      c += red[w][0];
-      m = fmax(m, red[w][1]);
-      s += red[w][2];
-    }
     stats[0] = c;
     stats[1] = sqrt(m);
     stats[2] = s;

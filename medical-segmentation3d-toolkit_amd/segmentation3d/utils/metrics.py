@@ -44,33 +44,47 @@ def _as_device_labels(vol, device):
     return vol.to(device).contiguous()
 
 
-def _device_pair(gt, seg, device):
+def _default_device(x):
+    return x.device if isinstance(x, torch.Tensor) and x.is_cuda else torch.device('cuda', torch.cuda.current_device())
+
+
+def _device_pair(gt, seg, device, grid3d=False):
+    """(gt, seg, device) as contiguous device tensors of one dtype; grid3d: both must be one 3-D [z, y, x] grid"""
     if device is None:
-        device = gt.device if isinstance(gt, torch.Tensor) and gt.is_cuda else torch.device('cuda', torch.cuda.current_device())
+        device = _default_device(gt)
     g, s = _as_device_labels(gt, device), _as_device_labels(seg, device)
     if g.dtype != s.dtype:                      # compare in a common type, like numpy's == does
         common = torch.float32 if torch.float32 in (g.dtype, s.dtype) else torch.int32
         g, s = g.to(common), s.to(common)
+    if grid3d and (g.dim() != 3 or g.shape != s.shape):
+        raise ValueError('ground truth shape {} and segmentation shape {} must be one 3-D [z, y, x] grid'.format(
+            tuple(g.shape), tuple(s.shape)))
     if g.numel() != s.numel():
         raise ValueError('ground truth and segmentation differ in size: {} vs {}'.format(tuple(g.shape), tuple(s.shape)))
     E.require_device(g, s)
     return g, s, device
 
 
-def label_overlap_counts(gt, seg, labels, device=None):
-    """[(area_gt, area_seg, intersection)] per label, as Python ints, from one device pass per 16 labels"""
-    g, s, device = _device_pair(gt, seg, device)
-    labels = [int(l) for l in labels]
+def _overlap_counts(entry, pair, sets, table):
+    """[(area_gt, area_seg, intersection)] per set, as Python ints, from one pass of `entry` over the device pair per 16
+    sets; table(chunk) is the entry's host argument for a chunk of sets"""
+    g, s, device = pair
     out = []
-    for k0 in range(0, len(labels), MAX_LABELS_PER_PASS):
-        chunk = labels[k0:k0 + MAX_LABELS_PER_PASS]
+    for k0 in range(0, len(sets), MAX_LABELS_PER_PASS):
+        chunk = list(sets[k0:k0 + MAX_LABELS_PER_PASS])
         counts = torch.zeros(3 * len(chunk), dtype=torch.int64, device=device)
-        arr = (ctypes.c_int * len(chunk))(*chunk)
-        E.call('seg3d_label_overlap_counts', E.ptr(g), E.ptr(s), _DTYPE_CODES[g.dtype], g.numel(), arr, len(chunk),
-               E.ptr(counts), E.stream_ptr())
+        E.call(entry, E.ptr(g), E.ptr(s), _DTYPE_CODES[g.dtype], g.numel(), table(chunk), len(chunk), E.ptr(counts),
+               E.stream_ptr())
         c = counts.cpu().tolist()
         out.extend((c[3 * k], c[3 * k + 1], c[3 * k + 2]) for k in range(len(chunk)))
     return out
+
+
+def label_overlap_counts(gt, seg, labels, device=None):
+    """[(area_gt, area_seg, intersection)] per label, as Python ints, from one device pass per 16 labels"""
+    pair = _device_pair(gt, seg, device)
+    return _overlap_counts('seg3d_label_overlap_counts', pair, [int(l) for l in labels],
+                           lambda chunk: (ctypes.c_int * len(chunk))(*chunk))
 
 
 def _classify(area_gt, area_seg, intersection, threshold):
@@ -100,17 +114,9 @@ def region_overlap_counts(gt, seg, regions, device=None):
     """[(area_gt, area_seg, intersection)] per region (a set of label ids: a voxel is in the region when its label is in the
     set), as Python ints, from one device pass per 16 regions (seg3d_region_overlap_counts)"""
     from segmentation3d.loss.region_loss import region_lut
-    g, s, device = _device_pair(gt, seg, device)
-    out = []
-    for k0 in range(0, len(regions), MAX_LABELS_PER_PASS):
-        chunk = list(regions[k0:k0 + MAX_LABELS_PER_PASS])
-        counts = torch.zeros(3 * len(chunk), dtype=torch.int64, device=device)
-        lut = (ctypes.c_uint * 256)(*region_lut(chunk))
-        E.call('seg3d_region_overlap_counts', E.ptr(g), E.ptr(s), _DTYPE_CODES[g.dtype], g.numel(), lut, len(chunk),
-               E.ptr(counts), E.stream_ptr())
-        c = counts.cpu().tolist()
-        out.extend((c[3 * k], c[3 * k + 1], c[3 * k + 2]) for k in range(len(chunk)))
-    return out
+    pair = _device_pair(gt, seg, device)
+    return _overlap_counts('seg3d_region_overlap_counts', pair, regions,
+                           lambda chunk: (ctypes.c_uint * 256)(*region_lut(chunk)))
 
 
 def cal_region_dsc(gt, seg, regions, threshold):
@@ -168,17 +174,7 @@ class _SurfacePlan(object):
 
     def __init__(self, gt, seg, spacing, device=None):
         self.spacing = _frame(gt, seg, spacing)
-        if device is None:
-            device = gt.device if isinstance(gt, torch.Tensor) and gt.is_cuda else torch.device(
-                'cuda', torch.cuda.current_device())
-        g, s = _as_device_labels(gt, device), _as_device_labels(seg, device)
-        if g.dtype != s.dtype:
-            common = torch.float32 if torch.float32 in (g.dtype, s.dtype) else torch.int32
-            g, s = g.to(common), s.to(common)
-        if g.dim() != 3 or g.shape != s.shape:
-            raise ValueError('ground truth shape {} and segmentation shape {} must be one 3-D [z, y, x] grid'.format(
-                tuple(g.shape), tuple(s.shape)))
-        E.require_device(g, s)
+        g, s, device = _device_pair(gt, seg, device, grid3d=True)
         self.g, self.s, self.code = g, s, _DTYPE_CODES[g.dtype]
         self.Z, self.Y, self.X = (int(v) for v in g.shape)
         nbytes = E.query('seg3d_surface_distance_workspace_bytes', self.X, self.Y, self.Z)
@@ -190,20 +186,20 @@ class _SurfacePlan(object):
         self.box_init = torch.tensor(_BOX_INIT, dtype=torch.int32, device=device)
         self.stats = torch.empty(6, dtype=torch.float64, device=device)
 
+    def _launch_surfaces(self, volumes, code, label):
+        self.box.copy_(self.box_init)
+        for k, vol in enumerate(volumes):
+            E.call('seg3d_label_surface', E.ptr(vol), code, self.X, self.Y, self.Z, int(label), E.ptr(self.surf[k]),
+                   E.ptr(self.box), E.ptr(self.box[6 + k:7 + k]), E.stream_ptr())
+
     def surfaces(self, label):
         """launch: both surface masks of `label`, their common box and their voxel counts (box[6], box[7])"""
-        self.box.copy_(self.box_init)
-        for k, vol in enumerate((self.g, self.s)):
-            E.call('seg3d_label_surface', E.ptr(vol), self.code, self.X, self.Y, self.Z, int(label), E.ptr(self.surf[k]),
-                   E.ptr(self.box), E.ptr(self.box[6 + k:7 + k]), E.stream_ptr())
+        self._launch_surfaces((self.g, self.s), self.code, label)
 
     def mask_surfaces(self, a, b):
         """surfaces() for two ready-made 0/1 uint8 device masks of the plan's grid (their label 1) in place of the two
         label volumes -- the per-lesion masks of cal_lesionwise"""
-        self.box.copy_(self.box_init)
-        for k, vol in enumerate((a, b)):
-            E.call('seg3d_label_surface', E.ptr(vol), _DTYPE_CODES[torch.uint8], self.X, self.Y, self.Z, 1,
-                   E.ptr(self.surf[k]), E.ptr(self.box), E.ptr(self.box[6 + k:7 + k]), E.stream_ptr())
+        self._launch_surfaces((a, b), _DTYPE_CODES[torch.uint8], 1)
 
     def distances(self, direction, dist2, index=None):
         """launch: squared distances of the query surface to the feature surface into dist2 (+ voxel index), and
@@ -445,10 +441,7 @@ def _ccl26(mask, shape, capacity):
 
 
 def _volume3d(vol, device):
-    if device is None:
-        device = vol.device if isinstance(vol, torch.Tensor) and vol.is_cuda else torch.device(
-            'cuda', torch.cuda.current_device())
-    v = _as_device_labels(vol, device)
+    v = _as_device_labels(vol, _default_device(vol) if device is None else device)
     if v.dim() != 3:
         raise ValueError('expected one 3-D [z, y, x] grid, got shape {}'.format(tuple(v.shape)))
     E.require_device(v)

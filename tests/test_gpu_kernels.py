@@ -1498,6 +1498,17 @@ def test_connected_components_and_bounding_box(hip_device):
     assert np.array_equal(got, numpy_ref.connected_component_filter(tie, [1], 'largest')) and got[1, 1, 3] == 1 and got[4, 4, 1] == 0
     for sel in (None, [2], [1, 3], [9]):
         assert image_tools.get_bounding_box_device(md, sel) == numpy_ref.get_bounding_box(mask, sel), sel
+    # tiny volumes: one voxel, one row that ends inside a thread's run of 32 voxels, and odd extents
+    for seed, tiny_shape in enumerate([(1, 1, 1), (1, 1, 70), (3, 5, 7)]):
+        tiny = np.random.RandomState(410 + seed).randint(0, 3, tiny_shape).astype(np.int8)
+        td = torch.from_numpy(tiny).to(hip_device)
+        for labels in ([1, 2], [2]):
+            got = image_tools.connected_component_filter_device(td, labels, 'largest').cpu().numpy()
+            assert np.array_equal(got, numpy_ref.connected_component_filter(tiny, labels, 'largest')), (tiny_shape, labels)
+            got = image_tools.connected_component_filter_device(td, labels, 'min_size', 2).cpu().numpy()
+            assert np.array_equal(got, numpy_ref.connected_component_filter(tiny, labels, 'min_size', 2)), (tiny_shape, labels)
+        for sel in (None, [2], [1, 2]):
+            assert image_tools.get_bounding_box_device(td, sel) == numpy_ref.get_bounding_box(tiny, sel), (tiny_shape, sel)
 
 
 def test_winograd_kernels_random_shapes_against_direct_kernels(hip_device):

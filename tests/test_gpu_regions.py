@@ -156,6 +156,38 @@ def test_region_overlap_counts_equal_numpy(hip_device, dtype):
         assert kind == 'TP' and score == 2 * c / (a + b)
 
 
+_LABELS17 = {                                  # 17 labels the dtype represents: one pass of 16 and one of 1
+    np.int8: [-128, -1, 127, 0, 1, 2, 3, 7, 10, 11, 18, 100, 5, 50, -100, 64, -64],
+    np.uint8: [200, 255, 0, 1, 2, 3, 7, 10, 11, 18, 100, 5, 50, 128, 64, 254, 199],
+    np.int16: [-255, 256, 300, 0, 1, 2, 3, 7, 10, 11, 18, 100, 255, -1, 5, 50, 1000],
+    np.int32: [-255, 256, 300, 0, 1, 2, 3, 7, 10, 11, 18, 100, 255, -1, 5, 50, 1000],
+    np.float32: [-255, 256, 300, 0, 1, 2, 3, 7, 10, 11, 18, 100, 255, -1, 5, 50, 1000],
+}
+
+
+@pytest.mark.parametrize('dtype', [np.int8, np.uint8, np.int16, np.int32, np.float32])
+def test_label_overlap_counts_every_dtype(hip_device, dtype):
+    """17 labels (two passes), n = 3 * 4099 (four blocks, the last partial) and n = 1, every dtype: negative labels, labels
+    above 255 and -- for float -- fractional voxels, which equal no label; equal to the numpy restatement as Python ints"""
+    from oracle import numpy_ref
+    from segmentation3d.utils.metrics import label_overlap_counts
+    labels = _LABELS17[dtype]
+    assert len(labels) == 17 and all(dtype(l) == l for l in labels)
+    rng = np.random.RandomState(12)
+    n = 3 * 4099
+    pool = np.array(labels[:14] + labels[16:] + [9, 33], np.int64)    # labels 14 and 15 stay absent, 9 and 33 are no labels
+    gt = pool[rng.randint(0, len(pool), n)].astype(dtype)
+    seg = np.where(rng.rand(n) < 0.6, gt, pool[rng.randint(0, len(pool), n)].astype(dtype)).astype(dtype)
+    if dtype == np.float32:
+        gt[:50], seg[25:75] = 1.5, 2.25
+    one = np.array([labels[16]], dtype)                               # n = 1: counted by the second pass
+    for g, s in ((gt.reshape(3, 4099), seg.reshape(3, 4099)), (one, one.copy())):
+        want = numpy_ref.label_overlap_counts(g, s, labels)
+        got = label_overlap_counts(g, s, labels, device=hip_device)
+        assert got == want and all(type(v) is int for row in got for v in row)
+        assert sum(c for _, _, c in want) > 0
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # 5. the sigmoid network
 # ---------------------------------------------------------------------------------------------------------------------
