@@ -24,7 +24,9 @@
 extern "C" {
 #endif
 
-#define SEG3D_ABI_VERSION 1
+/* Adding an entry keeps the version; removing one or changing a prototype raises it.
+ * 2: seg3d_adam_step_devstep removed (seg3d_optim_prepare + seg3d_adam_step_ctl do its work). */
+#define SEG3D_ABI_VERSION 2
 
 /* ---- library ------------------------------------------------------------------------------------------------ */
 const char* seg3d_last_error(void);
@@ -595,14 +597,12 @@ int seg3d_ds_head_bwd_finalize(const float* workspace, float* dw, float* db, int
 int seg3d_label_pyramid(const float* mask, float* out1, float* out2, float* out3, int N, int D, int H, int W, int levels,
                         void* stream);
 
-/* ---- optimizer: optim.Adam(...).step()  (core/seg_train.py:83,127) -------------------------------------------------- */
+/* ---- optimizer: optim.Adam(...).step()  (core/seg_train.py:83,127) --------------------------------------------------
+ * One call with every scalar a launch argument; step >= 1 counts the step being taken.  A train step captured in a
+ * hipGraph cannot change a launch argument: keep the count on the device with seg3d_optim_prepare (CONSTANT schedule,
+ * max_norm 0) + seg3d_adam_step_ctl below, which give the same bits. */
 int seg3d_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long long n, int step, float lr,
                     float beta1, float beta2, float eps, float weight_decay, float grad_scale, void* stream);
-/* the same update with the step count kept on the device (advanced by the call), for train steps captured in a hipGraph:
- * step_dev = steps taken so far, bc_dev = 2 floats of device scratch */
-int seg3d_adam_step_devstep(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long long n,
-                            int* step_dev, float* bc_dev, float lr, float beta1, float beta2, float eps,
-                            float weight_decay, float grad_scale, void* stream);
 
 /* ---- optimizer control block: gradient-norm clipping, learning-rate schedules, SGD (no counterpart in the reference) ---
  * The per-step scalars live on the device so that a step captured in a hipGraph can change them and the gradient norm

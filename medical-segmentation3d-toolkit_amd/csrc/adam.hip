@@ -1,5 +1,6 @@
-// adam.hip -- fused optimizer steps over one flat fp32 parameter buffer: Adam (host or device step count), and the
-// control-block family for gradient-norm clipping, learning-rate schedules and SGD (second half of the file).
+// adam.hip -- fused optimizer steps over one flat fp32 parameter buffer: Adam with its scalars as launch arguments (the
+// one-call entry), and the control-block family -- step count, gradient-norm clipping, learning-rate schedules on the
+// device -- for Adam and SGD (second half of the file).
 //
 // Reference: optim.Adam(net.parameters(), lr, betas) + opt.step() (core/seg_train.py:83,127); defaults eps 1e-8,
 // weight_decay 0, amsgrad off.  Update rule restated from torch.optim.Adam (single-tensor path):
@@ -52,37 +53,13 @@ __global__ __launch_bounds__(256) void adam_step_kernel(float* __restrict__ p, c
   adam_step_body(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2_sqrt, grad_scale);
 }
 
-// Device-resident step counter (a train step captured in a hipGraph cannot take the step number as a launch argument):
-// one thread advances *step and writes the two bias corrections, the update kernel reads them from memory.
-__global__ void adam_advance_kernel(int* __restrict__ step, float* __restrict__ bc, float beta1, float beta2) {
-  const int t = *step + 1;
-  *step = t;
-  bc[0] = (float)(1.0 - pow((double)beta1, (double)t));
-  bc[1] = (float)sqrt(1.0 - pow((double)beta2, (double)t));
-}
-
-__global__ __launch_bounds__(256) void adam_step_devstep_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                                  float* __restrict__ m, float* __restrict__ v, i64 n,
-                                                                  float lr, float beta1, float beta2, float eps,
-                                                                  float weight_decay, const float* __restrict__ bc,
-                                                                  float grad_scale) {
-  adam_step_body(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, bc[0], bc[1], grad_scale);
-}
-
-// step_dev: device int holding the number of steps taken so far (advanced here); bc_dev: 2 floats of device scratch.
-// Same update as seg3d_adam_step with step = *step_dev + 1.
-extern "C" int seg3d_adam_step_devstep(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long long n,
-                                       int* step_dev, float* bc_dev, float lr, float beta1, float beta2, float eps,
-                                       float weight_decay, float grad_scale, void* stream) {
-  SEG3D_REQUIRE(params && grads && exp_avg && exp_avg_sq && n > 0 && step_dev && bc_dev,
-                "seg3d_adam_step_devstep: bad arguments");
-  SEG3D_REQUIRE(((uintptr_t)params % 16) == 0 && ((uintptr_t)grads % 16) == 0 && ((uintptr_t)exp_avg % 16) == 0 &&
-                    ((uintptr_t)exp_avg_sq % 16) == 0,
-                "seg3d_adam_step_devstep: buffers must be 16-byte aligned");
-  hipLaunchKernelGGL(adam_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, step_dev, bc_dev, beta1, beta2);
-  hipLaunchKernelGGL(adam_step_devstep_kernel, dim3(seg3d_ew_grid(n / 4 + 1, 256)), dim3(256), 0, (hipStream_t)stream,
-                     params, grads, exp_avg, exp_avg_sq, (i64)n, lr, beta1, beta2, eps, weight_decay, bc_dev, grad_scale);
-  SEG3D_LAUNCH_CHECK("seg3d_adam_step_devstep");
+// What every update entry checks first: `args_ok`, its own null / range conditions, then the 16-byte alignment that the
+// float4 walk needs.  NULL counts as aligned: SGD without momentum has no state buffer.
+static int require_update_buffers(const char* entry, bool args_ok, const void* a, const void* b, const void* c,
+                                  const void* d) {
+  SEG3D_REQUIRE(args_ok, "%s: bad arguments", entry);
+  SEG3D_REQUIRE(((uintptr_t)a % 16) == 0 && ((uintptr_t)b % 16) == 0 && ((uintptr_t)c % 16) == 0 && ((uintptr_t)d % 16) == 0,
+                "%s: buffers must be 16-byte aligned", entry);
   return SEG3D_OK;
 }
 
@@ -91,10 +68,9 @@ extern "C" int seg3d_adam_step_devstep(float* params, const float* grads, float*
 extern "C" int seg3d_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long long n, int step,
                                float lr, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
                                void* stream) {
-  SEG3D_REQUIRE(params && grads && exp_avg && exp_avg_sq && n > 0 && step >= 1, "seg3d_adam_step: bad arguments");
-  SEG3D_REQUIRE(((uintptr_t)params % 16) == 0 && ((uintptr_t)grads % 16) == 0 && ((uintptr_t)exp_avg % 16) == 0 &&
-                    ((uintptr_t)exp_avg_sq % 16) == 0,
-                "seg3d_adam_step: buffers must be 16-byte aligned");
+  if (int rc = require_update_buffers("seg3d_adam_step", params && grads && exp_avg && exp_avg_sq && n > 0 && step >= 1,
+                                      params, grads, exp_avg, exp_avg_sq))
+    return rc;
   const double bc1 = 1.0 - pow((double)beta1, (double)step);
   const double bc2 = 1.0 - pow((double)beta2, (double)step);
   hipLaunchKernelGGL(adam_step_kernel, dim3(seg3d_ew_grid(n / 4 + 1, 256)), dim3(256), 0, (hipStream_t)stream, params, grads,
@@ -164,8 +140,9 @@ __device__ __forceinline__ double optim_lr(int s, int schedule, double base_lr, 
   return base_lr * w * d;
 }
 
-// One workgroup.  Generalises adam_advance_kernel: adds the nparts sum-of-squares slots (of ALL parameter groups) in a
-// fixed order in fp64, advances *step and writes the control block.
+// One workgroup: adds the nparts sum-of-squares slots (of ALL parameter groups) in a fixed order in fp64, advances *step
+// and writes the control block.  The bias corrections are seg3d_adam_step's expressions, evaluated here by the device's
+// pow: the same float32 bits for every step count tested (tests/test_gpu_optim.py).
 __global__ __launch_bounds__(256) void optim_prepare_kernel(int* __restrict__ step, float* __restrict__ ctl,
                                                               const double* __restrict__ part, int nparts, float grad_scale,
                                                               float max_norm, int schedule, float base_lr, int total_steps,
@@ -223,10 +200,9 @@ __global__ __launch_bounds__(256) void adam_step_ctl_kernel(float* __restrict__ 
 extern "C" int seg3d_adam_step_ctl(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long long n,
                                    const float* ctl, float beta1, float beta2, float eps, float weight_decay,
                                    void* stream) {
-  SEG3D_REQUIRE(params && grads && exp_avg && exp_avg_sq && n > 0 && ctl, "seg3d_adam_step_ctl: bad arguments");
-  SEG3D_REQUIRE(((uintptr_t)params % 16) == 0 && ((uintptr_t)grads % 16) == 0 && ((uintptr_t)exp_avg % 16) == 0 &&
-                    ((uintptr_t)exp_avg_sq % 16) == 0,
-                "seg3d_adam_step_ctl: buffers must be 16-byte aligned");
+  if (int rc = require_update_buffers("seg3d_adam_step_ctl", params && grads && exp_avg && exp_avg_sq && n > 0 && ctl,
+                                      params, grads, exp_avg, exp_avg_sq))
+    return rc;
   hipLaunchKernelGGL(adam_step_ctl_kernel, dim3(seg3d_ew_grid(n / 4 + 1, 256)), dim3(256), 0, (hipStream_t)stream, params,
                      grads, exp_avg, exp_avg_sq, (i64)n, ctl, beta1, beta2, eps, weight_decay);
   SEG3D_LAUNCH_CHECK("seg3d_adam_step_ctl");
@@ -277,11 +253,11 @@ __global__ __launch_bounds__(256) void sgd_step_ctl_kernel(float* __restrict__ p
 
 extern "C" int seg3d_sgd_step_ctl(float* params, const float* grads, float* momentum_buf, long long n, const float* ctl,
                                   float momentum, float weight_decay, int nesterov, void* stream) {
-  SEG3D_REQUIRE(params && grads && n > 0 && ctl, "seg3d_sgd_step_ctl: bad arguments");
+  if (int rc = require_update_buffers("seg3d_sgd_step_ctl", params && grads && n > 0 && ctl, params, grads, momentum_buf,
+                                      nullptr))
+    return rc;
   SEG3D_REQUIRE(momentum >= 0.f && (momentum == 0.f || momentum_buf), "seg3d_sgd_step_ctl: momentum needs its buffer");
   SEG3D_REQUIRE(!nesterov || momentum > 0.f, "seg3d_sgd_step_ctl: Nesterov needs momentum > 0");
-  SEG3D_REQUIRE(((uintptr_t)params % 16) == 0 && ((uintptr_t)grads % 16) == 0 && ((uintptr_t)momentum_buf % 16) == 0,
-                "seg3d_sgd_step_ctl: buffers must be 16-byte aligned");
   const dim3 grid(seg3d_ew_grid(n / 4 + 1, 256)), block(256);
   hipStream_t s = (hipStream_t)stream;
   if (momentum == 0.f)

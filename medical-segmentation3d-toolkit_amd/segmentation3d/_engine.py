@@ -234,7 +234,6 @@ _SIGNATURES = {
     'seg3d_ds_head_bwd_finalize': (_c_int, [_c_p] * 3 + [_c_int, _c_ll, _c_int, _c_int, _c_int, _c_p]),
     'seg3d_label_pyramid': (_c_int, [_c_p] * 4 + [_c_int] * 5 + [_c_p]),
     'seg3d_adam_step': (_c_int, [_c_p] * 4 + [_c_ll, _c_int] + [_c_f] * 6 + [_c_p]),
-    'seg3d_adam_step_devstep': (_c_int, [_c_p] * 4 + [_c_ll, _c_p, _c_p] + [_c_f] * 6 + [_c_p]),
     'seg3d_grad_sumsq_part_count': (_c_ll, [_c_ll]),
     'seg3d_grad_sumsq_partial': (_c_int, [_c_p, _c_ll, _c_p, _c_p]),
     'seg3d_optim_prepare': (_c_int, [_c_p, _c_p, _c_p, _c_int, _c_f, _c_f, _c_int, _c_f, _c_int, _c_int, _c_f, _c_f, _c_f,
@@ -287,7 +286,7 @@ def lib():
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args
-        if handle.seg3d_abi_version() != 1:
+        if handle.seg3d_abi_version() != 2:
             raise Seg3dEngineError('libseg3d_hip.so ABI version mismatch')
         _lib = handle
     return _lib

@@ -264,7 +264,7 @@ class TrainStep(object):
             self._gx, self._gt = crops.clone(), masks.clone()
             torch.cuda.synchronize()
             graph = torch.cuda.CUDAGraph()
-            host_steps = [None if f is None else f['step'] for f in self.opt._flat]
+            step_counts = self.opt.step_counts()
             try:
                 with torch.cuda.graph(graph):
                     self._gloss = self._eager(self._gx, self._gt)
@@ -272,15 +272,10 @@ class TrainStep(object):
                 import warnings
                 warnings.warn('TrainStep: hipGraph capture of the train step failed ({}); continuing eagerly'.format(exc))
                 torch.cuda.synchronize()
-                for f, st in zip(self.opt._flat, host_steps):
-                    if f is not None:
-                        f['step'] = st
-                        f['step_dev'].fill_(int(st))
+                self.opt.restore_step_counts(step_counts)
                 self.use_graph = False
                 return self._eager(crops, masks)
-            for f, st in zip(self.opt._flat, host_steps):     # capture ran the host side of opt.step() once, no kernels
-                if f is not None:
-                    f['step'] = st
+            self.opt.restore_step_counts(step_counts)         # capture ran the host side of opt.step() once, no kernels
             self._graph = graph
         self._gx.copy_(crops)
         self._gt.copy_(masks)

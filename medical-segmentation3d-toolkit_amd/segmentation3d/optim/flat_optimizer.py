@@ -6,10 +6,14 @@ data-parallel gradient all-reduce works on contiguous slices of the same buffer 
 With `direct_grads` (default) every parameter's slice of the gradient buffer is registered as a gradient sink
 (`_grad_sink.py`): the backward kernels accumulate into it themselves instead of autograd adding a temporary.
 
-Control-block path (`max_grad_norm` and / or `lr_schedule` given, and always for FusedSGD): the step count, the learning
-rate, the clip coefficient and the gradient norm live on the device (SEG3D_CTL_* of include/seg3d_hip.h), so that the
-same launches serve an eager step and a step captured in a hipGraph, and nothing is read back:
+A step is one of two things.  Without a control block (FusedAdam with neither `max_grad_norm` nor `lr_schedule`, stepping
+eagerly) it is one launch with host-side scalars, `seg3d_adam_step`.  With one -- `max_grad_norm` and / or `lr_schedule`
+given, always for FusedSGD, and for every optimizer after use_device_step(), which TrainStep calls before it captures a
+hipGraph -- the step count, the learning rate, the clip coefficient and the gradient norm live on the device (SEG3D_CTL_*
+of include/seg3d_hip.h), so that the same launches serve an eager step and a captured one, and nothing is read back:
     [seg3d_grad_sumsq_partial per group, only when clipping] -> per group: seg3d_optim_prepare -> the update kernel
+The host keeps its own count beside the device's (`step` and `step_dev` of a group) for `state_dict()` and the schedule's
+`group['lr']`; a graph replay advances the device's alone and the host follows in note_replayed_step().
 The norm is that of ALL groups together, times `grad_scale` (the mean gradient under data parallelism: every rank
 computes the same coefficient from the same reduced buffer).  As in torch.nn.utils.clip_grad_norm_, a step whose norm
 is not finite is not skipped.
@@ -40,16 +44,15 @@ class FlatBufferOptimizer(torch.optim.Optimizer):
         self._flat = []  # per group: dict(list, offsets, params, grads, <state buffers>, step, total)
         self.grad_scale = 1.0  # set to 1/world_size by the data-parallel wrapper after a sum all-reduce
         self.direct_grads = bool(direct_grads)
-        # device_step: the step count lives on the device and the kernel advances it itself, so that a whole train step
-        # can be captured in a hipGraph and replayed; the host count follows in note_replayed_step()
-        self.device_step = False
-        self._control = self._ALWAYS_CONTROL or self.max_grad_norm is not None or self.lr_schedule is not None
+        # _control: every group has a control block (step_dev, ctl) and the kernels count the steps on the device, so that
+        # a whole train step can be captured in a hipGraph and replayed; the host count follows in note_replayed_step()
+        self._control = False
         self._part, self._nparts = None, 0
         for group in self.param_groups:
             if self.lr_schedule is not None:
                 group.setdefault('initial_lr', group['lr'])     # torch's scheduler convention: the base rate
             self._flat.append(self._flatten_group(group))
-        if self._control:
+        if self._ALWAYS_CONTROL or self.max_grad_norm is not None or self.lr_schedule is not None:
             self._alloc_control()
 
     def _state_buffer_names(self, group):
@@ -57,7 +60,7 @@ class FlatBufferOptimizer(torch.optim.Optimizer):
         raise NotImplementedError
 
     def _launch(self, group, f):
-        """the update with host-side scalars (today's FusedAdam path)"""
+        """the update with host-side scalars, step count f['step'] included"""
         raise NotImplementedError
 
     def _launch_control(self, group, f):
@@ -114,20 +117,16 @@ class FlatBufferOptimizer(torch.optim.Optimizer):
             # one fp64 slot per workgroup of the sum-of-squares pass, the groups laid end to end
             self._part = torch.zeros(off, dtype=torch.float64, device=live[0]['params'].device)
             self._nparts = off
-        self.device_step = True
+        self._control = True
 
     def use_device_step(self):
-        """switch to the device-resident step counter (before capturing a train step in a hipGraph); idempotent"""
+        """count the steps on the device (before capturing a train step in a hipGraph): an optimizer on host-side scalars
+        gets its control block, and the device counters start from the host counts; idempotent"""
+        if not self._control:
+            self._alloc_control()
         for f in self._flat:
-            if f is None:
-                continue
-            if self._control:
-                f['step_dev'].fill_(int(f['step']))       # the control-block path counts on the device from the start
-                continue
-            dev = f['params'].device
-            f['step_dev'] = torch.full((1,), int(f['step']), dtype=torch.int32, device=dev)
-            f['bc_dev'] = torch.zeros(2, dtype=torch.float32, device=dev)
-        self.device_step = True
+            if f is not None:
+                f['step_dev'].fill_(int(f['step']))
 
     def _note_host_step(self, group, f):
         step_t = torch.tensor(float(f['step']))     # one host tensor shared by the group's per-parameter states
@@ -142,6 +141,21 @@ class FlatBufferOptimizer(torch.optim.Optimizer):
             if f is None:
                 continue
             f['step'] += 1
+            self._note_host_step(group, f)
+
+    def step_counts(self):
+        """the per-group host step counts (None for a group without parameters), for restore_step_counts()"""
+        return [None if f is None else f['step'] for f in self._flat]
+
+    def restore_step_counts(self, counts):
+        """rewind the host counts, the per-parameter `state['step']` and the device counters to `counts`: after a graph
+        capture, which ran step()'s host side without its kernels, or after one that failed"""
+        for group, f, count in zip(self.param_groups, self._flat, counts):
+            if f is None:
+                continue
+            f['step'] = count
+            if self._control:
+                f['step_dev'].fill_(int(count))
             self._note_host_step(group, f)
 
     def flat_grads(self):
@@ -160,7 +174,7 @@ class FlatBufferOptimizer(torch.optim.Optimizer):
 
     def _control_view(self, slot):
         for f in self._flat:
-            if f is not None and 'ctl' in f:
+            if f is not None and self._control:
                 return f['ctl'][slot]
         return None
 
@@ -297,7 +311,7 @@ class FlatBufferOptimizer(torch.optim.Optimizer):
                 step = max(step, int(float(st.get('step', 0.0))))
                 st['step'] = torch.tensor(float(step))
             f['step'] = step
-            if self.device_step and 'step_dev' in f:
-                f['step_dev'].fill_(int(step))        # a captured step reads its count from the device
+            if self._control:
+                f['step_dev'].fill_(int(step))        # a step through the control block reads its count from the device
             if self.lr_schedule is not None and step >= 1:
                 group['lr'] = lr_at(step, group['initial_lr'], **self.lr_schedule)

@@ -9,8 +9,9 @@ With `direct_grads` (default) every parameter's slice of the gradient buffer is 
 `state_dict()` / `load_state_dict()` keep torch.optim.Adam's structure (`step`, `exp_avg`, `exp_avg_sq` per
 parameter), so `optimizer.pth` files are interchangeable with the reference's.
 The flat-buffer machinery is optim/flat_optimizer.py's, shared with FusedSGD.  With `max_grad_norm` and `lr_schedule`
-both None (default) a step is `seg3d_adam_step` / `seg3d_adam_step_devstep`; with either set it goes through the
-device control block (`seg3d_adam_step_ctl`), eager and captured alike.
+both None (default) an eager step is one `seg3d_adam_step` with host-side scalars.  Everything else -- either option
+set, or the step count moved to the device for a captured train step (use_device_step) -- goes through the device
+control block: `seg3d_optim_prepare` -> `seg3d_adam_step_ctl`, the same update with the same bits.
 """
 from segmentation3d import _engine as E
 from segmentation3d.optim.flat_optimizer import FlatBufferOptimizer
@@ -30,15 +31,9 @@ class FusedAdam(FlatBufferOptimizer):
 
     def _launch(self, group, f):
         beta1, beta2 = group['betas']
-        if self.device_step:
-            E.call('seg3d_adam_step_devstep', E.ptr(f['params']), E.ptr(f['grads']), E.ptr(f['exp_avg']),
-                   E.ptr(f['exp_avg_sq']), f['total'], E.ptr(f['step_dev']), E.ptr(f['bc_dev']), float(group['lr']),
-                   float(beta1), float(beta2), float(group['eps']), float(group['weight_decay']),
-                   float(self.grad_scale), E.stream_ptr())
-        else:
-            E.call('seg3d_adam_step', E.ptr(f['params']), E.ptr(f['grads']), E.ptr(f['exp_avg']),
-                   E.ptr(f['exp_avg_sq']), f['total'], f['step'], float(group['lr']), float(beta1), float(beta2),
-                   float(group['eps']), float(group['weight_decay']), float(self.grad_scale), E.stream_ptr())
+        E.call('seg3d_adam_step', E.ptr(f['params']), E.ptr(f['grads']), E.ptr(f['exp_avg']), E.ptr(f['exp_avg_sq']),
+               f['total'], f['step'], float(group['lr']), float(beta1), float(beta2), float(group['eps']),
+               float(group['weight_decay']), float(self.grad_scale), E.stream_ptr())
 
     def _launch_control(self, group, f):
         beta1, beta2 = group['betas']

@@ -29,7 +29,7 @@ def test_ctypes_table_matches_header():
     from segmentation3d import _engine
     assert _engine.symbols() == _declared_symbols()
     lib = _engine.lib()
-    assert lib.seg3d_abi_version() == 1
+    assert lib.seg3d_abi_version() == 2
     assert lib.seg3d_target_arch() == b'gfx950'
     # size helpers are pure host arithmetic and must work without a GPU
     assert _engine.query('seg3d_gn_stats_count', 16384 * 3 + 1) == 4

@@ -150,7 +150,7 @@ def test_ctypes_table_holds_the_new_entries():
     names = ('seg3d_ds_head_supported', 'seg3d_ds_head_fwd', 'seg3d_ds_head_bwd_workspace_floats', 'seg3d_ds_head_bwd',
              'seg3d_ds_head_bwd_finalize', 'seg3d_label_pyramid')
     assert set(names) <= set(_engine.symbols())
-    assert _engine.lib().seg3d_abi_version() == 1
+    assert _engine.lib().seg3d_abi_version() == 2
     # the size helpers are host arithmetic
     for cin, c, ok in ((64, 2, 1), (256, 8, 1), (4, 1, 1), (260, 2, 0), (66, 2, 0), (64, 9, 0), (64, 0, 0), (0, 2, 0)):
         assert _engine.query('seg3d_ds_head_supported', cin, c) == ok, (cin, c)

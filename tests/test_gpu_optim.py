@@ -443,3 +443,188 @@ def test_train_with_sgd_poly_config_and_resume(hip_device, tmp_path):
     finally:
         _ops.set_activation_dtype('fp32')
         _ops.PACK_CACHE.clear()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 8. the device-resident step count: prepare -> update, against the host-argument step seg3d_adam_step
+# ---------------------------------------------------------------------------------------------------------------------
+ADAM_LR, ADAM_EPS = 1e-3, 1e-8
+ADAM_KW = dict(lr=ADAM_LR, betas=(0.9, 0.999), weight_decay=0.01)
+
+
+def _prepare_constant(step_dev, ctl, grad_scale, lr, beta1, beta2):
+    """seg3d_optim_prepare with no clipping (max_norm 0, no slots) and the constant schedule"""
+    from segmentation3d import _engine as E
+    E.call('seg3d_optim_prepare', E.ptr(step_dev), E.ptr(ctl), None, 0, grad_scale, 0.0, 0, lr, 1, 0, 0.9, beta1, beta2,
+           E.stream_ptr())
+
+
+def _step_with_grads(opt, ps, t, hip_device):
+    opt.zero_grad()
+    for b, g in zip(ps, _grads(t)):
+        b.grad.copy_(g.to(hip_device))
+    opt.step()
+
+
+def test_device_step_adam_equals_host_step_adam(hip_device):
+    """the default FusedAdam (host-side scalars) against one that counts its steps on the device, stepped eagerly:
+    parameters, both moments and the counters are bit-equal after every step"""
+    from segmentation3d.optim.fused_adam import FusedAdam
+    _, ps_a = _params(hip_device)
+    _, ps_b = _params(hip_device)
+    a, b = FusedAdam(ps_a, **ADAM_KW), FusedAdam(ps_b, **ADAM_KW)
+    a.grad_scale = b.grad_scale = 0.5
+    b.use_device_step()
+    fa, fb = a._flat[0], b._flat[0]
+    for t in range(1, 9):
+        _step_with_grads(a, ps_a, t, hip_device)
+        _step_with_grads(b, ps_b, t, hip_device)
+        for k in ('params', 'exp_avg', 'exp_avg_sq'):
+            assert torch.equal(fa[k], fb[k]), (t, k)
+        assert fa['step'] == fb['step'] == t and int(fb['step_dev'].item()) == t
+        assert all(float(a.state[x]['step']) == float(b.state[y]['step']) == t for x, y in zip(ps_a, ps_b))
+    assert float(fa['exp_avg'].abs().max()) > 0.0
+
+
+def _adam_float64(p, g, m, v, t, lr, beta1, beta2, eps, wd, grad_scale):
+    """torch.optim.Adam's single-tensor rule in float64, on the float32-rounded hyper-parameters the kernels receive"""
+    lr, beta1, beta2, eps, wd = (float(np.float32(x)) for x in (lr, beta1, beta2, eps, wd))
+    gg = g * grad_scale + wd * p
+    m = m + (gg - m) * (1.0 - beta1)
+    v = v * beta2 + (1.0 - beta2) * gg * gg
+    p = p - (lr / (1.0 - beta1 ** t)) * (m / (np.sqrt(v) / math.sqrt(1.0 - beta2 ** t) + eps))
+    return p, m, v
+
+
+@pytest.mark.parametrize('n', [1, 3, 4, 5, 255, 256, 257, 4099])
+def test_adam_entries_tail_and_alignment(hip_device, n):
+    """the sizes at which the float4 body and the scalar tail meet.  prepare -> seg3d_adam_step_ctl is bit-equal to
+    seg3d_adam_step with the same scalars, and both follow the float64 rule: the reference is evaluated on the same
+    float32 hyper-parameters, so what is left is the kernel's own roundings -- under ten per element and step, each
+    2^-24 = 6e-8 of a value no larger than the buffer's maximum, over three steps: held to 1e-6 of the buffer's maximum.
+    Four guard floats behind every buffer stay untouched."""
+    from segmentation3d import _engine as E
+    beta1, beta2, wd, scale = 0.9, 0.999, 0.01, 0.25
+    host = {k: detgen.normal(300 + n % 97, 'tail/' + k, (n,)) for k in ('p', 'g1', 'g2', 'g3')}
+
+    def buf(values):
+        t = torch.full((n + 4,), 7.0, dtype=torch.float32)
+        t[:n] = torch.from_numpy(values)
+        return t.to(hip_device)
+
+    zeros = np.zeros(n, dtype=np.float32)
+    A = {k: buf(x) for k, x in (('p', host['p']), ('m', zeros), ('v', zeros))}
+    B = {k: t.clone() for k, t in A.items()}
+    step_dev = torch.zeros(1, dtype=torch.int32, device=hip_device)
+    ctl = torch.zeros(8, dtype=torch.float32, device=hip_device)
+    p64, m64, v64 = host['p'].astype(np.float64), zeros.astype(np.float64), zeros.astype(np.float64)
+    for t in (1, 2, 3):
+        g = buf(host['g{}'.format(t)])
+        _prepare_constant(step_dev, ctl, scale, ADAM_LR, beta1, beta2)
+        E.call('seg3d_adam_step_ctl', E.ptr(A['p']), E.ptr(g), E.ptr(A['m']), E.ptr(A['v']), n, E.ptr(ctl), beta1, beta2,
+               ADAM_EPS, wd, E.stream_ptr())
+        E.call('seg3d_adam_step', E.ptr(B['p']), E.ptr(g), E.ptr(B['m']), E.ptr(B['v']), n, t, ADAM_LR, beta1, beta2,
+               ADAM_EPS, wd, scale, E.stream_ptr())
+        p64, m64, v64 = _adam_float64(p64, host['g{}'.format(t)].astype(np.float64), m64, v64, t, ADAM_LR, beta1, beta2,
+                                      ADAM_EPS, wd, scale)
+        assert int(step_dev.item()) == t
+        for k, want in (('p', p64), ('m', m64), ('v', v64)):
+            assert torch.equal(A[k], B[k]), (n, t, k)
+            assert torch.equal(A[k][n:].cpu(), torch.full((4,), 7.0)), (n, t, k)
+            rel = float(np.abs(A[k][:n].cpu().numpy().astype(np.float64) - want).max() / np.abs(want).max())
+            report('adam_tail_n{}_t{}_{}'.format(n, t, k), rel=rel)
+            assert rel < 1e-6, (n, t, k, rel)
+
+
+def test_adam_entries_tail_and_alignment_refusal(hip_device):
+    """a pointer 4 bytes past a 16-byte boundary is SEG3D_ERR_INVALID (ValueError) at every entry, with its message"""
+    from segmentation3d import _engine as E
+    n = 64
+    p, g, m, v = (torch.zeros(n + 4, dtype=torch.float32, device=hip_device) for _ in range(4))
+    ctl = torch.zeros(8, dtype=torch.float32, device=hip_device)
+    part = torch.zeros(4, dtype=torch.float64, device=hip_device)
+    s = E.stream_ptr()
+
+    def entries(bufs):
+        a, b, c, d = (E.ptr(x) for x in bufs)
+        return {
+            'seg3d_adam_step': (a, b, c, d, n, 1, ADAM_LR, 0.9, 0.999, ADAM_EPS, 0.0, 1.0, s),
+            'seg3d_adam_step_ctl': (a, b, c, d, n, E.ptr(ctl), 0.9, 0.999, ADAM_EPS, 0.0, s),
+            'seg3d_sgd_step_ctl': (a, b, c, n, E.ptr(ctl), 0.9, 0.0, 0, s),
+        }
+
+    for i in range(4):
+        bufs = [p, g, m, v]
+        bufs[i] = bufs[i][1:]
+        for name, args in entries(bufs).items():
+            if name == 'seg3d_sgd_step_ctl' and i == 3:
+                continue                                          # SGD has three buffers
+            with pytest.raises(ValueError) as err:
+                E.call(name, *args)
+            assert str(err.value) == name + ': buffers must be 16-byte aligned', (name, i)
+    with pytest.raises(ValueError) as err:
+        E.call('seg3d_grad_sumsq_partial', E.ptr(g[1:]), n, E.ptr(part), s)
+    assert str(err.value) == 'seg3d_grad_sumsq_partial: grads must be 16-byte aligned, part 8-byte aligned'
+    torch.cuda.synchronize()
+    assert all(float(x.abs().max()) == 0.0 for x in (p, g, m, v))     # a refused call launches nothing
+
+
+@pytest.mark.parametrize('betas', [(0.9, 0.999), (0.5, 0.9), (0.0, 0.99)])
+def test_prepare_bias_corrections_equal_host_pow(hip_device, betas):
+    """seg3d_adam_step takes 1 - beta1^t and sqrt(1 - beta2^t) from the host's pow, seg3d_optim_prepare from the
+    device's: for t = 1 .. 4096 the two float32 values are the same bits, so a run that moves its step count to the
+    device part-way (TrainStep captures after two eager steps) continues the curve it would have walked on the host"""
+    beta1, beta2 = (float(np.float32(b)) for b in betas)           # the entries take float arguments
+    T = 4096
+    step_dev = torch.zeros(1, dtype=torch.int32, device=hip_device)
+    ctl = torch.zeros(8, dtype=torch.float32, device=hip_device)
+    rows = torch.zeros((T, 8), dtype=torch.float32, device=hip_device)
+    for t in range(1, T + 1):
+        _prepare_constant(step_dev, ctl, 1.0, ADAM_LR, beta1, beta2)
+        rows[t - 1].copy_(ctl)
+    got = rows.cpu().numpy()
+    assert int(step_dev.item()) == T
+    want1 = np.array([np.float32(1.0 - math.pow(beta1, t)) for t in range(1, T + 1)], dtype=np.float32)
+    want2 = np.array([np.float32(math.sqrt(1.0 - math.pow(beta2, t))) for t in range(1, T + 1)], dtype=np.float32)
+    for name, g, w in (('bc1', got[:, 2].copy(), want1), ('bc2_sqrt', got[:, 3].copy(), want2)):
+        off = np.nonzero(g.view(np.uint32) != w.view(np.uint32))[0]
+        report('prepare_{}_b{}_{}'.format(name, betas[0], betas[1]), mismatches=float(off.size))
+        assert off.size == 0, (name, betas, [(int(i) + 1, float(g[i]), float(w[i])) for i in off[:8]])
+    assert np.array_equal(got[:, 0], np.full(T, np.float32(ADAM_LR))) and np.array_equal(got[:, 1], np.ones(T, np.float32))
+
+
+@pytest.mark.parametrize('on_device', [True, False], ids=['device_count', 'host_count'])
+def test_capture_failure_rewinds_both_counters(hip_device, on_device):
+    """what TrainStep does around a graph capture, around an eager step instead: the counters saved before the step
+    are back after restore_step_counts(), and the optimizer goes on exactly like a fresh one loaded from its state"""
+    from segmentation3d.optim.fused_adam import FusedAdam
+
+    def make(ps):
+        opt = FusedAdam(ps, **ADAM_KW)
+        if on_device:
+            opt.use_device_step()
+        return opt
+
+    def counts(opt):
+        f = opt._flat[0]
+        steps = {float(opt.state[q]['step']) for q in f['list']}
+        return (f['step'], int(f['step_dev'].item()) if on_device else None, steps)
+
+    _, ps_dev = _params(hip_device)
+    opt = make(ps_dev)
+    for t in (1, 2, 3):
+        _step_with_grads(opt, ps_dev, t, hip_device)
+    saved = opt.step_counts()
+    assert saved == [3]
+    _step_with_grads(opt, ps_dev, 4, hip_device)
+    assert counts(opt) == (4, 4 if on_device else None, {4.0})
+    opt.restore_step_counts(saved)
+    assert counts(opt) == (3, 3 if on_device else None, {3.0})
+    ps2 = [torch.nn.Parameter(q.detach().clone()) for q in ps_dev]
+    opt2 = make(ps2)
+    opt2.load_state_dict(copy.deepcopy(opt.state_dict()))
+    _step_with_grads(opt, ps_dev, 5, hip_device)
+    _step_with_grads(opt2, ps2, 5, hip_device)
+    assert counts(opt) == counts(opt2) == (4, 4 if on_device else None, {4.0})
+    for k in ('params', 'exp_avg', 'exp_avg_sq'):
+        assert torch.equal(opt._flat[0][k], opt2._flat[0][k]), k

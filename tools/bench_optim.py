@@ -4,7 +4,7 @@
 
 On flat buffers of the size of vnet(1, 2)'s (14.56 M floats, every parameter padded to 64), in ONE process, the variants
 alternated inside every repeat:
-  adam            seg3d_adam_step          (host-side scalars: today's path)        28 B / parameter
+  adam            seg3d_adam_step          (host-side scalars: the eager default)   28 B / parameter
   adam_ctl        seg3d_adam_step_ctl      (scalars from the control block)         28 B / parameter
   sgd_ctl         seg3d_sgd_step_ctl       (Nesterov 0.99, weight decay 3e-5)       20 B / parameter
   sumsq           seg3d_grad_sumsq_partial (the norm pass of a clipping step)        4 B / parameter
