@@ -44,6 +44,10 @@ int seg3d_copy_channels(const float* src, float* dst, long long nvox, int C, int
 /* ---- weight packers: W(a, b, t) = w[a*sa + b*sb + t], a = reduction channel, b = output channel, t = tap ---------- */
 int seg3d_pack_weights_tapmajor(const float* w, float* wp, int A, int B, int BP, int T, long long sa, long long sb,
                                 int flip, void* stream);
+/* MFMA image of one weight tensor (the one-job launch of the multi-pack below; the job is a kernel argument, nothing is
+ * allocated).  T = 36 / 48 select the Winograd F(2, 3) / F(2x2, 3x3) images of a 27-tap weight (fp32 only); any other T must
+ * be <= 27, the most source taps the packer stages per channel pair: T = 28.. other than 36 / 48 is refused (SEG3D_ERR_INVALID),
+ * by seg3d_pack_weights_mfma_bf16 too */
 int seg3d_pack_weights_mfma(const float* w, float* wp, int A, int B, int T, long long sa, long long sb, int flip,
                             void* stream);
 long long seg3d_packed_mfma_floats(int A, int B, int T);

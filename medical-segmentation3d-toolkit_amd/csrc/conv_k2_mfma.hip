@@ -12,7 +12,7 @@
 //       = ConvTranspose3d k2s2 forward, and the data-gradient of Conv3d k2s2
 //   pair-reduce kernel (k2_wgrad_mfma_kernel):  dW(t,a,b) = sum_v P[2v + t][a] Q[v][b]
 //       = weight gradient of both (conv: P = x, Q = dy; transposed: P = dy, Q = x)
-// Operand staging and the k = {r, 4 + r} pairing are those of conv_mfma.hip; weights come from pack_mfma_kernel
+// Operand staging and the k = {r, 4 + r} pairing are those of conv_mfma.hip; weights come from pack_mfma_chunk
 // with T = 8 (chunk image [8][half][32][4]).
 #include "seg3d_common.h"
 #include "seg3d_hip.h"

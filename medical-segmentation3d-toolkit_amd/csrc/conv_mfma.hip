@@ -11,7 +11,7 @@
 //   TZ x TY x TX of output voxels and one block of 32 output channels.  The input tile with its 1-voxel halo
 //   is staged in LDS 8 input channels at a time as [half][halo voxel][4 floats] so that a lane's A operands
 //   for 4 consecutive MFMAs come from ONE ds_read_b128; the matching weight chunk [27][half][32][4] is a
-//   straight copy of the packed weights (layout.hip: pack_mfma_kernel).  MFMA r of a group takes
+//   straight copy of the packed weights (layout.hip: pack_mfma_chunk).  MFMA r of a group takes
 //   k = {r, 4 + r} of the 8-channel chunk (lanes 0-31 / 32-63), which both operands agree on.
 //   Each wave keeps MA accumulators (32 voxels x 32 channels each).  Zero padding = zeros written to LDS.
 //   dgrad is the same kernel run on dy with flipped / transposed weights (pack with flip = 1).

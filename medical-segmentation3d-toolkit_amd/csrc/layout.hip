@@ -127,115 +127,13 @@ __device__ __forceinline__ float seg3d_wino_u(float g0, float g1, float g2, int 
 // chunk of the forward kernels, in which a lane (output channel j, K index r) finds the A operands of the four consecutive
 // steps 4 g .. 4 g + 3 in one aligned 16-byte word (ds_read_b128, conflict-free: tools/lds_bank_sim.py).
 #define SEG3D_WINO2D_T 48
-struct Seg3dW2StepTable {   // t48 of every step of the chunk's step order, built at compile time
-  unsigned char t[48];
-  constexpr Seg3dW2StepTable() : t() {
-    for (int s = 0; s < 48; ++s) t[s] = (unsigned char)seg3d_w2_step_t(s);
-  }
-};
-__device__ const Seg3dW2StepTable seg3d_w2_step_table;
-__device__ __forceinline__ void seg3d_wino2d_decode(int i, int& h, int& r, int& j, int& t48) {   // i = offset inside a chunk's 12288 floats
-  const int s4 = i & 3, g24 = i >> 9;         // g24 = h * 12 + g
-  j = (i >> 2) & 31;
-  r = (i >> 7) & 3;
-  h = g24 >= 12 ? 1 : 0;
-  t48 = seg3d_w2_step_table.t[4 * (g24 - 12 * h) + s4];   // (a table: the div / mod arithmetic of the step order per element made the multi-pack 17 % slower)
-}
-__device__ __forceinline__ float seg3d_wino2d_u(const float* g, int flip, int t48) {
-  const int kz = t48 >> 4, py = (t48 >> 2) & 3, px = t48 & 3;
-  float r[3];
-#pragma unroll
-  for (int ky = 0; ky < 3; ++ky) {
-    const int i = (kz * 3 + ky) * 3;
-    r[ky] = seg3d_wino_u(g[flip ? 26 - i : i], g[flip ? 25 - i : i + 1], g[flip ? 24 - i : i + 2], px);
-  }
-  return seg3d_wino_u(r[0], r[1], r[2], py);
-}
 
 // MFMA pack (conv_mfma.hip): wp[bb][ab][t][h][j][r] = W(a = ab*8 + h*4 + r, b = bb*32 + j, t), zero padded.
 // One (bb, ab) chunk = T*2*32*4 floats is exactly the LDS image a workgroup stages per K-chunk, so staging is
 // a straight 16-byte copy.
-__global__ __launch_bounds__(256) void pack_mfma_kernel(const float* __restrict__ w, float* __restrict__ wp, int A,
-                                                          int B, int AB, int BB, int T, i64 sa, i64 sb, int flip) {
-  i64 total = (i64)BB * AB * T * 256;
-  for (i64 idx = (i64)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (i64)gridDim.x * 256) {
-    int r = (int)(idx & 3);
-    int j = (int)((idx >> 2) & 31);
-    int h = (int)((idx >> 7) & 1);
-    i64 rest = idx >> 8;
-    int t = (int)(rest % T);
-    rest /= T;
-    int ab = (int)(rest % AB);
-    int bb = (int)(rest / AB);
-    if (T == SEG3D_WINO2D_T) seg3d_wino2d_decode((int)(idx % (48 * 256)), h, r, j, t);
-    int a = ab * 8 + h * 4 + r, b = bb * 32 + j;
-    float v = 0.f;
-    if (a < A && b < B) {
-      if (T == SEG3D_WINO_T) {   // t = (kz * 3 + ky) * 4 + p: Winograd F(2, 3) transform along kx of a 27-tap weight
-        const int t9 = t >> 2;
-        const float* g = w + a * sa + b * sb;
-        const float g0 = g[flip ? 26 - 3 * t9 : 3 * t9], g1 = g[flip ? 25 - 3 * t9 : 3 * t9 + 1], g2 = g[flip ? 24 - 3 * t9 : 3 * t9 + 2];
-        v = seg3d_wino_u(g0, g1, g2, t & 3);
-      } else if (T == SEG3D_WINO2D_T) {
-        v = seg3d_wino2d_u(w + a * sa + b * sb, flip, t);
-      } else {
-        v = w[a * sa + b * sb + (flip ? T - 1 - t : t)];
-      }
-    }
-    wp[idx] = v;
-  }
-}
-
-extern "C" int seg3d_pack_weights_mfma(const float* w, float* wp, int A, int B, int T, long long sa, long long sb,
-                                       int flip, void* stream) {
-  SEG3D_REQUIRE(w && wp && A > 0 && B > 0 && T > 0, "seg3d_pack_weights_mfma: bad arguments");
-  int AB = (A + 7) / 8, BB = (B + 31) / 32;
-  i64 total = (i64)BB * AB * T * 256;
-  hipLaunchKernelGGL(pack_mfma_kernel, dim3(seg3d_ew_grid(total, 256)), dim3(256), 0, (hipStream_t)stream, w, wp, A, B,
-                     AB, BB, T, (i64)sa, (i64)sb, flip);
-  SEG3D_LAUNCH_CHECK("seg3d_pack_weights_mfma");
-  return SEG3D_OK;
-}
-
 // bf16 MFMA pack (bf16 conv path): wp[bb][ab][t][h][j][r] = bf16(W(a = ab*16 + h*8 + r, b = bb*32 + j, t)), zero padded:
 // the same 1-KiB-per-tap LDS image as the fp32 pack with 8 bf16 channels where that has 4 floats.
-__global__ __launch_bounds__(256) void pack_mfma_bf16_kernel(const float* __restrict__ w, seg3d_bf16* __restrict__ wp,
-                                                               int A, int B, int AB, int BB, int T, i64 sa, i64 sb,
-                                                               int flip) {
-  i64 total = (i64)BB * AB * T * 512;
-  for (i64 idx = (i64)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (i64)gridDim.x * 256) {
-    int r = (int)(idx & 7);
-    int j = (int)((idx >> 3) & 31);
-    int h = (int)((idx >> 8) & 1);
-    i64 rest = idx >> 9;
-    int t = (int)(rest % T);
-    rest /= T;
-    int ab = (int)(rest % AB);
-    int bb = (int)(rest / AB);
-    int a = ab * 16 + h * 8 + r, b = bb * 32 + j;
-    float v = 0.f;
-    if (a < A && b < B) v = w[a * sa + b * sb + (flip ? T - 1 - t : t)];
-    wp[idx] = seg3d_f2bf(v);
-  }
-}
-
-extern "C" long long seg3d_packed_mfma_bf16_elems(int A, int B, int T) {
-  if (T == SEG3D_WINO_T || T == SEG3D_WINO2D_T) return -1;   // no bf16 Winograd image: callers must not size a buffer for one
-  return (long long)((B + 31) / 32) * ((A + 15) / 16) * T * 512;
-}
-
-extern "C" int seg3d_pack_weights_mfma_bf16(const float* w, void* wp, int A, int B, int T, long long sa, long long sb,
-                                            int flip, void* stream) {
-  SEG3D_REQUIRE(w && wp && A > 0 && B > 0 && T > 0, "seg3d_pack_weights_mfma_bf16: bad arguments");
-  SEG3D_REQUIRE(T != SEG3D_WINO_T && T != SEG3D_WINO2D_T,
-                "seg3d_pack_weights_mfma_bf16: T = 36 / 48 (Winograd images) exist in fp32 only");
-  int AB = (A + 15) / 16, BB = (B + 31) / 32;
-  i64 total = (i64)BB * AB * T * 512;
-  hipLaunchKernelGGL(pack_mfma_bf16_kernel, dim3(seg3d_ew_grid(total, 256)), dim3(256), 0, (hipStream_t)stream, w,
-                     (seg3d_bf16*)wp, A, B, AB, BB, T, (i64)sa, (i64)sb, flip);
-  SEG3D_LAUNCH_CHECK("seg3d_pack_weights_mfma_bf16");
-  return SEG3D_OK;
-}
+// One packer writes all of them (pack_mfma_chunk below, one workgroup per chunk); tests/pack_oracle.py restates the images.
 
 // fp32 <-> bf16 (round to nearest even) over n elements, n % 4 == 0 handled 4 per thread, tail by the last threads
 __global__ __launch_bounds__(256) void f32_to_bf16_kernel(const float* __restrict__ src, seg3d_bf16* __restrict__ dst,
@@ -294,10 +192,14 @@ template <> struct Seg3dPackTile<true> {
 };
 
 // WINO (jb.T = 36 / 48, fp32 images only): the 27 taps are read as usual, the packed chunk holds the WINO transformed "taps"
-template <int AW, bool BF, int TC, int WINO = 0>
-__device__ __forceinline__ void pack_mfma_chunk(const Seg3dPackJob& jb, int chunk,
+// PARTS (the one-job launch): PARTS workgroups share a chunk, workgroup `part` stages and writes the JN = 32 / PARTS output
+// channels from j0 = part * JN on
+template <int AW, bool BF, int TC, int WINO = 0, int PARTS = 1>
+__device__ __forceinline__ void pack_mfma_chunk(const Seg3dPackJob& jb, int chunk, int part,
                                                 typename Seg3dPackTile<BF>::type* __restrict__ tile) {
   typedef Seg3dPackTile<BF> TL;
+  constexpr int JN = 32 / PARTS;
+  const int j0 = PARTS == 1 ? 0 : part * JN;
   const int T = TC ? TC : jb.T;
   const int AB = (jb.A + AW - 1) / AW;
   const int ab = chunk % AB, bb = chunk / AB;
@@ -307,8 +209,8 @@ __device__ __forceinline__ void pack_mfma_chunk(const Seg3dPackJob& jb, int chun
     // w[b][a][t]: for a fixed output channel b the 8 x T values of this chunk are contiguous
     const int run = AW * T;
 #pragma unroll 6
-    for (int i = threadIdx.x; i < 32 * run; i += 256) {
-      const int b = i / run, r = i - b * run;
+    for (int i = threadIdx.x; i < JN * run; i += 256) {
+      const int bl = i / run, r = i - bl * run, b = j0 + bl;
       const int a = r / T, t = r - a * T;
       float v = 0.f;
       if (a0 + a < jb.A && b0 + b < jb.B) v = jb.w[(i64)(b0 + b) * jb.sb + (i64)a0 * T + r];
@@ -316,21 +218,21 @@ __device__ __forceinline__ void pack_mfma_chunk(const Seg3dPackJob& jb, int chun
     }
   } else if (T <= 27 && jb.sb == T) {
     // w[a][b][t]: for a fixed reduction channel a the 32 x T values are contiguous
-    const int run = 32 * T;
+    const int run = 32 * T, runp = JN * T;
 #pragma unroll 6
-    for (int i = threadIdx.x; i < AW * run; i += 256) {
-      const int a = i / run, r = i - a * run;
+    for (int i = threadIdx.x; i < AW * runp; i += 256) {
+      const int a = i / runp, r = j0 * T + (i - a * runp);
       float v = 0.f;
       if (a0 + a < jb.A && b0 + r / T < jb.B) v = jb.w[(i64)(a0 + a) * jb.sa + (i64)b0 * T + r];
       tile[a * run + r] = TL::put(v);
     }
   } else {
-    for (int i = threadIdx.x; i < n && T <= 27; i += 256) {
+    for (int i = threadIdx.x; i < n / PARTS && T <= 27; i += 256) {
       const int t = i % T, ab_ = i / T;
-      const int b = ab_ % 32, a = ab_ / 32;
+      const int b = j0 + ab_ % JN, a = ab_ / JN;
       float v = 0.f;
       if (a0 + a < jb.A && b0 + b < jb.B) v = jb.w[(a0 + a) * jb.sa + (b0 + b) * jb.sb + t];
-      tile[i] = TL::put(v);
+      tile[PARTS == 1 ? i : (a * 32 + b) * T + t] = TL::put(v);
     }
   }
   __syncthreads();
@@ -341,7 +243,7 @@ __device__ __forceinline__ void pack_mfma_chunk(const Seg3dPackJob& jb, int chun
     // all 3 x 16 transformed values in registers (the arithmetic of seg3d_wino2d_u, term by term), written as the twelve 16-byte
     // words [g] of the image -- for one g the 32 lanes j of a (h, r) write 512 contiguous bytes.  (Round 4's first form computed
     // every one of the 12 288 outputs on its own: nine tile reads, an index decode and the transform per element, 143 us per step.)
-    static_assert(AW == 8, "the T = 48 image is an fp32 image");
+    static_assert(AW == 8 && PARTS == 1, "the T = 48 image is an fp32 image, one workgroup per chunk");
     const int j = threadIdx.x & 31, r = (threadIdx.x >> 5) & 3, h = threadIdx.x >> 7;
     const float* g = tile + ((HW * h + r) * 32 + j) * 27;
     float gl[27];
@@ -370,22 +272,41 @@ __device__ __forceinline__ void pack_mfma_chunk(const Seg3dPackJob& jb, int chun
   }
   if constexpr (WINO == SEG3D_WINO_T && !BF) {
     const int nw = AW * 32 * WINO;
-    for (int i = threadIdx.x; i < nw; i += 256) {
-      const int r = i % HW, j = (i / HW) & 31, h = (i / (HW * 32)) & 1, tw = i / (HW * 64);
+    for (int i = threadIdx.x; i < nw / PARTS; i += 256) {
+      const int r = i % HW, j = j0 + ((i / HW) & (JN - 1)), h = (i / (HW * JN)) & 1, tw = i / (HW * 2 * JN);
       const float* g = tile + ((HW * h + r) * 32 + j) * 27;
       const int t9 = tw >> 2;
       const float g0 = g[jb.flip ? 26 - 3 * t9 : 3 * t9], g1 = g[jb.flip ? 25 - 3 * t9 : 3 * t9 + 1],
                   g2 = g[jb.flip ? 24 - 3 * t9 : 3 * t9 + 2];
-      jb.wp[(i64)chunk * nw + i] = seg3d_wino_u(g0, g1, g2, tw & 3);
+      jb.wp[(i64)chunk * nw + (PARTS == 1 ? i : ((tw * 2 + h) * 32 + j) * HW + r)] = seg3d_wino_u(g0, g1, g2, tw & 3);
     }
     return;
   }
 #pragma unroll 6
-  for (int i = threadIdx.x; i < n; i += 256) {
-    const int r = i % HW, j = (i / HW) & 31, h = (i / (HW * 32)) & 1, t = i / (HW * 64);
+  for (int i = threadIdx.x; i < n / PARTS; i += 256) {
+    const int r = i % HW, j = j0 + ((i / HW) & (JN - 1)), h = (i / (HW * JN)) & 1, t = i / (HW * 2 * JN);
     const typename TL::type v = tile[((HW * h + r) * 32 + j) * T + (jb.flip ? T - 1 - t : t)];
-    TL::store(jb.wp, (i64)chunk * n + i, v);
+    TL::store(jb.wp, (i64)chunk * n + (PARTS == 1 ? i : ((t * 2 + h) * 32 + j) * HW + r), v);
   }
+}
+
+// the LDS tile of a chunk: one array per image format, which the multi-job and the one-job kernel both stage through
+template <int AW, bool BF>
+__device__ __forceinline__ typename Seg3dPackTile<BF>::type* pack_mfma_tile() {
+  __shared__ typename Seg3dPackTile<BF>::type tile[AW * 32 * 27];   // bf16 images keep the tile in bf16: 27 KB, 5 workgroups per CU
+  return tile;
+}
+// workgroup blk = chunk * PARTS + part of one job (chunk = bb * AB + ab), by the job's tap count; the T = 48 image always has
+// one workgroup per chunk (blk = chunk): a thread writes the twelve words of its channel pair
+template <int AW, bool BF, int PARTS = 1>
+__device__ __forceinline__ void pack_mfma_job(const Seg3dPackJob& jb, int blk) {
+  typename Seg3dPackTile<BF>::type* tile = pack_mfma_tile<AW, BF>();
+  const int chunk = blk / PARTS, part = blk % PARTS;
+  if (jb.T == 27) pack_mfma_chunk<AW, BF, 27, 0, PARTS>(jb, chunk, part, tile);
+  else if (jb.T == SEG3D_WINO_T) pack_mfma_chunk<AW, BF, 27, SEG3D_WINO_T, PARTS>(jb, chunk, part, tile);
+  else if (jb.T == SEG3D_WINO2D_T) pack_mfma_chunk<AW, BF, 27, SEG3D_WINO2D_T>(jb, blk, 0, tile);
+  else if (jb.T == 8) pack_mfma_chunk<AW, BF, 8, 0, PARTS>(jb, chunk, part, tile);
+  else pack_mfma_chunk<AW, BF, 0, 0, PARTS>(jb, chunk, part, tile);
 }
 
 template <int AW, bool BF>
@@ -394,7 +315,6 @@ __device__ __forceinline__ void pack_mfma_multi_body(const Seg3dPackJob* __restr
   // conv kernels).  In both reference layouts one of the two channel strides equals T, so the chunk's source elements
   // form long contiguous runs: they are read in memory order (coalesced), transposed through LDS and written in packed
   // order (coalesced).  The first version gathered single floats straight from global memory and moved 5x the bytes.
-  __shared__ typename Seg3dPackTile<BF>::type tile[AW * 32 * 27];   // bf16 images keep the tile in bf16: 27 KB, 5 workgroups per CU
   __shared__ int sjob;
   if (threadIdx.x == 0) {
     int lo = 0, hi = njobs - 1;  // last job whose first_block <= blockIdx.x
@@ -406,12 +326,7 @@ __device__ __forceinline__ void pack_mfma_multi_body(const Seg3dPackJob* __restr
   }
   __syncthreads();
   const Seg3dPackJob jb = jobs[sjob];
-  const int chunk = (int)((i64)blockIdx.x - jb.first_block);   // = bb * AB + ab
-  if (jb.T == 27) pack_mfma_chunk<AW, BF, 27>(jb, chunk, tile);
-  else if (jb.T == SEG3D_WINO_T) pack_mfma_chunk<AW, BF, 27, SEG3D_WINO_T>(jb, chunk, tile);
-  else if (jb.T == SEG3D_WINO2D_T) pack_mfma_chunk<AW, BF, 27, SEG3D_WINO2D_T>(jb, chunk, tile);
-  else if (jb.T == 8) pack_mfma_chunk<AW, BF, 8>(jb, chunk, tile);
-  else pack_mfma_chunk<AW, BF, 0>(jb, chunk, tile);
+  pack_mfma_job<AW, BF>(jb, (int)((i64)blockIdx.x - jb.first_block));
 }
 
 __global__ __launch_bounds__(256) void pack_mfma_multi_kernel(const Seg3dPackJob* __restrict__ jobs, int njobs) {
@@ -452,6 +367,47 @@ extern "C" int seg3d_pack_weights_mfma_bf16_multi(const Seg3dPackJob* jobs_devic
   return SEG3D_OK;
 }
 
-extern "C" long long seg3d_packed_mfma_floats(int A, int B, int T) {
-  return (long long)((B + 31) / 32) * ((A + 7) / 8) * T * 256;
+// ONE weight tensor is the one-job case: the job travels as a kernel argument (no device table, nothing to allocate or
+// copy, so the launch can be captured).  A single tensor has few chunks (128 -> 128 channels: 64, bf16 32) and a workgroup per
+// chunk walks its 27 or 54 elements per thread one load latency after the other (8.2 / 15.6 us where the launch floor is
+// 1.8 us); sixteen workgroups per chunk, two output channels each: 2.9 / 3.0 us
+#define SEG3D_PACK_ONE_PARTS 16
+template <int AW, bool BF>
+__global__ __launch_bounds__(256) void pack_mfma_one_kernel(const Seg3dPackJob jb) {
+  pack_mfma_job<AW, BF, SEG3D_PACK_ONE_PARTS>(jb, (int)blockIdx.x);
+}
+
+extern "C" int seg3d_pack_weights_mfma(const float* w, float* wp, int A, int B, int T, long long sa, long long sb,
+                                       int flip, void* stream) {
+  SEG3D_REQUIRE(w && wp && A > 0 && B > 0 && T > 0, "seg3d_pack_weights_mfma: bad arguments");
+  SEG3D_REQUIRE(T <= 27 || T == SEG3D_WINO_T || T == SEG3D_WINO2D_T,
+                "seg3d_pack_weights_mfma: T = %d taps (the packer stages at most 27; 36 / 48 = Winograd images of 27)", T);
+  const long long blocks = seg3d_pack_job_blocks(A, B, T) * (T == SEG3D_WINO2D_T ? 1 : SEG3D_PACK_ONE_PARTS);
+  SEG3D_REQUIRE(blocks < (1ll << 31), "seg3d_pack_weights_mfma: too many chunks");
+  const Seg3dPackJob jb = {w, wp, sa, sb, 0, A, B, T, flip};
+  hipLaunchKernelGGL((pack_mfma_one_kernel<8, false>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, jb);
+  SEG3D_LAUNCH_CHECK("seg3d_pack_weights_mfma");
+  return SEG3D_OK;
+}
+
+extern "C" int seg3d_pack_weights_mfma_bf16(const float* w, void* wp, int A, int B, int T, long long sa, long long sb,
+                                            int flip, void* stream) {
+  SEG3D_REQUIRE(w && wp && A > 0 && B > 0 && T > 0, "seg3d_pack_weights_mfma_bf16: bad arguments");
+  SEG3D_REQUIRE(T != SEG3D_WINO_T && T != SEG3D_WINO2D_T,
+                "seg3d_pack_weights_mfma_bf16: T = 36 / 48 (Winograd images) exist in fp32 only");
+  SEG3D_REQUIRE(T <= 27, "seg3d_pack_weights_mfma_bf16: T = %d taps (the packer stages at most 27)", T);
+  const long long blocks = seg3d_pack_job_blocks_bf16(A, B, T) * SEG3D_PACK_ONE_PARTS;
+  SEG3D_REQUIRE(blocks < (1ll << 31), "seg3d_pack_weights_mfma_bf16: too many chunks");
+  const Seg3dPackJob jb = {w, (float*)wp, sa, sb, 0, A, B, T, flip};
+  hipLaunchKernelGGL((pack_mfma_one_kernel<16, true>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, jb);
+  SEG3D_LAUNCH_CHECK("seg3d_pack_weights_mfma_bf16");
+  return SEG3D_OK;
+}
+
+// image sizes: T * 256 floats (fp32), T * 512 bf16 elements per chunk
+extern "C" long long seg3d_packed_mfma_floats(int A, int B, int T) { return seg3d_pack_job_blocks(A, B, T) * T * 256; }
+
+extern "C" long long seg3d_packed_mfma_bf16_elems(int A, int B, int T) {
+  const long long blocks = seg3d_pack_job_blocks_bf16(A, B, T);   // -1: no bf16 Winograd image, callers must not size a buffer for one
+  return blocks < 0 ? -1 : blocks * T * 512;
 }

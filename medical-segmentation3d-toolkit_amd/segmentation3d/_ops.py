@@ -168,6 +168,23 @@ class _PackJob(ctypes.Structure):   # mirrors Seg3dPackJob (include/seg3d_hip.h)
                 ('flip', ctypes.c_int)]
 
 
+def _packed_image(w, A, B, T, bf16):
+    """uninitialised MFMA image of a weight of `w`'s device"""
+    if bf16:
+        return _empty((E.query('seg3d_packed_mfma_bf16_elems', A, B, T),), w, torch.bfloat16)
+    return _empty((E.query('seg3d_packed_mfma_floats', A, B, T),), w)
+
+
+def _pack_into(wp, w, A, B, T, sa, sb, flip, bf16):
+    E.call('seg3d_pack_weights_mfma_bf16' if bf16 else 'seg3d_pack_weights_mfma', E.ptr(w), E.ptr(wp), A, B, T, sa, sb, flip,
+           E.stream_ptr())
+    return wp
+
+
+def _pack_key(w, A, B, T, sa, sb, flip, bf16):
+    return (w.data_ptr(), w.device.index, A, B, T, sa, sb, flip, bf16)
+
+
 class PackedWeightCache(object):
     """Packed (MFMA-layout) images of conv weights kept across calls.
 
@@ -210,22 +227,25 @@ class PackedWeightCache(object):
         self.entries, self._table = {}, None
         self.epoch += 1
 
-    def get(self, w, A, B, T, sa, sb, flip, bf16=False):
-        key = (w.data_ptr(), w.device.index, A, B, T, sa, sb, flip, bf16)
+    def current(self, key, w):
+        """the registered image of `key` if it holds the present values of `w`, else None"""
         e = self.entries.get(key)
         if e is not None and e['epoch'] == self.epoch and e['version'] == w._version:
             return e['wp']
+        return None
+
+    def get(self, w, A, B, T, sa, sb, flip, bf16=False):
+        key = _pack_key(w, A, B, T, sa, sb, flip, bf16)
+        wp = self.current(key, w)
+        if wp is not None:
+            return wp
+        e = self.entries.get(key)
         if e is None:
-            if bf16:
-                wp = _empty((E.query('seg3d_packed_mfma_bf16_elems', A, B, T),), w, torch.bfloat16)
-            else:
-                wp = _empty((E.query('seg3d_packed_mfma_floats', A, B, T),), w)
-            e = {'w': w, 'wp': wp, 'args': (A, B, T, sa, sb, flip), 'bf16': bf16}
+            e = {'wp': _packed_image(w, A, B, T, bf16), 'args': (A, B, T, sa, sb, flip), 'bf16': bf16}
             self.entries[key] = e
             self._table = None
         e['w'] = w
-        E.call('seg3d_pack_weights_mfma_bf16' if bf16 else 'seg3d_pack_weights_mfma', E.ptr(w), E.ptr(e['wp']), A, B, T,
-               sa, sb, flip, E.stream_ptr())
+        _pack_into(e['wp'], w, A, B, T, sa, sb, flip, bf16)
         e['epoch'], e['version'] = self.epoch, w._version
         return e['wp']
 
@@ -272,18 +292,10 @@ def _pack_mfma(w, A, B, T, sa, sb, flip=0, bf16=False):
     if PACK_CACHE.enabled and not PACK_CACHE.read_only and not torch.cuda.is_current_stream_capturing():
         return PACK_CACHE.get(w, A, B, T, sa, sb, flip, bf16)
     if PACK_CACHE.enabled:   # inside a hipGraph capture or frozen(): only a current image may be used, the cache stays as it is
-        key = (w.data_ptr(), w.device.index, A, B, T, sa, sb, flip, bf16)
-        e = PACK_CACHE.entries.get(key)
-        if e is not None and e['epoch'] == PACK_CACHE.epoch and e['version'] == w._version:
-            return e['wp']
-    if bf16:
-        wp = _empty((E.query('seg3d_packed_mfma_bf16_elems', A, B, T),), w, torch.bfloat16)
-        E.call('seg3d_pack_weights_mfma_bf16', E.ptr(w), E.ptr(wp), A, B, T, sa, sb, flip, E.stream_ptr())
-        return wp
-    n = E.query('seg3d_packed_mfma_floats', A, B, T)
-    wp = _empty((n,), w)
-    E.call('seg3d_pack_weights_mfma', E.ptr(w), E.ptr(wp), A, B, T, sa, sb, flip, E.stream_ptr())
-    return wp
+        wp = PACK_CACHE.current(_pack_key(w, A, B, T, sa, sb, flip, bf16), w)
+        if wp is not None:
+            return wp
+    return _pack_into(_packed_image(w, A, B, T, bf16), w, A, B, T, sa, sb, flip, bf16)
 
 
 def _to_f32(t):
