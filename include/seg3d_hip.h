@@ -822,6 +822,42 @@ int seg3d_resample_deform_mc(const float* src, float* dst, int M, long long dst_
                              int Yo, int Zo, const double* affine_host, int linear, float pad, const double* l_host,
                              const float* ctrl, int gx, int gy, int gz, const double* t_host, int mirror_mask,
                              void* stream);
+/* ---- cubic B-spline interpolation (not in the reference) ----------------------------------
+ * The third interpolation of the resampler, exact: the interpolant passes through the samples.  DEFINITION (stated here
+ * and in DESIGN.md, nowhere else):
+ *   coefficients  per axis of n voxels the coefficients c of the samples s solve s[i] = (c[i-1] + 4 c[i] + c[i+1]) / 6 with
+ *                 indices outside 0 .. n-1 mirrored about the end samples (whole-sample mirror: -1 -> 1, n -> n - 2, in
+ *                 general period 2 (n - 1)); n = 1: c = s.  The 3-D coefficients are the three axes applied in turn
+ *                 (scipy.ndimage.spline_filter(order = 3, mode = 'mirror')).
+ *   recursion     z = sqrt(3) - 2:  c+[0] = sum_{k < 24} z^k s[mirror(k)],  c+[i] = s[i] + z c+[i-1],
+ *                 c-[n-1] = z / (z^2 - 1) (c+[n-1] + z c+[n-2]),  c-[i] = z (c-[i+1] - c+[i]),  c = 6 c-.  Running values in
+ *                 double; c+ and c are stored as fp32.
+ *   evaluation    at the continuous index (cx, cy, cz): per axis k = floor(c), f = c - k, taps k-1 .. k+2 with the same
+ *                 mirror, weights the uniform cubic basis B_0 .. B_3(f) written out above for the elastic field.  Double,
+ *                 one fixed order -- per (z, y) row the x taps k-1 .. k+2 added left to right, then the four rows with the
+ *                 y weights, then the four planes with the z weights -- rounded to float once (the convention of the
+ *                 trilinear branch).  Inside test and padding are those of seg3d_resample_affine: -0.5 <= c < size - 0.5,
+ *                 else `pad`.  Overshoot is not clamped (neither nnU-Net nor ITK clamp).
+ * seg3d_bspline_prefilter_mc: samples src [Z][Y][X][M] fp32 (M = 1..8) -> coefficients dst of the same shape; dst == src
+ * (in place) or disjoint; any axis length >= 1, 64-bit indexing.  Three passes (x, y, z; an axis of one voxel has none), no
+ * workspace, no atomics, no host sync: two runs are bit-equal, channel m equals the M = 1 call on plane m bit for bit,
+ * and in place equals out of place bit for bit. */
+int seg3d_bspline_prefilter_mc(const float* src, float* dst, int X, int Y, int Z, int M, void* stream);
+/* The resampling entries with the spline: arguments and geometry of seg3d_resample_affine(_mc) / seg3d_resample_deform(_mc)
+ * without `linear` (index map, inside test, elastic field, mirror mask, dst_stride and padding are theirs), src holds the
+ * COEFFICIENTS of seg3d_bspline_prefilter_mc.  A zero control grid gives the affine entry's result bit for bit; channel m
+ * of an _mc entry equals its M = 1, dst_stride = 1 case -- the entry without _mc -- on plane m bit for bit. */
+int seg3d_resample_bspline(const float* src, float* dst, int Xi, int Yi, int Zi, int Xo, int Yo, int Zo,
+                           const double* affine_host, float pad, void* stream);
+int seg3d_resample_bspline_mc(const float* src, float* dst, int M, long long dst_stride, int Xi, int Yi, int Zi, int Xo,
+                              int Yo, int Zo, const double* affine_host, float pad, void* stream);
+int seg3d_resample_bspline_deform(const float* src, float* dst, int Xi, int Yi, int Zi, int Xo, int Yo, int Zo,
+                                  const double* affine_host, float pad, const double* l_host, const float* ctrl, int gx,
+                                  int gy, int gz, const double* t_host, int mirror_mask, void* stream);
+int seg3d_resample_bspline_deform_mc(const float* src, float* dst, int M, long long dst_stride, int Xi, int Yi, int Zi,
+                                     int Xo, int Yo, int Zo, const double* affine_host, float pad, const double* l_host,
+                                     const float* ctrl, int gx, int gy, int gz, const double* t_host, int mirror_mask,
+                                     void* stream);
 /* Intensity augmentation of a normalised crop [Z][Y][X][M] (M = 1..8, channels-last; M = 1 is the planar crop), IN PLACE.
  * Per modality m, with (mn, mx, mean) of the crop's channel m (min / max exact, mean from an fp64 sum in a fixed order):
  *   brightness  y = x * brightness

@@ -13,6 +13,7 @@
 //   voxel in raster order -- the labels here are the component's smallest linear index, which gives the same order.
 // All kernels are HBM-bound byte movers / integer work.
 #include "seg3d_imagegrid.h"
+#include "seg3d_bspline.h"
 #include "label_device.h"
 #include "mc_device.h"
 #include "seg3d_hip.h"
@@ -286,6 +287,117 @@ extern "C" int seg3d_resample_deform(const float* src, float* dst, int Xi, int Y
                                      void* stream) {
   return resample_deform("seg3d_resample_deform", src, dst, 1, 1, Xi, Yi, Zi, Xo, Yo, Zo, affine_host, linear, pad, l_host,
                          ctrl, gx, gy, gz, t_host, mirror_mask, stream);
+}
+
+// ---- cubic B-spline evaluation -----------------------------------------------------------
+// The resampler above with the 64-tap spline of seg3d_bspline.h in place of the trilinear / NN branch: src holds the
+// COEFFICIENTS of seg3d_bspline_prefilter_mc.  Index map, inside test, deformation, dst_stride and padding are the
+// kernel's above (the same functions), so the geometry is the existing resampler's by construction.  A compile-time
+// width gathers its 64 rows as rows (16 live at a time: one (z, y) line of four); the runtime width walks the channels
+// one by one -- 64 rows of eight floats would not fit the register file.
+template <int MC, bool VEC, bool DEFORM>
+__global__ __launch_bounds__(256) void resample_bspline_mc_kernel(const float* __restrict__ src, float* __restrict__ dst,
+                                                                    int Mrt, i64 dst_stride, int Xi, int Yi, int Zi, int Xo,
+                                                                    int Yo, int Zo, Affine12 A, float pad,
+                                                                    DeformArgs<DEFORM> dfm) {
+  constexpr int MR = mc_regs<MC>;
+  const int M = mc_width<MC>(Mrt);
+  extern __shared__ double deform_smem[];
+  DeformLds lds;
+  if constexpr (DEFORM) lds = deform_stage(deform_smem, dfm, Xo, Yo, Zo);
+  const i64 total = (i64)Xo * Yo * Zo;
+  for (i64 idx = (i64)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (i64)gridDim.x * 256) {
+    const int x = (int)(idx % Xo);
+    const i64 t = idx / Xo;
+    const int y = (int)(t % Yo), z = (int)(t / Yo);
+    double cx, cy, cz;
+    affine12_apply(A, x, y, z, cx, cy, cz);
+    if constexpr (DEFORM) deform_apply(lds, dfm, x, y, z, Xo, Yo, Zo, cx, cy, cz);
+    float out[MR];
+#pragma unroll
+    for (int m = 0; m < MR; ++m) out[m] = pad;
+    if (SEG3D_INSIDE_BUFFER(cx, cy, cz, Xi, Yi, Zi)) {
+      BsplineTap tap;
+      bspline_tap(cx, cy, cz, Xi, Yi, Zi, tap);
+      if constexpr (MC > 0) {
+        bspline_eval<MC>(tap, Xi, Yi, [&](i64 voxel, float* v) { mc_load_row<MC, VEC>(src + voxel * MC, v); }, out);
+      } else {
+        for (int m = 0; m < M; ++m) {
+          float o;
+          bspline_eval<1>(tap, Xi, Yi, [&](i64 voxel, float* v) { v[0] = src[voxel * M + m]; }, &o);
+#pragma unroll
+          for (int k = 0; k < MR; ++k)   // static register index
+            if (k == m) out[k] = o;
+        }
+      }
+    }
+    mc_store_row<MC, VEC>(dst + idx * dst_stride, out, M);
+  }
+}
+
+template <int MC, bool VEC, bool DEFORM>
+static void resample_bspline_mc_launch(const float* src, float* dst, int M, i64 dst_stride, int Xi, int Yi, int Zi, int Xo,
+                                       int Yo, int Zo, const Affine12& A, float pad, const DeformArgs<DEFORM>& D, size_t lds,
+                                       hipStream_t s) {
+  hipLaunchKernelGGL((resample_bspline_mc_kernel<MC, VEC, DEFORM>), dim3(seg3d_ew_grid((i64)Xo * Yo * Zo, 256)), dim3(256),
+                     lds, s, src, dst, M, dst_stride, Xi, Yi, Zi, Xo, Yo, Zo, A, pad, D);
+}
+
+static int resample_bspline(const char* name, const float* src, float* dst, int M, long long dst_stride, int Xi, int Yi,
+                            int Zi, int Xo, int Yo, int Zo, const double* affine_host, float pad, void* stream) {
+  Affine12 A;
+  const int rc = resample_args(name, src, dst, M, dst_stride, Xi, Yi, Zi, Xo, Yo, Zo, affine_host, &A);
+  if (rc != SEG3D_OK) return rc;
+  MC_DISPATCH(resample_bspline_mc_launch, M, mc_vec_rows(M, src, dst, dst_stride),
+              (src, dst, M, (i64)dst_stride, Xi, Yi, Zi, Xo, Yo, Zo, A, pad, DeformArgs<false>(), 0, (hipStream_t)stream));
+  SEG3D_LAUNCH_CHECK(name);
+  return SEG3D_OK;
+}
+
+static int resample_bspline_deform(const char* name, const float* src, float* dst, int M, long long dst_stride, int Xi,
+                                   int Yi, int Zi, int Xo, int Yo, int Zo, const double* affine_host, float pad,
+                                   const double* l_host, const float* ctrl, int gx, int gy, int gz, const double* t_host,
+                                   int mirror_mask, void* stream) {
+  Affine12 A;
+  int rc = resample_args(name, src, dst, M, dst_stride, Xi, Yi, Zi, Xo, Yo, Zo, affine_host, &A);
+  if (rc != SEG3D_OK) return rc;
+  DeformArgs<true> D;
+  rc = deform_args(name, Xo, Yo, Zo, l_host, ctrl, gx, gy, gz, t_host, mirror_mask, &D);
+  if (rc != SEG3D_OK) return rc;
+  MC_DISPATCH(resample_bspline_mc_launch, M, mc_vec_rows(M, src, dst, dst_stride),
+              (src, dst, M, (i64)dst_stride, Xi, Yi, Zi, Xo, Yo, Zo, A, pad, D, deform_lds_bytes(Xo, Yo, Zo, D.g),
+               (hipStream_t)stream));
+  SEG3D_LAUNCH_CHECK(name);
+  return SEG3D_OK;
+}
+
+// coefficients [Zi][Yi][Xi][M] -> rows of M floats at dst + voxel * dst_stride: the spline sampled at c = M * (x, y, z, 1)
+extern "C" int seg3d_resample_bspline_mc(const float* src, float* dst, int M, long long dst_stride, int Xi, int Yi, int Zi,
+                                         int Xo, int Yo, int Zo, const double* affine_host, float pad, void* stream) {
+  return resample_bspline("seg3d_resample_bspline_mc", src, dst, M, dst_stride, Xi, Yi, Zi, Xo, Yo, Zo, affine_host, pad,
+                          stream);
+}
+
+// seg3d_resample_bspline_mc with the sampled point displaced by the elastic field, c = M (x, y, z, 1) + L u(x', y', z')
+extern "C" int seg3d_resample_bspline_deform_mc(const float* src, float* dst, int M, long long dst_stride, int Xi, int Yi,
+                                                int Zi, int Xo, int Yo, int Zo, const double* affine_host, float pad,
+                                                const double* l_host, const float* ctrl, int gx, int gy, int gz,
+                                                const double* t_host, int mirror_mask, void* stream) {
+  return resample_bspline_deform("seg3d_resample_bspline_deform_mc", src, dst, M, dst_stride, Xi, Yi, Zi, Xo, Yo, Zo,
+                                 affine_host, pad, l_host, ctrl, gx, gy, gz, t_host, mirror_mask, stream);
+}
+
+// the M = 1 case of the two entries above: coefficients [Zi][Yi][Xi] -> dst [Zo][Yo][Xo]
+extern "C" int seg3d_resample_bspline(const float* src, float* dst, int Xi, int Yi, int Zi, int Xo, int Yo, int Zo,
+                                      const double* affine_host, float pad, void* stream) {
+  return resample_bspline("seg3d_resample_bspline", src, dst, 1, 1, Xi, Yi, Zi, Xo, Yo, Zo, affine_host, pad, stream);
+}
+
+extern "C" int seg3d_resample_bspline_deform(const float* src, float* dst, int Xi, int Yi, int Zi, int Xo, int Yo, int Zo,
+                                             const double* affine_host, float pad, const double* l_host, const float* ctrl,
+                                             int gx, int gy, int gz, const double* t_host, int mirror_mask, void* stream) {
+  return resample_bspline_deform("seg3d_resample_bspline_deform", src, dst, 1, 1, Xi, Yi, Zi, Xo, Yo, Zo, affine_host, pad,
+                                 l_host, ctrl, gx, gy, gz, t_host, mirror_mask, stream);
 }
 
 // ---- bounding box -----------------------------------------------------------------------------------------------------

@@ -22,7 +22,7 @@ __C.dataset.sampling_method = 'HYBRID'                 # GLOBAL | MASK | HYBRID 
 __C.dataset.random_translation = [15, 15, 15]             # mm, uniform in [-t, t] per axis
 __C.dataset.random_scale = [0.9, 1.1]                     # crop spacing = spacing * uniform(lo, hi)
 __C.dataset.random_mirror_axes = []                       # e.g. ['x', 'y']: mirror each listed axis with probability 1/2
-__C.dataset.interpolation = 'LINEAR'                   # NN | LINEAR
+__C.dataset.interpolation = 'LINEAR'                   # NN | LINEAR | BSPLINE
 # on-device training augmentation (an extension of this build, everything off: the crops and the RNG stream are then
 # exactly those without the section).  Rotation and elastic deformation run inside the crop's resampling launch, the
 # intensity transforms in one fused pass over the normalised crop.  A transform is on when its probability is > 0 and

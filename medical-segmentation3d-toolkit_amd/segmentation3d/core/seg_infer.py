@@ -866,7 +866,9 @@ def _member_probabilities(model, cfg, images, bbox_start_voxel, bbox_end_voxel, 
     X, Y, Z = image.GetSize()
     Xp, Yp, Zp = image_tools.resampled_size((X, Y, Z), image.GetSpacing(), spacing, ms)
     interp = model.get('interpolation', 'LINEAR') or 'LINEAR'
-    # all modalities to the model grid in one launch: [Zp, Yp, Xp, M]
+    # all modalities to the model grid in one launch: [Zp, Yp, Xp, M].  A model trained with 'BSPLINE' gets the spline: the
+    # uploaded tensor is prefiltered into a temporary (src may be shared by the members of an ensemble, so not in place)
+    # and evaluated onto the model grid
     if src is None:
         src = image_tools.images_to_device(images, dev)
     vol = image_tools.resample_device_mc(src, img_frame, (Xp, Yp, Zp), iso_frame, interp, 0.0)

@@ -4,7 +4,8 @@ methods and RNG call order (dataloader/dataset.py:55-209), but the crop itself r
 The reference reads both volumes from disk, resamples a crop with SimpleITK and normalises it in a DataLoader worker
 for every sample; at >150 patches/s per GPU four such workers cannot feed eight GPUs.  Here every case is read ONCE
 (MetaImage, utils/mha_io.py), kept resident in HBM, and a sample costs two launches of the resampling kernel
-(csrc/postproc.hip: image LINEAR / NN, mask NN) plus the on-device normaliser (csrc/patch.hip) -- no worker
+(csrc/postproc.hip: image LINEAR / NN / BSPLINE -- the resident volume then holds the spline
+coefficients, prefiltered once at load, csrc/bspline.hip --, mask NN) plus the on-device normaliser (csrc/patch.hip) -- no worker
 processes, no host copies.  The random decisions (crop centre, translation, scale) stay on the host with numpy's
 global RNG in exactly the reference's order, so a seeded run draws the same crops.
 `DeviceCropLoader` batches the samples of a sampler into device tensors for core/seg_train.train().
@@ -121,9 +122,11 @@ class _Case(object):
     voxel of a label (in np.argwhere order) without scanning the volume.  `image` is one modality or a list of M
     co-registered modalities, kept as ONE channels-last [Z, Y, X, M] fp32 tensor `volume` (a BraTS case of
     240 x 240 x 155 x 4 is 143 MB resident); the attribute `image` is that tensor, or its [Z, Y, X] view for one
-    modality.  The mask and the histogram are the same for any M."""
+    modality.  The mask and the histogram are the same for any M.
+    bspline: `volume` is prefiltered in place once, here, and holds the cubic B-spline COEFFICIENTS of the image from then
+    on (same footprint; image_tools.bspline_prefilter_device), which is what a 'BSPLINE' crop evaluates."""
 
-    def __init__(self, image, seg, device):
+    def __init__(self, image, seg, device, bspline=False):
         images = image if isinstance(image, (list, tuple)) else [image]
         image = images[0]
         self.num_modality = len(images)
@@ -132,6 +135,8 @@ class _Case(object):
         self.size = image.GetSize()
         self.seg_size = seg.GetSize()
         self.volume = image_tools.images_to_device(images, device)          # [Z, Y, X, M]
+        if bspline:
+            image_tools.bspline_prefilter_device(self.volume, out=self.volume)
         self.image = self.volume[..., 0] if self.num_modality == 1 else self.volume
         self.seg_host = np.array(seg.array, order='C')                       # [z, y, x], label values as stored
         self.seg = torch.from_numpy(self.seg_host.astype(np.float32)).to(device)
@@ -331,7 +336,7 @@ class SegmentationDataset(Dataset):
         self.random_scale = np.array(random_scale, dtype=np.double)
         assert self.random_scale.size == 2, 'Only 2-element of random scale is supported'
         self.interpolation = interpolation
-        assert self.interpolation in ('LINEAR', 'NN'), 'interpolation must either be a LINEAR or NN'
+        assert self.interpolation in ('LINEAR', 'NN', 'BSPLINE'), 'interpolation must be LINEAR, NN or BSPLINE'
         self.crop_normalizers = crop_normalizers
         assert isinstance(self.crop_normalizers, list), 'crop normalizers must be a list'
         # mirror augmentation (not in the reference): every listed axis is mirrored with probability 1/2 per sample
@@ -395,7 +400,8 @@ class SegmentationDataset(Dataset):
         c = self._cases.get(index)
         if c is None:
             image = read_case_modalities(self.im_list[index], self.case_name(index))
-            c = _Case(image, read_image(self.seg_list[index], dtype=None), self.device)
+            c = _Case(image, read_image(self.seg_list[index], dtype=None), self.device,
+                      bspline=self.interpolation == 'BSPLINE')
             self._cases[index] = c
         return c
 
@@ -579,7 +585,7 @@ class SegmentationDataset(Dataset):
         else:
             first = out
         im = image_tools.crop_image_device_mc(case.volume, case.frame, center, self.crop_size, crop_spacing,
-                                              self.interpolation, out=first, mirror=mirror, **spatial)
+                                              self.interpolation, out=first, mirror=mirror, prefiltered=True, **spatial)
         im = image_tools.normalize_crop_device_mc(im, self._norm_params, out=im)
         for f in filters:
             im, other = f(im, other), im

@@ -5,7 +5,8 @@ Only the five functions that define the sliding-window semantics are provided (S
   add_image_region / add_image_value (image_tools.py:435-469) -> device kernels, see core/seg_infer.py
   convert_image_to_tensor / convert_tensor_to_image (image_tools.py:274-326)
 plus the geometry functions around the patch path, on the device:
-  resample / resample_spacing                         (image_tools.py:329-377)  trilinear / NN, ITK inside test and padding
+  resample / resample_spacing                         (image_tools.py:329-377)  trilinear / NN (and cubic B-spline, not in
+                                                      the reference), ITK inside test and padding
   pick_largest_connected_component / remove_small_connected_component (image_tools.py:380-432)  26-connectivity
   get_bounding_box                                    (image_tools.py:481-510)
 Images are `Image3d` (numpy [z, y, x] + spacing / origin / direction); the `*_device` variants take and return device
@@ -199,27 +200,50 @@ def _crop_index_map(src_frame, dst_frame, out_size, rotation, mirror):
     return np.ascontiguousarray(M, dtype=np.float64)
 
 
+def bspline_prefilter_device(volume, out=None):
+    """samples -> cubic B-spline coefficients (seg3d_bspline_prefilter_mc, whole-sample mirror): volume a float32 device
+    tensor [Z, Y, X] or [Z, Y, X, M], M <= 8; `out`: a contiguous tensor of the same shape, `volume` itself for in place.
+    Returns the coefficients: what the 'BSPLINE' resampling entries take with prefiltered=True."""
+    E.require_device(volume, out)
+    if volume.dim() not in (3, 4) or volume.dtype != torch.float32:
+        raise ValueError('volume must be a float32 [Z, Y, X] or [Z, Y, X, M] tensor')
+    if out is None:
+        volume = volume.contiguous()
+        out = torch.empty_like(volume)
+    elif (not volume.is_contiguous() or out.shape != volume.shape or not out.is_contiguous()
+          or out.dtype != torch.float32):
+        raise ValueError('volume and out must be contiguous float32 tensors of one shape')
+    Z, Y, X = (int(v) for v in volume.shape[:3])
+    M = int(volume.shape[3]) if volume.dim() == 4 else 1
+    E.call('seg3d_bspline_prefilter_mc', E.ptr(volume), E.ptr(out), X, Y, Z, M, E.stream_ptr())
+    return out
+
+
 def resample_device(src, src_frame, out_size, dst_frame, interp_method, padding_value=0.0, mirror=None, rotation=None,
-                    deform=None):
+                    deform=None, prefiltered=False):
     """src: float32 device tensor [Z, Y, X]; returns the float32 device tensor [Zo, Yo, Xo] of the destination grid: the
     M = 1 case of resample_device_mc (a [Z, Y, X] volume is the same memory as [Z, Y, X, 1])."""
     E.require_device(src)
     if src.dim() != 3:
         raise ValueError('src must be a [Z, Y, X] tensor')
     return resample_device_mc(src.unsqueeze(3), src_frame, out_size, dst_frame, interp_method, padding_value,
-                              mirror=mirror, rotation=rotation, deform=deform)[..., 0]
+                              mirror=mirror, rotation=rotation, deform=deform, prefiltered=prefiltered)[..., 0]
 
 
 def resample_device_mc(src, src_frame, out_size, dst_frame, interp_method, padding_value=0.0, out=None, mirror=None,
-                       rotation=None, deform=None):
+                       rotation=None, deform=None, prefiltered=False):
     """M co-registered channels in one launch: src float32 device tensor [Z, Y, X, M] (channels-last) -> [Zo, Yo, Xo, M].
     `out`: a contiguous [Zo, Yo, Xo, M] destination, e.g. slot b of an NDHWC batch.  Channel m equals resample_device
     on src[..., m] bit for bit (seg3d_resample_affine_mc; with `deform` seg3d_resample_deform_mc).
     mirror = (x, y, z) flags: the destination grid is sampled mirrored along those axes (mirror_index_affine).
     rotation = (gx, gy, gz) radians: the grid is rotated about its centre (rotate_index_affine).  deform = (ctrl, grid_mm):
     the sampled points are displaced by a cubic B-spline field (ctrl float32 device [gz, gy, gx, 3] mm,
-    bspline_control_dims points).  Without the last two this is the plain affine launch."""
-    if interp_method not in ('LINEAR', 'NN'):
+    bspline_control_dims points).  Without the last two this is the plain affine launch.
+    interp_method 'BSPLINE': exact cubic B-spline interpolation (seg3d_resample_bspline_mc / _deform_mc).  With
+    prefiltered=False src holds samples and is prefiltered into a temporary first (bspline_prefilter_device); with
+    prefiltered=True src already holds the coefficients and the call is the one evaluation launch.  The other methods
+    ignore the keyword."""
+    if interp_method not in ('LINEAR', 'NN', 'BSPLINE'):
         raise ValueError('Unsupported interpolation type.')
     E.require_device(src)
     if src.dim() != 4 or src.dtype != torch.float32:
@@ -232,6 +256,17 @@ def resample_device_mc(src, src_frame, out_size, dst_frame, interp_method, paddi
     elif tuple(out.shape) != (Zo, Yo, Xo, M) or not out.is_contiguous() or out.dtype != torch.float32:
         raise ValueError('out must be a contiguous float32 [{}, {}, {}, {}] tensor'.format(Zo, Yo, Xo, M))
     M_ = _crop_index_map(src_frame, dst_frame, (Xo, Yo, Zo), rotation, mirror)
+    if interp_method == 'BSPLINE':
+        coef = src if prefiltered else bspline_prefilter_device(src)
+        if deform is None:
+            E.call('seg3d_resample_bspline_mc', E.ptr(coef), E.ptr(out), int(M), int(M), Xi, Yi, Zi, Xo, Yo, Zo,
+                   M_.ctypes.data_as(ctypes.c_void_p), float(padding_value), E.stream_ptr())
+            return out
+        L, ctrl, g, t, mask = _deform_call_args(src_frame, dst_frame, (Xo, Yo, Zo), deform, mirror)
+        E.call('seg3d_resample_bspline_deform_mc', E.ptr(coef), E.ptr(out), int(M), int(M), Xi, Yi, Zi, Xo, Yo, Zo,
+               M_.ctypes.data_as(ctypes.c_void_p), float(padding_value), L.ctypes.data_as(ctypes.c_void_p), E.ptr(ctrl),
+               g[0], g[1], g[2], t.ctypes.data_as(ctypes.c_void_p), mask, E.stream_ptr())
+        return out
     if deform is None:
         E.call('seg3d_resample_affine_mc', E.ptr(src), E.ptr(out), int(M), int(M), Xi, Yi, Zi, Xo, Yo, Zo,
                M_.ctypes.data_as(ctypes.c_void_p), int(interp_method == 'LINEAR'), float(padding_value), E.stream_ptr())
@@ -431,11 +466,11 @@ def crop_origin(cropping_center, cropping_size, cropping_spacing):
 
 
 def crop_image_device(volume, frame, cropping_center, cropping_size, cropping_spacing, interp_method, mirror=None,
-                      rotation=None, deform=None):
+                      rotation=None, deform=None, prefiltered=False):
     """volume: float32 device tensor [Z, Y, X] with frame (spacing, origin, direction) -> crop [z, y, x]: the M = 1 case
     of crop_image_device_mc"""
     return crop_image_device_mc(volume.unsqueeze(3), frame, cropping_center, cropping_size, cropping_spacing, interp_method,
-                                mirror=mirror, rotation=rotation, deform=deform)[..., 0]
+                                mirror=mirror, rotation=rotation, deform=deform, prefiltered=prefiltered)[..., 0]
 
 
 def crop_image(image, cropping_center, cropping_size, cropping_spacing, interp_method):
@@ -455,16 +490,17 @@ def normalize_crop_device(crop, normalizer):
 
 
 def crop_image_device_mc(volume, frame, cropping_center, cropping_size, cropping_spacing, interp_method, out=None,
-                         mirror=None, rotation=None, deform=None):
+                         mirror=None, rotation=None, deform=None, prefiltered=False):
     """volume: float32 device tensor [Z, Y, X, M] (channels-last) with frame (spacing, origin, direction) -> crop
     [z, y, x, M] of `cropping_size` voxels at `cropping_spacing`, centred at the world point `cropping_center`, zero
     outside, one launch for all modalities; mirror = (x, y, z) flags: the crop comes out mirrored along those axes (same
-    launch, mirrored index map); rotation / deform: training augmentation inside the same launch, see resample_device_mc"""
+    launch, mirrored index map); rotation / deform: training augmentation inside the same launch, and prefiltered (the
+    volume holds 'BSPLINE' coefficients): see resample_device_mc"""
     size = [int(cropping_size[idx]) for idx in range(3)]
     spacing = [float(cropping_spacing[idx]) for idx in range(3)]
     dst_frame = (spacing, crop_origin(cropping_center, size, spacing), frame[2])
     return resample_device_mc(volume, frame, size, dst_frame, interp_method, 0.0, out=out, mirror=mirror,
-                              rotation=rotation, deform=deform)
+                              rotation=rotation, deform=deform, prefiltered=prefiltered)
 
 
 def normalize_crop_device_mc(crop, params, out=None):
