@@ -964,6 +964,50 @@ int seg3d_lesion_pairs(const int* dmap, const unsigned char* a, const int* pmap,
 int seg3d_lesion_select(const int* dmap, const unsigned char* a, const int* pmap, const unsigned char* flag, int kp,
                         int lesion, long long n, unsigned char* g, unsigned char* u, void* stream);
 
+/* ---- whole-volume statistics for case-level normalisation (not in the reference; DESIGN.md section 7 row f20;
+ * csrc/volume_stats.hip) --------------------------------------------------------------------------------------------------
+ * volume: fp32 channels-last [Z][Y][X][M], 1 <= M <= 8, `voxels` = Z*Y*X in [1, 2^31); sel: uint8 [Z][Y][X] or NULL.
+ * Selection set S_m of modality m:  mode 0 = every voxel;  mode 1 = x != 0, decided on the bits (-0.0 is out, a denormal
+ * is in);  mode 2 = sel[v] != 0, the same set for every m.
+ * Per modality, out[m][9] (device doubles) = n, min, max, mean, std, value(q_0) .. value(q_3):
+ *   n = |S_m|; min / max of S_m; -0.0 is reported as +0.0 everywhere;
+ *   value(q) = sorted(S_m)[k], k = floor(q (n - 1) + 0.5) computed in double on the device from the device's n, q in
+ *     [0, 1], Q <= 4 of them (entries past Q are 0).  This is the NEAREST RANK: it differs from the linearly interpolated
+ *     percentile (numpy's default) by less than the gap between two neighbouring order statistics;
+ *   mean and population std in fp64 of S_m, std floored at 1e-6; with clip != 0 (needs Q >= 2, q_0 <= q_1) of the values
+ *     clamped to [value(q_0), value(q_1)] (the CT rule);
+ *   n == 0: every output is 0 and std is the floor.
+ * The order statistics come from a three-level radix select (11 / 11 / 10 bits) over the order-preserving integer key of
+ * the float; n, min, max and the order statistics are exact, and with integer atomics only and a fixed-order fp64 sum of
+ * per-workgroup partials two runs are bit-equal in every output.  NaN / Inf are outside the value contract (the kernels
+ * stay inside their buffers and terminate).
+ * Split entries, so that histograms and moments can be accumulated over several volumes (a data set) before they are
+ * resolved; every volume must be passed to every level with the same M, mode and sel:
+ *   seg3d_volume_stats_begin                      zero the state
+ *   for level in 0, 1, 2 (level 0 alone when Q == 0):
+ *     seg3d_volume_stats_accumulate_hist          once per volume: this level's digit histograms (and min / max at level 0)
+ *     seg3d_volume_stats_resolve                  once: level 0 derives n and the ranks (equal ranks are resolved once);
+ *                                                 each level fixes its digit of every rank's key
+ *   seg3d_volume_stats_accumulate_moments         once per volume (after the resolves: the clamp and the pivot of the
+ *                                                 sums come from the state)
+ *   seg3d_volume_stats_finish                     out[m][9]
+ * seg3d_volume_stats is that sequence for one volume.  quantiles: Q doubles in HOST memory.  state:
+ * seg3d_volume_stats_state_bytes(M) bytes of device memory, 8-byte aligned (0: bad M); layout: control block (8 x 32
+ * int64: n, min key, max key, and per rank k, key prefix, rank inside the chosen bin, alias), level-0 histograms [M][2048],
+ * level-1 [M][4][2048], level-2 [M][4][1024] (all uint64), moment slots [2048][M][2] doubles.  No entry allocates, reads
+ * back or synchronises, nothing data-dependent is baked into a launch (capturable).  Rows of M floats are read as one
+ * 16- / 8-byte load when M is 4 / 2 and the volume is so aligned, else by scalar loads; the results do not depend on it. */
+long long seg3d_volume_stats_state_bytes(int M);
+int seg3d_volume_stats_begin(void* state, int M, void* stream);
+int seg3d_volume_stats_accumulate_hist(const float* volume, const unsigned char* sel, long long voxels, int M, int mode,
+                                       int level, void* state, void* stream);
+int seg3d_volume_stats_resolve(void* state, int M, int Q, const double* quantiles, int level, void* stream);
+int seg3d_volume_stats_accumulate_moments(const float* volume, const unsigned char* sel, long long voxels, int M, int mode,
+                                          int clip, void* state, void* stream);
+int seg3d_volume_stats_finish(void* state, int M, int Q, int clip, double* out, void* stream);
+int seg3d_volume_stats(const float* volume, const unsigned char* sel, long long voxels, int M, int mode, int Q,
+                       const double* quantiles, int clip, void* state, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

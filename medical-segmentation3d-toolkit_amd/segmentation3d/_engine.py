@@ -266,6 +266,13 @@ _SIGNATURES = {
     'seg3d_ccl26_label': (_c_int, [_c_p] + [_c_int] * 3 + [_c_p] * 3 + [_c_int, _c_p, _c_p]),
     'seg3d_lesion_pairs': (_c_int, [_c_p] * 3 + [_c_ll, _c_int] + [_c_p] * 3 + [_c_ll, _c_int, _c_p, _c_p]),
     'seg3d_lesion_select': (_c_int, [_c_p] * 4 + [_c_int, _c_int, _c_ll] + [_c_p] * 3),
+    'seg3d_volume_stats_state_bytes': (_c_ll, [_c_int]),
+    'seg3d_volume_stats_begin': (_c_int, [_c_p, _c_int, _c_p]),
+    'seg3d_volume_stats_accumulate_hist': (_c_int, [_c_p, _c_p, _c_ll, _c_int, _c_int, _c_int, _c_p, _c_p]),
+    'seg3d_volume_stats_resolve': (_c_int, [_c_p, _c_int, _c_int, _c_p, _c_int, _c_p]),
+    'seg3d_volume_stats_accumulate_moments': (_c_int, [_c_p, _c_p, _c_ll, _c_int, _c_int, _c_int, _c_p, _c_p]),
+    'seg3d_volume_stats_finish': (_c_int, [_c_p, _c_int, _c_int, _c_int, _c_p, _c_p]),
+    'seg3d_volume_stats': (_c_int, [_c_p, _c_p, _c_ll, _c_int, _c_int, _c_int, _c_p, _c_int, _c_p, _c_p, _c_p]),
 }
 
 _lib = None

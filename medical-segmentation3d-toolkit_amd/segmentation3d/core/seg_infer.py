@@ -802,8 +802,8 @@ def segmentation_voi(model, iso_image, start_voxel, end_voxel, use_gpu=True):
     iso_image = images[0]
     with torch.cuda.device(model['device']):
         vol = image_tools.images_to_device(images, model['device'])
+        norm = image_tools.resolve_normalizers(_model_normalizers(model, M), vol)
     box = [int(end_voxel[d] - start_voxel[d]) for d in range(3)]
-    norm = _model_normalizers(model, M)
     probs, _, _ = sliding_window_inference(model['net'], vol, [list(start_voxel)], box, model['out_channels'], norm,
                                            batch_size=1, use_graph=False)
     z0, y0, x0 = start_voxel[2], start_voxel[1], start_voxel[0]
@@ -871,6 +871,9 @@ def _member_probabilities(model, cfg, images, bbox_start_voxel, bbox_end_voxel, 
     # and evaluated onto the model grid
     if src is None:
         src = image_tools.images_to_device(images, dev)
+    # a VolumeNormalizer takes its numbers from the image as uploaded -- the samples on the image grid, before any
+    # resampling or prefilter -- once per member (and so once per cascade stage); without one this is the list itself
+    norm = image_tools.resolve_normalizers(_model_normalizers(model, len(images)), src)
     vol = image_tools.resample_device_mc(src, img_frame, (Xp, Yp, Zp), iso_frame, interp, 0.0)
     del src
     if cfg.partition_type == 'DISABLE':
@@ -889,8 +892,7 @@ def _member_probabilities(model, cfg, images, bbox_start_voxel, bbox_end_voxel, 
         box = tuple(ends[0][d] - starts[0][d] for d in range(3))
     else:
         raise ValueError('Unsupported partition type!')
-    norm = _model_normalizers(model, len(images))
-    order = model.get('region_class_order')     # region-based model: one sigmoid plane per region, composed label map
+    order = model.get('region_class_order')    # region-based model: one sigmoid plane per region, composed label map
     probs, net_mask, _ = sliding_window_inference(model['net'], vol, starts, box, num_classes, norm,
                                                   batch_size=min(batch_size, max(1, len(starts))), blend=blend,
                                                   sigma_scale=sigma_scale, mirror_axes=mirror_axes, regions_order=order)

@@ -126,7 +126,7 @@ class _Case(object):
     bspline: `volume` is prefiltered in place once, here, and holds the cubic B-spline COEFFICIENTS of the image from then
     on (same footprint; image_tools.bspline_prefilter_device), which is what a 'BSPLINE' crop evaluates."""
 
-    def __init__(self, image, seg, device, bspline=False):
+    def __init__(self, image, seg, device, bspline=False, volume_normalizers=None):
         images = image if isinstance(image, (list, tuple)) else [image]
         image = images[0]
         self.num_modality = len(images)
@@ -135,6 +135,12 @@ class _Case(object):
         self.size = image.GetSize()
         self.seg_size = seg.GetSize()
         self.volume = image_tools.images_to_device(images, device)          # [Z, Y, X, M]
+        # a data set with a VolumeNormalizer: this case's own numbers, from the SAMPLES (before the prefilter below)
+        self.normalizers = self.norm_params = None
+        if volume_normalizers is not None:
+            with torch.cuda.device(self.volume.device):
+                self.normalizers = image_tools.resolve_normalizers(volume_normalizers, self.volume)
+            self.norm_params = image_tools.normalizer_params(self.normalizers, self.num_modality)
         if bspline:
             image_tools.bspline_prefilter_device(self.volume, out=self.volume)
         self.image = self.volume[..., 0] if self.num_modality == 1 else self.volume
@@ -380,7 +386,11 @@ class SegmentationDataset(Dataset):
         if len(norms) != self._num_modality:
             raise ValueError('case {}: {} modalities but {} crop normalizers (one per modality, None for none)'.format(
                 self.case_name(0), self._num_modality, len(self.crop_normalizers)))
-        self._norm_params = image_tools.normalizer_params(norms, self._num_modality)
+        # a VolumeNormalizer (type 2) has no numbers until it meets a volume: every case resolves the list against its own
+        # volume at load and keeps its own struct (_Case.norm_params); without one the struct is the data set's, as ever
+        self._volume_normalizers = list(norms) if image_tools.has_volume_normalizer(norms) else None
+        self._norm_params = None if self._volume_normalizers is not None else \
+            image_tools.normalizer_params(norms, self._num_modality)
         self.device = device if device is not None else torch.device('cuda', torch.cuda.current_device())
         self._cases = {}
 
@@ -401,7 +411,7 @@ class SegmentationDataset(Dataset):
         if c is None:
             image = read_case_modalities(self.im_list[index], self.case_name(index))
             c = _Case(image, read_image(self.seg_list[index], dtype=None), self.device,
-                      bspline=self.interpolation == 'BSPLINE')
+                      bspline=self.interpolation == 'BSPLINE', volume_normalizers=self._volume_normalizers)
             self._cases[index] = c
         return c
 
@@ -586,7 +596,8 @@ class SegmentationDataset(Dataset):
             first = out
         im = image_tools.crop_image_device_mc(case.volume, case.frame, center, self.crop_size, crop_spacing,
                                               self.interpolation, out=first, mirror=mirror, prefiltered=True, **spatial)
-        im = image_tools.normalize_crop_device_mc(im, self._norm_params, out=im)
+        norm_params = self._norm_params if self._volume_normalizers is None else case.norm_params
+        im = image_tools.normalize_crop_device_mc(im, norm_params, out=im)
         for f in filters:
             im, other = f(im, other), im
         if aug is not None and aug['intensity'] is not None:
@@ -656,3 +667,68 @@ def collect_fixed_crops(dataset, crops_per_case, seed):
     if not crops:
         raise ValueError('the data set has no cases')
     return torch.stack(crops), torch.stack(masks)
+
+
+def intensity_fingerprint(imlist_file, percentiles=(0.5, 99.5), device=None, resident_bytes=8 << 30):
+    """per-modality intensity statistics of a training list over the union of all cases' voxels under mask > 0 (nnU-Net's
+    foreground intensity properties): the numbers of a ClipZScoreNormalizer for CT-like data.
+    percentiles = (lo, hi) in percent: nearest-rank order statistics (utils.normalizer.nearest_rank) of the pooled
+    foreground voxels; mean / population std are those of the values clamped to them.
+    The statistics are accumulated on the device over the cases with the split entries of csrc/volume_stats.hip (four
+    passes over the data set); cases stay resident up to `resident_bytes` in total and are re-read per pass beyond that.
+    -> list of M dicts(n, min, max, mean, std, lower, upper, normalizer = ClipZScoreNormalizer).  The mask must have the
+    image's size (ValueError naming the case otherwise)."""
+    from segmentation3d.utils.normalizer import ClipZScoreNormalizer
+    if imlist_file.endswith('txt'):
+        im_list, seg_list = read_train_txt(imlist_file)
+    elif imlist_file.endswith('csv'):
+        im_list, seg_list = read_train_csv(imlist_file)
+    else:
+        raise ValueError('imseg_list must be a txt file')
+    if not im_list:
+        raise ValueError('the data set has no cases')
+    lo, hi = (float(v) for v in percentiles)
+    if not 0.0 <= lo < hi <= 100.0:
+        raise ValueError('percentiles = {!r}: need 0 <= lo < hi <= 100'.format(tuple(percentiles)))
+    device = device if device is not None else torch.device('cuda', torch.cuda.current_device())
+    M = case_modalities(im_list[0])
+    resident, used = {}, [0]
+
+    def load(k):
+        if k in resident:
+            return resident[k]
+        entry = im_list[k]
+        first = entry if isinstance(entry, str) else entry[0]
+        name = os.path.basename(os.path.dirname(first)) + '_' + os.path.basename(first)
+        images = read_case_modalities(entry, name)
+        if len(images) != M:
+            raise ValueError('case {}: {} modalities, the first case has {}'.format(name, len(images), M))
+        seg = read_image(seg_list[k], dtype=None)
+        if tuple(seg.GetSize()) != tuple(images[0].GetSize()):
+            raise ValueError('case {}: the mask has size {}, the image {}'.format(name, tuple(seg.GetSize()),
+                                                                                 tuple(images[0].GetSize())))
+        volume = image_tools.images_to_device(images, device).contiguous()
+        sel = torch.from_numpy(np.ascontiguousarray(np.asarray(seg.array) > 0).astype(np.uint8)).to(device)
+        nbytes = volume.numel() * 4 + sel.numel()
+        if used[0] + nbytes <= resident_bytes:
+            resident[k] = (volume, sel)
+            used[0] += nbytes
+        return volume, sel
+
+    with torch.cuda.device(device):
+        acc = image_tools.VolumeStatsAccumulator(M, 'mask', [lo / 100.0, hi / 100.0], True, device)
+        for level in acc.levels():
+            for k in range(len(im_list)):
+                acc.add_hist(*load(k), level)
+            acc.resolve(level)
+        for k in range(len(im_list)):
+            acc.add_moments(*load(k))
+        stats = acc.finish()
+    out = []
+    for st in stats:
+        if st['n'] == 0:
+            raise ValueError('no voxel of the data set lies under mask > 0')
+        out.append({'n': st['n'], 'min': st['min'], 'max': st['max'], 'mean': st['mean'], 'std': st['std'],
+                    'lower': st['q'][0], 'upper': st['q'][1],
+                    'normalizer': ClipZScoreNormalizer(st['mean'], st['std'], st['q'][0], st['q'][1])})
+    return out

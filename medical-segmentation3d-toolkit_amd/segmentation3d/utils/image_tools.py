@@ -357,9 +357,166 @@ def normalizer_params(normalizers, num_modality):
         elif d['type'] == 1:
             sigma = float(d['clip_sigma'])
             n.type, n.mean, n.stddev, n.clip, n.clip_lo, n.clip_hi = 1, 0.0, 1.0, 1, -sigma, sigma
+        elif d['type'] == 3:
+            # the kernel clips the z-score, the rule clips the raw value: f(x) = fp32 (x - mean) / stddev is monotone
+            # including its rounding, so clip(f(x), f(lo), f(hi)) == f(clip(x, lo, hi)) bit for bit when the bounds are
+            # rounded as the kernel rounds them (fp32 subtract, correctly rounded fp32 divide, no contraction)
+            mean, std = np.float32(d['mean']), np.float32(d['stddev'])
+            if not std > 0:
+                raise ValueError('stddev must be positive, got {!r}'.format(d['stddev']))
+            lo, hi = d.get('lower'), d.get('upper')
+            f_lo = float('-inf') if lo is None else float((np.float32(lo) - mean) / std)
+            f_hi = float('inf') if hi is None else float((np.float32(hi) - mean) / std)
+            n.type, n.mean, n.stddev, n.clip, n.clip_lo, n.clip_hi = 0, float(mean), float(std), \
+                int(lo is not None or hi is not None), f_lo, f_hi
+            if n.clip == 0:
+                n.clip_lo, n.clip_hi = -1.0, 1.0
+        elif d['type'] == 2:
+            raise ValueError('a VolumeNormalizer (type 2) takes its numbers from a volume: resolve it first '
+                             '(image_tools.resolve_normalizers)')
         else:
             raise ValueError('Unsupported normalization type.')
     return params
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# whole-volume statistics (csrc/volume_stats.hip) and the case-level normalisers built on them
+# ---------------------------------------------------------------------------------------------------------------------
+_STAT_MODES = {'all': 0, 'nonzero': 1, 'mask': 2}
+
+
+class VolumeStatsAccumulator(object):
+    """the split entries of seg3d_volume_stats_*: statistics of the union of several volumes' selected voxels (a data set).
+    Every volume is passed once per pass, in any order, with the same M:
+        acc = VolumeStatsAccumulator(M, mode, quantiles, clip, device)
+        for level in acc.levels():
+            for volume, sel in volumes: acc.add_hist(volume, sel, level)
+            acc.resolve(level)
+        for volume, sel in volumes: acc.add_moments(volume, sel)
+        stats = acc.finish()
+    Nothing is read back before finish(), which makes the one device-to-host transfer."""
+
+    def __init__(self, num_modality, mode='nonzero', quantiles=(), clip=False, device=None, begin=True):
+        if mode not in _STAT_MODES:
+            raise ValueError("mode must be 'all', 'nonzero' or 'mask', got {!r}".format(mode))
+        self.M, self.mode = int(num_modality), _STAT_MODES[mode]
+        if not 1 <= self.M <= 8:
+            raise ValueError('{} modalities, 1..8 are supported'.format(self.M))
+        self.quantiles = [float(q) for q in quantiles]
+        if len(self.quantiles) > 4 or any(not 0.0 <= q <= 1.0 for q in self.quantiles):
+            raise ValueError('quantiles {!r}: at most four values in [0, 1]'.format(list(quantiles)))
+        self.clip = bool(clip)
+        if self.clip and (len(self.quantiles) < 2 or self.quantiles[0] > self.quantiles[1]):
+            raise ValueError('the clamp needs two quantiles q0 <= q1')
+        self.device = device if device is not None else _device()
+        self._q = (ctypes.c_double * 4)(*(self.quantiles + [0.0] * (4 - len(self.quantiles))))
+        self.state = torch.empty((E.query('seg3d_volume_stats_state_bytes', self.M) // 8,), dtype=torch.int64,
+                                 device=self.device)
+        E.require_device(self.state)
+        if begin:   # (the one-volume entry zeroes the state itself)
+            E.call('seg3d_volume_stats_begin', E.ptr(self.state), self.M, E.stream_ptr())
+
+    def levels(self):
+        return (0, 1, 2) if self.quantiles else (0,)
+
+    def _check(self, volume, sel):
+        E.require_device(volume, sel)
+        if volume.dtype != torch.float32 or volume.dim() != 4 or not volume.is_contiguous() \
+                or int(volume.shape[3]) != self.M:
+            raise ValueError('volume must be a contiguous float32 [Z, Y, X, {}] tensor'.format(self.M))
+        nv = int(volume.shape[0]) * int(volume.shape[1]) * int(volume.shape[2])
+        if not 0 < nv < 2 ** 31:
+            raise ValueError('{} voxels: 1 .. 2^31 - 1 per call'.format(nv))
+        if self.mode == 2:
+            if sel is None or sel.dtype != torch.uint8 or not sel.is_contiguous() \
+                    or tuple(sel.shape) != tuple(volume.shape[:3]):
+                raise ValueError("mode 'mask' needs a contiguous uint8 selection plane of the volume's [Z, Y, X]")
+        return nv
+
+    def add_hist(self, volume, sel, level):
+        nv = self._check(volume, sel)
+        E.call('seg3d_volume_stats_accumulate_hist', E.ptr(volume), E.ptr(sel) if self.mode == 2 else None, nv, self.M,
+               self.mode, int(level), E.ptr(self.state), E.stream_ptr())
+
+    def resolve(self, level):
+        E.call('seg3d_volume_stats_resolve', E.ptr(self.state), self.M, len(self.quantiles), self._q, int(level),
+               E.stream_ptr())
+
+    def add_moments(self, volume, sel):
+        nv = self._check(volume, sel)
+        E.call('seg3d_volume_stats_accumulate_moments', E.ptr(volume), E.ptr(sel) if self.mode == 2 else None, nv, self.M,
+               self.mode, int(self.clip), E.ptr(self.state), E.stream_ptr())
+
+    def finish(self):
+        out = torch.empty((self.M, 9), dtype=torch.float64, device=self.device)
+        E.call('seg3d_volume_stats_finish', E.ptr(self.state), self.M, len(self.quantiles), int(self.clip), E.ptr(out),
+               E.stream_ptr())
+        return _stats_rows(out, len(self.quantiles))
+
+
+def _stats_rows(out, Q):
+    rows = out.cpu().numpy()
+    return [{'n': int(r[0]), 'min': float(r[1]), 'max': float(r[2]), 'mean': float(r[3]), 'std': float(r[4]),
+             'q': [float(v) for v in r[5:5 + Q]]} for r in rows]
+
+
+def volume_stats_device(volume, mode='nonzero', sel=None, quantiles=(), clip=False):
+    """exact statistics of a whole float32 channels-last device volume [Z, Y, X, M] (seg3d_volume_stats): per modality a
+    dict(n, min, max, mean, std, q) over the voxels selected by mode 'all' | 'nonzero' (x != 0) | 'mask' (sel != 0, a uint8
+    [Z, Y, X] device tensor).  q: the order statistics sorted(S)[floor(q_i (n - 1) + 0.5)] of up to four `quantiles` in
+    [0, 1] -- the nearest rank, not numpy's linear interpolation.  mean / population std (floored at 1e-6) in float64, with
+    clip=True of the values clamped to [q[0], q[1]].  n == 0: all 0 and std = 1e-6.  One device-to-host transfer."""
+    if volume.dim() != 4:
+        raise ValueError('volume must be a float32 [Z, Y, X, M] tensor')
+    with torch.cuda.device(volume.device):
+        acc = VolumeStatsAccumulator(int(volume.shape[3]), mode, quantiles, clip, volume.device, begin=False)
+        nv = acc._check(volume, sel)
+        out = torch.empty((acc.M, 9), dtype=torch.float64, device=volume.device)
+        E.call('seg3d_volume_stats', E.ptr(volume), E.ptr(sel) if acc.mode == 2 else None, nv, acc.M, acc.mode,
+               len(acc.quantiles), acc._q, int(acc.clip), E.ptr(acc.state), E.ptr(out), E.stream_ptr())
+        return _stats_rows(out, len(acc.quantiles))
+
+
+def _normalizer_dict(n):
+    return n.to_dict() if n is not None and hasattr(n, 'to_dict') else n
+
+
+def has_volume_normalizer(normalizers):
+    """does the list hold a VolumeNormalizer (type 2), i.e. does it need a volume before it can be applied?"""
+    return any(d is not None and d['type'] == 2 for d in (_normalizer_dict(n) for n in normalizers))
+
+
+def resolve_normalizers(normalizers, volume):
+    """normalisers of the modalities of `volume` (float32 channels-last device [Z, Y, X, M], holding SAMPLES -- before any
+    B-spline prefilter) -> a list in which every VolumeNormalizer / type-2 dict is replaced by the type-3 dict of its
+    numbers for this volume; the other entries are returned as they are, and without a type 2 nothing is launched.
+    Modalities that share (foreground, clip_percentiles) share one statistics call; a modality whose non-zero selection is
+    empty is resolved over all voxels."""
+    from segmentation3d.utils.normalizer import resolved_normalizer
+    dicts = [_normalizer_dict(n) for n in normalizers]
+    if not any(d is not None and d['type'] == 2 for d in dicts):
+        return list(normalizers)
+    if volume.dim() != 4 or int(volume.shape[3]) != len(dicts):
+        raise ValueError('{} normalizers for a volume of shape {}: one per modality of [Z, Y, X, M]'.format(
+            len(dicts), tuple(volume.shape)))
+    out, cache = list(normalizers), {}
+
+    def stats(foreground, pct):
+        key = (foreground, None if pct is None else tuple(pct))
+        if key not in cache:
+            q = [] if pct is None else [float(p) / 100.0 for p in pct]
+            cache[key] = volume_stats_device(volume, foreground, quantiles=q, clip=bool(q))
+        return cache[key]
+
+    for m, d in enumerate(dicts):
+        if d is None or d['type'] != 2:
+            continue
+        foreground, pct = d.get('foreground', 'nonzero'), d.get('clip_percentiles')
+        st = stats(foreground, pct)[m]
+        if st['n'] == 0 and foreground != 'all':
+            st = stats('all', pct)[m]
+        out[m] = resolved_normalizer(d, st).to_dict()
+    return out
 
 
 def _frame(image):
