@@ -822,6 +822,21 @@ int seg3d_resample_deform_mc(const float* src, float* dst, int M, long long dst_
                              int Yo, int Zo, const double* affine_host, int linear, float pad, const double* l_host,
                              const float* ctrl, int gx, int gy, int gz, const double* t_host, int mirror_mask,
                              void* stream);
+/* ---- typed sources (compact resident training cases) -------------------------------------
+ * seg3d_resample_affine_mc / seg3d_resample_deform_mc for a source kept in the element type of its file: src_dtype is
+ * 0 int8, 1 uint8, 2 int16 or 4 float32; code 3 (int32, not exact in a float) and any other value set an error text and
+ * return SEG3D_ERR_UNSUPPORTED.  Every element read is converted with (float), which is exact for the four types, and
+ * everything after the load is the float entries' arithmetic: the result equals theirs on the converted volume bit for bit,
+ * and src_dtype = 4 IS the float entry.  dst is fp32.  Rows of 2-byte elements move as one 8- / 4-byte access at
+ * M = 4 / 2 when src is aligned to them (and dst as for the float entries); 1-byte elements take scalar loads.  The B-spline
+ * entries have no typed form: they read coefficients. */
+int seg3d_resample_affine_typed_mc(const void* src, int src_dtype, float* dst, int M, long long dst_stride, int Xi, int Yi,
+                                   int Zi, int Xo, int Yo, int Zo, const double* affine_host, int linear, float pad,
+                                   void* stream);
+int seg3d_resample_deform_typed_mc(const void* src, int src_dtype, float* dst, int M, long long dst_stride, int Xi, int Yi,
+                                   int Zi, int Xo, int Yo, int Zo, const double* affine_host, int linear, float pad,
+                                   const double* l_host, const float* ctrl, int gx, int gy, int gz, const double* t_host,
+                                   int mirror_mask, void* stream);
 /* ---- cubic B-spline interpolation (not in the reference) ----------------------------------
  * The third interpolation of the resampler, exact: the interpolant passes through the samples.  DEFINITION (stated here
  * and in DESIGN.md, nowhere else):

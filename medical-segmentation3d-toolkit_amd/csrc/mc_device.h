@@ -8,7 +8,10 @@
 //   width            mc_regs<MC> (MR), mc_width<MC>(M)
 //   rows             mc_load_row / mc_store_row: the load fills the registers past M with a value of the caller's, the
 //                    store writes m < M only
-//   host             mc_vec_rows (may the rows be moved as vectors?) and MC_DISPATCH ((M, vec) -> <MC, VEC>)
+//   typed rows       mc_load_row / mc_load_elem of a short / unsigned char / signed char source (the resampler's compact
+//                    volumes): the same registers, every element through (float)
+//   host             mc_vec_rows (may the rows be moved as vectors?; mc_vec_rows_typed for a typed source) and MC_DISPATCH
+//                    ((M, vec) -> <MC, VEC>)
 //   statistics       mc_chunk_walk (MC_STAT_CHUNK voxels per workgroup, 256 threads) and the fixed-order fp64 block sum
 //                    mc_stat_park -> barrier -> mc_stat_total of patch_stats_partial_mc_kernel and augment_stats_partial_kernel
 // Left local on purpose: the trilinear branch of resample_affine_mc_kernel at MC = 0 reads its eight rows channel by channel
@@ -25,6 +28,14 @@
 static inline bool mc_vec_rows(int M, const void* a, const void* b = nullptr, i64 stride = 0) {
   if (M != 4 && M != 2) return false;
   return (((uintptr_t)a | (uintptr_t)b) & (uintptr_t)(4 * M - 1)) == 0 && stride % M == 0;
+}
+
+// mc_vec_rows for a launch that reads rows of M elements of `src_elem` bytes and writes rows of M floats: the source base
+// must be aligned to its row's bytes (2-byte elements: one 8-byte access at M = 4, one 4-byte access at M = 2), the
+// destination rule is the one above; 1-byte elements take scalar loads.  src_elem = 4 is mc_vec_rows(M, src, dst, stride).
+static inline bool mc_vec_rows_typed(int M, const void* src, size_t src_elem, const void* dst, i64 stride) {
+  if (src_elem < 2) return false;
+  return mc_vec_rows(M, nullptr, dst, stride) && ((uintptr_t)src & (uintptr_t)(src_elem * M - 1)) == 0;
 }
 
 // F<MC, VEC> __VA_ARGS__ for the instantiation of (M, vec); F may carry a leading `return`
@@ -93,6 +104,37 @@ __device__ __forceinline__ void mc_store_row(float* p, const float* v, int M) {
       if (m < M) p[m] = v[m];
   }
 }
+
+// ---- typed source rows (the resampler reads volumes as the files store them): SRC = short, unsigned char or signed
+// char; every element goes through (float), which is exact for these types, into the registers the float overloads fill.
+// VEC is honoured for 2-byte elements only (the launcher never asks for it otherwise, mc_vec_rows_typed).
+template <int MC, bool VEC, typename SRC>
+__device__ __forceinline__ void mc_load_row(const SRC* p, float* v) {
+  static_assert(MC > 0, "the runtime width needs M and a fill value");
+  static_assert(sizeof(SRC) <= 2, "float rows take the overload above");
+  if constexpr (VEC && MC == 4 && sizeof(SRC) == 2) {
+    const short4 t = *reinterpret_cast<const short4*>(p);
+    v[0] = (float)t.x; v[1] = (float)t.y; v[2] = (float)t.z; v[3] = (float)t.w;
+  } else if constexpr (VEC && MC == 2 && sizeof(SRC) == 2) {
+    const short2 t = *reinterpret_cast<const short2*>(p);
+    v[0] = (float)t.x; v[1] = (float)t.y;
+  } else {
+#pragma unroll
+    for (int m = 0; m < MC; ++m) v[m] = (float)p[m];
+  }
+}
+template <int MC, bool VEC, typename SRC>
+__device__ __forceinline__ void mc_load_row(const SRC* p, float* v, int M, float fill) {
+  if constexpr (MC > 0) {
+    mc_load_row<MC, VEC>(p, v);
+  } else {
+#pragma unroll
+    for (int m = 0; m < 8; ++m) v[m] = m < M ? (float)p[m] : fill;
+  }
+}
+// channel m of a row as a float: the runtime width's trilinear branch reads its eight rows channel by channel
+template <typename SRC>
+__device__ __forceinline__ float mc_load_elem(const SRC* p, int m) { return (float)p[m]; }
 
 // ---- chunked statistics: workgroup blockIdx.x of 256 threads owns voxels [blockIdx.x * MC_STAT_CHUNK, + MC_STAT_CHUNK) of
 // nv; thread i takes e = e0 + i, e0 + 256 + i, ...: row_of(e) is the voxel's row, acc(r) adds its registers (0 past M) to the

@@ -145,8 +145,11 @@ static int deform_args(const char* name, int Xo, int Yo, int Zo, const double* l
 // padding whatever M is, so channel m of an M-channel launch equals the M = 1 launch on plane m bit for bit.  A single volume [Zi][Yi][Xi] is the M = 1, dst_stride = 1 case of the same memory:
 // seg3d_resample_affine / seg3d_resample_deform are those entries.
 // <MC, VEC>: the row width of the instantiation, mc_device.h.
-template <int MC, bool VEC, bool DEFORM>
-__global__ __launch_bounds__(256) void resample_affine_mc_kernel(const float* __restrict__ src, float* __restrict__ dst,
+// SRC: the element type of src -- float, or short / unsigned char / signed char for a volume kept as its file stores it
+// (seg3d_resample_*_typed_mc).  Only the row loads know it: they convert each element with (float), which is exact for these
+// types, so a typed launch equals the float launch on the converted volume bit for bit; dst is always fp32.
+template <typename SRC, int MC, bool VEC, bool DEFORM>
+__global__ __launch_bounds__(256) void resample_affine_mc_kernel(const SRC* __restrict__ src, float* __restrict__ dst,
                                                                    int Mrt, i64 dst_stride, int Xi, int Yi, int Zi, int Xo,
                                                                    int Yo, int Zo, Affine12 A, int linear, float pad,
                                                                    DeformArgs<DEFORM> dfm) {
@@ -171,10 +174,10 @@ __global__ __launch_bounds__(256) void resample_affine_mc_kernel(const float* __
         TrilinearTap tap;
         trilinear_tap(cx, cy, cz, Xi, Yi, Zi, tap);
         const double dx = tap.dx, dy = tap.dy, dz = tap.dz;
-        const float *p000 = src + (tap.r00 + tap.x0) * M, *p100 = src + (tap.r00 + tap.x1) * M,
-                    *p010 = src + (tap.r01 + tap.x0) * M, *p110 = src + (tap.r01 + tap.x1) * M,
-                    *p001 = src + (tap.r10 + tap.x0) * M, *p101 = src + (tap.r10 + tap.x1) * M,
-                    *p011 = src + (tap.r11 + tap.x0) * M, *p111 = src + (tap.r11 + tap.x1) * M;
+        const SRC *p000 = src + (tap.r00 + tap.x0) * M, *p100 = src + (tap.r00 + tap.x1) * M,
+                  *p010 = src + (tap.r01 + tap.x0) * M, *p110 = src + (tap.r01 + tap.x1) * M,
+                  *p001 = src + (tap.r10 + tap.x0) * M, *p101 = src + (tap.r10 + tap.x1) * M,
+                  *p011 = src + (tap.r11 + tap.x0) * M, *p111 = src + (tap.r11 + tap.x1) * M;
         if constexpr (MC > 0) {
           float t000[MC], t100[MC], t010[MC], t110[MC], t001[MC], t101[MC], t011[MC], t111[MC];
           mc_load_row<MC, VEC>(p000, t000);
@@ -192,7 +195,9 @@ __global__ __launch_bounds__(256) void resample_affine_mc_kernel(const float* __
 #pragma unroll
           for (int m = 0; m < MR; ++m)
             if (m < M)
-              out[m] = trilinear_lerp(p000[m], p100[m], p010[m], p110[m], p001[m], p101[m], p011[m], p111[m], dx, dy, dz);
+              out[m] = trilinear_lerp(mc_load_elem(p000, m), mc_load_elem(p100, m), mc_load_elem(p010, m),
+                                      mc_load_elem(p110, m), mc_load_elem(p001, m), mc_load_elem(p101, m),
+                                      mc_load_elem(p011, m), mc_load_elem(p111, m), dx, dy, dz);
         }
       } else {
         int xn = (int)floor(cx + 0.5), yn = (int)floor(cy + 0.5), zn = (int)floor(cz + 0.5);
@@ -206,18 +211,18 @@ __global__ __launch_bounds__(256) void resample_affine_mc_kernel(const float* __
   }
 }
 
-// MC_DISPATCH's callee: DEFORM comes from the argument.  Vector rows need the source base, the destination base and the
-// destination stride aligned to the row width.
-template <int MC, bool VEC, bool DEFORM>
-static void resample_mc_launch(const float* src, float* dst, int M, i64 dst_stride, int Xi, int Yi, int Zi, int Xo, int Yo,
+// MC_DISPATCH's callee: SRC and DEFORM come from the arguments.  Vector rows need the source base, the destination base
+// and the destination stride aligned to the row width (mc_vec_rows_typed).
+template <int MC, bool VEC, typename SRC, bool DEFORM>
+static void resample_mc_launch(const SRC* src, float* dst, int M, i64 dst_stride, int Xi, int Yi, int Zi, int Xo, int Yo,
                                int Zo, const Affine12& A, int lin, float pad, const DeformArgs<DEFORM>& D, size_t lds,
                                hipStream_t s) {
-  hipLaunchKernelGGL((resample_affine_mc_kernel<MC, VEC, DEFORM>), dim3(seg3d_ew_grid((i64)Xo * Yo * Zo, 256)), dim3(256), lds,
-                     s, src, dst, M, dst_stride, Xi, Yi, Zi, Xo, Yo, Zo, A, lin, pad, D);
+  hipLaunchKernelGGL((resample_affine_mc_kernel<SRC, MC, VEC, DEFORM>), dim3(seg3d_ew_grid((i64)Xo * Yo * Zo, 256)), dim3(256),
+                     lds, s, src, dst, M, dst_stride, Xi, Yi, Zi, Xo, Yo, Zo, A, lin, pad, D);
 }
 
 // the four entries' common checks and the by-value affine argument
-static int resample_args(const char* name, const float* src, const float* dst, int M, long long dst_stride, int Xi, int Yi,
+static int resample_args(const char* name, const void* src, const float* dst, int M, long long dst_stride, int Xi, int Yi,
                          int Zi, int Xo, int Yo, int Zo, const double* affine_host, Affine12* A) {
   SEG3D_REQUIRE(src && dst && affine_host, "%s: null pointer", name);
   SEG3D_REQUIRE(M >= 1 && M <= 8, "%s: M = %d channels, 1..8 are supported", name, M);
@@ -227,20 +232,40 @@ static int resample_args(const char* name, const float* src, const float* dst, i
   return SEG3D_OK;
 }
 
-static int resample_affine(const char* name, const float* src, float* dst, int M, long long dst_stride, int Xi, int Yi,
-                           int Zi, int Xo, int Yo, int Zo, const double* affine_host, int linear, float pad, void* stream) {
+// launch(T()) for the source element type T behind `src_dtype`, the codes of label_device.h: 0 int8, 1 uint8, 2 int16,
+// 4 float32.  Code 3 (int32) is refused with the unknown codes: an int32 is not exact in a float.
+template <typename F>
+static inline int resample_src_dispatch(int src_dtype, const char* name, F&& launch) {
+  switch (src_dtype) {
+    case 0: launch((signed char)0); return SEG3D_OK;
+    case 1: launch((unsigned char)0); return SEG3D_OK;
+    case 2: launch((short)0); return SEG3D_OK;
+    case 4: launch(0.0f); return SEG3D_OK;
+    default:
+      SEG3D_UNSUPPORTED("%s: source dtype code %d: 0 (int8), 1 (uint8), 2 (int16) and 4 (float32) are supported%s", name,
+                        src_dtype, src_dtype == 3 ? "; an int32 is not exact in a float" : "");
+  }
+}
+
+static int resample_affine(const char* name, const void* src, int src_dtype, float* dst, int M, long long dst_stride, int Xi,
+                           int Yi, int Zi, int Xo, int Yo, int Zo, const double* affine_host, int linear, float pad,
+                           void* stream) {
   Affine12 A;
-  const int rc = resample_args(name, src, dst, M, dst_stride, Xi, Yi, Zi, Xo, Yo, Zo, affine_host, &A);
+  int rc = resample_args(name, src, dst, M, dst_stride, Xi, Yi, Zi, Xo, Yo, Zo, affine_host, &A);
   if (rc != SEG3D_OK) return rc;
-  MC_DISPATCH(resample_mc_launch, M, mc_vec_rows(M, src, dst, dst_stride),
-              (src, dst, M, (i64)dst_stride, Xi, Yi, Zi, Xo, Yo, Zo, A, linear ? 1 : 0, pad, DeformArgs<false>(), 0,
-               (hipStream_t)stream));
+  rc = resample_src_dispatch(src_dtype, name, [&](auto tag) {
+    typedef decltype(tag) SRC;
+    MC_DISPATCH(resample_mc_launch, M, mc_vec_rows_typed(M, src, sizeof(SRC), dst, dst_stride),
+                ((const SRC*)src, dst, M, (i64)dst_stride, Xi, Yi, Zi, Xo, Yo, Zo, A, linear ? 1 : 0, pad, DeformArgs<false>(),
+                 0, (hipStream_t)stream));
+  });
+  if (rc != SEG3D_OK) return rc;
   SEG3D_LAUNCH_CHECK(name);
   return SEG3D_OK;
 }
 
-static int resample_deform(const char* name, const float* src, float* dst, int M, long long dst_stride, int Xi, int Yi,
-                           int Zi, int Xo, int Yo, int Zo, const double* affine_host, int linear, float pad,
+static int resample_deform(const char* name, const void* src, int src_dtype, float* dst, int M, long long dst_stride, int Xi,
+                           int Yi, int Zi, int Xo, int Yo, int Zo, const double* affine_host, int linear, float pad,
                            const double* l_host, const float* ctrl, int gx, int gy, int gz, const double* t_host,
                            int mirror_mask, void* stream) {
   Affine12 A;
@@ -249,9 +274,13 @@ static int resample_deform(const char* name, const float* src, float* dst, int M
   DeformArgs<true> D;
   rc = deform_args(name, Xo, Yo, Zo, l_host, ctrl, gx, gy, gz, t_host, mirror_mask, &D);
   if (rc != SEG3D_OK) return rc;
-  MC_DISPATCH(resample_mc_launch, M, mc_vec_rows(M, src, dst, dst_stride),
-              (src, dst, M, (i64)dst_stride, Xi, Yi, Zi, Xo, Yo, Zo, A, linear ? 1 : 0, pad, D,
-               deform_lds_bytes(Xo, Yo, Zo, D.g), (hipStream_t)stream));
+  rc = resample_src_dispatch(src_dtype, name, [&](auto tag) {
+    typedef decltype(tag) SRC;
+    MC_DISPATCH(resample_mc_launch, M, mc_vec_rows_typed(M, src, sizeof(SRC), dst, dst_stride),
+                ((const SRC*)src, dst, M, (i64)dst_stride, Xi, Yi, Zi, Xo, Yo, Zo, A, linear ? 1 : 0, pad, D,
+                 deform_lds_bytes(Xo, Yo, Zo, D.g), (hipStream_t)stream));
+  });
+  if (rc != SEG3D_OK) return rc;
   SEG3D_LAUNCH_CHECK(name);
   return SEG3D_OK;
 }
@@ -261,7 +290,7 @@ static int resample_deform(const char* name, const float* src, float* dst, int M
 extern "C" int seg3d_resample_affine_mc(const float* src, float* dst, int M, long long dst_stride, int Xi, int Yi, int Zi,
                                         int Xo, int Yo, int Zo, const double* affine_host, int linear, float pad,
                                         void* stream) {
-  return resample_affine("seg3d_resample_affine_mc", src, dst, M, dst_stride, Xi, Yi, Zi, Xo, Yo, Zo, affine_host, linear,
+  return resample_affine("seg3d_resample_affine_mc", src, 4, dst, M, dst_stride, Xi, Yi, Zi, Xo, Yo, Zo, affine_host, linear,
                          pad, stream);
 }
 
@@ -271,21 +300,38 @@ extern "C" int seg3d_resample_deform_mc(const float* src, float* dst, int M, lon
                                         int Xo, int Yo, int Zo, const double* affine_host, int linear, float pad,
                                         const double* l_host, const float* ctrl, int gx, int gy, int gz,
                                         const double* t_host, int mirror_mask, void* stream) {
-  return resample_deform("seg3d_resample_deform_mc", src, dst, M, dst_stride, Xi, Yi, Zi, Xo, Yo, Zo, affine_host, linear, pad,
-                         l_host, ctrl, gx, gy, gz, t_host, mirror_mask, stream);
+  return resample_deform("seg3d_resample_deform_mc", src, 4, dst, M, dst_stride, Xi, Yi, Zi, Xo, Yo, Zo, affine_host, linear,
+                         pad, l_host, ctrl, gx, gy, gz, t_host, mirror_mask, stream);
 }
 
-// the M = 1 case of the two entries above: src [Zi][Yi][Xi] -> dst [Zo][Yo][Xo]
+// the two entries above for a source of another element type: src_dtype 0 int8, 1 uint8, 2 int16, 4 float32 (the codes of
+// label_device.h; 4 is the entry above); the row loads convert with (float), everything else is the same launch
+extern "C" int seg3d_resample_affine_typed_mc(const void* src, int src_dtype, float* dst, int M, long long dst_stride, int Xi,
+                                              int Yi, int Zi, int Xo, int Yo, int Zo, const double* affine_host, int linear,
+                                              float pad, void* stream) {
+  return resample_affine("seg3d_resample_affine_typed_mc", src, src_dtype, dst, M, dst_stride, Xi, Yi, Zi, Xo, Yo, Zo,
+                         affine_host, linear, pad, stream);
+}
+
+extern "C" int seg3d_resample_deform_typed_mc(const void* src, int src_dtype, float* dst, int M, long long dst_stride, int Xi,
+                                              int Yi, int Zi, int Xo, int Yo, int Zo, const double* affine_host, int linear,
+                                              float pad, const double* l_host, const float* ctrl, int gx, int gy, int gz,
+                                              const double* t_host, int mirror_mask, void* stream) {
+  return resample_deform("seg3d_resample_deform_typed_mc", src, src_dtype, dst, M, dst_stride, Xi, Yi, Zi, Xo, Yo, Zo,
+                         affine_host, linear, pad, l_host, ctrl, gx, gy, gz, t_host, mirror_mask, stream);
+}
+
+// the M = 1 case of the float entries above: src [Zi][Yi][Xi] -> dst [Zo][Yo][Xo]
 extern "C" int seg3d_resample_affine(const float* src, float* dst, int Xi, int Yi, int Zi, int Xo, int Yo, int Zo,
                                      const double* affine_host, int linear, float pad, void* stream) {
-  return resample_affine("seg3d_resample_affine", src, dst, 1, 1, Xi, Yi, Zi, Xo, Yo, Zo, affine_host, linear, pad, stream);
+  return resample_affine("seg3d_resample_affine", src, 4, dst, 1, 1, Xi, Yi, Zi, Xo, Yo, Zo, affine_host, linear, pad, stream);
 }
 
 extern "C" int seg3d_resample_deform(const float* src, float* dst, int Xi, int Yi, int Zi, int Xo, int Yo, int Zo,
                                      const double* affine_host, int linear, float pad, const double* l_host,
                                      const float* ctrl, int gx, int gy, int gz, const double* t_host, int mirror_mask,
                                      void* stream) {
-  return resample_deform("seg3d_resample_deform", src, dst, 1, 1, Xi, Yi, Zi, Xo, Yo, Zo, affine_host, linear, pad, l_host,
+  return resample_deform("seg3d_resample_deform", src, 4, dst, 1, 1, Xi, Yi, Zi, Xo, Yo, Zo, affine_host, linear, pad, l_host,
                          ctrl, gx, gy, gz, t_host, mirror_mask, stream);
 }
 

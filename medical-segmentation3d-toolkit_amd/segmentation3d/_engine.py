@@ -82,6 +82,10 @@ _SIGNATURES = {
                               + [_c_p, _c_int, _c_p]),
     'seg3d_resample_deform_mc': (_c_int, [_c_p, _c_p, _c_int, _c_ll] + [_c_int] * 6 + [_c_p, _c_int, _c_f, _c_p, _c_p]
                                  + [_c_int] * 3 + [_c_p, _c_int, _c_p]),
+    'seg3d_resample_affine_typed_mc': (_c_int, [_c_p, _c_int, _c_p, _c_int, _c_ll] + [_c_int] * 6
+                                       + [_c_p, _c_int, _c_f, _c_p]),
+    'seg3d_resample_deform_typed_mc': (_c_int, [_c_p, _c_int, _c_p, _c_int, _c_ll] + [_c_int] * 6
+                                       + [_c_p, _c_int, _c_f, _c_p, _c_p] + [_c_int] * 3 + [_c_p, _c_int, _c_p]),
     'seg3d_bspline_prefilter_mc': (_c_int, [_c_p, _c_p] + [_c_int] * 4 + [_c_p]),
     'seg3d_resample_bspline': (_c_int, [_c_p, _c_p] + [_c_int] * 6 + [_c_p, _c_f, _c_p]),
     'seg3d_resample_bspline_mc': (_c_int, [_c_p, _c_p, _c_int, _c_ll] + [_c_int] * 6 + [_c_p, _c_f, _c_p]),

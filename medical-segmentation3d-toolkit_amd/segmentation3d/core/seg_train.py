@@ -148,7 +148,8 @@ def build_validator(cfg, val_cfg, step, num_modality):
         imlist_file=val_cfg['imseg_list'], num_classes=cfg.dataset.num_classes, spacing=cfg.dataset.spacing,
         crop_size=cfg.dataset.crop_size, sampling_method=cfg.dataset.sampling_method, random_translation=[0, 0, 0],
         random_scale=[1, 1], interpolation=cfg.dataset.interpolation, crop_normalizers=cfg.dataset.crop_normalizers,
-        device=step.device)
+        device=step.device, resident_storage=getattr(cfg.dataset, 'resident_storage', 'fp32'),
+        resident_budget_gb=getattr(cfg.dataset, 'resident_budget_gb', None))   # a budget of its own, of the same size
     if held_out.num_modality() != num_modality:
         raise ValueError('the validation cases of {} have {} modalities, the training set has {}'.format(
             val_cfg['imseg_list'], held_out.num_modality(), num_modality))
@@ -354,7 +355,9 @@ def train(train_config_file, data_iter_factory=None):
             interpolation=cfg.dataset.interpolation, crop_normalizers=cfg.dataset.crop_normalizers, device=None,
             random_mirror_axes=getattr(cfg.dataset, 'random_mirror_axes', None) or (),
             augmentation=getattr(cfg.dataset, 'augmentation', None),
-            resolution_augmentation=getattr(cfg.dataset, 'resolution_augmentation', None))
+            resolution_augmentation=getattr(cfg.dataset, 'resolution_augmentation', None),
+            resident_storage=getattr(cfg.dataset, 'resident_storage', 'fp32'),
+            resident_budget_gb=getattr(cfg.dataset, 'resident_budget_gb', None))
         num_modality = dataset.num_modality()
         configured = getattr(cfg.dataset, 'num_modality', None)
         if configured is not None and int(configured) != num_modality:
@@ -402,6 +405,7 @@ def train(train_config_file, data_iter_factory=None):
                 validator.load_state_dict(stored)   # the moving average and the best value continue
         step.validator = validator
     steps_this_run = 0
+    residency_pending = dataset is not None
     boundary_epoch = None
     for batch in batches:
         crops, masks = batch[0], batch[1]
@@ -434,6 +438,12 @@ def train(train_config_file, data_iter_factory=None):
             if boundary_schedule is not None:
                 line += ', boundary_weight: {:.6g}'.format(step.loss_func.boundary_weight)
             logger.info(line)
+            if (residency_pending and dataset.has_budget()
+                    and epoch_of_batch(batch_idx, cfg.train.batchsize, num_samples, world_size) >= 1):
+                # a run with dataset.resident_budget_gb: what the first pass over the cases left where
+                residency_pending = False
+                logger.info('resident cases: {}, staged cases: {}, resident bytes: {}'.format(
+                    dataset.num_resident(), dataset.num_staged(), dataset.resident_bytes()))
         if validator is not None and epoch_idx != 0 and epoch_idx % val_cfg['epochs'] == 0 and last_val_epoch != epoch_idx:
             result = validator.run(epoch_idx)     # every rank: the counts are all-reduced
             last_val_epoch = epoch_idx

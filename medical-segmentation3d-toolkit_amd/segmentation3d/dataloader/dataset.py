@@ -14,6 +14,9 @@ elastic deformation inside the resampling launches, intensity transforms in one 
 (csrc/augment.hip); its random decisions are drawn after the reference's, and none is drawn while it is off.
 A second optional section, `resolution_augmentation` (row f13): Gaussian blur and low-resolution simulation of the
 normalised crop (csrc/augment_filter.hip), drawn after every other decision of the sample and before the intensity pass.
+How the cases are kept (row f21, two optional keys, defaults = everything above): `resident_storage = 'compact'` keeps integer
+images as int16 and masks as uint8 -- the resampling kernels convert on load, the crops are bit-identical -- and
+`resident_budget_gb` stages the cases that do not fit in pinned host memory and uploads them per sample.
 """
 import os
 
@@ -107,14 +110,42 @@ def case_modalities(entry):
     return len(paths)
 
 
-def read_case_modalities(entry, case):
-    """list of M Image3d of one case (one 4-D NIfTI or M 3-D files), checked to share one grid"""
+def read_case_modalities(entry, case, dtype=np.float32):
+    """list of M Image3d of one case (one 4-D NIfTI or M 3-D files), checked to share one grid; dtype=None keeps the
+    stored element types"""
     paths = [entry] if isinstance(entry, str) else list(entry)
     images = []
     for path in paths:
-        images += read_image_modalities(path)
+        images += read_image_modalities(path, dtype)
     check_modalities(images, case)
     return images
+
+
+# how the cases are kept for the run (not in the reference; DESIGN.md section 7 row f21): the two optional keys
+# dataset.resident_storage / dataset.resident_budget_gb
+RESIDENT_STORAGE = ('fp32', 'compact')
+RESIDENT_GB = 10 ** 9       # bytes of one GB of resident_budget_gb
+
+
+def validate_resident_options(storage, budget):
+    """(dataset.resident_storage, dataset.resident_budget_gb) -> (storage, budget in bytes or None).  ValueError for a
+    storage that is not 'fp32' or 'compact' and for a budget that is neither None nor a finite positive number."""
+    if not isinstance(storage, str) or storage not in RESIDENT_STORAGE:
+        raise ValueError('dataset.resident_storage = {!r}: one of {}'.format(storage, RESIDENT_STORAGE))
+    if budget is None:
+        return storage, None
+    if isinstance(budget, bool) or not isinstance(budget, (int, float, np.integer, np.floating)):
+        raise ValueError('dataset.resident_budget_gb = {!r}: None or a positive number of GB'.format(budget))
+    if not (np.isfinite(budget) and budget > 0):
+        raise ValueError('dataset.resident_budget_gb = {!r} must be finite and positive'.format(budget))
+    return storage, float(budget) * RESIDENT_GB
+
+
+def _pinned_copy(tensor):
+    """a device tensor downloaded into pinned host memory (a blocking copy)"""
+    host = torch.empty(tensor.shape, dtype=tensor.dtype, pin_memory=True)
+    host.copy_(tensor)
+    return host
 
 
 class _Case(object):
@@ -124,9 +155,13 @@ class _Case(object):
     240 x 240 x 155 x 4 is 143 MB resident); the attribute `image` is that tensor, or its [Z, Y, X] view for one
     modality.  The mask and the histogram are the same for any M.
     bspline: `volume` is prefiltered in place once, here, and holds the cubic B-spline COEFFICIENTS of the image from then
-    on (same footprint; image_tools.bspline_prefilter_device), which is what a 'BSPLINE' crop evaluates."""
+    on (same footprint; image_tools.bspline_prefilter_device), which is what a 'BSPLINE' crop evaluates.
+    compact: `volume` / `seg` are int16 / uint8 (or int16) tensors where the values allow it, 3 bytes per voxel and modality
+    instead of 8; the resampling kernels convert on load, so every crop is the fp32 case's bit for bit.
+    staged (a data set with a budget that these bytes no longer fit): `volume` / `seg` / `image` are None, the arrays wait
+    in pinned host memory (`volume_pinned`, `seg_pinned`) and tensors() uploads them per sample."""
 
-    def __init__(self, image, seg, device, bspline=False, volume_normalizers=None):
+    def __init__(self, image, seg, device, bspline=False, volume_normalizers=None, compact=False, admit=None):
         images = image if isinstance(image, (list, tuple)) else [image]
         image = images[0]
         self.num_modality = len(images)
@@ -134,19 +169,48 @@ class _Case(object):
         self.seg_frame = (seg.GetSpacing(), seg.GetOrigin(), seg.GetDirection())
         self.size = image.GetSize()
         self.seg_size = seg.GetSize()
-        self.volume = image_tools.images_to_device(images, device)          # [Z, Y, X, M]
+        self.seg_host = np.array(seg.array, order='C')                       # [z, y, x], label values as stored
+        # compact: image and mask stay in the integer type that holds them exactly
+        # (image_tools.storage_dtype); the B-spline coefficients of an image are no integers, so that image stays fp32
+        image_dtype = image_tools.case_storage_dtype(images) if compact and not bspline else np.dtype(np.float32)
+        seg_dtype = image_tools.storage_dtype(self.seg_host, 'mask') if compact else np.dtype(np.float32)
+        # the fp32 samples on the device: the resident tensor itself, or -- a compact image that needs its statistics -- a
+        # temporary that is freed once the numbers are known
+        volume = None
+        if image_dtype == np.float32 or volume_normalizers is not None:
+            volume = image_tools.images_to_device(images, device)           # [Z, Y, X, M]
         # a data set with a VolumeNormalizer: this case's own numbers, from the SAMPLES (before the prefilter below)
         self.normalizers = self.norm_params = None
         if volume_normalizers is not None:
-            with torch.cuda.device(self.volume.device):
-                self.normalizers = image_tools.resolve_normalizers(volume_normalizers, self.volume)
+            with torch.cuda.device(volume.device):
+                self.normalizers = image_tools.resolve_normalizers(volume_normalizers, volume)
             self.norm_params = image_tools.normalizer_params(self.normalizers, self.num_modality)
-        if bspline:
-            image_tools.bspline_prefilter_device(self.volume, out=self.volume)
-        self.image = self.volume[..., 0] if self.num_modality == 1 else self.volume
-        self.seg_host = np.array(seg.array, order='C')                       # [z, y, x], label values as stored
-        self.seg = torch.from_numpy(self.seg_host.astype(np.float32)).to(device)
+        if image_dtype != np.float32:
+            volume = image_tools.images_to_device(images, device, image_dtype)
+        elif bspline:
+            image_tools.bspline_prefilter_device(volume, out=volume)
+        seg_volume = torch.from_numpy(self.seg_host.astype(seg_dtype)).to(device)
+        self.nbytes = volume.numel() * volume.element_size() + seg_volume.numel() * seg_volume.element_size()
+        # a data set with a budget asks `admit` whether these bytes still fit; if not the case is STAGED: its two arrays
+        # wait in pinned host memory and tensors() uploads them for every sample
+        self.staged = admit is not None and not admit(self.nbytes)
+        self._device = volume.device
+        self.volume_pinned = self.seg_pinned = None
+        if self.staged:
+            self.volume_pinned, self.seg_pinned = _pinned_copy(volume), _pinned_copy(seg_volume)
+            volume = seg_volume = None
+        self.volume, self.seg = volume, seg_volume
+        self.image = None if self.staged else (volume[..., 0] if self.num_modality == 1 else volume)
         self._slice_counts = {}
+
+    def tensors(self):
+        """(volume, seg) on the device.  A resident case hands out its tensors; a staged one uploads its pinned arrays
+        on the current stream (two asynchronous copies), and the caller drops the result once the sample's launches are
+        queued: the caching allocator is stream-ordered, so the memory is reused only after those launches have run."""
+        if not self.staged:
+            return self.volume, self.seg
+        return (self.volume_pinned.to(self._device, non_blocking=True),
+                self.seg_pinned.to(self._device, non_blocking=True))
 
     def label_voxel(self, label, draw):
         """`draw(n)` -> index in [0, n) of the voxel to take among the n voxels equal to `label`, enumerated like
@@ -322,7 +386,10 @@ class SegmentationDataset(Dataset):
 
     def __init__(self, imlist_file, num_classes, spacing, crop_size, sampling_method, random_translation, random_scale,
                  interpolation, crop_normalizers, device=None, random_mirror_axes=(), augmentation=None,
-                 resolution_augmentation=None):
+                 resolution_augmentation=None, resident_storage='fp32', resident_budget_gb=None):
+        # how the cases are kept: 'compact' stores integer data in its integer type, a budget (GB of 1e9 bytes) stages the
+        # cases that no longer fit in pinned host memory.  The defaults are the data set of always: fp32, everything resident
+        self.resident_storage, self._budget_bytes = validate_resident_options(resident_storage, resident_budget_gb)
         if imlist_file.endswith('txt'):
             self.im_list, self.seg_list = read_train_txt(imlist_file)
         elif imlist_file.endswith('csv'):
@@ -407,13 +474,36 @@ class SegmentationDataset(Dataset):
 
     # ---- resident volumes --------------------------------------------------------------------------------------------
     def case(self, index):
+        """the case, loaded at first touch.  With a budget it becomes resident if the bytes already resident plus its own
+        (image + mask tensor in their storage dtype) fit, and is staged otherwise; nothing is ever evicted -- first come,
+        first resident -- so a seeded sampler gives the same split every run.  (The first touch of a staged case still
+        passes through the device once: that is where its layout, statistics and B-spline coefficients are made.)"""
         c = self._cases.get(index)
         if c is None:
-            image = read_case_modalities(self.im_list[index], self.case_name(index))
+            compact = self.resident_storage == 'compact'
+            image = read_case_modalities(self.im_list[index], self.case_name(index), None if compact else np.float32)
             c = _Case(image, read_image(self.seg_list[index], dtype=None), self.device,
-                      bspline=self.interpolation == 'BSPLINE', volume_normalizers=self._volume_normalizers)
+                      bspline=self.interpolation == 'BSPLINE', volume_normalizers=self._volume_normalizers,
+                      compact=compact, admit=None if self._budget_bytes is None else self._admit)
             self._cases[index] = c
         return c
+
+    def has_budget(self):
+        return self._budget_bytes is not None
+
+    def _admit(self, nbytes):
+        return self.resident_bytes() + nbytes <= self._budget_bytes
+
+    def resident_bytes(self):
+        """bytes of the image and mask tensors of the cases resident on the device"""
+        return sum(c.nbytes for c in self._cases.values() if not c.staged)
+
+    def num_resident(self):
+        return sum(1 for c in self._cases.values() if not c.staged)
+
+    def num_staged(self):
+        """cases touched so far that did not fit the budget and are uploaded per sample"""
+        return sum(1 for c in self._cases.values() if c.staged)
 
     # ---- crop centres (host, numpy global RNG, reference call order) ------------------------------------------------------
     def global_sample(self, case):
@@ -594,7 +684,10 @@ class SegmentationDataset(Dataset):
             first, other = (out, scratch) if len(filters) % 2 == 0 else (scratch, out)
         else:
             first = out
-        im = image_tools.crop_image_device_mc(case.volume, case.frame, center, self.crop_size, crop_spacing,
+        # a staged case is uploaded here, on the current stream, and the two tensors die with this call: every launch
+        # that reads them is queued by then, and the allocator hands the memory out again in stream order
+        volume, seg_volume = case.tensors()
+        im = image_tools.crop_image_device_mc(volume, case.frame, center, self.crop_size, crop_spacing,
                                               self.interpolation, out=first, mirror=mirror, prefiltered=True, **spatial)
         norm_params = self._norm_params if self._volume_normalizers is None else case.norm_params
         im = image_tools.normalize_crop_device_mc(im, norm_params, out=im)
@@ -603,7 +696,7 @@ class SegmentationDataset(Dataset):
         if aug is not None and aug['intensity'] is not None:
             image_tools.augment_intensity_device(im, aug['intensity'], aug['seed'])
         im = im.permute(3, 0, 1, 2)
-        seg = image_tools.crop_image_device(case.seg, case.seg_frame, center, self.crop_size, crop_spacing, 'NN',
+        seg = image_tools.crop_image_device(seg_volume, case.seg_frame, center, self.crop_size, crop_spacing, 'NN',
                                             mirror=mirror, **spatial)
         origin = image_tools.crop_origin(center, self.crop_size, crop_spacing)
         direction = list(case.seg_frame[2])

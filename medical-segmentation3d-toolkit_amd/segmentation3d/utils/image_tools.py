@@ -219,10 +219,16 @@ def bspline_prefilter_device(volume, out=None):
     return out
 
 
+# element types a 'LINEAR' / 'NN' resampling source may have -> the dtype code of the typed entries (csrc/label_device.h);
+# every value of the three integer types is exact in a float, which is what makes a compact source lossless
+_SRC_DTYPE_CODES = {torch.int8: 0, torch.uint8: 1, torch.int16: 2, torch.float32: 4}
+
+
 def resample_device(src, src_frame, out_size, dst_frame, interp_method, padding_value=0.0, mirror=None, rotation=None,
                     deform=None, prefiltered=False):
-    """src: float32 device tensor [Z, Y, X]; returns the float32 device tensor [Zo, Yo, Xo] of the destination grid: the
-    M = 1 case of resample_device_mc (a [Z, Y, X] volume is the same memory as [Z, Y, X, 1])."""
+    """src: float32 (or, for 'LINEAR' / 'NN', int16 / uint8 / int8) device tensor [Z, Y, X]; returns the float32 device
+    tensor [Zo, Yo, Xo] of the destination grid: the M = 1 case of resample_device_mc (a [Z, Y, X] volume is the same
+    memory as [Z, Y, X, 1])."""
     E.require_device(src)
     if src.dim() != 3:
         raise ValueError('src must be a [Z, Y, X] tensor')
@@ -242,12 +248,20 @@ def resample_device_mc(src, src_frame, out_size, dst_frame, interp_method, paddi
     interp_method 'BSPLINE': exact cubic B-spline interpolation (seg3d_resample_bspline_mc / _deform_mc).  With
     prefiltered=False src holds samples and is prefiltered into a temporary first (bspline_prefilter_device); with
     prefiltered=True src already holds the coefficients and the call is the one evaluation launch.  The other methods
-    ignore the keyword."""
+    ignore the keyword.
+    'LINEAR' and 'NN' also take a CONTIGUOUS int16, uint8 or int8 src, a volume kept as its file stores it
+    (seg3d_resample_affine_typed_mc / seg3d_resample_deform_typed_mc): the result, always float32, equals the call on
+    src.float() bit for bit.  'BSPLINE' with such a source and any other dtype raise ValueError."""
     if interp_method not in ('LINEAR', 'NN', 'BSPLINE'):
         raise ValueError('Unsupported interpolation type.')
     E.require_device(src)
-    if src.dim() != 4 or src.dtype != torch.float32:
-        raise ValueError('src must be a float32 [Z, Y, X, M] tensor')
+    if src.dim() != 4 or src.dtype not in _SRC_DTYPE_CODES:
+        raise ValueError('src must be a float32 (or int16 / uint8 / int8) [Z, Y, X, M] tensor')
+    typed = src.dtype != torch.float32
+    if typed and interp_method == 'BSPLINE':
+        raise ValueError("'BSPLINE' evaluates fp32 coefficients: a {} source takes 'LINEAR' or 'NN'".format(src.dtype))
+    if typed and not src.is_contiguous():
+        raise ValueError('a {} source must be contiguous'.format(src.dtype))
     src = src.contiguous()
     Zi, Yi, Xi, M = src.shape
     Xo, Yo, Zo = (int(v) for v in out_size)
@@ -267,12 +281,14 @@ def resample_device_mc(src, src_frame, out_size, dst_frame, interp_method, paddi
                M_.ctypes.data_as(ctypes.c_void_p), float(padding_value), L.ctypes.data_as(ctypes.c_void_p), E.ptr(ctrl),
                g[0], g[1], g[2], t.ctypes.data_as(ctypes.c_void_p), mask, E.stream_ptr())
         return out
+    # a float source calls the float entries; any other goes through the typed ones with its dtype code
+    suffix, source = ('_typed_mc', (E.ptr(src), _SRC_DTYPE_CODES[src.dtype])) if typed else ('_mc', (E.ptr(src),))
     if deform is None:
-        E.call('seg3d_resample_affine_mc', E.ptr(src), E.ptr(out), int(M), int(M), Xi, Yi, Zi, Xo, Yo, Zo,
+        E.call('seg3d_resample_affine' + suffix, *source, E.ptr(out), int(M), int(M), Xi, Yi, Zi, Xo, Yo, Zo,
                M_.ctypes.data_as(ctypes.c_void_p), int(interp_method == 'LINEAR'), float(padding_value), E.stream_ptr())
         return out
     L, ctrl, g, t, mask = _deform_call_args(src_frame, dst_frame, (Xo, Yo, Zo), deform, mirror)
-    E.call('seg3d_resample_deform_mc', E.ptr(src), E.ptr(out), int(M), int(M), Xi, Yi, Zi, Xo, Yo, Zo,
+    E.call('seg3d_resample_deform' + suffix, *source, E.ptr(out), int(M), int(M), Xi, Yi, Zi, Xo, Yo, Zo,
            M_.ctypes.data_as(ctypes.c_void_p), int(interp_method == 'LINEAR'), float(padding_value),
            L.ctypes.data_as(ctypes.c_void_p), E.ptr(ctrl), g[0], g[1], g[2], t.ctypes.data_as(ctypes.c_void_p), mask,
            E.stream_ptr())
@@ -329,8 +345,43 @@ def planar_to_channels_last(planes):
     return out
 
 
-def images_to_device(images, device):
-    """list of M co-registered Image3d -> resident float32 [Z, Y, X, M] device tensor"""
+def storage_dtype(array, kind):
+    """numpy dtype a host array is kept resident as under dataset.resident_storage = 'compact' (pure host function).
+    kind 'image': an array of an integer element type whose min and max lie in [-32768, 32767] -> int16; anything else --
+    float files, a NIfTI with scl_slope / scl_inter (already floats), uint16 above 32767 -- -> float32.
+    kind 'mask': integer values all in [0, 255] -> uint8; otherwise all in [-32768, 32767] -> int16; else float32.
+    Every value of the chosen integer type is exact in a float, so the crops of the compact case are those of the
+    float32 case bit for bit."""
+    if kind not in ('image', 'mask'):
+        raise ValueError("kind must be 'image' or 'mask', got {!r}".format(kind))
+    array = np.asarray(array)
+    if not np.issubdtype(array.dtype, np.integer):
+        return np.dtype(np.float32)
+    lo, hi = (int(array.min()), int(array.max())) if array.size else (0, 0)
+    if kind == 'mask' and lo >= 0 and hi <= 255:
+        return np.dtype(np.uint8)
+    if lo >= -32768 and hi <= 32767:
+        return np.dtype(np.int16)
+    return np.dtype(np.float32)
+
+
+def case_storage_dtype(images):
+    """storage_dtype of a case's image volume: int16 only if EVERY modality qualifies, else the whole volume is float32"""
+    compact = all(storage_dtype(im.array, 'image') == np.int16 for im in images)
+    return np.dtype(np.int16 if compact else np.float32)
+
+
+def images_to_host(images, dtype):
+    """list of M co-registered Image3d -> the channels-last [Z, Y, X, M] host array of a non-float storage dtype, built
+    once per case with np.stack(..., axis=-1)"""
+    return np.ascontiguousarray(np.stack([np.asarray(im.array).astype(dtype, copy=False) for im in images], axis=-1))
+
+
+def images_to_device(images, device, dtype=np.float32):
+    """list of M co-registered Image3d -> resident [Z, Y, X, M] device tensor, float32 by default; a non-float `dtype`
+    (a storage_dtype) is laid out channels-last on the host (images_to_host) and uploaded as it is"""
+    if np.dtype(dtype) != np.float32:
+        return torch.from_numpy(images_to_host(images, dtype)).to(device)
     planes = torch.from_numpy(np.stack([np.asarray(im.array, dtype=np.float32) for im in images], 0)).to(device)
     if len(images) == 1:                    # [1, Z, Y, X] is the same memory as [Z, Y, X, 1]
         return planes[0].unsqueeze(3)
@@ -624,8 +675,8 @@ def crop_origin(cropping_center, cropping_size, cropping_spacing):
 
 def crop_image_device(volume, frame, cropping_center, cropping_size, cropping_spacing, interp_method, mirror=None,
                       rotation=None, deform=None, prefiltered=False):
-    """volume: float32 device tensor [Z, Y, X] with frame (spacing, origin, direction) -> crop [z, y, x]: the M = 1 case
-    of crop_image_device_mc"""
+    """volume: float32 (or, for 'LINEAR' / 'NN', int16 / uint8 / int8) device tensor [Z, Y, X] with frame (spacing, origin,
+    direction) -> float32 crop [z, y, x]: the M = 1 case of crop_image_device_mc"""
     return crop_image_device_mc(volume.unsqueeze(3), frame, cropping_center, cropping_size, cropping_spacing, interp_method,
                                 mirror=mirror, rotation=rotation, deform=deform, prefiltered=prefiltered)[..., 0]
 
@@ -652,7 +703,8 @@ def crop_image_device_mc(volume, frame, cropping_center, cropping_size, cropping
     [z, y, x, M] of `cropping_size` voxels at `cropping_spacing`, centred at the world point `cropping_center`, zero
     outside, one launch for all modalities; mirror = (x, y, z) flags: the crop comes out mirrored along those axes (same
     launch, mirrored index map); rotation / deform: training augmentation inside the same launch, and prefiltered (the
-    volume holds 'BSPLINE' coefficients): see resample_device_mc"""
+    volume holds 'BSPLINE' coefficients): see resample_device_mc.  'LINEAR' and 'NN' also take a contiguous int16 / uint8 /
+    int8 volume (a compact resident case); the crop is float32 and equals the crop of volume.float() bit for bit."""
     size = [int(cropping_size[idx]) for idx in range(3)]
     spacing = [float(cropping_spacing[idx]) for idx in range(3)]
     dst_frame = (spacing, crop_origin(cropping_center, size, spacing), frame[2])
