@@ -873,6 +873,32 @@ int seg3d_resample_bspline_deform_mc(const float* src, float* dst, int M, long l
                                      int Xo, int Yo, int Zo, const double* affine_host, float pad, const double* l_host,
                                      const float* ctrl, int gx, int gy, int gz, const double* t_host, int mirror_mask,
                                      void* stream);
+/* ---- per-label trilinear vote for label maps, 'LABEL_LINEAR' (not in the reference) -------
+ * The fourth interpolation of the resampler, for LABEL MAPS only (one channel).  DEFINITION (stated here and in DESIGN.md,
+ * nowhere else).  For an output voxel with the continuous source index c:
+ *   1. c is the resampler's own: the affine map M (x, y, z, 1), with the elastic field, rotation and mirror handling of
+ *      seg3d_resample_deform in the _deform entry.
+ *   2. c outside the buffer (not -0.5 <= c < size - 0.5 on every axis): the result is `pad`.
+ *   3. Otherwise the eight clamped taps and the weights (dx, dy, dz) are those of the linear branch.
+ *   4. For every distinct value l among the eight taps -- compared after the exact (float) conversion of the source element
+ *      -- the membership s_l is the linear branch's interpolation (double, order x, y, z, rounded to float once) of the
+ *      indicator taps (tap == l ? 1.0 : 0.0).
+ *   5. The voxel gets the l with the largest s_l; among equal s_l the smallest l wins.
+ *   6. The result is written as a float, as the nearest-neighbour mask crop is.
+ * Equivalence: for the labels l of the volume in ascending order (with `pad` added in its sorted place when it is not one of
+ * them) let plane_l = seg3d_resample_affine((src == l) as 0 / 1 floats, linear = 1, pad = (l == pad ? 1 : 0)); the result
+ * equals the first-maximum arg-max over the planes bit for bit, voxel for voxel (a label that is not among the taps has
+ * s_l = 0 and cannot win).  Eight equal taps give that value exactly (1 + (1 - 1) d = 1), without a lerp.  Labels are copied,
+ * not interpreted: an ignore label (255) or an out-of-range id votes like any other value.  It is an ARG-MAX, not a
+ * threshold: unlike a sequential `>= 0.5` overwrite per label, a voxel where no label reaches 0.5 still gets its strongest
+ * label.  src [Zi][Yi][Xi] contiguous of src_dtype 0 int8, 1 uint8, 2 int16 or 4 float32 (finite values); code 3 and unknown
+ * codes return SEG3D_ERR_UNSUPPORTED as the typed entries do.  One launch of one thread per output voxel, no workspace, no
+ * atomics, 64-bit indexing: two runs are bit-equal.  A zero control grid gives the affine entry's result bit for bit. */
+int seg3d_resample_label(const void* src, int src_dtype, float* dst, int Xi, int Yi, int Zi, int Xo, int Yo, int Zo,
+                         const double* affine_host, float pad, void* stream);
+int seg3d_resample_label_deform(const void* src, int src_dtype, float* dst, int Xi, int Yi, int Zi, int Xo, int Yo, int Zo,
+                                const double* affine_host, float pad, const double* l_host, const float* ctrl, int gx,
+                                int gy, int gz, const double* t_host, int mirror_mask, void* stream);
 /* Intensity augmentation of a normalised crop [Z][Y][X][M] (M = 1..8, channels-last; M = 1 is the planar crop), IN PLACE.
  * Per modality m, with (mn, mx, mean) of the crop's channel m (min / max exact, mean from an fp64 sum in a fixed order):
  *   brightness  y = x * brightness

@@ -9,6 +9,9 @@
 //   double); inside test  -0.5 <= c < size - 0.5  per axis (ImageFunction::IsInsideBuffer), else the default pixel;
 //   LinearInterpolateImageFunction clamps the 8-neighbourhood at the borders (a coordinate in [-0.5, 0) or
 //   (size - 1, size - 0.5) takes the edge value); NearestNeighbor rounds half up.
+//   Label maps also take 'LABEL_LINEAR' (not in the reference): every label's indicator interpolated linearly, as ITK's label
+//   interpolators and batchgenerators' order-1 segmentation resampling do, and the arg-max over the labels (not the latter's
+//   sequential `>= 0.5` overwrite), fused into one pass without the planes (resample_label_kernel below).
 //   ConnectedComponentImageFilter(FullyConnected) + RelabelComponent: components ordered by size, ties by first
 //   voxel in raster order -- the labels here are the component's smallest linear index, which gives the same order.
 // All kernels are HBM-bound byte movers / integer work.
@@ -444,6 +447,81 @@ extern "C" int seg3d_resample_bspline_deform(const float* src, float* dst, int X
                                              int gx, int gy, int gz, const double* t_host, int mirror_mask, void* stream) {
   return resample_bspline_deform("seg3d_resample_bspline_deform", src, dst, 1, 1, Xi, Yi, Zi, Xo, Yo, Zo, affine_host, pad,
                                  l_host, ctrl, gx, gy, gz, t_host, mirror_mask, stream);
+}
+
+// ---- per-label trilinear vote for label maps, 'LABEL_LINEAR'  ------------------------------
+// The resampler above for one channel of LABELS: index map, deformation, inside test and the eight clamped taps are its own
+// functions; in place of the lerp of the tap values stands label_linear_vote (seg3d_imagegrid.h) -- every distinct tap value's
+// indicator is interpolated and the largest membership wins.  That is the arg-max over per-label 'LINEAR' planes without the
+// planes: one launch of the size of the 'NN' launch, no workspace, no atomics.  A tap is converted with (float) like every
+// typed element load and compared as a float; dst is fp32 as the 'NN' mask crop is.
+template <typename SRC, bool DEFORM>
+__global__ __launch_bounds__(256) void resample_label_kernel(const SRC* __restrict__ src, float* __restrict__ dst, int Xi,
+                                                               int Yi, int Zi, int Xo, int Yo, int Zo, Affine12 A, float pad,
+                                                               DeformArgs<DEFORM> dfm) {
+  extern __shared__ double deform_smem[];
+  DeformLds lds;
+  if constexpr (DEFORM) lds = deform_stage(deform_smem, dfm, Xo, Yo, Zo);
+  const i64 total = (i64)Xo * Yo * Zo;
+  for (i64 idx = (i64)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (i64)gridDim.x * 256) {
+    const int x = (int)(idx % Xo);
+    const i64 t = idx / Xo;
+    const int y = (int)(t % Yo), z = (int)(t / Yo);
+    double cx, cy, cz;
+    affine12_apply(A, x, y, z, cx, cy, cz);
+    if constexpr (DEFORM) deform_apply(lds, dfm, x, y, z, Xo, Yo, Zo, cx, cy, cz);
+    float out = pad;
+    if (SEG3D_INSIDE_BUFFER(cx, cy, cz, Xi, Yi, Zi)) {
+      TrilinearTap tap;
+      trilinear_tap(cx, cy, cz, Xi, Yi, Zi, tap);
+      out = label_linear_vote(mc_load_elem(src + tap.r00 + tap.x0, 0), mc_load_elem(src + tap.r00 + tap.x1, 0),
+                              mc_load_elem(src + tap.r01 + tap.x0, 0), mc_load_elem(src + tap.r01 + tap.x1, 0),
+                              mc_load_elem(src + tap.r10 + tap.x0, 0), mc_load_elem(src + tap.r10 + tap.x1, 0),
+                              mc_load_elem(src + tap.r11 + tap.x0, 0), mc_load_elem(src + tap.r11 + tap.x1, 0), tap.dx,
+                              tap.dy, tap.dz);
+    }
+    dst[idx] = out;
+  }
+}
+
+template <bool DEFORM>
+static int resample_label_launch(const char* name, const void* src, int src_dtype, float* dst, int Xi, int Yi, int Zi,
+                                 int Xo, int Yo, int Zo, const Affine12& A, float pad, const DeformArgs<DEFORM>& D,
+                                 size_t lds, void* stream) {
+  const int rc = resample_src_dispatch(src_dtype, name, [&](auto tag) {
+    typedef decltype(tag) SRC;
+    hipLaunchKernelGGL((resample_label_kernel<SRC, DEFORM>), dim3(seg3d_ew_grid((i64)Xo * Yo * Zo, 256)), dim3(256), lds,
+                       (hipStream_t)stream, (const SRC*)src, dst, Xi, Yi, Zi, Xo, Yo, Zo, A, pad, D);
+  });
+  if (rc != SEG3D_OK) return rc;
+  SEG3D_LAUNCH_CHECK(name);
+  return SEG3D_OK;
+}
+
+// label map src [Zi][Yi][Xi] of element type src_dtype (0 int8, 1 uint8, 2 int16, 4 float32) -> dst [Zo][Yo][Xo] fp32
+extern "C" int seg3d_resample_label(const void* src, int src_dtype, float* dst, int Xi, int Yi, int Zi, int Xo, int Yo,
+                                    int Zo, const double* affine_host, float pad, void* stream) {
+  const char* name = "seg3d_resample_label";
+  Affine12 A;
+  const int rc = resample_args(name, src, dst, 1, 1, Xi, Yi, Zi, Xo, Yo, Zo, affine_host, &A);
+  if (rc != SEG3D_OK) return rc;
+  return resample_label_launch(name, src, src_dtype, dst, Xi, Yi, Zi, Xo, Yo, Zo, A, pad, DeformArgs<false>(), 0, stream);
+}
+
+// seg3d_resample_label with the sampled point displaced by the elastic field, c = M (x, y, z, 1) + L u(x', y', z')
+extern "C" int seg3d_resample_label_deform(const void* src, int src_dtype, float* dst, int Xi, int Yi, int Zi, int Xo, int Yo,
+                                           int Zo, const double* affine_host, float pad, const double* l_host,
+                                           const float* ctrl, int gx, int gy, int gz, const double* t_host, int mirror_mask,
+                                           void* stream) {
+  const char* name = "seg3d_resample_label_deform";
+  Affine12 A;
+  int rc = resample_args(name, src, dst, 1, 1, Xi, Yi, Zi, Xo, Yo, Zo, affine_host, &A);
+  if (rc != SEG3D_OK) return rc;
+  DeformArgs<true> D;
+  rc = deform_args(name, Xo, Yo, Zo, l_host, ctrl, gx, gy, gz, t_host, mirror_mask, &D);
+  if (rc != SEG3D_OK) return rc;
+  return resample_label_launch(name, src, src_dtype, dst, Xi, Yi, Zi, Xo, Yo, Zo, A, pad, D,
+                               deform_lds_bytes(Xo, Yo, Zo, D.g), stream);
 }
 
 // ---- bounding box -----------------------------------------------------------------------------------------------------

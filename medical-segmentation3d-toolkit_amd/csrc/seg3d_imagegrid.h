@@ -1,4 +1,5 @@
-// seg3d_imagegrid.h -- the affine index map, the trilinear tap of one output voxel and the two label rules with the by-value
+// seg3d_imagegrid.h -- the affine index map, the trilinear tap of one output voxel, the per-label vote over its eight taps
+// (resample_label_kernel, postproc.hip) and the two label rules with the by-value
 // region order: one copy for resample_affine_mc_kernel (postproc.hip), finalize_argmax_kernel / finalize_regions_kernel
 // (patch.hip) and ensemble_accumulate_kernel (ensemble.hip), so that the accumulate interpolates as the resampler and
 // labels as the finalize kernels by construction (-ffp-contract=off: one expression, one sequence of roundings).
@@ -76,5 +77,34 @@ __device__ __forceinline__ float trilinear_lerp(double v000, double v100, double
   const double a10 = v001 + (v101 - v001) * dx, a11 = v011 + (v111 - v011) * dx;
   const double b0 = a00 + (a01 - a00) * dy, b1 = a10 + (a11 - a10) * dy;
   return (float)(b0 + (b1 - b0) * dz);
+}
+
+// 'LABEL_LINEAR' (seg3d_resample_label): the eight tap VALUES of a label map, same corner
+// order.  Every distinct value l is a candidate with the membership s_l = trilinear_lerp of its indicator (tap == l ? 1 : 0);
+// the largest s_l wins, equal s_l go to the smallest l.  Candidates are enumerated in tap order -- a tap that repeats an
+// earlier one is skipped -- with static selects only: no private array indexed at run time, so no scratch.  Eight equal taps
+// return their value without a lerp: 1 + (1 - 1) d is exactly 1, the answer the general walk gives.
+__device__ __forceinline__ float label_linear_vote(float t000, float t100, float t010, float t110, float t001, float t101,
+                                                   float t011, float t111, double dx, double dy, double dz) {
+  if (t100 == t000 && t010 == t000 && t110 == t000 && t001 == t000 && t101 == t000 && t011 == t000 && t111 == t000)
+    return t000;
+  float label = t000, best = -1.f;   // every s_l >= 0: the first candidate always takes over
+  auto candidate = [&](float l, bool repeated) {
+    if (repeated) return;
+    const float s = trilinear_lerp(t000 == l ? 1.0 : 0.0, t100 == l ? 1.0 : 0.0, t010 == l ? 1.0 : 0.0,
+                                   t110 == l ? 1.0 : 0.0, t001 == l ? 1.0 : 0.0, t101 == l ? 1.0 : 0.0,
+                                   t011 == l ? 1.0 : 0.0, t111 == l ? 1.0 : 0.0, dx, dy, dz);
+    if (s > best || (s == best && l < label)) best = s, label = l;
+  };
+  candidate(t000, false);
+  candidate(t100, t100 == t000);
+  candidate(t010, t010 == t000 || t010 == t100);
+  candidate(t110, t110 == t000 || t110 == t100 || t110 == t010);
+  candidate(t001, t001 == t000 || t001 == t100 || t001 == t010 || t001 == t110);
+  candidate(t101, t101 == t000 || t101 == t100 || t101 == t010 || t101 == t110 || t101 == t001);
+  candidate(t011, t011 == t000 || t011 == t100 || t011 == t010 || t011 == t110 || t011 == t001 || t011 == t101);
+  candidate(t111, t111 == t000 || t111 == t100 || t111 == t010 || t111 == t110 || t111 == t001 || t111 == t101 ||
+                      t111 == t011);
+  return label;
 }
 #endif

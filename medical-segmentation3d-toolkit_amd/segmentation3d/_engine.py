@@ -93,6 +93,9 @@ _SIGNATURES = {
                                       + [_c_p, _c_int, _c_p]),
     'seg3d_resample_bspline_deform_mc': (_c_int, [_c_p, _c_p, _c_int, _c_ll] + [_c_int] * 6 + [_c_p, _c_f, _c_p, _c_p]
                                          + [_c_int] * 3 + [_c_p, _c_int, _c_p]),
+    'seg3d_resample_label': (_c_int, [_c_p, _c_int, _c_p] + [_c_int] * 6 + [_c_p, _c_f, _c_p]),
+    'seg3d_resample_label_deform': (_c_int, [_c_p, _c_int, _c_p] + [_c_int] * 6 + [_c_p, _c_f, _c_p, _c_p] + [_c_int] * 3
+                                    + [_c_p, _c_int, _c_p]),
     'seg3d_augment_intensity_workspace_doubles': (_c_ll, [_c_int] * 4),
     'seg3d_augment_intensity': (_c_int, [_c_p, _c_p] + [_c_int] * 4 + [IntensityParams, _c_int, _c_p]),
     'seg3d_augment_blur': (_c_int, [_c_p, _c_p] + [_c_int] * 4 + [BlurParams, _c_p]),

@@ -149,7 +149,8 @@ def build_validator(cfg, val_cfg, step, num_modality):
         crop_size=cfg.dataset.crop_size, sampling_method=cfg.dataset.sampling_method, random_translation=[0, 0, 0],
         random_scale=[1, 1], interpolation=cfg.dataset.interpolation, crop_normalizers=cfg.dataset.crop_normalizers,
         device=step.device, resident_storage=getattr(cfg.dataset, 'resident_storage', 'fp32'),
-        resident_budget_gb=getattr(cfg.dataset, 'resident_budget_gb', None))   # a budget of its own, of the same size
+        resident_budget_gb=getattr(cfg.dataset, 'resident_budget_gb', None),   # a budget of its own, of the same size
+        mask_interpolation=getattr(cfg.dataset, 'mask_interpolation', 'NN'))
     if held_out.num_modality() != num_modality:
         raise ValueError('the validation cases of {} have {} modalities, the training set has {}'.format(
             val_cfg['imseg_list'], held_out.num_modality(), num_modality))
@@ -357,7 +358,8 @@ def train(train_config_file, data_iter_factory=None):
             augmentation=getattr(cfg.dataset, 'augmentation', None),
             resolution_augmentation=getattr(cfg.dataset, 'resolution_augmentation', None),
             resident_storage=getattr(cfg.dataset, 'resident_storage', 'fp32'),
-            resident_budget_gb=getattr(cfg.dataset, 'resident_budget_gb', None))
+            resident_budget_gb=getattr(cfg.dataset, 'resident_budget_gb', None),
+            mask_interpolation=getattr(cfg.dataset, 'mask_interpolation', 'NN'))
         num_modality = dataset.num_modality()
         configured = getattr(cfg.dataset, 'num_modality', None)
         if configured is not None and int(configured) != num_modality:

@@ -5,7 +5,8 @@ The reference reads both volumes from disk, resamples a crop with SimpleITK and 
 for every sample; at >150 patches/s per GPU four such workers cannot feed eight GPUs.  Here every case is read ONCE
 (MetaImage, utils/mha_io.py), kept resident in HBM, and a sample costs two launches of the resampling kernel
 (csrc/postproc.hip: image LINEAR / NN / BSPLINE -- the resident volume then holds the spline
-coefficients, prefiltered once at load, csrc/bspline.hip --, mask NN) plus the on-device normaliser (csrc/patch.hip) -- no worker
+coefficients, prefiltered once at load, csrc/bspline.hip --, mask NN or, with `mask_interpolation = 'LABEL_LINEAR'`,
+the per-label trilinear vote of row f22) plus the on-device normaliser (csrc/patch.hip) -- no worker
 processes, no host copies.  The random decisions (crop centre, translation, scale) stay on the host with numpy's
 global RNG in exactly the reference's order, so a seeded run draws the same crops.
 `DeviceCropLoader` batches the samples of a sampler into device tensors for core/seg_train.train().
@@ -139,6 +140,18 @@ def validate_resident_options(storage, budget):
     if not (np.isfinite(budget) and budget > 0):
         raise ValueError('dataset.resident_budget_gb = {!r} must be finite and positive'.format(budget))
     return storage, float(budget) * RESIDENT_GB
+
+
+# how the mask crop is interpolated (not in the reference): the optional key
+# dataset.mask_interpolation.  'NN' is the reference's nearest-neighbour lookup, 'LABEL_LINEAR' the per-label trilinear vote
+MASK_INTERPOLATION = ('NN', 'LABEL_LINEAR')
+
+
+def validate_mask_interpolation(value):
+    """dataset.mask_interpolation -> the value; ValueError for anything that is not 'NN' or 'LABEL_LINEAR'"""
+    if not isinstance(value, str) or value not in MASK_INTERPOLATION:
+        raise ValueError('dataset.mask_interpolation = {!r}: one of {}'.format(value, MASK_INTERPOLATION))
+    return value
 
 
 def _pinned_copy(tensor):
@@ -386,10 +399,12 @@ class SegmentationDataset(Dataset):
 
     def __init__(self, imlist_file, num_classes, spacing, crop_size, sampling_method, random_translation, random_scale,
                  interpolation, crop_normalizers, device=None, random_mirror_axes=(), augmentation=None,
-                 resolution_augmentation=None, resident_storage='fp32', resident_budget_gb=None):
+                 resolution_augmentation=None, resident_storage='fp32', resident_budget_gb=None, mask_interpolation='NN'):
         # how the cases are kept: 'compact' stores integer data in its integer type, a budget (GB of 1e9 bytes) stages the
         # cases that no longer fit in pinned host memory.  The defaults are the data set of always: fp32, everything resident
         self.resident_storage, self._budget_bytes = validate_resident_options(resident_storage, resident_budget_gb)
+        # how the mask crop is cut: 'NN' (the reference, the default) or the per-label trilinear vote 'LABEL_LINEAR'
+        self.mask_interpolation = validate_mask_interpolation(mask_interpolation)
         if imlist_file.endswith('txt'):
             self.im_list, self.seg_list = read_train_txt(imlist_file)
         elif imlist_file.endswith('csv'):
@@ -696,8 +711,8 @@ class SegmentationDataset(Dataset):
         if aug is not None and aug['intensity'] is not None:
             image_tools.augment_intensity_device(im, aug['intensity'], aug['seed'])
         im = im.permute(3, 0, 1, 2)
-        seg = image_tools.crop_image_device(seg_volume, case.seg_frame, center, self.crop_size, crop_spacing, 'NN',
-                                            mirror=mirror, **spatial)
+        seg = image_tools.crop_image_device(seg_volume, case.seg_frame, center, self.crop_size, crop_spacing,
+                                            self.mask_interpolation, mirror=mirror, **spatial)
         origin = image_tools.crop_origin(center, self.crop_size, crop_spacing)
         direction = list(case.seg_frame[2])
         if any(mirror):

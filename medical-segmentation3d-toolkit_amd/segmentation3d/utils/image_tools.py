@@ -226,7 +226,7 @@ _SRC_DTYPE_CODES = {torch.int8: 0, torch.uint8: 1, torch.int16: 2, torch.float32
 
 def resample_device(src, src_frame, out_size, dst_frame, interp_method, padding_value=0.0, mirror=None, rotation=None,
                     deform=None, prefiltered=False):
-    """src: float32 (or, for 'LINEAR' / 'NN', int16 / uint8 / int8) device tensor [Z, Y, X]; returns the float32 device
+    """src: float32 (or, for 'LINEAR' / 'NN' / 'LABEL_LINEAR', int16 / uint8 / int8) device tensor [Z, Y, X]; returns the float32 device
     tensor [Zo, Yo, Xo] of the destination grid: the M = 1 case of resample_device_mc (a [Z, Y, X] volume is the same
     memory as [Z, Y, X, 1])."""
     E.require_device(src)
@@ -251,12 +251,23 @@ def resample_device_mc(src, src_frame, out_size, dst_frame, interp_method, paddi
     ignore the keyword.
     'LINEAR' and 'NN' also take a CONTIGUOUS int16, uint8 or int8 src, a volume kept as its file stores it
     (seg3d_resample_affine_typed_mc / seg3d_resample_deform_typed_mc): the result, always float32, equals the call on
-    src.float() bit for bit.  'BSPLINE' with such a source and any other dtype raise ValueError."""
-    if interp_method not in ('LINEAR', 'NN', 'BSPLINE'):
+    src.float() bit for bit.  'BSPLINE' with such a source and any other dtype raise ValueError.
+    interp_method 'LABEL_LINEAR': for LABEL MAPS, M = 1 only (seg3d_resample_label / seg3d_resample_label_deform; defined
+    in include/seg3d_hip.h and DESIGN.md section 7 row f22): every distinct value among a voxel's eight trilinear taps is
+    interpolated as its 0 / 1 indicator and the value with the largest membership is written, ties to the smallest value --
+    the first-maximum arg-max over per-label 'LINEAR' planes, in one launch and without the planes.  An arg-max, not a
+    `>= 0.5` threshold: a voxel where no label reaches 0.5 still gets its strongest label.  Takes the same sources, mirror,
+    rotation, deform and padding_value; M > 1 and prefiltered=True raise ValueError."""
+    if interp_method not in ('LINEAR', 'NN', 'BSPLINE', 'LABEL_LINEAR'):
         raise ValueError('Unsupported interpolation type.')
     E.require_device(src)
     if src.dim() != 4 or src.dtype not in _SRC_DTYPE_CODES:
         raise ValueError('src must be a float32 (or int16 / uint8 / int8) [Z, Y, X, M] tensor')
+    if interp_method == 'LABEL_LINEAR':
+        if int(src.shape[3]) != 1:
+            raise ValueError("'LABEL_LINEAR' interpolates one label map: M = {} channels".format(int(src.shape[3])))
+        if prefiltered:
+            raise ValueError("'LABEL_LINEAR' reads labels, not B-spline coefficients: prefiltered=True")
     typed = src.dtype != torch.float32
     if typed and interp_method == 'BSPLINE':
         raise ValueError("'BSPLINE' evaluates fp32 coefficients: a {} source takes 'LINEAR' or 'NN'".format(src.dtype))
@@ -278,6 +289,16 @@ def resample_device_mc(src, src_frame, out_size, dst_frame, interp_method, paddi
             return out
         L, ctrl, g, t, mask = _deform_call_args(src_frame, dst_frame, (Xo, Yo, Zo), deform, mirror)
         E.call('seg3d_resample_bspline_deform_mc', E.ptr(coef), E.ptr(out), int(M), int(M), Xi, Yi, Zi, Xo, Yo, Zo,
+               M_.ctypes.data_as(ctypes.c_void_p), float(padding_value), L.ctypes.data_as(ctypes.c_void_p), E.ptr(ctrl),
+               g[0], g[1], g[2], t.ctypes.data_as(ctypes.c_void_p), mask, E.stream_ptr())
+        return out
+    if interp_method == 'LABEL_LINEAR':   # one entry for every source type: the dtype code is always passed
+        if deform is None:
+            E.call('seg3d_resample_label', E.ptr(src), _SRC_DTYPE_CODES[src.dtype], E.ptr(out), Xi, Yi, Zi, Xo, Yo, Zo,
+                   M_.ctypes.data_as(ctypes.c_void_p), float(padding_value), E.stream_ptr())
+            return out
+        L, ctrl, g, t, mask = _deform_call_args(src_frame, dst_frame, (Xo, Yo, Zo), deform, mirror)
+        E.call('seg3d_resample_label_deform', E.ptr(src), _SRC_DTYPE_CODES[src.dtype], E.ptr(out), Xi, Yi, Zi, Xo, Yo, Zo,
                M_.ctypes.data_as(ctypes.c_void_p), float(padding_value), L.ctypes.data_as(ctypes.c_void_p), E.ptr(ctrl),
                g[0], g[1], g[2], t.ctypes.data_as(ctypes.c_void_p), mask, E.stream_ptr())
         return out
@@ -675,8 +696,9 @@ def crop_origin(cropping_center, cropping_size, cropping_spacing):
 
 def crop_image_device(volume, frame, cropping_center, cropping_size, cropping_spacing, interp_method, mirror=None,
                       rotation=None, deform=None, prefiltered=False):
-    """volume: float32 (or, for 'LINEAR' / 'NN', int16 / uint8 / int8) device tensor [Z, Y, X] with frame (spacing, origin,
-    direction) -> float32 crop [z, y, x]: the M = 1 case of crop_image_device_mc"""
+    """volume: float32 (or, for 'LINEAR' / 'NN' / 'LABEL_LINEAR', int16 / uint8 / int8) device tensor [Z, Y, X] with frame
+    (spacing, origin, direction) -> float32 crop [z, y, x]: the M = 1 case of crop_image_device_mc.  'LABEL_LINEAR' is the
+    mode for a label map (resample_device_mc)"""
     return crop_image_device_mc(volume.unsqueeze(3), frame, cropping_center, cropping_size, cropping_spacing, interp_method,
                                 mirror=mirror, rotation=rotation, deform=deform, prefiltered=prefiltered)[..., 0]
 
@@ -704,7 +726,8 @@ def crop_image_device_mc(volume, frame, cropping_center, cropping_size, cropping
     outside, one launch for all modalities; mirror = (x, y, z) flags: the crop comes out mirrored along those axes (same
     launch, mirrored index map); rotation / deform: training augmentation inside the same launch, and prefiltered (the
     volume holds 'BSPLINE' coefficients): see resample_device_mc.  'LINEAR' and 'NN' also take a contiguous int16 / uint8 /
-    int8 volume (a compact resident case); the crop is float32 and equals the crop of volume.float() bit for bit."""
+    int8 volume (a compact resident case); the crop is float32 and equals the crop of volume.float() bit for bit.
+    'LABEL_LINEAR' (M = 1, a label map): the per-label trilinear vote, see resample_device_mc."""
     size = [int(cropping_size[idx]) for idx in range(3)]
     spacing = [float(cropping_spacing[idx]) for idx in range(3)]
     dst_frame = (spacing, crop_origin(cropping_center, size, spacing), frame[2])
