@@ -38,6 +38,10 @@ int seg3d_device_count(void);
  *      NCDHW <-> (x,y,z) contract; torch.cat((up, skip), 1) at network/module/vnet_upblock.py:21) ------------------ */
 int seg3d_ncdhw_to_ndhwc(const float* in, float* out, int N, int C, long long S, void* stream);
 int seg3d_ndhwc_to_ncdhw(const float* in, float* out, int N, int C, long long S, void* stream);
+/* dst[v][dst_off + c] = src[v][src_off + c] for c < C, v < nvox; rows of src_ld / dst_ld floats, the other channels of dst
+ * are left alone.  Needs src_off + C <= src_ld and dst_off + C <= dst_ld.  Any base, pitch and offset is accepted: the copy
+ * moves 16 bytes per access when C, src_ld, src_off, dst_ld and dst_off are all multiples of 4 AND src and dst are both
+ * 16-byte aligned, and one float per access otherwise; the result is the same bits either way. */
 int seg3d_copy_channels(const float* src, float* dst, long long nvox, int C, int src_ld, int src_off, int dst_ld,
                         int dst_off, void* stream);
 

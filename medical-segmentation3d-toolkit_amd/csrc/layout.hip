@@ -50,10 +50,12 @@ extern "C" int seg3d_ndhwc_to_ncdhw(const float* in, float* out, int N, int C, l
 
 // ---- channel-slice copy: dst[v][dst_off + c] = src[v][src_off + c], c < C -----------------------
 // Used for torch.cat((up, skip), 1) (network/module/vnet_upblock.py:21) and its backward split.
+// VEC: one 16-byte access per four channels (the launcher guarantees the alignment, copy_channels_vec)
+template <bool VEC>
 __global__ __launch_bounds__(256) void copy_channels_kernel(const float* __restrict__ src, float* __restrict__ dst,
                                                               i64 nvox, int C, int src_ld, int src_off, int dst_ld,
                                                               int dst_off) {
-  if ((C & 3) == 0 && (src_ld & 3) == 0 && (dst_ld & 3) == 0 && (src_off & 3) == 0 && (dst_off & 3) == 0) {
+  if constexpr (VEC) {
     const int CQ = C >> 2;
     i64 total = nvox * CQ;
     for (i64 idx = (i64)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (i64)gridDim.x * 256) {
@@ -72,13 +74,24 @@ __global__ __launch_bounds__(256) void copy_channels_kernel(const float* __restr
   }
 }
 
+// every float4 of a slice is 16-byte aligned: the width, both row pitches and both offsets are multiples of 4 floats and both
+// bases are 16-byte aligned (the rule of mc_vec_rows, mc_device.h); anything else is copied float by float
+static inline bool copy_channels_vec(const void* src, const void* dst, int C, int src_ld, int src_off, int dst_ld, int dst_off) {
+  return ((C | src_ld | dst_ld | src_off | dst_off) & 3) == 0 && (((uintptr_t)src | (uintptr_t)dst) & 15) == 0;
+}
+
 extern "C" int seg3d_copy_channels(const float* src, float* dst, long long nvox, int C, int src_ld, int src_off,
                                    int dst_ld, int dst_off, void* stream) {
   SEG3D_REQUIRE(src && dst && nvox > 0 && C > 0, "seg3d_copy_channels: bad arguments");
   SEG3D_REQUIRE(src_off + C <= src_ld && dst_off + C <= dst_ld, "seg3d_copy_channels: slice exceeds row pitch");
-  i64 work = (i64)nvox * ((C & 3) ? C : C / 4);
-  hipLaunchKernelGGL(copy_channels_kernel, dim3(seg3d_ew_grid(work, 256)), dim3(256), 0, (hipStream_t)stream, src, dst,
-                     (i64)nvox, C, src_ld, src_off, dst_ld, dst_off);
+  const bool vec = copy_channels_vec(src, dst, C, src_ld, src_off, dst_ld, dst_off);
+  i64 work = (i64)nvox * (vec ? C / 4 : C);
+  if (vec)
+    hipLaunchKernelGGL(copy_channels_kernel<true>, dim3(seg3d_ew_grid(work, 256)), dim3(256), 0, (hipStream_t)stream, src, dst,
+                       (i64)nvox, C, src_ld, src_off, dst_ld, dst_off);
+  else
+    hipLaunchKernelGGL(copy_channels_kernel<false>, dim3(seg3d_ew_grid(work, 256)), dim3(256), 0, (hipStream_t)stream, src, dst,
+                       (i64)nvox, C, src_ld, src_off, dst_ld, dst_off);
   SEG3D_LAUNCH_CHECK("seg3d_copy_channels");
   return SEG3D_OK;
 }
