@@ -279,12 +279,15 @@ __device__ __forceinline__ void compound_bwd_body(const float* __restrict__ prob
 #pragma unroll
     for (int j = 0; j < W; ++j) pt[j] = 0.f;
     if constexpr (CT <= 5 && W == 4) {
+      int ti[W];   // the class of the counting rule, (int)t: a target such as 1.7 selects p_1, as in the forward
+#pragma unroll
+      for (int j = 0; j < W; ++j) ti[j] = compound_class(t[j], C, ignore);
 #pragma unroll
       for (int c = 0; c < CT; ++c) {
         float p[W];
         compound_load<W>(p, pb + (i64)c * S + s);
 #pragma unroll
-        for (int j = 0; j < W; ++j) pt[j] = t[j] == (float)c ? p[j] : pt[j];
+        for (int j = 0; j < W; ++j) pt[j] = ti[j] == c ? p[j] : pt[j];
       }
     } else {
 #pragma unroll

@@ -50,25 +50,43 @@ def _nan(n, device, dtype=torch.float32):
     return torch.full((n,), NAN, dtype=dtype, device=device)
 
 
-class Guarded:
-    """`n` elements inside a NaN-filled buffer with `guard` elements in front and behind"""
+INT_SENTINEL = {torch.int64: 0x5A5A5A5A5A5A5A5A, torch.int32: 0x5A5A5A5A, torch.uint8: 0x5A}   # the fill of an integer buffer
+_BITS = {torch.bfloat16: torch.int16, torch.float32: torch.int32}                              # (an integer buffer is its own)
 
-    def __init__(self, n, guard, device, dtype=torch.float32, fill=None):
-        assert guard > 0 and (guard * (2 if dtype == torch.bfloat16 else 4)) % 16 == 0
-        self.n, self.guard = n, guard
-        self.buf = _nan(n + 2 * guard, device, dtype)
+
+class Guarded:
+    """`n` elements inside a NaN-filled buffer with `guard` elements in front and behind; an integer buffer (int64, int32, uint8)
+    is filled with the fixed pattern INT_SENTINEL instead.  `shift` moves the n elements that many elements past the 16-byte
+    boundary they otherwise start on (the rear guard keeps its `guard` elements)"""
+
+    def __init__(self, n, guard, device, dtype=torch.float32, fill=None, shift=0):
+        assert guard > 0 and (guard * torch.empty((), dtype=dtype).element_size()) % 16 == 0 and shift >= 0
+        self.n, self.guard, self.front = n, guard, guard + shift
+        if dtype in INT_SENTINEL:
+            self.buf = torch.full((n + 2 * guard + shift,), INT_SENTINEL[dtype], dtype=dtype, device=device)
+        else:
+            self.buf = _nan(n + 2 * guard + shift, device, dtype)
         self.before = self.buf.clone()
-        self.t = self.buf[guard:guard + n]
+        self.t = self.buf[self.front:self.front + n]
         if fill is not None:
             self.t.copy_(fill.reshape(-1))
 
     def guards_untouched(self):
-        bits = torch.int16 if self.buf.dtype == torch.bfloat16 else torch.int32
-        a, b, g = self.buf.view(bits), self.before.view(bits), self.guard
+        bits = _BITS.get(self.buf.dtype, self.buf.dtype)
+        a, b, g = self.buf.view(bits), self.before.view(bits), self.front
         return bool(torch.equal(a[:g], b[:g])) and bool(torch.equal(a[g + self.n:], b[g + self.n:]))
 
     def all_nan(self):
+        """every element still holds its fill (NaN, or the integer pattern)"""
+        if self.buf.dtype in INT_SENTINEL:
+            return bool((self.t == INT_SENTINEL[self.buf.dtype]).all())
         return bool(torch.isnan(self.t).all())
+
+    def written(self):
+        """no element still holds its fill: finite for a float buffer, not the pattern for an integer one"""
+        if self.buf.dtype in INT_SENTINEL:
+            return bool((self.t != INT_SENTINEL[self.buf.dtype]).all())
+        return bool(torch.isfinite(self.t).all())
 
 
 def _wide_slice(t, ld, device):

@@ -32,8 +32,8 @@ CASES = [('5x7x9_C{}'.format(C), C, (2, 5, 7, 9), 10.0, False) for C in (1, 2, 3
 CASES += [('4x4x8_C3_k25', 3, (2, 4, 4, 8), 25.0, False),                                        # 16-byte path
           ('1x1x1_C2', 2, (1, 1, 1, 1), 10.0, False),
           ('17^3_C3', 3, (3, 17, 17, 17), 10.0, False),
-          ('33x32x32_C2', 2, (2, 33, 32, 32), 10.0, False),                                      # several workgroups and the
-          ('33x32x32_C5', 5, (2, 33, 32, 32), 10.0, False)]                                      # grid-stride loop
+          ('33x32x32_C2', 2, (2, 33, 32, 32), 10.0, False),                                      # several workgroups (66 of a cap of 512:
+          ('33x32x32_C5', 5, (2, 33, 32, 32), 10.0, False)]                                      # no stride; tests/compound_cases.py has those)
 CASES += [('5x7x9_C{}_ignore'.format(C), C, (2, 5, 7, 9), 10.0, True) for C in (1, 2, 3, 5, 16)]
 CASES += [('17^3_C3_ignore', 3, (3, 17, 17, 17), 10.0, True)]
 CASES += [('5x7x9_C3_k{}'.format(k), 3, (2, 5, 7, 9), k, False) for k in (0.01, 50.0, 100.0)]
