@@ -578,6 +578,35 @@ int seg3d_sigmoid_fwd(const float* in_ndhwc, float* probs_ncdhw, int N, int C, l
 int seg3d_sigmoid_bwd(const float* probs_ncdhw, const float* dprobs_ncdhw, float* din_ndhwc, int N, int C, long long S,
                       void* stream);
 
+/* Region loss (no counterpart in the reference): soft Dice + binary cross-entropy / focal on
+ * the sigmoid probabilities of a region-based model.  The stock-torch chain it stands for is a table gather of R binary
+ * targets, 3 R masked sums and F.binary_cross_entropy.  probs [N][R][S] planar fp32 (1 <= R <= 16), target [N][S] float label
+ * ids, lut_host: 256 HOST words, bit r of lut_host[l] set iff label l is in region r (copied into the kernel arguments, so
+ * a captured graph keeps the table it was captured with).
+ *   counting rule: l = the integer in [0, 256) that t is, else -1; a voxel counts iff l >= 0 && t != ignore_label (any
+ *             ignore_label outside [0, 256) means none).  A voxel that does not count enters no sum and gets gradient 0 on
+ *             every plane.  The target of region r is z_r = (lut[l] >> r) & 1: a label in no region is background everywhere.
+ *   L_dice  = the compound loss's soft-Dice term with planes as classes, from the same device code: I = sum p z, P = sum p,
+ *             T = sum z over counted voxels, d[n,r] = (2 I + 1e-5) / (P + T + 1e-5), sum_r wdice_r (1 - mean_n d[n,r]);
+ *             wdice: R floats normalised over the regions; batch_dice != 0 sums over n before the ratio.
+ *   L_bce   = sum_v sum_r alpha_r l_r / (n_counted sum_r alpha_r), 0 when nothing counts;  q = z ? p : 1 - p,
+ *             l_r = (1 - qc)^gamma (-log qc), qc = max(q, 1e-12): one logarithm per plane and voxel.  With unit alpha and
+ *             gamma = 0 this is F.binary_cross_entropy(p, z) (mean) over the counted voxels.
+ *   L = dice_weight * L_dice + bce_weight * L_bce, both weights >= 0 and not both 0; a term whose weight is 0 does not
+ *   enter L.  One pass over probs and target, no atomics, fp64 finalize in fixed order: bit-reproducible, capturable.
+ * part: seg3d_region_loss_part_floats(N, R, S) floats of workspace ([N][blocks][3 R + 2]: the (I, P, T) triples, the BCE
+ * numerator, the counted voxels); loss: 3 floats (L, L_dice, L_bce); coef: 2 * Rd * R + 1 floats kept for the backward,
+ * Rd = batch_dice ? 1 : N -- the pairs (A, B) of seg3d_compound_loss_fwd, then bce_weight / (n_counted sum_r alpha_r). */
+long long seg3d_region_loss_part_floats(int N, int R, long long S);
+int seg3d_region_loss_fwd(const float* probs, const float* target, const unsigned* lut_host, const float* wdice,
+                          const float* alpha, float* part, float* coef, float* loss, int N, int R, long long S, float gamma,
+                          float dice_weight, float bce_weight, int batch_dice, float ignore_label, void* stream);
+/* dprobs[n][r][s] = gout[0] * [(z ? A + B : B) + coef_bce alpha_r d/dq[(1 - q)^gamma (-log q)] (z ? 1 : -1)] on counted
+ * voxels, 0 elsewhere; the BCE part is 0 where q < 1e-12 (the clamp's gradient).  All R planes in one pass. */
+int seg3d_region_loss_bwd(const float* probs, const float* target, const unsigned* lut_host, const float* coef,
+                          const float* alpha, const float* gout, float* dprobs, int N, int R, long long S, float gamma,
+                          int batch_dice, float ignore_label, void* stream);
+
 /* ---- deep supervision (no counterpart in the reference): auxiliary heads on the lower decoder levels + label pyramid -- */
 /* Fused head: what nn.Conv3d(Cin, C, 1) + nn.Softmax(dim=1) compute on a decoder feature, in one streaming pass.
  *   x: NDHWC fp32 rows [N * S][Cin] at a row stride of ldx floats (0 = Cin; else a multiple of 4 >= Cin: a channel slice of
@@ -770,6 +799,13 @@ int seg3d_region_overlap_counts(const void* gt, const void* seg, int dtype, long
  * no synchronisation, so the call can be captured into a hipGraph. */
 int seg3d_confusion_counts(const float* probs, const float* target, long long* counts, int N, int C, long long S,
                            float ignore_label, void* stream);
+/* The same for a region-based model (row f23; stands for R thresholds and 3 R masked sums in stock torch): probs [N][R][S]
+ * sigmoid probabilities, the prediction of region r is p_r > 0.5 STRICTLY (the rule of seg3d_finalize_regions), its target
+ * bit r of lut[l], and a voxel counts by the rule of seg3d_region_loss_fwd.  counts[3r..3r+2] += (tp, fp, fn) of region r
+ * into 3 * R caller-owned device int64 words.  lut_host: 256 host words.  Integer arithmetic only, at most 3 R 64-bit
+ * integer atomics per workgroup; no allocation and no synchronisation. */
+int seg3d_region_confusion_counts(const float* probs, const float* target, const unsigned* lut_host, long long* counts, int N,
+                                  int R, long long S, float ignore_label, void* stream);
 
 /* ---- surface-distance metrics: HD, HD95, ASSD of one label --------------------------------
  * seg3d_label_surface: surface[i] = 1 on the voxels of (labels == label) that have a 6-neighbour outside the label

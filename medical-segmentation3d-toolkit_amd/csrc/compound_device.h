@@ -1,6 +1,7 @@
 // compound_device.h -- what the compound loss family shares: Dice + CE / focal (loss.hip), Dice + top-k (topk_loss.hip),
-// Dice + boundary (boundary_loss.hip) and Dice + clDice (cldice_loss.hip); validation.hip takes the counting rule.
-// Definitions: loss.hip ("compound loss") and DESIGN.md section 7, rows f7, f15, f16 and f17.
+// Dice + boundary (boundary_loss.hip), Dice + clDice (cldice_loss.hip) and the region loss on sigmoid planes (region_loss.hip:
+// planes as classes, its own per-voxel rule); validation.hip takes the counting rule.
+// Definitions: loss.hip ("compound loss") and DESIGN.md section 7, rows f7, f15, f16, f17 and f23.
 //
 // Every loss of the family streams probs [N][C][S] and target [N][S] once, forward and backward:
 //   counting rule  a voxel counts iff 0 <= t < C && t != ignore; its class is (int)t  (compound_class)

@@ -241,6 +241,9 @@ _SIGNATURES = {
     'seg3d_cldice_loss_bwd': (_c_int, [_c_p] * 5 + [_c_int] * 5 + [ClassList, _c_int, _c_int, _c_f, _c_int, _c_f, _c_p]),
     'seg3d_sigmoid_fwd': (_c_int, [_c_p, _c_p, _c_int, _c_int, _c_ll, _c_p]),
     'seg3d_sigmoid_bwd': (_c_int, [_c_p, _c_p, _c_p, _c_int, _c_int, _c_ll, _c_p]),
+    'seg3d_region_loss_part_floats': (_c_ll, [_c_int, _c_int, _c_ll]),
+    'seg3d_region_loss_fwd': (_c_int, [_c_p] * 8 + [_c_int, _c_int, _c_ll, _c_f, _c_f, _c_f, _c_int, _c_f, _c_p]),
+    'seg3d_region_loss_bwd': (_c_int, [_c_p] * 7 + [_c_int, _c_int, _c_ll, _c_f, _c_int, _c_f, _c_p]),
     'seg3d_ds_head_supported': (_c_int, [_c_int] * 2),
     'seg3d_ds_head_fwd': (_c_int, [_c_p, _c_int, _c_p, _c_p, _c_p, _c_int, _c_ll, _c_int, _c_int, _c_p]),
     'seg3d_ds_head_bwd_workspace_floats': (_c_ll, [_c_int, _c_ll, _c_int, _c_int]),
@@ -263,6 +266,7 @@ _SIGNATURES = {
     'seg3d_finalize_regions': (_c_int, [_c_p, _c_p, _c_p, _c_int, _c_p, _c_ll, _c_ll, _c_p]),
     'seg3d_region_overlap_counts': (_c_int, [_c_p, _c_p, _c_int, _c_ll, _c_p, _c_int, _c_p, _c_p]),
     'seg3d_confusion_counts': (_c_int, [_c_p, _c_p, _c_p, _c_int, _c_int, _c_ll, _c_f, _c_p]),
+    'seg3d_region_confusion_counts': (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_int, _c_int, _c_ll, _c_f, _c_p]),
     'seg3d_patch_gather_normalize_flip': (_c_int, [_c_p] * 5 + [_c_int] * 8 + [_c_f, _c_f, _c_int, _c_f, _c_int, _c_p]),
     'seg3d_patch_gather_normalize_mc_flip': (_c_int, [_c_p] * 5 + [_c_int] * 8 + [Normalizers, _c_int, _c_p]),
     'seg3d_patch_scatter_blend': (_c_int, [_c_p] * 6 + [_c_int] * 8 + [_c_ll, _c_p]),

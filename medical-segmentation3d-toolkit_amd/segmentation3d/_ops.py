@@ -1464,6 +1464,48 @@ class CompoundLossFunction(torch.autograd.Function):
         return (dp,) + (None,) * 8
 
 
+def _region_table(lut):
+    """the 256-word table of region_lut as the host array the entries copy into their kernel arguments"""
+    if len(lut) != 256:
+        raise ValueError('the region table has {} words, not 256'.format(len(lut)))
+    return (ctypes.c_uint * 256)(*lut)
+
+
+class RegionLossFunction(torch.autograd.Function):
+    """RegionDiceBCELoss.forward (loss/region_loss.py): soft Dice + binary cross-entropy / focal on the R sigmoid planes of
+    a region-based model as one fused reduction + one elementwise backward.  `lut` is region_lut's table, `wdice` the region
+    weights normalised over the R regions, `alpha` the weights of the BCE mean; `ignore` is a float outside [0, 256) for "no
+    ignore label".  Every buffer is allocated per call.  Returns (loss, terms): the 0-dim loss and the device tensor
+    (L, L_dice, L_bce), which carries no gradient."""
+
+    @staticmethod
+    def forward(ctx, probs, target, lut, wdice, alpha, gamma, dice_weight, bce_weight, batch_dice, ignore):
+        p, t, N, R, S = _loss_inputs(probs, target, wdice, alpha)
+        cfg = (float(gamma), int(bool(batch_dice)), float(ignore))
+        table = _region_table(lut)
+        part = _empty((E.query('seg3d_region_loss_part_floats', N, R, S),), p)
+        coef = _empty((2 * (1 if cfg[1] else N) * R + 1,), p)
+        terms = _empty((3,), p)
+        E.call('seg3d_region_loss_fwd', E.ptr(p), E.ptr(t), table, E.ptr(wdice), E.ptr(alpha), E.ptr(part), E.ptr(coef),
+               E.ptr(terms), N, R, S, cfg[0], float(dice_weight), float(bce_weight), cfg[1], cfg[2], E.stream_ptr())
+        ctx.save_for_backward(p, t, coef, alpha)
+        ctx.cfg, ctx.table = cfg, table
+        ctx.mark_non_differentiable(terms)
+        return terms[0], terms
+
+    @staticmethod
+    def backward(ctx, gout, _gterms):
+        p, t, coef, alpha = ctx.saved_tensors
+        gamma, batch_dice, ignore = ctx.cfg
+        N, R = p.shape[0], p.shape[1]
+        S = p[0, 0].numel()
+        g = _gout1(gout)
+        dp = torch.empty_like(p)
+        E.call('seg3d_region_loss_bwd', E.ptr(p), E.ptr(t), ctx.table, E.ptr(coef), E.ptr(alpha), E.ptr(g), E.ptr(dp), N, R,
+               S, gamma, batch_dice, ignore, E.stream_ptr())
+        return (dp,) + (None,) * 9
+
+
 class TopKLossFunction(torch.autograd.Function):
     """DiceTopKLoss.forward (loss/topk_loss.py): soft Dice + cross-entropy over the hardest k_percent of the batch's counted
     voxels.  The k-th largest per-voxel loss comes from an on-device radix select (seg3d_topk_loss_fwd): no read-back, so
@@ -1808,12 +1850,9 @@ def label_pyramid(mask, levels):
     return outs
 
 
-def confusion_counts(probs, target, ignore_label=None, out=None):
-    """per-class (tp, fp, fn) of the arg-max of `probs` [N, C, *spatial] (float32 probabilities) against `target` (float
-    class ids, N * spatial elements) in ONE pass: device int64 [C, 3].  A voxel counts iff 0 <= t < C and t != ignore_label
-    (the compound loss's rule); its prediction is the first maximum over the classes.  `out` (int64 [C, 3], contiguous) is
-    ADDED to and returned, so a validation pass accumulates on the device; without it a zeroed tensor is made.  Nothing is
-    synchronised or read back."""
+def _count_inputs(name, what, probs, target, out):
+    """the shared prologue of the confusion-count entries: checks, contiguous float32 probabilities p [N, C, *spatial], float
+    target t, and `out` (int64 [C, 3], contiguous; a zeroed tensor when None); returns (p, t, out, N, C, S)"""
     E.require_device(probs, target, out)
     if probs.dtype != torch.float32:
         raise ValueError('probabilities must be float32, got {}'.format(probs.dtype))
@@ -1821,7 +1860,7 @@ def confusion_counts(probs, target, ignore_label=None, out=None):
         raise ValueError('probabilities must be [N, C, *spatial], got shape {}'.format(tuple(probs.shape)))
     N, C = int(probs.shape[0]), int(probs.shape[1])
     if not 1 <= C <= 16:
-        raise ValueError('confusion_counts: {} classes, 1..16 are supported'.format(C))
+        raise ValueError('{}: {} {}, 1..16 are supported'.format(name, C, what))
     S = probs[0, 0].numel()
     if target.numel() != N * S:
         raise ValueError('target shape {} does not match input {}'.format(tuple(target.shape), tuple(probs.shape)))
@@ -1829,8 +1868,29 @@ def confusion_counts(probs, target, ignore_label=None, out=None):
         out = torch.zeros((C, 3), dtype=torch.int64, device=probs.device)
     elif out.dtype != torch.int64 or tuple(out.shape) != (C, 3) or not out.is_contiguous():
         raise ValueError('out must be a contiguous int64 [{}, 3] tensor, got {} {}'.format(C, out.dtype, tuple(out.shape)))
-    p = probs.contiguous()
-    t = target.contiguous().float()
+    return probs.contiguous(), target.contiguous().float(), out, N, C, S
+
+
+def confusion_counts(probs, target, ignore_label=None, out=None):
+    """per-class (tp, fp, fn) of the arg-max of `probs` [N, C, *spatial] (float32 probabilities) against `target` (float
+    class ids, N * spatial elements) in ONE pass: device int64 [C, 3].  A voxel counts iff 0 <= t < C and t != ignore_label
+    (the compound loss's rule); its prediction is the first maximum over the classes.  `out` (int64 [C, 3], contiguous) is
+    ADDED to and returned, so a validation pass accumulates on the device; without it a zeroed tensor is made.  Nothing is
+    synchronised or read back."""
+    p, t, out, N, C, S = _count_inputs('confusion_counts', 'classes', probs, target, out)
     ignore = -1.0 if ignore_label is None else float(ignore_label)   # any value outside [0, C): no ignore label
     E.call('seg3d_confusion_counts', E.ptr(p), E.ptr(t), E.ptr(out), N, C, S, ignore, E.stream_ptr())
+    return out
+
+
+def region_confusion_counts(probs, target, lut, ignore_label=None, out=None):
+    """per-region (tp, fp, fn) of the thresholded sigmoid probabilities `probs` [N, R, *spatial] against `target` (float
+    label ids) in ONE pass: device int64 [R, 3].  `lut` is region_lut's 256-word table.  A voxel counts iff its label is an
+    integer in [0, 256) and not ignore_label (the region loss's rule); region r is predicted where p_r > 0.5, strictly
+    (inference's rule), and labelled where bit r of lut[label] is set.  `out` is ADDED to and returned, as in
+    confusion_counts.  Nothing is synchronised or read back."""
+    p, t, out, N, R, S = _count_inputs('region_confusion_counts', 'regions', probs, target, out)
+    ignore = -1.0 if ignore_label is None else float(ignore_label)   # any value outside [0, 256): no ignore label
+    E.call('seg3d_region_confusion_counts', E.ptr(p), E.ptr(t), _region_table(lut), E.ptr(out), N, R, S, ignore,
+           E.stream_ptr())
     return out

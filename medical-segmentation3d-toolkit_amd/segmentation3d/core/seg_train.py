@@ -26,21 +26,36 @@ from segmentation3d.loss.cross_entropy_loss import CrossEntropyLoss
 from segmentation3d.loss.deep_supervision_loss import DeepSupervisionLoss, normalise_level_weights
 from segmentation3d.loss.focal_loss import FocalLoss
 from segmentation3d.loss.multi_dice_loss import MultiDiceLoss
+from segmentation3d.loss.region_loss import RegionDiceBCELoss, check_region_class_order, check_regions
 from segmentation3d.loss.topk_loss import DiceTopKLoss
 from segmentation3d.optim.fused_adam import FusedAdam
 from segmentation3d.optim.fused_sgd import FusedSGD
 
 
+REGION_LOSSES = ('RegionDiceBCE', 'RegionDiceFocal')
+
+
 def build_loss(name, num_classes, obj_weight=None, focal_gamma=2, use_gpu=True, dice_weight=1.0, ce_weight=1.0,
                include_background=True, batch_dice=False, ignore_label=None, topk_percent=10.0, boundary_weight=0.01,
-               spacing=(1, 1, 1), cldice_weight=1.0, cldice_iters=3, cldice_classes=None):
+               spacing=(1, 1, 1), cldice_weight=1.0, cldice_iters=3, cldice_classes=None, regions=None):
     """loss selection of core/seg_train.py:91-102, plus the compound losses 'DiceCE' (soft Dice + cross-entropy),
     'DiceFocal' (soft Dice + focal with focal_gamma), 'DiceTopK' (soft Dice + cross-entropy over the hardest
     topk_percent of the batch's voxels) and 'DiceBoundary' (soft Dice + boundary loss on signed distance maps in units of
     `spacing`, weighted by boundary_weight; ce_weight is not read) and 'DiceClDice' (soft Dice + soft-clDice topology
     loss on soft skeletons of cldice_iters iterations for the classes cldice_classes, weighted by cldice_weight; ce_weight
     is not read); the keyword options after use_gpu apply to those five only, topk_percent to 'DiceTopK' only,
-    boundary_weight and spacing to 'DiceBoundary' only, the cldice_ options to 'DiceClDice' only"""
+    boundary_weight and spacing to 'DiceBoundary' only, the cldice_ options to 'DiceClDice' only.
+    'RegionDiceBCE' and 'RegionDiceFocal' (focal_gamma) are the losses of a region-based model (loss/region_loss.py): they
+    need `regions`, obj_weight then has one weight per region, ce_weight is the weight of the BCE term, and num_classes and
+    include_background are not read (a region-based model has no background channel); no other loss takes `regions`"""
+    if name in REGION_LOSSES:
+        if regions is None:
+            raise ValueError('loss {!r} needs regions'.format(name))
+        return RegionDiceBCELoss(regions, weights=obj_weight, dice_weight=dice_weight, bce_weight=ce_weight,
+                                 gamma=focal_gamma if name == 'RegionDiceFocal' else 0.0, batch_dice=batch_dice,
+                                 ignore_label=ignore_label)
+    if regions is not None:
+        raise ValueError('loss {!r} takes no regions (RegionDiceBCE and RegionDiceFocal do)'.format(name))
     if name == 'DiceClDice':
         return DiceClDiceLoss(num_classes, weights=obj_weight, dice_weight=dice_weight, cldice_weight=cldice_weight,
                               iters=cldice_iters, cldice_classes=cldice_classes, include_background=include_background,
@@ -71,7 +86,8 @@ def loss_options_from_config(loss_cfg):
     """the optional keys of the config's `loss` section that the compound losses read, with their defaults (a config
     without them -- every reference config -- loads unchanged); `topk_percent` ('DiceTopK'), `boundary_weight`
     ('DiceBoundary') and `cldice_weight`, `cldice_iters`, `cldice_classes` ('DiceClDice'; defaults 1.0, 3, None = every
-    foreground class) are passed on only when the section has them"""
+    foreground class) are passed on only when the section has them, and so is `regions` (regions_from_config: checked,
+    and only together with `region_class_order`)"""
     opts = {'dice_weight': getattr(loss_cfg, 'dice_weight', 1.0), 'ce_weight': getattr(loss_cfg, 'ce_weight', 1.0),
             'include_background': getattr(loss_cfg, 'include_background', True),
             'batch_dice': getattr(loss_cfg, 'batch_dice', False), 'ignore_label': getattr(loss_cfg, 'ignore_label', None)}
@@ -82,7 +98,23 @@ def loss_options_from_config(loss_cfg):
     for key in ('cldice_weight', 'cldice_iters', 'cldice_classes'):
         if hasattr(loss_cfg, key):
             opts[key] = getattr(loss_cfg, key)
+    regions, _ = regions_from_config(loss_cfg)
+    if regions is not None:
+        opts['regions'] = regions
     return opts
+
+
+def regions_from_config(loss_cfg):
+    """(regions, region_class_order) of the config's `loss` section -- the label-id sets a region-based model is trained on
+    and the label inference writes for each of them -- or (None, None) when the section has neither key.  One key without
+    the other and anything check_regions / check_region_class_order refuse raise ValueError."""
+    regions, order = getattr(loss_cfg, 'regions', None), getattr(loss_cfg, 'region_class_order', None)
+    if regions is None and order is None:
+        return None, None
+    if regions is None or order is None:
+        raise ValueError('loss.regions and loss.region_class_order are required together')
+    regions = check_regions(regions)
+    return regions, check_region_class_order(order, len(regions))
 
 
 def boundary_schedule_from_config(loss_cfg):
@@ -162,7 +194,7 @@ def build_validator(cfg, val_cfg, step, num_modality):
                            **loss_options)   # a second object: the training loss's .last_terms stays the train step's
     batchsize = val_cfg['batchsize'] if val_cfg['batchsize'] is not None else cfg.train.batchsize
     return Validator(step.net, loss_func, crops, masks, batchsize, ignore_label=loss_options['ignore_label'],
-                     ema=val_cfg['ema'])
+                     ema=val_cfg['ema'], regions=loss_options.get('regions'))
 
 
 def validation_log_line(epoch_idx, result):
@@ -197,14 +229,33 @@ class TrainStep(object):
     for loss_name='DiceClDice'); `optimizer` / `optim_options` are
     build_optimizer's (gradient-norm clipping, lr schedule, SGD);
     `deep_supervision` = L in 1..3 builds the network with L auxiliary heads and trains on the weighted per-level losses
-    (loss/deep_supervision_loss.py; `deep_supervision_weights`: L + 1 weights, None = halving per level)"""
+    (loss/deep_supervision_loss.py; `deep_supervision_weights`: L + 1 weights, None = halving per level);
+    `regions` (R label-id sets) with `region_class_order` makes it a region-based model: the network gets R sigmoid outputs
+    in place of num_classes soft-max ones and loss_name must be one of REGION_LOSSES -- either without the other raises,
+    and so does the combination with deep supervision (the fused auxiliary heads end in a soft-max)"""
 
     def __init__(self, net_name, in_channels, num_classes, loss_name='Dice', obj_weight=None, focal_gamma=2, lr=1e-4,
                  betas=(0.9, 0.999), device=None, seed=0, distributed=None, num_buckets=4, use_graph=False,
-                 loss_options=None, optimizer='Adam', optim_options=None, deep_supervision=0, deep_supervision_weights=None):
+                 loss_options=None, optimizer='Adam', optim_options=None, deep_supervision=0, deep_supervision_weights=None,
+                 regions=None, region_class_order=None):
         if loss_name == 'DiceBoundary' and int(deep_supervision) > 0:
             # one loss object would be called at levels whose spacing is 2^k times the nominal one
             raise ValueError("loss_name='DiceBoundary' is not combined with deep supervision")
+        loss_options = dict(loss_options or {})
+        if regions is None:
+            regions = loss_options.get('regions')
+        if (loss_name in REGION_LOSSES) != (regions is not None):
+            raise ValueError('loss_name={!r} {} regions: a region-based model is trained with one of {}'.format(
+                loss_name, 'needs' if regions is None else 'takes no', REGION_LOSSES))
+        if regions is None and region_class_order is not None:
+            raise ValueError('region_class_order given without regions')
+        self.regions, self.region_class_order = None, None
+        if regions is not None:
+            self.regions = check_regions(regions)
+            self.region_class_order = check_region_class_order(region_class_order, len(self.regions))
+            if int(deep_supervision) > 0:
+                raise ValueError('a region-based model is not combined with deep supervision')
+            loss_options['regions'] = self.regions
         self.device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
         if self.device.type == 'cuda' and self.device.index is not None:
             torch.cuda.set_device(self.device)   # the engine launches on the current device's stream (_engine.stream_ptr)
@@ -217,7 +268,9 @@ class TrainStep(object):
         elif deep_supervision_weights is not None:
             raise ValueError('deep_supervision_weights given but deep_supervision is 0')
         torch.manual_seed(seed)
-        if self.deep_supervision:
+        if self.regions is not None:
+            self.net = net_module.SegmentationNet(in_channels, len(self.regions), output_activation='sigmoid')
+        elif self.deep_supervision:
             self.net = net_module.SegmentationNet(in_channels, num_classes, deep_supervision=self.deep_supervision)
         else:
             self.net = net_module.SegmentationNet(in_channels, num_classes)
@@ -226,7 +279,7 @@ class TrainStep(object):
         self.net = self.net.to(self.device)
         self.opt = build_optimizer(optimizer, self.net.parameters(), lr, betas, optim_options)   # core/seg_train.py:83
         _ops.weight_cache(True)   # packed conv weights are refreshed by the optimizer's step() with one launch per step
-        self.loss_func = build_loss(loss_name, num_classes, obj_weight, focal_gamma, use_gpu=True, **(loss_options or {}))
+        self.loss_func = build_loss(loss_name, num_classes, obj_weight, focal_gamma, use_gpu=True, **loss_options)
         if self.deep_supervision:
             self.loss_func = DeepSupervisionLoss(self.loss_func, self.deep_supervision, deep_supervision_weights)
         if distributed is None:
@@ -328,6 +381,7 @@ def train(train_config_file, data_iter_factory=None):
     # raise before anything is built
     val_cfg = validate_validation(getattr(cfg, 'validation', None), cfg.dataset.num_classes)
     boundary_schedule = boundary_schedule_from_config(cfg.loss) if cfg.loss.name == 'DiceBoundary' else None   # likewise
+    regions, region_class_order = regions_from_config(cfg.loss)   # likewise; (None, None): an exclusive-class run
     model_folder = os.path.join(cfg.general.save_dir, cfg.general.model_scale)
     distributed = dist.is_available() and dist.is_initialized()
     rank = dist.get_rank() if distributed else 0
@@ -382,7 +436,7 @@ def train(train_config_file, data_iter_factory=None):
                      cfg.loss.focal_gamma, cfg.train.lr, tuple(cfg.train.betas), seed=cfg.general.seed,
                      use_graph=bool(getattr(cfg.train, 'use_graph', False)),
                      loss_options=loss_options, optimizer=optim_options.pop('optimizer'),
-                     optim_options=optim_options, **deep)
+                     optim_options=optim_options, regions=regions, region_class_order=region_class_order, **deep)
     assert np.all(np.array(cfg.dataset.crop_size) % step.max_stride == 0), 'crop size not divisible by max stride'
     last_save_epoch, batch_idx = 0, 0
     if cfg.general.resume_epoch >= 0:
@@ -453,11 +507,12 @@ def train(train_config_file, data_iter_factory=None):
                 logger.info(validation_log_line(epoch_idx, result))
             if rank == 0 and result['improved'] and val_cfg['save_best']:
                 folder = save_checkpoint(step.net, step.opt, epoch_idx, batch_idx, cfg, step.max_stride, num_modality,
-                                         validation=validator.state_dict(), folder_name=BEST_FOLDER)
+                                         regions, region_class_order, validation=validator.state_dict(),
+                                         folder_name=BEST_FOLDER)
                 with open(os.path.join(folder, 'validation.json'), 'w') as f:
                     json.dump(dict(result, epoch=epoch_idx, batch=batch_idx), f, indent=1)
         if rank == 0 and epoch_idx != 0 and epoch_idx % cfg.train.save_epochs == 0 and last_save_epoch != epoch_idx:
-            save_checkpoint(step.net, step.opt, epoch_idx, batch_idx, cfg, step.max_stride, num_modality,
-                            validation=None if validator is None else validator.state_dict())
+            save_checkpoint(step.net, step.opt, epoch_idx, batch_idx, cfg, step.max_stride, num_modality, regions,
+                            region_class_order, validation=None if validator is None else validator.state_dict())
             last_save_epoch = epoch_idx
     return step

@@ -8,13 +8,15 @@ stay on the device for the whole pass and are read back once.
 
   dice[c]    = 2 tp / (2 tp + fp + fn)          nan for a class that neither labels nor prediction contain
   mean_dice  = nan-mean of dice over the foreground classes 1 .. C-1
+               (region-based model: dice has one value per region and the mean runs over all R of them)
   ema_dice   = the first finite mean_dice, then a * ema + (1 - a) * mean_dice; a nan mean leaves it unchanged
   improved   = ema_dice is strictly above every earlier value (the run keeps that checkpoint in `checkpoints/best`)
   val_loss   = mean over the crops of the batch losses (each batch weighted by its size)
 
 The pass runs eagerly: it is never captured into a hipGraph of its own next to a captured train step (two captured steps of one
-process share the packed-weight tables, tools/bench_loss.py).  Whole-volume sliding-window validation and validation of
-sigmoid / region networks are out of scope.
+process share the packed-weight tables, tools/bench_loss.py).  A region-based model (`regions`; row f23) goes through the
+same pass with seg3d_region_confusion_counts in place of the arg-max counts: region r is predicted where p_r > 0.5.
+Whole-volume sliding-window validation, thresholds other than 0.5 and surface metrics on regions are out of scope.
 """
 import math
 
@@ -22,7 +24,8 @@ import torch
 import torch.distributed as dist
 
 from segmentation3d import _ops
-from segmentation3d.utils.metrics import dice_from_counts, mean_foreground_dice
+from segmentation3d.loss.region_loss import check_regions, region_lut
+from segmentation3d.utils.metrics import dice_from_counts, mean_foreground_dice, mean_region_dice
 
 # keys and defaults of the optional `validation` section of a training config
 VALIDATION_DEFAULTS = {
@@ -125,11 +128,13 @@ class Validator(object):
     :param batchsize: crops per forward
     :param ignore_label: the loss's ignore label: such voxels enter no count
     :param ema: the moving average's coefficient in [0, 1)
+    :param regions: the R label-id sets of a region-based model (None: exclusive classes); the network then has R sigmoid
+                outputs, the counts are per region and the mean Dice runs over all of them
     Under data parallelism rank r takes crops r::world_size and the counts and loss sums are all-reduced, so every rank
     returns identical numbers (and every rank must call run()).
     """
 
-    def __init__(self, net, loss_func, crops, masks, batchsize, ignore_label=None, ema=0.9):
+    def __init__(self, net, loss_func, crops, masks, batchsize, ignore_label=None, ema=0.9, regions=None):
         if crops.dim() != 5 or masks.dim() != 5 or crops.shape[0] != masks.shape[0] or crops.shape[0] < 1:
             raise ValueError('crops / masks must be [V, M, z, y, x] / [V, 1, z, y, x] with V >= 1, got {} and {}'.format(
                 tuple(crops.shape), tuple(masks.shape)))
@@ -137,12 +142,14 @@ class Validator(object):
         self.net, self.loss_func = net, loss_func
         self.ignore_label = None if ignore_label is None else float(ignore_label)
         self.tracker = DiceEma(ema)
+        self.regions = None if regions is None else check_regions(regions)
+        self._lut = None if regions is None else region_lut(self.regions)
         self.distributed = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
         rank, world = (dist.get_rank(), dist.get_world_size()) if self.distributed else (0, 1)
         if crops.shape[0] < world:
             raise ValueError('validation has {} crops for {} ranks: every rank needs one'.format(crops.shape[0], world))
         self.crops, self.masks = crops[rank::world].contiguous(), masks[rank::world].contiguous()
-        self.counts = None        # int64 [C, 3], made at the first batch (C is the network's)
+        self.counts = None        # int64 [C, 3], made at the first batch (C is the network's; with regions it is R)
         self._loss = torch.zeros(2, dtype=torch.float64, device=crops.device)   # (sum of batch loss * batch size, crops)
 
     def accumulate(self):
@@ -162,7 +169,13 @@ class Validator(object):
                 if self.counts is None:
                     self.counts = torch.zeros((int(probs.shape[1]), 3), dtype=torch.int64, device=probs.device)
                 loss = self.loss_func(probs, t)
-                _ops.confusion_counts(probs, t, self.ignore_label, out=self.counts)
+                if self.regions is None:
+                    _ops.confusion_counts(probs, t, self.ignore_label, out=self.counts)
+                else:
+                    if int(probs.shape[1]) != len(self.regions):
+                        raise ValueError('the network has {} outputs for {} regions'.format(int(probs.shape[1]),
+                                                                                           len(self.regions)))
+                    _ops.region_confusion_counts(probs, t, self._lut, self.ignore_label, out=self.counts)
                 n = int(x.shape[0])
                 self._loss[0] += loss.detach().double() * n
                 self._loss[1] += n
@@ -176,7 +189,7 @@ class Validator(object):
         host = torch.cat([self.counts.reshape(-1).double(), self._loss]).cpu().tolist()
         counts = [[int(v) for v in host[3 * c:3 * c + 3]] for c in range(int(self.counts.shape[0]))]
         loss_sum, ncrops = host[-2], host[-1]
-        mean = mean_foreground_dice(counts)
+        mean = mean_foreground_dice(counts) if self.regions is None else mean_region_dice(counts)
         improved = self.tracker.update(mean, epoch)
         return {'val_loss': loss_sum / ncrops if ncrops > 0 else float('nan'), 'dice': dice_from_counts(counts),
                 'mean_dice': mean, 'ema_dice': self.tracker.ema_dice, 'improved': improved}

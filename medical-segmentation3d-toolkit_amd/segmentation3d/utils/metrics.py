@@ -575,3 +575,10 @@ def mean_foreground_dice(counts):
     """nan-mean of dice_from_counts over the foreground classes 1 .. C-1; nan when every foreground class is empty"""
     fg = [d for d in dice_from_counts(counts)[1:] if not math.isnan(d)]
     return sum(fg) / len(fg) if fg else float('nan')
+
+
+def mean_region_dice(counts):
+    """nan-mean of dice_from_counts over all R rows of [R, 3] region counts (_ops.region_confusion_counts): a region-based
+    model has no background channel, so no row is excluded; nan when every region is empty"""
+    rows = [d for d in dice_from_counts(counts) if not math.isnan(d)]
+    return sum(rows) / len(rows) if rows else float('nan')

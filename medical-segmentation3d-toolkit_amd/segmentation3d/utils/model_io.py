@@ -116,11 +116,13 @@ def checkpoint_regions(epoch_idx, save_dir):
 def checkpoint_state(net, epoch_idx, batch_idx, cfg, max_stride, num_modality, regions=None, region_class_order=None,
                      validation=None):
     """the `params.pth` dictionary (fields of utils/model_io.py:75-84; tensors moved to the host); `regions` /
-    `region_class_order` of a region-based run are stored next to the channel counts with the head's activation;
+    `region_class_order` of a region-based run are stored next to the channel counts (out_channels is then the number of
+    regions) with the head's activation;
     `validation` (a Validator's state dict) adds the key of that name, a run without validation keeps the key set"""
     weights = OrderedDict((key, value.detach().cpu()) for key, value in net.state_dict().items())
     geometry = {'spacing': cfg.dataset.spacing, 'interpolation': cfg.dataset.interpolation, 'max_stride': max_stride}
-    channels = {'in_channels': num_modality, 'out_channels': cfg.dataset.num_classes,
+    channels = {'in_channels': num_modality,   # a region-based network has one output per region
+                'out_channels': cfg.dataset.num_classes if regions is None else len(regions),
                 'deep_supervision': int(getattr(getattr(net, 'module', net), 'deep_supervision', 0))}
     state = {'epoch': epoch_idx, 'batch': batch_idx, 'net': cfg.net.name, 'state_dict': weights,
              'crop_normalizers': [None if n is None else n.to_dict() for n in cfg.dataset.crop_normalizers]}
