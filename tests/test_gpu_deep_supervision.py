@@ -115,9 +115,10 @@ def test_head_matches_float64(hip_device, cin, C, sliced):
 
 
 def test_head_grid_stride_loop(hip_device):
-    """1 x 52^3 = 140608 voxels of 64 channels: more tiles than the persistent grids of either kernel hold workgroups
-    (at most 8 x 256 forward, 1024 backward, 64 voxels a tile), so every workgroup walks several tiles, the last one partial;
-    the backward fills all 1024 slabs of its workspace"""
+    """1 x 52^3 = 140608 voxels of 64 channels, C = 2: both kernels walk 16 groups x 8 voxels = 128 voxels a tile, 1099 tiles, the
+    last one half full.  The forward grid holds up to 8 x 256 = 2048 workgroups, so it launches 1099 and NO workgroup takes a second
+    tile; the backward grid is capped at 1024, so 75 workgroups walk two tiles and all 1024 slabs of the workspace are filled
+    (tests/test_ds_head_cases.py derives these counts; the forward's second trip is taken in tests/test_gpu_ds_head_float64.py)"""
     from segmentation3d import _ops
     g = torch.Generator().manual_seed(5)
     xn = torch.randn((1, 52, 52, 52, 64), generator=g)
